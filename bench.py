@@ -14,13 +14,18 @@ N > 1: one process per GPU over RCCL (the driver starts them with torch.distribu
        adaptation schedules are timed: the reference's (``value``) and the pipeline's one-sweep-late schedule
        (``delayed_adaptation``); ``weak_base`` is one such shard alone on one GPU, the N = 1 point of the same series.
 
-W untimed warm-up steps, then BLOCKS timed blocks of exactly K steps each, every block bracketed by a barrier +
-synchronize on both sides and reduced with MAX over ranks; ``ms_per_step`` / ``value`` come from the MEDIAN block
-(``block_ms`` lists all of them).  BLOCKS = max(5, ceil(2000 / K)), at most 120: SURVEY 8d's protocol times >= 2000 iterations
-(median of 5 at the default K = 2000); with short blocks - the driver runs K = 20, W = 5 - five blocks would all fall into the
-first 2 ms after the GPU leaves its idle clocks, where an iteration runs ~3 % slower than 10 ms later (tools/block_series.py,
-profiles/r04b_block_series.txt: 368 -> 357 us per block over the first 25 blocks).  ``cold_blocks`` reports the median of
-the FIRST five blocks beside the headline.  Prints ONE JSON line (rank 0).
+W untimed warm-up steps, then exactly K timed steps, split into blocks_for(K) blocks (five where every block gets at least
+MIN_BLOCK_STEPS steps, fewer for short runs, one below 2 x MIN_BLOCK_STEPS), every block bracketed by a barrier + synchronize on
+both sides and reduced with MAX over ranks; ``ms_per_step`` / ``value`` come from the MEDIAN block's time per step (``block_ms``
+lists all of them).  The first ~2 ms after the GPU leaves its idle clocks run ~3 % slower than 10 ms later
+(tools/block_series.py, profiles/r04b_block_series.txt): W covers that.  Prints ONE JSON line (rank 0).
+
+A plain run does only that: set up, warm up, time the K steps, write the outputs (``--dump-outputs DIR``: the state the last
+timed step left - coordinates, log-likelihood, log-prior, ladder - as DIR/<name>.npy, float64, a fixed seeded sample of the
+walkers where that would exceed 64 MB) and print the line.  ``--full`` adds every secondary figure: per-launch durations and the
+per-kernel roofline (further profiled calls), the live counter traffic (two rocprofv3 passes), the device copy rate, the other
+BASELINE configs' single-GPU timings (``other_shapes``, TIMED_ITERATIONS steps each), the CPU baselines; for N > 1 the
+weak-scaling base, the delayed adaptation schedule, the per-rank wait breakdown and the RCCL neighbour-exchange leg.
 """
 import argparse
 import json
@@ -38,8 +43,10 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
-BLOCKS = 5                     # set per run: blocks_for(K)
-TIMED_ITERATIONS = 2000        # time >= 2000 iterations
+MAX_BLOCKS = 5                 # the K timed steps: median of at most five blocks ...
+MIN_BLOCK_STEPS = 1000         # ... of at least this many steps each (a block's synchronisation stays below 0.1 % of it)
+TIMED_ITERATIONS = 2000        # time >= 2000 iterations (--full: each of the other shapes)
+OUTPUT_BYTES = 64_000_000      # --dump-outputs: at most this many bytes in all
 METRIC = "walker-steps/sec (ntemps x nwalkers x iters/s), Gaussian logL"
 
 
@@ -389,6 +396,15 @@ def whole_path(roof, T, W, D, f_sw, acc, value):
         roof.setdefault("warnings", []).append("whole-path fraction above 1: check the byte accounting")
 
 
+def plain_roofline(T, D, f_sw, value):
+    """A plain run's roofline: the whole iteration in SURVEY 8d's algorithmic bytes over the timed iteration - no run of its own
+    (the per-kernel figures take further profiled calls: --full)."""
+    w8 = (b_stretch(D) + b_pt(T, D, f_sw)) * value / 1e9
+    return {"bound": "hbm", "kernel": "whole iteration (per-kernel figures: --full)", "achieved": w8, "peak": HBM_PEAK_GBS,
+            "unit": "GB/s", "frac": w8 / HBM_PEAK_GBS, "traffic": None,
+            "bytes": "SURVEY 8d's algorithmic bytes per walker-step (B_stretch + B_pt) x the timed walker-steps/s"}
+
+
 def measured_copy_bandwidth():
     """the box's own HBM rate beside the spec peak - a device-to-device copy of 1 GiB (read + write), GB/s."""
     try:
@@ -411,20 +427,44 @@ def measured_copy_bandwidth():
 
 
 def blocks_for(steps):
-    return int(max(5, min(120, -(-TIMED_ITERATIONS // max(int(steps), 1)))))
+    return int(max(1, min(MAX_BLOCKS, int(steps) // MIN_BLOCK_STEPS)))
 
 
-def cold_blocks(times, steps, units):
-    """The first five blocks of the run (a GPU that has just left its idle clocks) beside the median of all blocks."""
-    dt = float(np.median(times[:5]))
-    return {"ms_per_step": dt / steps * 1e3, "value": units * steps / dt, "blocks": 5}
+def block_sizes(steps):
+    """`steps` timed steps in blocks_for(steps) blocks of (nearly) equal size: they add up to exactly `steps`."""
+    b = blocks_for(steps)
+    return [steps // b + (1 if i < steps % b else 0) for i in range(b)]
+
+
+def step_seconds(times, steps):
+    """Seconds per step of the median block (blocks of timed_blocks(..., steps))."""
+    return float(np.median([t / k for t, k in zip(times, block_sizes(steps))]))
+
+
+def timing_label(steps, ranks=False):
+    return f"median of {blocks_for(steps)} block(s), {steps} timed steps in all" + (", max over ranks" if ranks else "")
+
+
+def dump_outputs(d, arrays, nwalkers):
+    """--dump-outputs: every array as d/<name>.npy in float64.  Arrays are [ntemps, nwalkers, ...]-shaped (or the ladder); above
+    OUTPUT_BYTES in all, the same fixed, seeded sample of walkers is kept from each walker-indexed array."""
+    os.makedirs(d, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    per_walker = sum(a.nbytes for a in arrays.values() if a.ndim >= 2 and a.shape[1] == nwalkers) / nwalkers
+    rest = sum(a.nbytes for a in arrays.values()) - per_walker * nwalkers + 1024 * len(arrays)      # (+ the .npy headers)
+    keep = int((OUTPUT_BYTES - rest) // per_walker) if per_walker else nwalkers
+    if keep < nwalkers:
+        idx = np.sort(np.random.RandomState(0).choice(nwalkers, keep, replace=False))
+        arrays = {k: (a[:, idx] if a.ndim >= 2 and a.shape[1] == nwalkers else a) for k, a in arrays.items()}
+    for k, a in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), np.ascontiguousarray(a))
 
 
 def timed_blocks(step, sync, steps, dist=None, device=None):
-    """BLOCKS blocks of exactly `steps` steps; per block MAX over ranks.  Every rank runs the same collectives
+    """block_sizes(steps) blocks, `steps` steps in all; per block MAX over ranks.  Every rank runs the same collectives
     whether or not its own stepping raised (a flag wait that timed out), and learns whether ALL ranks are fine."""
     times, ok = [], 1
-    for _ in range(BLOCKS):
+    for k in block_sizes(steps):
         torch.cuda.synchronize()
         if dist is not None:
             dist.barrier()
@@ -432,7 +472,7 @@ def timed_blocks(step, sync, steps, dist=None, device=None):
         t0 = time.perf_counter()
         try:
             if ok:
-                step(steps)
+                step(k)
                 # the engine's own stream first (a pipeline rank's flag-wait errors surface here; and hipStreamSynchronize on
                 # the one stream with work returns ~10 us sooner than the device-wide synchronisation that follows finds out)
                 sync()
@@ -455,7 +495,7 @@ def timed_blocks(step, sync, steps, dist=None, device=None):
 
 
 def time_other_shape(T, W, D, steps, warmup, rosen_mix=False):
-    """One further single-GPU shape timed exactly like the headline (W warm-up steps, BLOCKS blocks of `steps` steps, median;
+    """One further single-GPU shape timed exactly like the headline (W warm-up steps, `steps` timed steps, median block;
     then a pass with per-launch HIP events): one GPU's shard of config 3 (8 x 16384 x 64: 67 MB of rows, more than the L2s hold)
     and of config 5 (4 x 8192 x 128 Rosenbrock, stretch + Gaussian move 50 / 50), each stepping alone as a ladder of its own."""
     from eryn_amd.engine import HipEnsemble
@@ -476,21 +516,19 @@ def time_other_shape(T, W, D, steps, warmup, rosen_mix=False):
     eng.synchronize()
     eng.reset_counters()
     times, _ = timed_blocks(eng.step, eng.synchronize, steps)
-    dt = float(np.median(times))
+    dt = step_seconds(times, steps)
     c = eng.counters()
-    nit = max(steps * BLOCKS, 1)
-    f_sw = float(np.mean(c["swaps_total"] / W / nit))
+    f_sw = float(np.mean(c["swaps_total"] / W / max(steps, 1)))
     acc = float(c["accepted"].mean() / max(c["num_proposals"], 1))
-    tm = profiled_pass(eng, steps, expect_us=dt / steps * 1e6)
+    tm = profiled_pass(eng, block_sizes(steps)[0], expect_us=dt * 1e6)
     eng.close()
-    value = T * W * steps / dt
+    value = T * W / dt
     roof = kernel_roofline(tm, T, T, W, D, f_sw, acc)
     whole_path(roof, T, W, D, f_sw, acc, value)
-    consistency(roof, dt / steps * 1e3)
+    consistency(roof, dt * 1e3)
     flag_accounting(roof)
     return {"shape": f"ntemps={T}, nwalkers={W}, ndim={D}, " + ("Rosenbrock, StretchMove + GaussianMove 50/50" if rosen_mix else "dense Gaussian, StretchMove") + " + adaptive PT",
-            "ms_per_step": dt / steps * 1e3, "value": value, "block_ms": [t * 1e3 for t in times],
-            "cold_blocks": cold_blocks(times, steps, T * W), "stretch_acceptance": acc,
+            "ms_per_step": dt * 1e3, "value": value, "block_ms": [t * 1e3 for t in times], "stretch_acceptance": acc,
             "swap_fraction": f_sw, **other_roofline(roof)}
 
 
@@ -522,57 +560,60 @@ def run_single(args):
     eng.synchronize()
     eng.reset_counters()
     times, _ = timed_blocks(eng.step, eng.synchronize, args.steps)
-    dt = float(np.median(times))
+    dt = step_seconds(times, args.steps)
+    if args.dump_outputs:
+        x, L, P, betas = eng.download()
+        dump_outputs(args.dump_outputs, {"coords": x, "log_like": L, "log_prior": P, **({"betas": betas} if betas is not None else {})}, W)
     c = eng.counters()
-    nit = max(args.steps * BLOCKS, 1)
-    f_sw = float(np.mean(c["swaps_total"] / W / nit)) if T > 1 else 0.0
+    f_sw = float(np.mean(c["swaps_total"] / W / max(args.steps, 1))) if T > 1 else 0.0
     acc = float(c["accepted"].mean() / max(c["num_proposals"], 1))
-
-    # per-launch durations: further calls of K steps on the SAME queue with a completion signal per packet (dispatch timestamps)
-    tm = profiled_pass(eng, args.steps, expect_us=dt / args.steps * 1e6)
+    value = T * W / dt
+    if args.full:
+        # per-launch durations: further calls on the SAME queue with a completion signal per packet (dispatch timestamps)
+        tm = profiled_pass(eng, min(block_sizes(args.steps)[0], TIMED_ITERATIONS), expect_us=dt * 1e6)
     eng.close()
-    value = T * W * args.steps / dt
-    live, live_src = (None, "skipped (--no-cpu: the bare line)") if (args.no_cpu or args.no_live_traffic) else live_traffic(T, W, D)
-    roof = kernel_roofline(tm, T, T, W, D, f_sw, acc, traffic_live=live, traffic_live_source=live_src)
-    if live is None and not args.no_cpu:
-        roof["traffic_live_unavailable"] = live_src
-    whole_path(roof, T, W, D, f_sw, acc, value)
-    consistency(roof, dt / args.steps * 1e3)
-    flag_accounting(roof)
-    if not args.no_cpu:                      # (the secondary figures of the default run; --no-cpu = the bare line)
-        bw = measured_copy_bandwidth()
-        roof["measured_copy_GBps"] = bw       # this box's device-to-device copy rate, beside the 8 TB/s spec peak
-        roof["whole_path_frac_of_measured_copy"] = None if not bw else roof["whole_path_GBps"] / bw
+    if args.full:
+        live, live_src = (None, "skipped (--no-cpu: the bare line)") if (args.no_cpu or args.no_live_traffic) else live_traffic(T, W, D)
+        roof = kernel_roofline(tm, T, T, W, D, f_sw, acc, traffic_live=live, traffic_live_source=live_src)
+        if live is None and not args.no_cpu:
+            roof["traffic_live_unavailable"] = live_src
+        whole_path(roof, T, W, D, f_sw, acc, value)
+        consistency(roof, dt * 1e3)
+        flag_accounting(roof)
+        if not args.no_cpu:                      # (the secondary figures of the full run; --no-cpu = without them)
+            bw = measured_copy_bandwidth()
+            roof["measured_copy_GBps"] = bw       # this box's device-to-device copy rate, beside the 8 TB/s spec peak
+            roof["whole_path_frac_of_measured_copy"] = None if not bw else roof["whole_path_GBps"] / bw
+    else:
+        roof = plain_roofline(T, D, f_sw, value)
     out = {
         "metric": METRIC, "value": value, "unit": "walker-steps/s", "n_gpus": 1, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+        "warmup": args.warmup, "ms_per_step": dt * 1e3, "higher_is_better": True, "scaling": "weak",
         "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-        "block_ms": [t * 1e3 for t in times], "timing": f"median of {BLOCKS} blocks of {args.steps} steps",
-        "cold_blocks": cold_blocks(times, args.steps, T * W),
+        "block_ms": [t * 1e3 for t in times], "timing": timing_label(args.steps),
         "config": {"workload": f"{'config 2' if (T, W, D) == (16, 4096, 32) else 'custom shape'}: ntemps={T}, nwalkers={W}, ndim={D} dense-covariance Gaussian, box prior +-50, "
                                f"StretchMove(a=2)+adaptive PT, Philox RNG", "ntemps": T, "nwalkers": W, "ndim": D,
                    "parallelism": "single GPU", "stretch_acceptance": acc, "swap_fraction": f_sw},
         "roofline": roof,
     }
+    if not args.full:
+        return out
     if (T, W, D) == (16, 4096, 32) and not args.no_other:
         # the shapes whose state does not fit the caches, timed by the same clock in the same run (a few ms of GPU time each),
         # and BASELINE configs 4 and 5 whole on this one GPU (0.3 s of GPU time each): every config's single-GPU figure in one line
-        out["other_shapes"] = {"config_3_shard": time_other_shape(8, 16384, 64, args.steps, args.warmup),
-                               "config_5_shard": time_other_shape(4, 8192, 128, args.steps, args.warmup, rosen_mix=True)}
+        out["other_shapes"] = {"config_3_shard": time_other_shape(8, 16384, 64, TIMED_ITERATIONS, args.warmup),
+                               "config_5_shard": time_other_shape(4, 8192, 128, TIMED_ITERATIONS, args.warmup, rosen_mix=True)}
         sub = argparse.Namespace(**vars(args))
         sub.ntemps = sub.nwalkers = sub.ndim = None
+        sub.steps, sub.dump_outputs = TIMED_ITERATIONS, None
         for name, fn in (("config_4", run_cfg4), ("config_5_one_gpu", run_cfg5)):
             try:
                 r = fn(sub)
                 out["other_shapes"][name] = {"shape": r["config"]["workload"], "ms_per_step": r["ms_per_step"], "value": r["value"],
-                                             "cold_blocks": cold_blocks([t_ / 1e3 for t_ in r["block_ms"]], args.steps, r["config"]["ntemps"] * r["config"]["nwalkers"]),
                                              "config": {k: v for k, v in r["config"].items() if k != "workload"},
                                              "roofline": other_roofline(r["roofline"])}
             except Exception as exc:                  # noqa: BLE001  (a secondary figure must not cost the headline line)
                 out["other_shapes"][name] = {"error": f"{type(exc).__name__}: {exc}"}
-        for v in out["other_shapes"].values():        # (the line is long enough: the other shapes keep their first five blocks only)
-            if "block_ms" in v:
-                v["block_ms"] = v["block_ms"][:5]
     if not args.no_cpu:
         out["cpu_baseline"] = cpu_baseline(T, W, D, seconds=args.cpu_seconds)
         out["vs_cpu"] = value / out["cpu_baseline"]["value"]
@@ -598,23 +639,29 @@ def run_cfg5(args):
     eng.synchronize()
     eng.reset_counters()
     times, _ = timed_blocks(eng.step, eng.synchronize, args.steps)
-    dt = float(np.median(times))
+    dt = step_seconds(times, args.steps)
+    if args.dump_outputs:
+        x, L, P, betas = eng.download()
+        dump_outputs(args.dump_outputs, {"coords": x, "log_like": L, "log_prior": P, "betas": betas}, W)
     c, m = eng.counters(), eng.mh_counters()
-    f_sw = float(np.mean(c["swaps_total"] / W / max(args.steps * BLOCKS, 1)))
-    tm = profiled_pass(eng, args.steps, calls=3, expect_us=dt / args.steps * 1e6)
-    eng.close()
-    value = T * W * args.steps / dt
+    f_sw = float(np.mean(c["swaps_total"] / W / max(args.steps, 1)))
+    value = T * W / dt
     acc5 = float(c["accepted"].mean() / max(c["num_proposals"], 1))
-    roof = kernel_roofline(tm, T, T, W, D, f_sw, acc5)
-    whole_path(roof, T, W, D, f_sw, acc5, value)
-    consistency(roof, dt / args.steps * 1e3)
-    flag_accounting(roof)
+    if args.full:
+        tm = profiled_pass(eng, min(block_sizes(args.steps)[0], TIMED_ITERATIONS), calls=3, expect_us=dt * 1e6)
+        roof = kernel_roofline(tm, T, T, W, D, f_sw, acc5)
+        whole_path(roof, T, W, D, f_sw, acc5, value)
+        consistency(roof, dt * 1e3)
+        flag_accounting(roof)
+    else:
+        roof = plain_roofline(T, D, f_sw, value)
+    eng.close()
     return {
         "metric": "walker-steps/sec (ntemps x nwalkers x iters/s), Rosenbrock logL, move mix", "value": value,
         "unit": "walker-steps/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "ms_per_step": dt * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         "dtype": "f64", "data": "synthetic", "block_ms": [t_ * 1e3 for t_ in times],
-        "timing": f"median of {BLOCKS} blocks of {args.steps} steps",
+        "timing": timing_label(args.steps),
         "config": {"workload": f"config 5 on one GPU: Rosenbrock ndim={D}, ntemps={T}, nwalkers={W}, StretchMove(a=2) + "
                                f"GaussianMove(iso, sigma=5e-3) 50/50 + adaptive PT, Philox RNG", "ntemps": T, "nwalkers": W,
                    "ndim": D, "stretch_acceptance": float(c["accepted"].mean() / max(c["num_proposals"], 1)),
@@ -699,21 +746,24 @@ def run_cfg4(args):
     eng.step(args.warmup)
     eng.synchronize()
     times, _ = timed_blocks(eng.step, eng.synchronize, args.steps)
-    dt = float(np.median(times))
-    _, inds1, _, _, _ = eng.download()
+    dt = step_seconds(times, args.steps)
+    x1, inds1, L1, P1, betas1 = eng.download()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {**{f"coords_{k}": v for k, v in x1.items()}, **{f"inds_{k}": v for k, v in inds1.items()},
+                                         "log_like": L1, "log_prior": P1, "betas": betas1}, W)
     c = eng.counters()
     leaves = float(sum(v.sum() for v in inds1.values())) / (T * W)
     eng.close()
-    value = T * W * args.steps / dt
+    value = T * W / dt
     evals = 2 * leaves * N * value                   # template point evaluations per second (two likelihoods per step)
     rw = 2 * NL * 3 + 2
     alg = 2 * (2 * rw * 8 + 32) + N * 16 * 2         # per walker-step: two moves x (record read + write + L, P) + the data
     return {
         "metric": "walker-steps/sec (ntemps x nwalkers x iters/s), RJ Gaussian-pulse model", "value": value,
         "unit": "walker-steps/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "ms_per_step": dt * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         "dtype": "f64", "data": "synthetic", "block_ms": [t_ * 1e3 for t_ in times],
-        "timing": f"median of {BLOCKS} blocks of {args.steps} steps",
+        "timing": timing_label(args.steps),
         "config": {"workload": f"config 4: RJ multi-branch template model (Gaussian pulses + sines, 2 branches x nleaves_max={NL}), "
                                f"ntemps={T}, nwalkers={W}, {N} data points, in-model Gaussian move + birth/death + PT, Philox RNG",
                    "ntemps": T, "nwalkers": W, "mean_active_leaves_per_walker": leaves,
@@ -869,21 +919,20 @@ def run_sharded(args):
 
     # weak-scaling base: ONE shard of the same size alone on this GPU (rank 0's), the N = 1 point of the series
     base = None
-    if rank == 0 and not args.no_base:
+    if rank == 0 and args.full and not args.no_base:
         e = make_engine(0, rung_range=(0, Tl), ntemps=Tl, x=start(Tl))
         e.step(args.warmup)
         e.synchronize()
         bt, _ = timed_blocks(e.step, e.synchronize, args.steps)
         e.close()
-        bdt = float(np.median(bt))
-        base = {"value": Tl * W * args.steps / bdt, "ms_per_step": bdt / args.steps * 1e3,
+        bdt = step_seconds(bt, args.steps)
+        base = {"value": Tl * W / bdt, "ms_per_step": bdt * 1e3,
                 "workload": f"one shard alone on one GPU: ntemps={Tl}, nwalkers={W}, ndim={D} (a {Tl}-rung ladder of its own)"}
     dist.barrier()
 
     def summary(times, **kw):
-        sdt = float(np.median(times))
-        out_ = {"value": T * W * args.steps / sdt, "ms_per_step": sdt / args.steps * 1e3, "block_ms": [t * 1e3 for t in times],
-                "cold_blocks": cold_blocks(times, args.steps, T * W)}
+        sdt = step_seconds(times, args.steps)
+        out_ = {"value": T * W / sdt, "ms_per_step": sdt * 1e3, "block_ms": [t * 1e3 for t in times]}
         if base:                                   # weak scaling: one shard alone on one GPU / the same shard as a rank
             out_["efficiency"] = base["ms_per_step"] / out_["ms_per_step"]
         out_.update(kw)
@@ -894,12 +943,12 @@ def run_sharded(args):
         result = pipeline_run(0)
         if result is not None:
             transport = "xGMI one-sided puts into HIP-IPC mailboxes + device flags (ladder pipeline)"
-            d = pipeline_run(1)
+            d = pipeline_run(1) if args.full else None
             if d is not None:
                 delayed = summary(d[1], schedule="adaptation_delay=1: the swap ratios of sweep s move the ladder before iteration "
                                                  "s+2 (not the reference's schedule; lets the ranks pipeline)")
                 d[0].close()
-            if not args.no_waits:
+            if args.full and not args.no_waits:
                 waits = {"adaptation_delay_0": wait_breakdown(0), "adaptation_delay_1": wait_breakdown(1),
                          "unit": "us per iteration and rank, summed over the waiting workgroups' lead threads (a separate pass "
                                  "with HENS_PIPE_STATS=1; the timed passes run without the statistics)"}
@@ -911,21 +960,21 @@ def run_sharded(args):
         eng, times, transport = fallback_run()
     else:
         eng, times = result
-    dt = float(np.median(times))
+    dt = step_seconds(times, args.steps)
     c = eng.counters()
-    f_sw = float(np.mean(c["swaps_total"] / W / max(args.steps * BLOCKS, 1)))
+    f_sw = float(np.mean(c["swaps_total"] / W / max(args.steps, 1)))
     tm = None
-    if mode == "pipeline" and result is not None:     # per-launch durations of this rank's kernels
+    if args.full and mode == "pipeline" and result is not None:     # per-launch durations of this rank's kernels
         eng.set_profiling(2)                            # (a rank steps on the HIP stream: an event pair per launch)
         try:
-            eng.step(args.steps)
+            eng.step(min(block_sizes(args.steps)[0], TIMED_ITERATIONS))
             eng.synchronize()
             tm = eng.timing()
         except RuntimeError:
             tm = None
         eng.set_profiling(0)
     dist.barrier()
-    value = T * W * args.steps / dt
+    value = T * W / dt
     out = None
     if rank == 0:
         whole = (b_stretch(D) + b_pt(T, D, f_sw)) * value / 1e9
@@ -940,9 +989,9 @@ def run_sharded(args):
             model = "Rosenbrock, StretchMove(a=2) + GaussianMove(iso, sigma=5e-3) 50/50"
         out = {
             "metric": METRIC.replace("Gaussian logL", "Rosenbrock logL, move mix") if rosen else METRIC, "value": value, "unit": "walker-steps/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+            "warmup": args.warmup, "ms_per_step": dt * 1e3, "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "block_ms": [t * 1e3 for t in times], "timing": f"median of {BLOCKS} blocks of {args.steps} steps, max over ranks",
+            "block_ms": [t * 1e3 for t in times], "timing": timing_label(args.steps, ranks=True),
             "config": {"workload": f"{cfgname}: ladder sharded over {world} GPU(s), ntemps={T} ({Tl} rungs/GPU), nwalkers={W}, "
                                    f"ndim={D} {model}+adaptive PT on the reference's "
                                    f"adaptation schedule, Philox RNG.  WEAK scaling: the ladder grows with N (one fixed-size shard per GPU), so "
@@ -961,7 +1010,7 @@ def run_sharded(args):
             out["rank_waits"] = waits
         if base:
             out["weak_base"] = base
-        if not args.no_cpu and not rosen:             # (the CPU leg times the Gaussian stretch + PT oracle)
+        if args.full and not args.no_cpu and not rosen:             # (the CPU leg times the Gaussian stretch + PT oracle)
             out["cpu_baseline"] = cpu_baseline(Tl, W, D, seconds=args.cpu_seconds)
             out["cpu_baseline"]["sample"] += " = one GPU's shard as a ladder of its own"
     eng.close()
@@ -969,7 +1018,7 @@ def run_sharded(args):
     # The transport north_star names, timed in the same run as the LAST leg: RCCL point-to-point between ladder neighbours,
     # enqueued by the library (hens_comm_init).  It has never run between physical GPUs (a one-GPU box cannot host two RCCL ranks),
     # so a watchdog stands behind it: if the leg does not finish, rank 0 prints the line measured so far and every rank leaves.
-    if mode == "pipeline" and result is not None and not args.no_staged:
+    if args.full and mode == "pipeline" and result is not None and not args.no_staged:
         import threading
         limit = float(os.environ.get("BENCH_STAGED_TIMEOUT_S", "120"))
 
@@ -1019,23 +1068,28 @@ def main():
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--no-live-traffic", action="store_true", help="N = 1: roofline.traffic from profiles/traffic.json instead of two rocprofv3 --pmc passes of this run")
     ap.add_argument("--traffic-child", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--full", action="store_true", help="every secondary figure beside the headline: per-kernel roofline, live "
+                    "counter traffic, copy rate, other shapes, CPU baselines; N > 1: weak-scaling base, delayed schedule, waits, RCCL leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="single GPU: write the state the last timed step left as "
+                    "DIR/<name>.npy (float64, at most 64 MB)")
     args = ap.parse_args()
     if args.traffic_child:
         traffic_child(args)
         return
-    global BLOCKS
+    if args.steps is not None and args.steps < 1:
+        raise SystemExit("bench.py: --steps must be at least 1")
     world = int(os.environ.get("WORLD_SIZE", "0"))
     n = max(args.gpus, world, 1)
+    if args.dump_outputs and n > 1:
+        raise SystemExit("bench.py --dump-outputs: single-GPU workloads only")
     if args.workload == "cfg4":
         if n > 1:
             raise SystemExit("bench.py --workload cfg4 is a single-GPU workload")
         args.steps = args.steps or 200
-        BLOCKS = blocks_for(args.steps)
         print(json.dumps(run_cfg4(args)), flush=True)
         return
     if args.workload == "cfg5" and n == 1:
         args.steps = args.steps or 500
-        BLOCKS = blocks_for(args.steps)
         print(json.dumps(run_cfg5(args)), flush=True)
         return
     if n > 1 and world == 0:
@@ -1057,14 +1111,12 @@ def main():
         else:
             args.ntemps, args.nwalkers, args.ndim = args.ntemps or 16 * n, args.nwalkers or 4096, args.ndim or 32
             args.steps = args.steps or 2000
-        BLOCKS = blocks_for(args.steps)
         out = run_sharded(args)
     else:
         args.ntemps = args.ntemps or 16
         args.nwalkers = args.nwalkers or 4096
         args.ndim = args.ndim or 32
         args.steps = args.steps or 2000
-        BLOCKS = blocks_for(args.steps)
         out = run_single(args)
     if out is not None:
         print(json.dumps(out), flush=True)

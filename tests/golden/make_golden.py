@@ -38,6 +38,26 @@ from eryn.prior import ProbDistContainer, uniform_dist  # noqa: E402
 from eryn.moves.tempering import make_ladder  # noqa: E402
 
 HERE = os.path.dirname(os.path.abspath(__file__))
+SPLIT_ABOVE = 1 << 20          # a fixture of more bytes is written in pieces of at most PART_BYTES (tests/golden_io.py reads them)
+PART_BYTES = 1 << 19
+
+
+def save(name, out):
+    """NAME.npz, or - above SPLIT_ABOVE bytes - NAME.npz, NAME.part1.npz, ... with the arrays in the order they were recorded."""
+    parts = [{}]
+    if sum(np.asarray(v).nbytes for v in out.values()) > SPLIT_ABOVE:
+        size = 0
+        for k, v in out.items():
+            if parts[-1] and size + np.asarray(v).nbytes > PART_BYTES:
+                parts.append({})
+                size = 0
+            parts[-1][k] = v
+            size += np.asarray(v).nbytes
+    else:
+        parts[0] = out
+    for j, p in enumerate(parts):
+        np.savez_compressed(os.path.join(HERE, name + (f".part{j}" if j else "") + ".npz"), **p)
+    return os.path.join(HERE, name + ".npz"), len(parts)
 
 
 def gaussian_problem(D, dense=True):
@@ -257,9 +277,8 @@ def capture(name, T, W, D, nsteps, box, dense=True, vectorize=True, seed_constru
         out["num_proposals"] = int(move.num_proposals)
     finally:
         np.random.shuffle, np.random.permutation, np.random.uniform = orig_shuffle, orig_perm, orig_unif
-    path = os.path.join(HERE, name + ".npz")
-    np.savez_compressed(path, **out)
-    print(f"{name}: {os.path.getsize(path) / 1024:.0f} KiB, "
+    path, nfiles = save(name, out)
+    print(f"{name}: {os.path.getsize(path) / 1024:.0f} KiB ({nfiles} file(s)), "
           f"mean accept {out['accepted_total'].mean() / nsteps:.3f}")
 
 

@@ -18,7 +18,7 @@ def test_bench_two_ranks_dry_run_has_every_key():
                HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("WORLD_SIZE", None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--ntemps", "8", "--nwalkers", "256",
-                        "--ndim", "32", "--steps", "6", "--warmup", "4", "--no-cpu"], env=env, cwd=ROOT, capture_output=True,
+                        "--ndim", "32", "--steps", "6", "--warmup", "4", "--full", "--no-cpu"], env=env, cwd=ROOT, capture_output=True,
                        text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]

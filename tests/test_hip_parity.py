@@ -14,6 +14,7 @@ import os
 import numpy as np
 import pytest
 
+from tests import golden_io
 from tests import parity_utils as pu
 from tests import tolerance_log as tol
 from oracle import eryn_oracle as orc
@@ -41,7 +42,7 @@ def _fixture_oracle(fx):
                                   "f5_nopermute", "f6_medium", "f7_tmaxinf", "f8_nsplits3"])
 def test_golden_fixture_teacher_forced(name, golden_dir):
     """Replay the reference's own recorded draws (committed fixtures) through the HIP path."""
-    fx = np.load(os.path.join(golden_dir, name + ".npz"))
+    fx = golden_io.load(golden_dir, name)
     o, mu, invcov = _fixture_oracle(fx)
     dense = bool(fx["dense"])
     eng = pu.make_engine(o, mu, invcov, dense=True)

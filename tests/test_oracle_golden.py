@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from oracle import eryn_oracle as orc
+from tests import golden_io
 
 FIXTURES = ["f1_plumbing", "f2_pt", "f3_oddW", "f4_narrowbox", "f5_noadapt",
             "f5_nopermute", "f6_medium", "f7_tmaxinf", "f8_nsplits3"]
@@ -50,7 +51,7 @@ def _same(a, b, what):
 
 @pytest.mark.parametrize("name", FIXTURES)
 def test_oracle_reproduces_reference(name, golden_dir):
-    fx = np.load(os.path.join(golden_dir, name + ".npz"))
+    fx = golden_io.load(golden_dir, name)
     T = int(fx["T"])
     o = build_oracle(fx)
     _same(o.P, fx["P0"], "P0")

@@ -57,23 +57,12 @@ def test_callable_likelihood_equals_the_oracle(seed):
     assert np.array_equal(part[1], want[1]) and like.ncalls - n0 == 7
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="the reference tree exists in the build container only")
 @pytest.mark.parametrize("vectorize", [False, True])
-def test_callable_likelihood_equals_the_reference_compute_log_like(vectorize):
-    """The REAL ``EnsembleSampler.compute_log_like`` (imported read-only) on the same state with the same user function: per group
-    (ensemble.py:1420-1480) and vectorised with ``provide_groups=True`` (:1376-1409)."""
-    for m in ("corner", "seaborn"):
-        sys.modules.setdefault(m, types.ModuleType(m))
-    if REF not in sys.path:
-        sys.path.insert(0, REF)
-    old = sys.dont_write_bytecode
-    sys.dont_write_bytecode = True
-    try:
-        from eryn.ensemble import EnsembleSampler
-        from eryn.moves import GaussianMove
-        from eryn.prior import uniform_dist
-    finally:
-        sys.dont_write_bytecode = old
+def test_callable_likelihood_equals_the_reference_compute_log_like(vectorize, golden_dir):
+    """The REAL ``EnsembleSampler.compute_log_like`` on the same state with the same user function: per group
+    (ensemble.py:1420-1480) and vectorised with ``provide_groups=True`` (:1376-1409).  Its output is recorded in
+    tests/golden/rjc_compute_log_like.npy ([per group, vectorised]); where the reference can be imported (read-only) it is
+    recomputed as well and must equal the recording."""
     from eryn_amd.rj import CallableLikelihood
     t, y, sigma = _data()
 
@@ -87,14 +76,30 @@ def test_callable_likelihood_equals_the_reference_compute_log_like(vectorize):
 
     fn = vec_fn if vectorize else orj.lorentz_chirp_log_like
     x, inds, logp = _random_state(11)
+    want = np.load(os.path.join(golden_dir, "rjc_compute_log_like.npy"))[int(vectorize)]
+    got = CallableLikelihood(fn, args=[t, y, sigma], vectorize=vectorize, provide_groups=vectorize)(x, inds, logp, ["gauss", "sine"])
+    assert np.array_equal(got, want)
+    if not os.path.isdir(REF):
+        return
+    for m in ("corner", "seaborn"):
+        sys.modules.setdefault(m, types.ModuleType(m))
+    if REF not in sys.path:
+        sys.path.insert(0, REF)
+    old = sys.dont_write_bytecode
+    sys.dont_write_bytecode = True
+    try:
+        from eryn.ensemble import EnsembleSampler
+        from eryn.moves import GaussianMove
+        from eryn.prior import uniform_dist
+    finally:
+        sys.dont_write_bytecode = old
     T, W = logp.shape
     priors = {"gauss": {i: uniform_dist(0.0, 1.0) for i in range(3)}, "sine": {i: uniform_dist(0.0, 2.0) for i in range(3)}}
     s = EnsembleSampler(W, {"gauss": 3, "sine": 3}, fn, priors, args=[t, y, sigma], tempering_kwargs=dict(ntemps=T), nbranches=2,
                         branch_names=["gauss", "sine"], nleaves_max={"gauss": 4, "sine": 3}, nleaves_min={"gauss": 0, "sine": 0}, vectorize=vectorize,
                         provide_groups=vectorize, rj_moves=True, moves=GaussianMove({k: np.eye(3) * 1e-3 for k in ("gauss", "sine")}))
-    want = s.compute_log_like({k: v.copy() for k, v in x.items()}, inds={k: v.copy() for k, v in inds.items()}, logp=logp.copy())[0]
-    got = CallableLikelihood(fn, args=[t, y, sigma], vectorize=vectorize, provide_groups=vectorize)(x, inds, logp, ["gauss", "sine"])
-    assert np.array_equal(got, want)
+    live = s.compute_log_like({k: v.copy() for k, v in x.items()}, inds={k: v.copy() for k, v in inds.items()}, logp=logp.copy())[0]
+    assert np.array_equal(live, want)
 
 
 # ---- the device path -----------------------------------------------------------------------------------------------------

@@ -9,7 +9,7 @@ OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 export PYTHONPATH=$R
 cd /tmp && export TMPDIR=/tmp
-ARGS="--steps 500 --warmup 100 --no-cpu $*"
+ARGS="--steps 500 --warmup 100 --full --no-cpu $*"
 # 1) kernel trace + stats (per-kernel time)
 rm -rf /tmp/p1; rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p1 -o kt -- python $R/bench.py $ARGS > $OUT/bench_under_rocprof.json 2> $OUT/rocprof_stderr.log
 cp $(find /tmp/p1 -name '*kernel_stats.csv' | head -1) $OUT/kernel_stats.csv 2>/dev/null
@@ -28,7 +28,7 @@ for k, v in sorted(agg.items(), key=lambda kv: -sum(kv[1])):
 PY
 # 2) HBM traffic counters, one pass each (TCC slots: FETCH_SIZE 3, WRITE_SIZE 2)
 for C in FETCH_SIZE WRITE_SIZE; do
-  rm -rf /tmp/p2; rocprofv3 --kernel-trace --pmc $C --output-format csv -d /tmp/p2 -o pmc -- python $R/bench.py --steps 100 --warmup 20 --no-cpu $* > /dev/null 2>> $OUT/rocprof_stderr.log
+  rm -rf /tmp/p2; rocprofv3 --kernel-trace --pmc $C --output-format csv -d /tmp/p2 -o pmc -- python $R/bench.py --steps 100 --warmup 20 --full --no-cpu $* > /dev/null 2>> $OUT/rocprof_stderr.log
   python - <<PY > $OUT/pmc_$C.txt
 import csv, glob, collections
 f = glob.glob('/tmp/p2/**/*counter_collection.csv', recursive=True)
