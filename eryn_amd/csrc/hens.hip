@@ -506,8 +506,10 @@ int launch_stretch_like(hens_ctx_impl* c, int like, int mode, StretchArgs a, int
                 a.xcd_shift = 0;
                 static const bool xcd = getenv("HENS_NO_XCD") == nullptr;
                 if (xcd && (gx & (gx - 1)) == 0 && ((long)gx * c->Tl) % 8 == 0) { int sh = 0; while ((1 << sh) < gx) ++sh; a.xcd_shift = sh + 1; }
-                static const bool say = getenv("HENS_TILE2_LOG") != nullptr;      // (tests: which kernel a context's first launches went to)
-                if (say && c->iter < 3) fprintf(stderr, "hens: k_stretch2<pipe=%d> grid %d x %d, ad_on %d, cnt_push %d\n", pipe ? 1 : 0, gx, c->Tl, a.ad_on, a.cnt_push);
+                static const bool say = getenv("HENS_TILE2_LOG") != nullptr;      // (tests: which kernel a context's first launches, and
+                if (say && (c->iter < 3 || (c->iter + 8) % KEY_WINDOW < 16))       //  those around a round-key window's edge, went to)
+                    fprintf(stderr, "hens: k_stretch2<pipe=%d> grid %d x %d, ad_on %d, cnt_push %d, iter %llu\n", pipe ? 1 : 0, gx, c->Tl, a.ad_on,
+                            a.cnt_push, (unsigned long long)c->iter);
                 return launch_by_ptr(c, k2, "k_stretch2", dim3(gx, c->Tl), NW * 64, tile2_lds_bytes(c->D, like), false,
                                      c->aql_now ? nullptr : c->ext_start, c->ext_stop, a);
             }
@@ -2333,6 +2335,15 @@ int hens_eval_state(hens_ctx* ctx) {
     return HENS_OK;
 }
 
+// The iteration counter is an int64 at the C ABI (hens_set_iteration / hens_get_iteration), and the leaf-packing cascades key their
+// draws on 2 iter and 2 iter + 1: a call that would carry it past INT64_MAX is refused before it runs (beyond it hens_get_iteration
+// would turn negative and 2 iter would wrap to iteration 0's keys).
+static int counter_room(hens_ctx_impl* c, int64_t n) {
+    if (n > 0 && (uint64_t)n > (uint64_t)INT64_MAX - c->iter)
+        return fail(c, HENS_ERR_INVALID, "iteration counter %llu + %lld iterations would pass INT64_MAX", (unsigned long long)c->iter, (long long)n);
+    return HENS_OK;
+}
+
 // shared front half of the parity-mode half-steps: labels -> ascending split lists, draws -> device
 static int prepare_split(hens_ctx_impl* c, int32_t split, const uint8_t* labels, const int64_t* rint,
                          const double* u_zz, const double* u_acc, int* Ns_out) {
@@ -2343,6 +2354,8 @@ static int prepare_split(hens_ctx_impl* c, int32_t split, const uint8_t* labels,
         return fail(c, HENS_ERR_STATE, "split calls must run 0 .. %d in order (expected %d)", NSP - 1, c->expect_split);
     if (c->pt_pending) return fail(c, HENS_ERR_STATE, "sharded PT exchange in flight");
     if (c->propose_pending) return fail(c, HENS_ERR_STATE, "hens_propose_split without its hens_accept_split");
+    int r;
+    if ((r = counter_room(c, 1))) return r;          // (the iteration's last half-step, or its cascade, advances the counter)
     HIPCHK(c, hipSetDevice(c->cfg.device_id));
     flush_adapt(c);
     const int Tl = c->Tl, W = c->W;
@@ -2529,6 +2542,7 @@ int hens_pt_sweep(hens_ctx* ctx, const int64_t* iperm, const int64_t* i1perm, co
     if (!c->cfg.tempered) return fail(c, HENS_ERR_STATE, "context is not tempered");
     if (c->Tl != c->T) return fail(c, HENS_ERR_STATE, "hens_pt_sweep needs the whole ladder resident; use hens_pt_plan_sharded");
     if (c->expect_split != 0) return fail(c, HENS_ERR_STATE, "PT sweep between split 0 and split 1");
+    if ((r = counter_room(c, 1))) return r;
     if (!iperm || !i1perm || !u_swap) return fail(c, HENS_ERR_INVALID, "null argument");
     HIPCHK(c, hipSetDevice(c->cfg.device_id));
     state_to_fields(c);                       // (hens_step leaves the state in record mode)
@@ -2598,6 +2612,7 @@ int hens_step(hens_ctx* ctx, int64_t n_iters) {
     int r = ready(c, true);
     if (r) return r;
     if (n_iters < 0) return fail(c, HENS_ERR_INVALID, "n_iters < 0");
+    if ((r = counter_room(c, n_iters))) return r;
     const bool piped = pipe_active(c);
     if (c->Tl != c->T && !piped)
         return fail(c, HENS_ERR_STATE, "hens_step on a ladder shard needs the pipeline connected (hens_pipe_init / hens_pipe_connect)");
@@ -2808,6 +2823,8 @@ int hens_step_marked(hens_ctx* ctx, int64_t n_before, int64_t n_last) {
     if (!c) return fail(c, HENS_ERR_INVALID, "null context");
     if (n_before < 0 || n_last < 0) return fail(c, HENS_ERR_INVALID, "negative iteration count");
     int r;
+    if (n_before > INT64_MAX - n_last) return fail(c, HENS_ERR_INVALID, "iteration count past INT64_MAX");
+    if ((r = counter_room(c, n_before + n_last))) return r;
     if (n_before > 0 && (r = hens_step(ctx, n_before))) return r;
     if ((r = aql_settle(c))) return r;        // (what follows uses the HIP stream)
     HIPCHK(c, hipSetDevice(c->cfg.device_id));
@@ -2830,6 +2847,7 @@ int hens_step_report(hens_ctx* ctx, int64_t n_iters, int64_t n_last, uint8_t* ac
     if (!c) return fail(c, HENS_ERR_INVALID, "null context");
     if (n_last < 1 || n_iters < n_last) return fail(c, HENS_ERR_INVALID, "hens_step_report: 1 <= n_last <= n_iters");
     int r;
+    if ((r = counter_room(c, n_iters))) return r;
     const size_t TW = (size_t)c->Tl * c->W;
     // The accept counts of the last n_last iterations = the counters now minus the counters in front of those iterations.  The
     // "before" copy is kept from report to report (report_prev: updated by the kernel that forms the difference), so the usual
@@ -3234,6 +3252,7 @@ int hens_rj_mh_step(hens_ctx* ctx, const double* step, const double* u_acc, uint
     int r = rj_ready(c);
     if (r) return r;
     if (!step || !u_acc) return fail(c, HENS_ERR_INVALID, "null argument");
+    if ((r = counter_room(c, 1))) return r;
     HIPCHK(c, hipSetDevice(c->cfg.device_id));
     state_to_fields(c);                       // (hens_step leaves the state in record mode)
     flush_adapt(c);
@@ -3261,6 +3280,7 @@ int hens_rj_stretch_split(hens_ctx* ctx, int32_t split, const uint8_t* labels, c
     if (!labels || !rint || !u_zz || !u_acc) return fail(c, HENS_ERR_INVALID, "null argument");
     if (split < 0 || split > 1) return fail(c, HENS_ERR_INVALID, "split must be 0 or 1 (two sets)");
     if (split != c->expect_split) return fail(c, HENS_ERR_STATE, "split calls must run 0, 1 in order (expected %d)", c->expect_split);
+    if ((r = counter_room(c, 1))) return r;
     const int Tl = c->Tl, W = c->W, nb = c->rj.nb;
     if (!c->cfg.live_dangerously && W < 2 * c->rj.ind_off)                          // red_blue.py:103-114 (every slot of every branch counts)
         return fail(c, HENS_ERR_TOO_FEW_WALKERS, "It is unadvisable to use a red-blue move with fewer walkers than twice the number of dimensions. "
@@ -3378,6 +3398,7 @@ int hens_rj_step(hens_ctx* ctx, int64_t n_iters) {
     int r = rj_ready(c);
     if (r) return r;
     if (n_iters < 0) return fail(c, HENS_ERR_INVALID, "n_iters < 0");
+    if ((r = counter_room(c, n_iters))) return r;
     if (!c->rj_have_scale) return fail(c, HENS_ERR_STATE, "in-model step scale not set (hens_rj_set_mh_scale)");
     HIPCHK(c, hipSetDevice(c->cfg.device_id));
     state_to_fields(c);                       // (hens_step leaves the state in record mode)
@@ -3571,7 +3592,7 @@ int hens_rj_debug_draws(hens_ctx* ctx, int64_t iter, double* step, double* u_mh,
         if (!ds || !du) return fail(c, HENS_ERR_HIP, "hens_rj_debug_draws: out of device memory");
         for (int k = 0; k < 2; ++k) {
             hipLaunchKernelGGL(k_debug_pt, dim3(grid_for((int64_t)n)), dim3(256), 0, c->stream, ds, du, c->T, c->W, c->idx_bits,
-                               c->cfg.seed, (uint64_t)(2 * iter + k));
+                               c->cfg.seed, 2 * (uint64_t)iter + (uint64_t)k);
             HIPCHK(c, hipGetLastError());
             HIPCHK(c, hipMemcpyAsync(k ? slot_bd : slot_mh, ds, n * 4, hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipMemcpyAsync(k ? uswap_bd : uswap_mh, du, (size_t)(c->T - 1) * c->W * 8, hipMemcpyDeviceToHost, c->stream));
@@ -3599,6 +3620,26 @@ int hens_rj_get_counters(hens_ctx* ctx, double* accepted_bd, int64_t* num_mh, in
     return HENS_OK;
 }
 
+int hens_rj_debug_resident(hens_ctx* ctx, double* rec, double* logl) {
+    hens_ctx_impl* c = enter(ctx);
+    if (!c) return fail(c, HENS_ERR_INVALID, "null context");
+    if (c->cfg.likelihood_kind != HENS_LIKE_TEMPLATE || c->rj.nb <= 0) return fail(c, HENS_ERR_STATE, "hens_rj_set_model first");
+    if (!c->have_state) return fail(c, HENS_ERR_STATE, "no state uploaded");
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    state_to_fields(c);                       // (hens_step leaves the state in record mode)
+    flush_adapt(c);
+    const size_t TW = (size_t)c->Tl * c->W;
+    // (hens_download_state without the evaluation in front of its copy: the log-likelihoods as hens_rj_step's +- leaf updates left them)
+    if (rec) {
+        hipLaunchKernelGGL(k_gather_rows, dim3(grid_for((int64_t)TW * c->D)), dim3(256), 0, c->stream, c->pool,
+                           c->loc[c->cur], c->xtmp, (int64_t)TW, c->D, guest_delta(c));
+        HIPCHK(c, hipMemcpyAsync(rec, c->xtmp, TW * c->D * 8, hipMemcpyDeviceToHost, c->stream));
+    }
+    if (logl) HIPCHK(c, hipMemcpyAsync(logl, c->L[c->cur], TW * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return HENS_OK;
+}
+
 // ---- ladder sharding ---------------------------------------------------------------------------------
 int hens_get_device_buffers(hens_ctx* ctx, hens_device_buffers* out) {
     hens_ctx_impl* c = enter(ctx);
@@ -3622,6 +3663,7 @@ int hens_stretch_iter(hens_ctx* ctx) {
     int r = ready(c, true);
     if (r) return r;
     if (c->expect_split != 0) return fail(c, HENS_ERR_STATE, "hens_stretch_iter between split 0 and split 1");
+    if ((r = counter_room(c, 1))) return r;
     if (c->cfg.likelihood_kind == HENS_LIKE_HOST) return fail(c, HENS_ERR_UNSUPPORTED, "hens_stretch_iter needs a device likelihood");
     if (c->pt_pending) return fail(c, HENS_ERR_STATE, "sharded PT exchange in flight");
     HIPCHK(c, hipSetDevice(c->cfg.device_id));
@@ -3649,6 +3691,7 @@ int hens_pt_plan_sharded(hens_ctx* ctx, const int64_t* iperm, const int64_t* i1p
     if (r) return r;
     if (!c->cfg.tempered || c->T < 2) return fail(c, HENS_ERR_STATE, "context is not tempered");
     if (c->expect_split != 0) return fail(c, HENS_ERR_STATE, "PT sweep between split 0 and split 1");
+    if ((r = counter_room(c, 1))) return r;
     if (c->pt_pending) return fail(c, HENS_ERR_STATE, "previous sharded PT exchange not finished");
     if (!rank_of_rung || !send_counts || !recv_counts) return fail(c, HENS_ERR_INVALID, "null argument");
     if (nranks < 1 || nranks > MAX_RANKS || my_rank < 0 || my_rank >= nranks)
@@ -3753,6 +3796,7 @@ int hens_mh_step(hens_ctx* ctx, const double* step, const double* u_acc, uint8_t
     if (c->cfg.likelihood_kind == HENS_LIKE_HOST) return fail(c, HENS_ERR_UNSUPPORTED, "hens_mh_step needs a device likelihood");
     if (c->expect_split != 0) return fail(c, HENS_ERR_STATE, "hens_mh_step between split 0 and split 1");
     if (c->pt_pending) return fail(c, HENS_ERR_STATE, "sharded PT exchange in flight");
+    if ((r = counter_room(c, 1))) return r;
     HIPCHK(c, hipSetDevice(c->cfg.device_id));
     state_to_fields(c);                       // (hens_step leaves the state in record mode)
     if ((r = ensure_mh_buffers(c))) return r;
@@ -3985,6 +4029,7 @@ static int pipe_stage_impl(hens_ctx_impl* c, int32_t stage) {
     int r = ready(c, true);
     if (r) return r;
     if (!c->pipe.staged) return fail(c, HENS_ERR_STATE, "hens_pipe_connect_staged first");
+    if ((r = counter_room(c, 1))) return r;
     HIPCHK(c, hipSetDevice(c->cfg.device_id));
     state_to_fields(c);                       // (hens_step leaves the state in record mode)
     switch (stage) {

@@ -364,6 +364,18 @@ class RJEngine:
                 out[k] = out[k][:1]
         return out
 
+    def debug_resident(self):
+        """(x, inds, log_like) as they sit on the device, without the re-evaluation a download runs first
+        (include/hipensemble.h: hens_rj_debug_resident): the log-likelihoods carry the +- leaf updates since the last refresh."""
+        rec = np.empty((self.T, self.W, self.RW))
+        L = np.empty((self.T, self.W))
+        check(self.lib.hens_rj_debug_resident(self.ctx, ptr(rec), ptr(L)), self.ctx)
+        x, inds = self.unpack(rec)
+        return x, inds, L
+
+    def set_iteration(self, it):
+        self.eng.set_iteration(it)
+
     def iteration(self):
         return self.eng.iteration()
 

@@ -445,6 +445,11 @@ int hens_rj_get_counters(hens_ctx* ctx, double* accepted_bd, int64_t* num_mh, in
 int hens_rj_debug_draws(hens_ctx* ctx, int64_t iter, double* step, double* u_mh, int32_t* branch, int8_t* coin, uint32_t* sel,
                         double* birth, double* u_bd, int32_t* slot_mh, double* uswap_mh, int32_t* slot_bd, double* uswap_bd);
 
+/* Read-only view of the resident state of a leaf-packing context: records [Tl][W][RW] and log-likelihoods [Tl][W] as they sit on
+ * the device, WITHOUT the evaluation from the coordinates that hens_download_state runs in front of its copy - i.e. with the
+ * +- leaf updates of hens_rj_step since the last refresh in them (tests measure that drift).  Either pointer may be NULL. */
+int hens_rj_debug_resident(hens_ctx* ctx, double* rec, double* logl);
+
 /* The between-model schedule of hens_rj_step (the sampler's rj_moves string, ensemble.py:434-480):
  *   0  "separate_branches" (default): one DistributionGenerateRJ per branch, one of them chosen per iteration
  *   1  "iterate_branches": ONE move that walks through every branch in turn (birth / death, accept, update per branch), then
@@ -493,7 +498,10 @@ int hens_get_iteration(hens_ctx* ctx, int64_t* iter_out);
  * walker), so a chain continues bit-identically from an uploaded State when the counter (and the adaptation time,
  * hens_set_adapt_time) are restored to the values that State was taken at - the device-side form of the reference's
  * random_state checkpoint (backends/backend.py:1014-1091 stores R's state with every step, ensemble.py:605-647 restores
- * it).  Not on a connected pipeline rank (the ranks' sweep counters would have to move together). */
+ * it).  Not on a connected pipeline rank (the ranks' sweep counters would have to move together).  Every call that advances the
+ * counter (hens_step and its variants, hens_stretch_iter, the sharded and staged PT steps, the parity API's half-steps, sweeps and
+ * MH steps, hens_rj_step, hens_rj_mh_step, hens_rj_stretch_split) fails with HENS_ERR_INVALID before it runs if it would carry the counter past
+ * INT64_MAX (the leaf-packing cascades key on 2 iter + 1). */
 int hens_set_iteration(hens_ctx* ctx, int64_t iter);
 
 /* Debug / parity: the Philox draws hens_step consumes in iteration `iter` (a pure function of seed, iteration,

@@ -7,6 +7,7 @@
 env PIPE_TEST_DELAY=1 runs everything with adaptation_delay = 1 (then "single" is a 1-rank pipeline).
   timeout                                            rank 1 never steps: rank 0 must raise, not hang
   replay <nranks> <T> <W> <D> <iters>                N local shards against the ORACLE fed with the exported Philox draws
+  replay_from <nranks> <T> <W> <D> <start> <n,n,..>  the same after an unobserved call of <start> iterations, in calls of n
 """
 import os
 import sys
@@ -175,6 +176,47 @@ def main():
             ru.assert_state_equal(st, *[np.concatenate([s[k] for s in snaps], axis=0) for k in range(3)], snaps[0][3],
                                   counters=cnt, what=f"{nranks}-shard pipeline after {done} iterations")
         assert st.swaps_total.sum() > 0 and st.min_margin > 1e-12
+    elif mode == "replay_from":
+        # ... from iteration <start> on (tests/test_hip_counter_edges.py: the round-key window's edge, which a rank plans for
+        # its rungs AND the rung below them)
+        from oracle import eryn_oracle as orc
+        from tests import replay_utils as ru
+        nranks, T, W, D, start = map(int, sys.argv[2:7])
+        calls = [int(v) for v in sys.argv[7].split(",")]
+        mu, invcov, x0, betas0 = problem(T, W, D)
+        _, bounds = rung_partition(T, nranks)
+        engs = [make(T, W, D, b) for b in bounds]
+        LadderPipeline.connect_local(engs)
+        whole = make(T, W, D)
+        for k in range(0, start, 8):         # (in rounds: one rank's call must not fill its queue while the other waits to be queued)
+            for e in engs:
+                e.step(min(8, start - k))
+        for e in engs:
+            e.synchronize()
+        snaps = [e.download() for e in engs]
+        cs = [e.counters() for e in engs]
+        assert all(e.iteration() == start for e in engs) and cs[0]["adapt_time"] == start
+        st = ru.OracleState(*[np.concatenate([s[k] for s in snaps], axis=0) for k in range(3)], snaps[0][3], time=start)
+        st.accepted = np.concatenate([c["accepted"] for c in cs], axis=0)
+        st.swaps_total, st.swaps_last = cs[0]["swaps_total"].copy(), cs[0]["swaps_last"].copy()
+        acc0, swaps0 = st.accepted.sum(), st.swaps_total.sum()
+        fn = lambda q: orc.gaussian_log_like(q, mu, invcov)      # noqa: E731
+        done = start
+        for n in calls:
+            for e in engs:
+                e.step(n)
+            for e in engs:
+                e.synchronize()
+            ru.replay(whole, st, done, n, fn, np.full(D, -6.0), np.full(D, 6.0))
+            done += n
+            snaps = [e.download() for e in engs]
+            cs = [e.counters() for e in engs]
+            cnt = dict(accepted=np.concatenate([c["accepted"] for c in cs], axis=0), swaps_total=cs[0]["swaps_total"],
+                       swaps_last=cs[0]["swaps_last"])
+            ru.assert_state_equal(st, *[np.concatenate([s[k] for s in snaps], axis=0) for k in range(3)], snaps[0][3],
+                                  counters=cnt, what=f"{nranks}-shard pipeline after {done} iterations")
+        assert st.accepted.sum() > acc0 and st.swaps_total.sum() > swaps0 and st.min_margin > 1e-12
+        print(f"replay_from ok: {nranks} ranks, iterations {start}..{done - 1}")
     elif mode == "timeout":
         # a neighbour that never steps: the waiting rank must fail with an error, not hang the GPU
         _, bounds = rung_partition(4, 2)

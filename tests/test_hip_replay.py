@@ -25,7 +25,12 @@ def _engine(T, W, D, like, box, seed, **kw):
     return HipEnsemble(T, W, D, like, -box, box, seed=seed, **kw)
 
 
-def _run_case(T, W, D, like_kind="dense", box=50.0, seed=77, calls=(1, 3), x_scale=1.0, mh=None, period=None, nsplits=2, **kw):
+def _run_case(T, W, D, like_kind="dense", box=50.0, seed=77, calls=(1, 3), x_scale=1.0, mh=None, period=None, nsplits=2,
+              start_iter=0, set_iter=None, plans=None, **kw):
+    """Replay ``calls`` of hens_step through the oracle.  ``set_iter``: the counter (and, with adaptation on, the adaptation time)
+    moved on the freshly uploaded state first (hens_set_iteration: a resumed chain); ``start_iter``: an unobserved call of that many
+    iterations in front of the replay, whose end state and counters the oracle starts from; ``plans``: a list that receives each
+    replayed call's (first iteration, iterations, round-key window plans inside the call, plans of the state read-back after it)."""
     from eryn_amd.likelihood import GaussianLikelihood, RosenbrockLikelihood
     mu, invcov = pu.gaussian_problem(D, dense=(like_kind == "dense"))
     if like_kind == "dense":
@@ -48,26 +53,41 @@ def _run_case(T, W, D, like_kind="dense", box=50.0, seed=77, calls=(1, 3), x_sca
         eng.set_periodic(period)
     if nsplits != 2:
         eng.set_nsplits(nsplits)
+    if set_iter is not None:
+        eng.set_iteration(set_iter)
+        if tempered and kw.get("adaptive", True):
+            eng.set_adapt_time(set_iter)
+    if start_iter:
+        eng.step(start_iter)
     x, L, P, betas = eng.download()
-    st = ru.OracleState(x, L, P, betas, time=0)
+    st = ru.OracleState(x, L, P, betas, time=0 if (set_iter is None and not start_iter) else eng.counters()["adapt_time"])
+    if start_iter:                     # (the counters the unobserved call left: the oracle's go on from them)
+        c0 = eng.counters()
+        st.accepted, st.swaps_total, st.swaps_last = c0["accepted"].copy(), c0["swaps_total"].copy(), c0["swaps_last"].copy()
+        if mh is not None:
+            st.mh_accepted = eng.mh_counters()["accepted"].copy()
+    acc0, swaps0 = st.accepted.sum() + st.mh_accepted.sum(), st.swaps_total.sum()
     kinds = []
-    done = 0
+    done = start_iter
     for n in calls:
         it0 = eng.iteration()
         eng.step(n)
         eng.synchronize()
+        in_call = eng.timing()["n_plan"] if plans is not None else 0
         kinds += ru.replay(eng, st, it0, n, fn, lo, hi, mh=mh is not None, period=period, nsplits=nsplits,
                            adaptive=kw.get("adaptive", True), stop_adaptation=kw.get("stop_adaptation", -1))
         x, L, P, betas = eng.download()
+        if plans is not None:              # (the timing of a call is reset by the next call only: it goes on counting the read-back)
+            plans.append((it0, n, in_call, eng.timing()["n_plan"] - in_call))
         ru.assert_state_equal(st, x, L, P, betas, counters=eng.counters(),
                               mh_counters=eng.mh_counters() if mh is not None else None,
                               what=f"({T},{W},{D}) {like_kind} after {done + n} iterations")
         done += n
         assert st.min_margin > 1e-12, "a decision sat on the knife edge; pick another seed for this case"
-    acc = st.accepted.sum() + st.mh_accepted.sum()
+    acc = st.accepted.sum() + st.mh_accepted.sum() - acc0
     assert acc > 0, "nothing was ever accepted: the case does not exercise the update"
     if tempered:
-        assert st.swaps_total.sum() > 0
+        assert st.swaps_total.sum() - swaps0 > 0
     eng.close()
     return kinds
 

@@ -463,7 +463,14 @@ def _replay_oracle_class():
     return ReplayRJ
 
 
-def _replay_rj(T, W, nl_max, nl_min, ndata, iters, seed, start_leaves=(2, 1), calls=None, schedule="separate_branches"):
+def _replay_rj(T, W, nl_max, nl_min, ndata, iters, seed, start_leaves=(2, 1), calls=None, schedule="separate_branches",
+               set_iter=None, downloads=True, pulse_amp=(2.5, 3.5), inj_amp=None, start_amp=None, resident=None):
+    """hens_rj_step replayed through the oracle.  ``set_iter``: counter and adaptation time moved on the uploaded state first;
+    ``downloads=False``: no download between calls (the resident templates are then refreshed by the counter only) - the state is
+    read with hens_rj_debug_resident instead, which does not refresh; ``pulse_amp`` / ``inj_amp``: the pulse amplitude box and the
+    injected amplitudes; ``start_amp``: {branch: amplitude per started slot (None: the injected one)} of the starting leaves;
+    ``resident``: a dict that receives, per call end, the largest relative distance of the resident
+    log-likelihoods from the exact float64 template likelihood of the resident coordinates."""
     from oracle import eryn_oracle_rj as orj
     from eryn_amd.moves.tempering import make_ladder
     from eryn_amd.rj import RJEngine, TemplateBranch
@@ -471,10 +478,12 @@ def _replay_rj(T, W, nl_max, nl_min, ndata, iters, seed, start_leaves=(2, 1), ca
     t = np.linspace(-1, 1, ndata)
     gauss_inj = np.array([[3.3, -0.2, 0.1], [2.6, -0.1, 0.1], [3.4, 0.0, 0.1], [2.9, 0.3, 0.1]])
     sine_inj = np.array([[1.3, 10.1, 1.0], [0.8, 4.6, 1.2]])
+    if inj_amp is not None:
+        gauss_inj[:, 0], sine_inj[:, 0] = inj_amp
     sigma = 2.0
     y = sum(a * np.exp(-((t - b) ** 2) / (2 * c ** 2)) for a, b, c in gauss_inj) + \
         sum(a * np.sin(2 * np.pi * b * t + c) for a, b, c in sine_inj) + sigma * rs.randn(ndata)
-    boxes = {"gauss": [(2.5, 3.5), (-1.0, 1.0), (0.01, 0.21)], "sine": [(0.5, 1.5), (1.0, 20.0), (0.0, 2 * np.pi)]}
+    boxes = {"gauss": [pulse_amp, (-1.0, 1.0), (0.01, 0.21)], "sine": [(0.5, 1.5), (1.0, 20.0), (0.0, 2 * np.pi)]}
     kinds = {"gauss": "pulse", "sine": "sine"}
     scale = np.array([[1e-2, 1e-2, 1e-3], [1e-2, 1e-2, 1e-2]])
     names = ["gauss", "sine"]
@@ -487,15 +496,22 @@ def _replay_rj(T, W, nl_max, nl_min, ndata, iters, seed, start_leaves=(2, 1), ca
         for n in range(min(start_leaves[i], nl_max[i])):
             x[k][:, :, n] = inj[k][n % len(inj[k])] + 1e-2 * rs.randn(T, W, 3) * [1, 1, 0.1 if k == "gauss" else 1]
             inds[k][:, :, n] = True
+            if start_amp and k in start_amp and start_amp[k][n] is not None:
+                x[k][:, :, n, 0] += start_amp[k][n] - inj[k][n % len(inj[k])][0]
     betas0 = make_ladder(3 * sum(start_leaves), ntemps=T)
     eng.upload(x, inds, betas=betas0)
     eng.eval_state()
     eng.set_mh_scale(scale)
     eng.set_schedule(schedule)
+    if set_iter is not None:
+        eng.set_iteration(set_iter)
+        eng.set_adapt_time(set_iter)
     x0, inds0, L0, P0, _ = eng.download()
     okind = {"pulse": orj.KIND_PULSE, "sine": orj.KIND_SINE}
     obr = [orj.Branch(k, okind[kinds[k]], boxes[k], nl_max[i], nl_min[i], cov=np.diag(scale[i] ** 2)) for i, k in enumerate(names)]
     o = _replay_oracle_class()(obr, x0, inds0, t, y, sigma, None, None, betas0, schedule=schedule)
+    if set_iter is not None:
+        o.time = set_iter
     assert np.array_equal(o.st.P, P0)
     tol.check_logl(L0, o.st.L, RTOL_L, 'template log-like')
     offsets = {b.name: eng.off[i] for i, b in enumerate(brs)}
@@ -514,8 +530,19 @@ def _replay_rj(T, W, nl_max, nl_min, ndata, iters, seed, start_leaves=(2, 1), ca
             else:
                 nbd[bi] += 1
         done += n
-        x1, inds1, L1, P1, betas1 = eng.download()
         what = f"hens_rj_step vs oracle after {done} iterations"
+        if not downloads or resident is not None:
+            xr, indr, Lr = eng.debug_resident()
+            exact = orj.compute_log_like(xr, indr, o.st.P, obr, t, y, sigma)       # (float64, with the reference's fill values)
+            if resident is not None:
+                resident[eng.iteration()] = tol.max_rel(Lr, exact)
+            for k in names:
+                assert np.array_equal(indr[k], o.st.inds[k]) and np.array_equal(xr[k], o.st.x[k]), f"{what} (resident): {k}"
+            tol.check_logl(Lr, exact, RTOL_L, f"{what}: resident log-likelihood vs the exact one of its coordinates")
+            tol.check_logl(Lr, o.st.L, RTOL_L, f"{what}: resident log-likelihood vs the oracle")
+            if not downloads and done < sum(calls or (iters,)):
+                continue
+        x1, inds1, L1, P1, betas1 = eng.download()
         for k in names:
             assert np.array_equal(inds1[k], o.st.inds[k]), f"{what}: leaf masks of {k}"
             assert np.array_equal(x1[k], o.st.x[k]), f"{what}: coordinates of {k} (dead slots included)"

@@ -61,9 +61,14 @@ def test_plan_structure(T, W):
     assert np.all((d["u_zz"] >= 0) & (d["u_zz"] < 1) & (d["u_acc"] >= 0) & (d["u_acc"] < 1))
 
 
+# iteration-counter edges: the round-key window's (KEY_WINDOW = 1024 iterations; the window is planned again at 1023), the
+# carries of the low Philox word into the high one (2^31: the sign bit of an int, 2^32), a large high word, the top of the range
+EDGES = (1023, 1024, (1 << 31) - 1, 1 << 31, (1 << 32) - 1, 1 << 32, (1 << 40) + (1 << 32) - 3, (1 << 63) - 2)
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("T,W,D,its", [(16, 256, 32, (0, 5)), (64, 128, 8, (3,)), (2, 128, 16, (1,)), (3, 100, 8, (0, 4)),
-                                       (8, 4096, 16, ((1 << 32) + 3,)), (10, 256, 32, (2,)), (3, 96, 16, (0,)),
+@pytest.mark.parametrize("T,W,D,its", [(16, 256, 32, (0, 5) + EDGES), (64, 128, 8, (3,)), (2, 128, 16, (1,)), (3, 100, 8, (0, 4) + EDGES),
+                                       (8, 4096, 16, ((1 << 32) + 3,)), (10, 256, 32, (2,) + EDGES), (3, 96, 16, (0,)),
                                        (24, 64, 8, (7,))])
 def test_device_draws_equal_the_specification(T, W, D, its):
     from eryn_amd.engine import HipEnsemble
