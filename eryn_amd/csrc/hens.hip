@@ -3152,10 +3152,36 @@ int hens_rj_set_model(hens_ctx* ctx, int32_t nbranches, const int32_t* kinds, co
         M.leaf_logp[b] = leaf_logp[b];
     }
     {   // data points on a uniform grid (np.linspace): the sine leaves' rotation scheme of k_rj applies
+        const double eps = 2.220446049250313e-16;
         const double dt = ndata > 1 ? (t[ndata - 1] - t[0]) / (double)(ndata - 1) : 0.0;
         double tmax = 0.0, dev = 0.0;
         for (int i = 0; i < ndata; ++i) { tmax = std::max(tmax, std::fabs(t[i])); dev = std::max(dev, std::fabs(t[i] - (t[0] + (double)i * dt))); }
-        M.t_step64 = (ndata > 64 && dt > 0.0 && dev <= 4.0 * 2.220446049250313e-16 * std::max(tmax, std::fabs(dt))) ? 64.0 * dt : 0.0;
+        bool uniform = ndata > 64 && dt > 0.0 && dev <= 4.0 * eps * std::max(tmax, std::fabs(dt));
+        // ... and the pulses' recurrence is exact enough on it: k_rj evaluates a lane's point i0 + k at t[i0] + k dt, not at t[i0 + k].
+        // A distance d between the two moves a pulse by the relative |t - b| d / c^2 (up to 0.61 d / c of its amplitude), against
+        // the float64 formula's own ~eps (3 + 3 (t - b)^2 / (2 c^2)).  Grids far from 0 (1000 + linspace(0, 1, N): d ~ ulp(1000) =
+        // 6e4 eps h) made that thousands of times the formula's error; they take the per-point form.  The constant 128 is not
+        // derived from an error bound: it is the power of two that keeps config 4's grid on the recurrence (linspace(-1, 1, 500):
+        // d = 1.06 eps, 106 eps c against its narrowest pulse c = 0.01).  With the uniform-grid test alone,
+        // tests/test_hip_template_accuracy.py (4 B bar) measured cases up to 885 eps c_min within 3.6 B, and the first case over
+        // 4 B at 384 eps c_min (a 3-ulp jittered linspace).  The sines' rotation shares t_step64 and goes per point with
+        // the pulses, although its phase error is the size of the float64 formula's own: a narrow pulse box on a fine grid
+        // costs such a model the rotation as well (config 4 keeps both).
+        if (uniform) {
+            double d = 0.0, cmin = INFINITY;
+            for (int i = 0; i < ndata; ++i) {            // d = |(t[i] - t[i0]) - k dt|, the difference and the product kept exact
+                const double a = t[i], b = -t[i & ~7], s = a + b, bv = s - a, e1 = (a - (s - bv)) + (b - bv);
+                const double kk = (double)(i & 7), p = kk * dt, e2 = std::fma(kk, dt, -p);
+                d = std::max(d, std::fabs((s - p) + (e1 - e2)));
+            }
+            for (int b = 0; b < nbranches; ++b)
+                if (kinds[b] == RJ_KIND_PULSE) {
+                    const double clo = lo[b * RJ_ND + 2], chi = hi[b * RJ_ND + 2];
+                    cmin = std::min(cmin, (clo <= 0.0 && chi >= 0.0) ? 0.0 : std::min(std::fabs(clo), std::fabs(chi)));
+                }
+            uniform = d <= 128.0 * eps * cmin;           // (no pulse branch: cmin = inf)
+        }
+        M.t_step64 = uniform ? 64.0 * dt : 0.0;
     }
     M.ind_off = off;
     M.RW = c->D;

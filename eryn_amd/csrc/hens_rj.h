@@ -555,11 +555,15 @@ __global__ __launch_bounds__(RJ_WAVES * 64) __attribute__((amdgpu_waves_per_eu(R
     //          g = exp(-h^2 / c^2) - two exps and two products per further point instead of an exp per point (14 FP64-rate operations each);
     //   sine   a sin(w (t0 + k h) + c): the rotation of (sin, cos) at t0 by the leaf's angle w h - one sincos per lane and leaf.
     // 1 / (2 c^2), g and the rotation are formed once per leaf SLOT, a lane per slot (one division, one exp, one sincos per wave).
-    // Against the direct formulas a pulse's value at the lane's last point carries <= ~1e-14 relative (7 roundings of e, 21 of r and
-    // g, the argument roundings of r_0), a sine's ~7 eps; the log-likelihood moves by ~1e-15 relative (bar 1e-12; the replay tests
-    // run this path).  A pulse narrower than the grid step (|c| < h: e_0 may underflow where a later point does not) takes an exp per
-    // point.  With |c| >= h the exponent of r_0 is below ndata in magnitude: no overflow.  The parity API (tm == nullptr) and
-    // non-uniform grids keep the reference's exp / sin per point, a lane's points 64 apart (below).
+    // Both put the lane's point k at t0 + k h, not at tdata[i0 + k]: the distance d between the two (~ulp(t)) moves a pulse by the
+    // relative |t - b| d / c^2 and a sine's phase by w d.  Beside that, a pulse's value at the lane's last point carries 7 roundings
+    // of e and 21 of r and g, a sine's ~7 eps.  hens_rj_set_model keeps a grid on this path only while d <= 128 eps c_min (the pulse
+    // box's narrowest |c|): config 4's linspace(-1, 1, 500), d = 1.06 eps against c = 0.01, stays; 1000 + linspace(0, 1, N) (d ~
+    // 6e4 eps h) does not.  Observed against exact arithmetic (tests/test_hip_template_accuracy.py: |L - L*| <= 4 B, B the a-priori
+    // error bound of a plain float64 evaluation): <= ~1 B on the cases that stay; 2e3 B on the offset grids before they left.  A
+    // pulse narrower than the grid step (|c| < h: e_0 may underflow where a later point does not) takes an exp per point, at the
+    // same positions.  With |c| >= h the exponent of r_0 is below ndata in magnitude: no overflow.  The parity API (tm == nullptr)
+    // and non-uniform grids keep the reference's exp / sin per point, a lane's points 64 apart (below).
     const bool rot = HAVE_TM && M.t_step64 != 0.0;
     constexpr int NPT = 4, MAXCH = 2;                        // (strided form: template points per lane and chunk; chunks a lane keeps: ndata <= 512)
     constexpr int RJ_PPL = NPT * MAXCH;                      // (uniform grid: consecutive points per lane)

@@ -406,7 +406,13 @@ int hens_debug_permutation(hens_ctx* ctx, int32_t which, int32_t rung, int64_t i
  *   a parity-API move, hens_download_state) and whenever iteration % 64 == 63, so a log-likelihood carries the rounding of at
  *   most 63 iterations of +- updates (observed <= 6e-16 relative against the oracle, bar 1e-12) and a chain is a function of
  *   (State, seed, iteration counter, adaptation time): resumed from a downloaded State in a new context it is the uninterrupted
- *   chain bit for bit.
+ *   chain bit for bit.  On a uniform time grid (every point within 4 eps max|t| of t0 + i dt) the model is evaluated eight
+ *   consecutive points at a time by recurrence (pulses) and rotation (sines), which places point i0 + k at t[i0] + k dt; a grid
+ *   whose points lie farther from those positions than 128 eps times the narrowest pulse width of the prior box is evaluated
+ *   point by point instead (its sines too).  This is an engineering limit, not a bound: at the limit a pulse value's position
+ *   error can reach ~0.61 * 128 eps |a|, many times that point's share of B, the error bound of a plain float64 evaluation.
+ *   Observed on the case matrix of tests/test_hip_template_accuracy.py (offset, wide, tiny and jittered grids): within 1.1 B
+ *   of the exact log-likelihood on every path; before the limit, over 2 000 B on grids far from t = 0.
  * hens_rj_get_counters: accept counts of the birth / death move (hens_get_counters has the in-model move's). */
 int hens_rj_set_model(hens_ctx* ctx, int32_t nbranches, const int32_t* kinds, const int32_t* nleaves_max,
                       const int32_t* nleaves_min, const double* lo, const double* hi, const double* leaf_logp,
