@@ -156,7 +156,7 @@ struct hens_ctx_impl {
         uint32_t sweep = 0;
         long long budget = 0;              // wall-clock ticks a flag wait may take
         // fused iteration of a pipeline rank (k_stretch_fast + k_split1_pt<PIPE>, rows in place): decided at the first
-        // hens_step call from properties every rank shares (pipe_fused_possible), fixed from then on
+        // hens_step call from properties every rank shares (step_path), fixed from then on
         bool fused = false, fused_decided = false;
         int cbl = 0, cbl_shift = 0;        // columns per workgroup of the fused launch: 128 / Tl
         int32_t* ghome = nullptr;          // [2][2][W] home rows of the guests (StretchArgs::ghome)
@@ -268,6 +268,44 @@ int dalloc(hens_ctx_impl* c, Tp** p, size_t n) {
     return HENS_OK;
 }
 
+// ---- environment switches ---------------------------------------------------------------------------------------------------
+// Every switch this file reads, read once per process at first use.  HENS_AQL_STATS and HENS_PIPE_STATS are read
+// per context where they are used.
+#ifdef HENS_DEV_BUILD       // (dev build, tools/devbuild.sh: the dense-Gaussian D = 32 kernels only - seconds instead of minutes)
+constexpr bool DEV_BUILD = true;
+#else
+constexpr bool DEV_BUILD = false;
+#endif
+struct Env {
+    bool no_aql, aql_release, step_events;                       // queue: HIP stream only / keep the release fence / event pair per call
+    bool no_fused, pipe_no_fused, no_iter, no_col, no_fold, pt_no_acc, rj_no_templates;   // A/B knobs of the path decision
+    bool no_xcd, no_tile2, no_tile2_pipe, tile2_pipe_waits, tile2_log, pipe_force_late, debug_noflip;
+    int tile2_force, aql_flush, aql_nobar;                       // aql_flush: -1 unset; aql_nobar, debug_noflip: dev-build probes
+    long iter_max, pipe_inject_cycles;
+    double pipe_timeout_s;                                       // wait budget of the pipeline's flags (default 20 s)
+};
+const Env& env() {
+    static const Env e = [] {
+        auto on = [](const char* name) { return getenv(name) != nullptr; };
+        auto num = [](const char* name, double dflt) { const char* v = getenv(name); return v ? atof(v) : dflt; };
+        auto whole = [](const char* name, long dflt) { const char* v = getenv(name); return v ? atol(v) : dflt; };
+        Env v{};
+        v.no_aql = on("HENS_NO_AQL"); v.aql_release = on("HENS_AQL_RELEASE"); v.step_events = on("HENS_STEP_EVENTS");
+        v.no_fused = on("HENS_NO_FUSED"); v.pipe_no_fused = on("HENS_PIPE_NO_FUSED"); v.no_iter = on("HENS_NO_ITER");
+        v.no_col = on("HENS_NO_COL"); v.no_fold = on("HENS_NO_FOLD"); v.pt_no_acc = on("HENS_PT_NO_ACC");
+        v.rj_no_templates = on("HENS_RJ_NO_TEMPLATES");
+        v.no_xcd = on("HENS_NO_XCD"); v.no_tile2 = on("HENS_NO_TILE2"); v.no_tile2_pipe = on("HENS_NO_TILE2_PIPE");
+        v.tile2_pipe_waits = on("HENS_TILE2_PIPE_WAITS"); v.tile2_log = on("HENS_TILE2_LOG");
+        v.pipe_force_late = on("HENS_PIPE_FORCE_LATE"); v.debug_noflip = on("HENS_DEBUG_NOFLIP");
+        v.tile2_force = (int)whole("HENS_TILE2_FORCE", 0); v.aql_flush = (int)whole("HENS_AQL_FLUSH", -1);
+        v.aql_nobar = (int)whole("HENS_AQL_NOBAR", 0);
+        v.iter_max = whole("HENS_ITER_MAX", 0); v.pipe_inject_cycles = whole("HENS_PIPE_INJECT_CYCLES", 0);
+        v.pipe_timeout_s = num("HENS_PIPE_TIMEOUT_S", 20.0);
+        return v;
+    }();
+    return e;
+}
+
 // ---- the two queues of a context ------------------------------------------------------------------------------------------
 // Stepping launches of hens_step go to the context's AQL queue (hens_aql.h) where they can; everything else uses the HIP stream.
 // The host orders the two: aql_settle before any HIP work (every entry point: enter()), hipStreamSynchronize before the first
@@ -276,8 +314,7 @@ int aql_settle(hens_ctx_impl* c) {
     if (!c || !c->aql_on) return HENS_OK;
     c->hip_dirty = true;                       // (the caller is about to use the HIP stream)
     if (!c->aql.pending) return HENS_OK;
-    static const double tmo = getenv("HENS_PIPE_TIMEOUT_S") ? atof(getenv("HENS_PIPE_TIMEOUT_S")) + 10.0 : 30.0;
-    if (!c->aql.drain(tmo)) {
+    if (!c->aql.drain(env().pipe_timeout_s + 10.0)) {
         c->have_state = false;                 // nothing a later call could read consistently
         return fail(c, HENS_ERR_HIP, "%s", c->aql.err.c_str());
     }
@@ -346,57 +383,29 @@ int launch_by_ptr(hens_ctx_impl* c, const void* fn, const char* what, dim3 grid,
     return HENS_OK;
 }
 
-// the kernel tables of the per-likelihood translation units, by LIKE_*
-const void* ktab_stretch_fast(int like, int mode, int D, bool pipe, bool per) {
-    switch (like) {
-        case LIKE_DENSE: return ktab_stretch_fast_dense(mode, D, pipe, per);
-#ifndef HENS_DEV_BUILD       // (dev build, tools/devbuild.sh: the dense-Gaussian D = 32 kernels only - seconds instead of minutes)
-        case LIKE_DIAG: return ktab_stretch_fast_diag(mode, D, pipe, per);
-        case LIKE_ROSEN: return ktab_stretch_fast_rosen(mode, D, pipe, per);
-#endif
-    }
-    return nullptr;
-}
-const void* ktab_stretch2(int like, int D, bool pipe) {
-    switch (like) {
-        case LIKE_DENSE: return ktab_stretch2_dense(D, pipe);
+// The likelihood kinds with device kernels: hens_config::likelihood_kind -> LIKE_* and the kernel tables of the kind's translation
+// unit (hens_ktable.h).  A kind this build leaves out has no entry.
+struct LikeKernels {
+    int kind, like;
+    const void* (*stretch_fast)(int mode, int D, bool pipe, bool per);
+    const void* (*stretch)(int mode);
+    const void* (*stretch2)(int D, bool pipe);
+    const void* (*split1_pt)(int D, bool per, bool shrt, bool pipe, bool col);
+    const void* (*iter)(int D, bool per);
+};
+#define HENS_LIKE_KERNELS(KIND_, LIKE_, U) {KIND_, LIKE_, ktab_stretch_fast_##U, ktab_stretch_##U, ktab_stretch2_##U, ktab_split1_pt_##U, ktab_iter_##U}
+const LikeKernels* like_kernels(int likelihood_kind) {
+    static const LikeKernels tab[] = {
+        HENS_LIKE_KERNELS(HENS_LIKE_GAUSS_DENSE, LIKE_DENSE, dense),
 #ifndef HENS_DEV_BUILD
-        case LIKE_DIAG: return ktab_stretch2_diag(D, pipe);
-        case LIKE_ROSEN: return ktab_stretch2_rosen(D, pipe);
+        HENS_LIKE_KERNELS(HENS_LIKE_GAUSS_DIAG, LIKE_DIAG, diag),
+        HENS_LIKE_KERNELS(HENS_LIKE_ROSENBROCK, LIKE_ROSEN, rosen),
 #endif
-    }
+    };
+    for (const LikeKernels& k : tab) if (k.kind == likelihood_kind) return &k;
     return nullptr;
 }
-const void* ktab_stretch(int like, int mode) {
-    switch (like) {
-        case LIKE_DENSE: return ktab_stretch_dense(mode);
-#ifndef HENS_DEV_BUILD
-        case LIKE_DIAG: return ktab_stretch_diag(mode);
-        case LIKE_ROSEN: return ktab_stretch_rosen(mode);
-#endif
-    }
-    return nullptr;
-}
-const void* ktab_split1_pt(int like, int D, bool per, bool shrt, bool pipe, bool col) {
-    switch (like) {
-        case LIKE_DENSE: return ktab_split1_pt_dense(D, per, shrt, pipe, col);
-#ifndef HENS_DEV_BUILD
-        case LIKE_DIAG: return ktab_split1_pt_diag(D, per, shrt, pipe, col);
-        case LIKE_ROSEN: return ktab_split1_pt_rosen(D, per, shrt, pipe, col);
-#endif
-    }
-    return nullptr;
-}
-const void* ktab_iter(int like, int D, bool per) {
-    switch (like) {
-        case LIKE_DENSE: return ktab_iter_dense(D, per);
-#ifndef HENS_DEV_BUILD
-        case LIKE_DIAG: return ktab_iter_diag(D, per);
-        case LIKE_ROSEN: return ktab_iter_rosen(D, per);
-#endif
-    }
-    return nullptr;
-}
+#undef HENS_LIKE_KERNELS
 
 // a piece of HIP-stream work in the middle of a call that steps on the AQL queue (packing the state at the head of the first call
 // after another entry point, an adaptation that cannot be folded): the queue drains, the work runs, the stream drains
@@ -453,18 +462,24 @@ size_t fast_lds_bytes(int D, int NW, int like) {
     return ((size_t)TILE * (D + 2) + TILE + (size_t)NW * TILE + 128) * 8 + (4 * (size_t)TILE + 128) * 4 + mf_lds_extra(D, like);
 }
 
-int launch_stretch_like(hens_ctx_impl* c, int like, int mode, StretchArgs a, int ntiles) {
+// Consecutive workgroups go round-robin to the 8 XCDs, each with an L2 of its own that keeps its lines from launch to
+// launch: renumbered, an XCD works on WHOLE rungs (T = 16: two of them), so the rows a rung's half-step gathers - every
+// row of the rung, as own row or as complement - are the rows the same XCD gathered an iteration ago, minus what the
+// second launch (column blocks over all rungs: no such order possible) pushed out in between.  Config 2, same box:
+// 8.45 -> 8.0 us per first launch (7.65 with the second launch's row traffic removed: the ceiling of the idea);
+// 16 x 16384 x 32 27.7 -> 27.3; HENS_NO_XCD=1 is the A/B knob.
+// StretchArgs::xcd_shift of a grid of gx x Tl workgroups (0: numbered as launched)
+int xcd_shift(const hens_ctx_impl* c, int gx) {
+    if (env().no_xcd || (gx & (gx - 1)) != 0 || ((long)gx * c->Tl) % 8 != 0) return 0;
+    int sh = 0;
+    while ((1 << sh) < gx) ++sh;
+    return sh + 1;
+}
+
+int launch_stretch_like(hens_ctx_impl* c, const LikeKernels& lk, int mode, StretchArgs a, int ntiles) {
     const dim3 grid(ntiles, c->Tl);
-    {
-        // Consecutive workgroups go round-robin to the 8 XCDs, each with an L2 of its own that keeps its lines from launch to
-        // launch: renumbered, an XCD works on WHOLE rungs (T = 16: two of them), so the rows a rung's half-step gathers - every
-        // row of the rung, as own row or as complement - are the rows the same XCD gathered an iteration ago, minus what the
-        // second launch (column blocks over all rungs: no such order possible) pushed out in between.  Config 2, same box:
-        // 8.45 -> 8.0 us per first launch (7.65 with the second launch's row traffic removed: the ceiling of the idea);
-        // 16 x 16384 x 32 27.7 -> 27.3; HENS_NO_XCD=1 is the A/B knob.
-        static const bool xcd = getenv("HENS_NO_XCD") == nullptr;
-        if (xcd && (ntiles & (ntiles - 1)) == 0 && ((long)ntiles * c->Tl) % 8 == 0) { int sh = 0; while ((1 << sh) < ntiles) ++sh; a.xcd_shift = sh + 1; }
-    }
+    const int like = lk.like;
+    a.xcd_shift = xcd_shift(c, ntiles);
     if (fast_path(c)) {
         // (periodic parameters: an instantiation of their own - on a pipeline rank too - but not for the evaluation launch, which
         //  proposes nothing)
@@ -475,12 +490,9 @@ int launch_stretch_like(hens_ctx_impl* c, int like, int mode, StretchArgs a, int
             // software-pipelined kernel (hens_tile2.h) - hens_step's in-place first launch on column-ordered records, the adaptation
             // folded the way its lambdas are ported (counts in accumulation rows, ladders of up to 128 rungs).  HENS_NO_TILE2=1: the
             // rounds of k_stretch_fast; HENS_TILE2_FORCE=n: n tiles per workgroup on any grid that divides (tests).
-            static const bool off = getenv("HENS_NO_TILE2") != nullptr;
-            static const int force = getenv("HENS_TILE2_FORCE") ? atoi(getenv("HENS_TILE2_FORCE")) : 0;
             // A rank of the ladder pipeline stepping with the two in-place launches (pipe_fused_iteration) has the kernel's PIPE
             // instantiation, for what that ports of k_stretch_fast<PIPE>: the lead workgroup's adaptation (ad_on == 2, the counts in
             // the mailbox's one row), counts pushed by the publishing wave (cnt_push != 1), no (L, P) publishing, no injection hook.
-            static const bool off_pipe = getenv("HENS_NO_TILE2_PIPE") != nullptr;
             const bool ad_ok = pipe ? (a.ad_on == 0 || (a.ad_on == 2 && a.ad.nblocks <= 8 * a.ad.row_groups && a.ad.row_groups == 1))
                                     : (a.ad_on == 0 || (a.ad_on == 1 && a.ad.nblocks <= 8 * a.ad.row_groups));
             // (cnt_push == 1 - the delayed schedule's push through k_stretch_fast's count-reduction machinery: here the publishing wave's,
@@ -492,29 +504,26 @@ int launch_stretch_like(hens_ctx_impl* c, int like, int mode, StretchArgs a, int
             // k_stretch_fast's rounds of workgroups absorb 6.5 us of it (the last workgroups go to whichever slot frees first;
             // DESIGN 6.1, profiles/r05_pipe_slack_*).  A lone rank, the delayed schedule (the counts it needs arrived a sweep ago) and
             // launches without a pending adaptation have no such wait.  HENS_TILE2_PIPE_WAITS=1 (tests): everywhere.
-            static const bool with_waits = getenv("HENS_TILE2_PIPE_WAITS") != nullptr;
-            const bool wait_ok = with_waits || (a.wmask >> PF_CNT0) == 0ull || a.wtarget_cnt < c->pipe.sweep;      // (counts of an EARLIER sweep: there)
-            const bool pipe_ok = !pipe || (!off_pipe && c->pipe.fused && a.ghome && !a.pub_lp && push_ok && a.inject_c64 <= 0 && wait_ok);
-            const void* k2 = (!off && mode == MODE_STRETCH && pipe_ok && !per && a.inplace && a.col && a.wrec && a.ikeys && a.ns_x == 0 && !a.trace &&
-                              ad_ok) ? ktab_stretch2(like, c->D, pipe) : nullptr;
+            const bool wait_ok = env().tile2_pipe_waits || (a.wmask >> PF_CNT0) == 0ull || a.wtarget_cnt < c->pipe.sweep;      // (counts of an EARLIER sweep: there)
+            const bool pipe_ok = !pipe || (!env().no_tile2_pipe && c->pipe.fused && a.ghome && !a.pub_lp && push_ok && a.inject_c64 <= 0 && wait_ok);
+            const void* k2 = (!env().no_tile2 && mode == MODE_STRETCH && pipe_ok && !per && a.inplace && a.col && a.wrec && a.ikeys && a.ns_x == 0 && !a.trace &&
+                              ad_ok) ? lk.stretch2(c->D, pipe) : nullptr;
             int tp = 0;                  // (the kernel walks TWO tiles per workgroup; grids beyond 1 024 tiles run as rounds of pairs)
-            if (k2 && ntiles % 2 == 0 && (force > 0 || (long)ntiles * c->Tl > 512)) tp = 2;
+            if (k2 && ntiles % 2 == 0 && (env().tile2_force > 0 || (long)ntiles * c->Tl > 512)) tp = 2;
             if (tp > 1 && tile2_lds_bytes(c->D, like) <= 80 * 1024) {
                 const int gx = ntiles / tp;
                 a.tiles_per_wg = tp;
                 if (pipe && a.cnt_push == 1) a.cnt_push = 3;
-                a.xcd_shift = 0;
-                static const bool xcd = getenv("HENS_NO_XCD") == nullptr;
-                if (xcd && (gx & (gx - 1)) == 0 && ((long)gx * c->Tl) % 8 == 0) { int sh = 0; while ((1 << sh) < gx) ++sh; a.xcd_shift = sh + 1; }
-                static const bool say = getenv("HENS_TILE2_LOG") != nullptr;      // (tests: which kernel a context's first launches, and
-                if (say && (c->iter < 3 || (c->iter + 8) % KEY_WINDOW < 16))       //  those around a round-key window's edge, went to)
+                a.xcd_shift = xcd_shift(c, gx);
+                // (HENS_TILE2_LOG, tests: which kernel a context's first launches, and those around a round-key window's edge, went to)
+                if (env().tile2_log && (c->iter < 3 || (c->iter + 8) % KEY_WINDOW < 16))
                     fprintf(stderr, "hens: k_stretch2<pipe=%d> grid %d x %d, ad_on %d, cnt_push %d, iter %llu\n", pipe ? 1 : 0, gx, c->Tl, a.ad_on,
                             a.cnt_push, (unsigned long long)c->iter);
                 return launch_by_ptr(c, k2, "k_stretch2", dim3(gx, c->Tl), NW * 64, tile2_lds_bytes(c->D, like), false,
                                      c->aql_now ? nullptr : c->ext_start, c->ext_stop, a);
             }
         }
-        return launch_by_ptr(c, ktab_stretch_fast(like, mode, c->D, pipe, per), "k_stretch_fast", grid, NW * 64, fast_lds_bytes(c->D, NW, like), false,
+        return launch_by_ptr(c, lk.stretch_fast(mode, c->D, pipe, per), "k_stretch_fast", grid, NW * 64, fast_lds_bytes(c->D, NW, like), false,
                              c->aql_now ? nullptr : c->ext_start, c->ext_stop, a);
     }
     int RS;
@@ -524,7 +533,7 @@ int launch_stretch_like(hens_ctx_impl* c, int like, int mode, StretchArgs a, int
     a.ad_on = 0;
     const bool was_aql = c->aql_now;           // (the generic-width kernel always goes through the HIP stream, as it did)
     c->aql_now = false;
-    const int r = launch_by_ptr(c, ktab_stretch(like, mode), "k_stretch", grid, 256, lds, false, c->ext_start, c->ext_stop, a);
+    const int r = launch_by_ptr(c, lk.stretch(mode), "k_stretch", grid, 256, lds, false, c->ext_start, c->ext_stop, a);
     c->aql_now = was_aql;
     return r;
 }
@@ -545,10 +554,10 @@ int launch_hostlike_eval(hens_ctx_impl* c, StretchArgs a, int ntiles) {
 
 template <int MODE>
 int launch_stretch(hens_ctx_impl* c, const StretchArgs& a, int ntiles) {
+    if (const LikeKernels* lk = like_kernels(c->cfg.likelihood_kind)) return launch_stretch_like(c, *lk, MODE, a, ntiles);
     switch (c->cfg.likelihood_kind) {
-        case HENS_LIKE_GAUSS_DENSE: return launch_stretch_like(c, LIKE_DENSE, MODE, a, ntiles);
-        case HENS_LIKE_GAUSS_DIAG: return launch_stretch_like(c, LIKE_DIAG, MODE, a, ntiles);
-        case HENS_LIKE_ROSENBROCK: return launch_stretch_like(c, LIKE_ROSEN, MODE, a, ntiles);
+        case HENS_LIKE_GAUSS_DENSE: case HENS_LIKE_GAUSS_DIAG: case HENS_LIKE_ROSENBROCK:       // (a kind the dev build leaves out)
+            return fail(c, HENS_ERR_UNSUPPORTED, "k_stretch: no such instantiation in this build (likelihood kind %d)", c->cfg.likelihood_kind);
         case HENS_LIKE_TEMPLATE:
             return fail(c, HENS_ERR_STATE, "leaf-packing context: step with hens_rj_* (the stretch move is not defined on variable-dimension records)");
         case HENS_LIKE_HOST:
@@ -649,6 +658,23 @@ void acc_commit(hens_ctx_impl* c) {
     for (int i = 0; i < 3; ++i) if (c->acc_state[i] == 3) c->acc_state[i] = 1;
 }
 
+// The adaptation's books.  A cascade ran: the record buffers flip and its swap counts wait for the adaptation - `rows` rows at
+// `src` (an accumulation buffer, the mailbox's reduced counts), or swap_part with a row per workgroup (src = nullptr)
+void cascade_ran(hens_ctx_impl* c, const uint32_t* src, int rows, bool adaptive) {
+    c->cur ^= 1;
+    c->adapt_pending = true;
+    c->adapt_pending_adaptive = adaptive;
+    c->adapt_src = src;
+    if (src) c->adapt_nblocks = rows;
+}
+// ... and the launch being built (or k_adapt) takes the pending adaptation; flip: it writes the new ladder into the other buffer
+void adapt_taken(hens_ctx_impl* c, bool flip) {
+    if (c->adapt_pending_adaptive) c->adapt_time += 1;               // tempering.py:596
+    c->adapt_pending = false;
+    c->adapt_src = nullptr;
+    if (flip) c->bcur ^= 1;
+}
+
 // reduce the pending cascade's swap counts and adapt the ladder as a kernel of its own
 void flush_adapt(hens_ctx_impl* c) {
     if (!c->adapt_pending) return;
@@ -658,9 +684,7 @@ void flush_adapt(hens_ctx_impl* c) {
         (void)hipMemsetAsync(c->swap_acc[0], 0, (size_t)3 * SWAP_ACC_ROWS_MAX * c->T * 4, c->stream);
         c->acc_state[0] = c->acc_state[1] = c->acc_state[2] = 0;
     }
-    if (c->adapt_pending_adaptive) c->adapt_time += 1;               // tempering.py:596
-    c->adapt_pending = false;
-    c->adapt_src = nullptr;
+    adapt_taken(c, false);
 }
 
 // how the folded adaptation is shared out: 2 (default) = workgroup (0,0) reduces the counts and adapts once, the
@@ -673,8 +697,7 @@ int fold_mode(const hens_ctx_impl*) {
 
 // can the pending adaptation ride in the next split-0 stretch launch?
 bool can_fold_adapt(const hens_ctx_impl* c) {
-    static const bool off = getenv("HENS_NO_FOLD") != nullptr;
-    if (off || !c->adapt_pending || !fast_path(c) || c->T > 128) return false;
+    if (env().no_fold || !c->adapt_pending || !fast_path(c) || c->T > 128) return false;
     const int nw = fast_nw(c->D);
     const int64_t nblocks = c->adapt_src ? c->adapt_nblocks : pt_blocks(c);
     return nw >= 2 && nblocks * (c->T - 1) <= (int64_t)8 * nw * 64;
@@ -830,9 +853,8 @@ void pipe_wait(hens_ctx_impl* c, std::initializer_list<int> which, bool counts, 
 // dev hook: HENS_PIPE_INJECT_CYCLES=n - the previous sweep's swap-count flags count as raised only n shader cycles after the adapting
 // workgroup of the first launch has started (StretchArgs::inject_c64; tools/pipe_slack.sh measures the slack with it)
 int32_t pipe_inject_c64() {
-    static const long n = getenv("HENS_PIPE_INJECT_CYCLES") ? atol(getenv("HENS_PIPE_INJECT_CYCLES")) : 0;
-    static const bool force_late = getenv("HENS_PIPE_FORCE_LATE") != nullptr;     // (any build: the late path on every adaptation)
-    return n > 0 ? (int32_t)((n + 63) / 64) : (force_late ? -1 : 0);
+    const long n = env().pipe_inject_cycles;
+    return n > 0 ? (int32_t)((n + 63) / 64) : (env().pipe_force_late ? -1 : 0);   // (HENS_PIPE_FORCE_LATE, any build: the late path on every adaptation)
 }
 unsigned long long pipe_prewait_mask(const hens_ctx_impl* c) {
     if (!pipe_active(c) || c->pipe.sweep == 0 || c->pipe.staged) return 0ull;
@@ -956,6 +978,26 @@ hipEvent_t new_event(hens_ctx_impl* c) {
     c->evpool.push_back(e);
     return e;
 }
+// Per-launch timing of a hens_step call on the HIP stream (hens_set_profiling): an event pair per launch and the kind of launch it
+// brackets - 0 stretch / MH launch, 1 cascade (a pipeline rank: its sweep), 2 second half-step + cascade, 3 k_iter
+struct LaunchTimer {
+    std::vector<hipEvent_t> evs;
+    std::vector<char> kind;
+};
+void time_launch(hens_ctx_impl* c, LaunchTimer* tm, int kind, hipEvent_t& e0, hipEvent_t& e1) {
+    if (!tm) return;
+    e0 = new_event(c); e1 = new_event(c);
+    tm->evs.push_back(e0); tm->evs.push_back(e1);
+    tm->kind.push_back((char)kind);
+}
+// a stretch / MH launch; timed, the dispatch packet records its own begin / end (ext_start / ext_stop, launch_stretch_like)
+template <int MODE>
+int launch_stretch_timed(hens_ctx_impl* c, const StretchArgs& a, int ntiles, LaunchTimer* tm) {
+    time_launch(c, tm, 0, c->ext_start, c->ext_stop);
+    const int r = launch_stretch<MODE>(c, a, ntiles);
+    c->ext_start = c->ext_stop = nullptr;
+    return r;
+}
 
 // fused pipeline iteration: what the head of the next iteration's first launch would say, as a kernel of its own (end of a
 // hens_step call; an adaptation that cannot be folded) - the previous sweep's pushes are complete (cold neighbour's
@@ -1048,10 +1090,7 @@ void attach_iteration_head(hens_ctx_impl* c, StretchArgs& a) {
         a.ad = adapt_args(c, c->adapt_pending_adaptive, c->betas[c->bcur], c->betas[c->bcur ^ 1]);
         if (acc) acc_fold(c, a.ad);
         a.betas = c->betas[c->bcur];
-        if (c->adapt_pending_adaptive) c->adapt_time += 1;
-        c->adapt_pending = false;
-        c->adapt_src = nullptr;
-        c->bcur ^= 1;
+        adapt_taken(c, true);
     } else {
         if (pipe_active(c) && !c->pipe.staged && c->adapt_src && c->pipe.nranks > 1)
             pipe_wait(c, {}, true, c->pipe.due_sweep + 1);   // every rank's counts first
@@ -1079,7 +1118,7 @@ void attach_publish(hens_ctx_impl* c, StretchArgs& a, bool final, int ntiles) {
 
 // both halves of one Philox iteration from draw buffer `which`, batch slot `ib`
 // inplace (hens_step on one GPU, compile-time row widths): rows are updated where they are, see StretchArgs::inplace
-int stretch_pair(hens_ctx_impl* c, int which, int ib, std::vector<hipEvent_t>* evs, bool inplace = false) {
+int stretch_pair(hens_ctx_impl* c, int which, int ib, LaunchTimer* tm, bool inplace = false) {
     const int Tl = c->Tl, W = c->W;
     for (int split = 0; split < 2; ++split) {
         StretchArgs a = base_args(c);
@@ -1090,14 +1129,7 @@ int stretch_pair(hens_ctx_impl* c, int which, int ib, std::vector<hipEvent_t>* e
         if (split == 0) attach_iteration_head(c, a);
         const int Ns = split == 0 ? c->N0 : W - c->N0;
         attach_publish(c, a, split == 1, (Ns + TILE - 1) / TILE);
-        if (evs) {           // per-kernel timing: the dispatch packet's own begin/end timestamps
-            c->ext_start = new_event(c);
-            c->ext_stop = new_event(c);
-            evs->push_back(c->ext_start);
-            evs->push_back(c->ext_stop);
-        }
-        const int r = launch_stretch<MODE_STRETCH>(c, a, (Ns + TILE - 1) / TILE);
-        c->ext_start = c->ext_stop = nullptr;
+        const int r = launch_stretch_timed<MODE_STRETCH>(c, a, (Ns + TILE - 1) / TILE, tm);
         if (r) return r;
     }
     if (!inplace) c->parity ^= 1;                  // (in place: the free half of the pool stays the free one)
@@ -1108,7 +1140,7 @@ int stretch_pair(hens_ctx_impl* c, int which, int ib, std::vector<hipEvent_t>* e
 
 // one Philox iteration of a red-blue move of nsplits > 2 sets: plan (labels, order, draws of every position), then set after set
 // with the copying launches - each against the others' CURRENT rows (red_blue.py:148-323; the parity API's launches)
-int stretch_sets(hens_ctx_impl* c, std::vector<hipEvent_t>* evs) {
+int stretch_sets(hens_ctx_impl* c, LaunchTimer* tm) {
     const int Tl = c->Tl, W = c->W, NSP = c->nsplits;
     c->seg_off.assign((size_t)NSP + 1, 0);
     for (int k = 0; k < NSP; ++k) c->seg_off[k + 1] = c->seg_off[k] + (W - k + NSP - 1) / NSP;
@@ -1127,12 +1159,7 @@ int stretch_sets(hens_ctx_impl* c, std::vector<hipEvent_t>* evs) {
         a.ns_x = c->seg_off[split + 1] - c->seg_off[split]; a.soff_x = c->seg_off[split];
         a.home_off = c->parity * Tl * W;
         if (split == 0) attach_iteration_head(c, a);
-        if (evs) {
-            c->ext_start = new_event(c); c->ext_stop = new_event(c);
-            evs->push_back(c->ext_start); evs->push_back(c->ext_stop);
-        }
-        const int r = launch_stretch<MODE_STRETCH>(c, a, (a.ns_x + TILE - 1) / TILE);
-        c->ext_start = c->ext_stop = nullptr;
+        const int r = launch_stretch_timed<MODE_STRETCH>(c, a, (a.ns_x + TILE - 1) / TILE, tm);
         if (r) return r;
     }
     c->parity ^= 1;
@@ -1140,42 +1167,103 @@ int stretch_sets(hens_ctx_impl* c, std::vector<hipEvent_t>* evs) {
     return HENS_OK;
 }
 
-// ---- fused second half-step + cascade (k_split1_pt) ----------------------------------------------------------
-// whole ladder resident, tempered, block-balanced labels, compile-time row width, device likelihood
-bool fused_ok(const hens_ctx_impl* c) {
-    static const bool off = getenv("HENS_NO_FUSED") != nullptr;             // A/B knob: three launches per iteration
-    return !off && c->label_cb > 0 && has_pt(c) && c->Tl == c->T && !c->pipe.on && fast_path(c) && c->nsplits == 2 &&
-           c->cfg.likelihood_kind != HENS_LIKE_HOST;
+// ---- which launches one iteration of a hens_step call is ------------------------------------------------------------------------
+enum class Iteration {
+    COPYING,         // k_stretch_fast / k_stretch x 2 on the by-field arrays, then k_pt_cascade
+    SETS,            // hens_set_nsplits > 2: a copying launch per set (stretch_sets), then k_pt_cascade
+    INPLACE2,        // walker records: k_stretch_fast / k_stretch2 (first half-step, rows in place), then k_split1_pt
+    ONE_LAUNCH,      // walker records: k_iter
+    PIPE_COPYING,    // a rank of the ladder pipeline: the copying launches, then the sweep's kernels (pipe_sweep)
+    PIPE_INPLACE2,   // ... with the two in-place launches (k_split1_pt<PIPE>)
+};
+struct StepPath {
+    Iteration it = Iteration::COPYING;
+    bool col = false;        // the records are PACKED in column order (c->colmode: the order they are in)
+    bool records() const { return it == Iteration::INPLACE2 || it == Iteration::ONE_LAUNCH || it == Iteration::PIPE_INPLACE2; }
+    bool piped() const { return it == Iteration::PIPE_COPYING || it == Iteration::PIPE_INPLACE2; }
+    // draws in registers: the launches need the rungs' round keys (iteration_keys) and no draw plan
+    bool keys_only() const { return it == Iteration::INPLACE2 || it == Iteration::PIPE_INPLACE2; }
+    // launches that can go to the context's AQL queue
+    bool aql_able() const { return it == Iteration::INPLACE2 || it == Iteration::ONE_LAUNCH; }
+};
+
+// The path of one hens_step call, decided once at its head; everything downstream reads the verdict.  Nothing it depends on
+// changes inside a call: the shape, the likelihood kind, label_cb and db[0].rec1 are fixed by hens_create, the pipeline by
+// hens_pipe_*, nsplits / period / mh_kind by entry points of their own between calls, the switches once per process.
+StepPath step_path(hens_ctx_impl* c) {
+    const Env& e = env();
+    const int kind = c->cfg.likelihood_kind;
+    // walker records + k_split1_pt: tempered, block-balanced labels, compile-time row width, device likelihood
+    // (HENS_NO_FUSED=1, A/B knob: the copying launches - three per iteration)
+    const bool rec_shape = !e.no_fused && c->label_cb > 0 && has_pt(c) && fast_path(c) && kind != HENS_LIKE_HOST;
+    // Column-ordered records (StretchArgs::col): the two-launch iteration on full tiles - every record shape that does not take
+    // the single launch, has no periodic parameters and no MH move in the mix (those launches address the records by slot).
+    // Round 3, config 2: both launches' index phases were a round key -> permutation -> scattered record load chain
+    // (4 600 / 4 700 cycles to the first barrier); in column order the records load coalesced at the head of the launch and the
+    // first launch looks rows up in an LDS copy of its rung's table.  HENS_NO_COL=1, A/B knob: records by slot.
+    const bool col_able = !e.no_col && !c->period && c->mh_kind < 0 && (c->W & 3) == 0;
+    StepPath p;
+    if (pipe_active(c)) {
+        // The two in-place launches on a rank of the ladder pipeline (round 3).  Round 2's pipeline rank ran round 1's three copying
+        // launches (stretch x 2 -> k_pipe_walk): a config-3 shard stepped at 89 us per iteration as a rank against 59 us as a ladder
+        // of its own.  Now: k_stretch_fast (first half-step, in place, draws in registers, carries the adaptation and the waits for
+        // the previous sweep's arrivals) -> k_split1_pt<PIPE> (second half-step + the rank's segment of the cascade + both
+        // boundaries, hand-offs per column block).  Decided at the rank's first call from what every rank shares - a function of
+        // (T, W, D, nranks, likelihood kind) only - and fixed from then on.  HENS_PIPE_NO_FUSED=1: A/B knob.
+        hens_ctx_impl::Pipe& pp = c->pipe;
+        if (!pp.fused_decided) {
+            auto shards_fit = [&] {                // equal shards of 128 / Tl columns x Tl rungs = one full tile
+                const int Tl = c->Tl;
+                if (c->T % pp.nranks != 0 || Tl != c->T / pp.nranks || c->cfg.rung_begin != pp.rank * Tl) return false;
+                if (Tl < 2 || Tl > 64 || (Tl & (Tl - 1)) != 0) return false;
+                const int cbl = 2 * TILE / Tl;
+                return cbl >= c->label_cb && cbl % c->label_cb == 0 && c->W % cbl == 0;
+            };
+            pp.fused = rec_shape && !e.pipe_no_fused && !pp.staged && kind != HENS_LIKE_TEMPLATE && shards_fit();
+            pp.fused_decided = true;
+        }
+        p.it = pp.fused ? Iteration::PIPE_INPLACE2 : Iteration::PIPE_COPYING;
+        p.col = pp.fused && col_able;              // (every rank reaches the same verdict)
+        return p;
+    }
+    if (!rec_shape || c->Tl != c->T || c->pipe.on || c->nsplits != 2) {      // (records: the whole ladder resident, two sets)
+        p.it = c->nsplits > 2 ? Iteration::SETS : Iteration::COPYING;
+        return p;
+    }
+    // One launch per iteration (k_iter, hens_iter.h): the record shapes that leave the chip half empty (latency-bound: see
+    // hens_iter.h), row widths with three tiles in half a CU's LDS.  Measured on one box (tools/iter_sweep.sh, us per iteration,
+    // one launch vs two):
+    //   4 x 4096 x 32  14.7 / 18.2     8 x 4096 x 32  15.5 / 18.8    16 x 2048 x 32  15.6 / 18.3    32 x 1024 x 32  17.1 / 20.1
+    //   16 x 4096 x 16  16.4 / 19.7   16 x 4096 x 32 (config 2)  22.4 / 22.5     8 x 8192 x 32  22.0 / 22.7
+    //   32 x 2048 x 32  23.9 / 23.8   16 x 6144 x 32  33.5 / 34.5
+    // Up to one workgroup per CU at D = 32 (two at D = 16, whose workgroups are half as heavy) the single launch wins
+    // 15-19 %; with two D = 32 workgroups per CU its extra gathers and likelihoods cost what the second launch did, and the
+    // profiled two-launch path stays.  (Round 5's last library, same columns: 4 x 4096 x 32 11.9 / 13.1, 8 x 4096 x 32 13.3 / 13.8,
+    // 16 x 2048 x 32 14.0 / 14.6, 32 x 1024 x 32 15.7 / 16.5, 16 x 4096 x 16 15.2 / 15.6; 8 x 8192 x 32 19.3 / 16.4 - the rule stands, the margin
+    // is 3-12 % now.)  The grid is W / cb workgroups (short tiles of ladders that do not divide 128 included:
+    // 10 x 2048 x 32 15.2 / 18.5, 6 x 4096 x 32 15.0 / 18.1).  HENS_NO_ITER=1, A/B knob: two launches per iteration;
+    // HENS_ITER_MAX=n: workgroups per CU allowed.
+    const long nwg = c->W / c->label_cb, per_cu = e.iter_max ? e.iter_max : (c->D == 16 ? 2 : 1);
+    const bool one = !e.no_iter && (c->D == 16 || c->D == 32) && c->T <= 128 && c->W <= 32768 && c->db[0].rec1 && nwg <= per_cu * (long)c->num_cu;
+    p.it = one ? Iteration::ONE_LAUNCH : Iteration::INPLACE2;
+    p.col = !one && col_able && c->T * c->label_cb == 2 * TILE;       // (full tiles: 128 / T columns x T rungs)
+    return p;
 }
 
-int launch_fused_like(hens_ctx_impl* c, int like, const FusedArgs& f, hipEvent_t e0, hipEvent_t e1, bool pipe = false, bool col = false) {
-    const dim3 grid(pipe ? c->W / c->pipe.cbl : c->W / c->label_cb);
-    const int NW = fast_nw(c->D);
-    // the instantiation: column order knows neither periodic parameters nor short tiles, a pipeline rank no short tiles (their
-    // callers refuse)
-    const bool plain = !pipe && !col, per = !col && f.period, shrt = plain && c->T * c->label_cb != 2 * TILE;
-    // (the iteration's last launch: the call's last one carries the completion signal)
-    return launch_by_ptr(c, ktab_split1_pt(like, c->D, per, shrt, pipe, col), "k_split1_pt", grid, NW * 64, fused_lds_bytes(c->D, NW, like, pipe),
-                         c->aql_last, e0, e1, f);
-}
-
-// one Philox iteration in two launches: first half-step (k_stretch_fast, carrying the pending ladder adaptation), then
-// second half-step + cascade + swap counts (k_split1_pt)
-// the state as one record per walker (k_split1_pt, k_stretch_fast with StretchArgs::wrec) <-> by-field arrays (everything else)
-const uint32_t* iteration_keys(hens_ctx_impl* c);
-bool col_ok(const hens_ctx_impl* c);
 // The stepping launches of one GPU (k_stretch_fast + k_split1_pt in record mode, k_iter) go out WITHOUT a release fence (hens_aql.h: norel_next): everything a
 // later launch reads they store write-through, and their waves end behind the stores' acknowledgements (hens_kernels.h: wt_store,
 // launch_end_wait).  HENS_AQL_RELEASE=1 keeps the fence (A/B knob).
 bool norel_ok(const hens_ctx_impl* c) {
-    static const bool keep = getenv("HENS_AQL_RELEASE") != nullptr;
-    return ROWSTORE_WRITE_THROUGH && !keep && c->aql_now && !c->pipe.on;      // (rows must leave write-through: hens_kernels.h)
+    return ROWSTORE_WRITE_THROUGH && !env().aql_release && c->aql_now && !c->pipe.on;      // (rows must leave write-through: hens_kernels.h)
 }
-bool pipe_col_ok(const hens_ctx_impl* c);
-void state_to_records(hens_ctx_impl* c) {
+
+// the state as one record per walker (k_split1_pt, k_iter, k_stretch_fast with StretchArgs::wrec) <-> by-field arrays (everything
+// else); col: StepPath::col of the call that packs
+const uint32_t* iteration_keys(hens_ctx_impl* c);
+void state_to_records(hens_ctx_impl* c, bool col) {
     if (c->packed) return;
     const int64_t n = (int64_t)c->Tl * c->W;
-    if (col_ok(c) || pipe_col_ok(c)) {
+    if (col) {
         // column order of iteration c->iter, into the OTHER buffers (the compact row table is permuted too: not in place)
         // (a pipeline rank: its Tl rungs, whose round keys start at rung_begin)
         const uint32_t* keys = iteration_keys(c) + (size_t)c->cfg.rung_begin * 8;
@@ -1233,10 +1321,71 @@ const uint32_t* iteration_keys(hens_ctx_impl* c) {
     return c->ikeys + (size_t)(c->iter - c->ikeys_iter0) * c->T * 8;
 }
 
-int fused_iteration(hens_ctx_impl* c, std::vector<hipEvent_t>* evs) {
-    const int T = c->T, W = c->W;
+// ---- the launches on walker records -----------------------------------------------------------------------------------------------
+// the in-place first launch (k_stretch_fast / k_stretch2): first half-step, draws in registers (stretch_draws_at) from the
+// iteration's round keys; the caller attaches the iteration's head
+StretchArgs inplace_first_args(hens_ctx_impl* c, const uint32_t* keys) {
+    StretchArgs a = base_args(c);
+    a.wrec = c->wrec[c->cur];
+    a.inplace = 1;
+    a.ikeys = keys;
+    a.iseed = c->cfg.seed; a.iiter = c->iter; a.ia = c->cfg.a;
+    a.idx_bits = c->idx_bits; a.hb_shift = c->label_cb_shift - 1; a.ndim_active = dim_active(c);
+    a.split = 0;
+    a.home_off = c->parity * c->Tl * c->W;
+    // (column-ordered records.  Round 3 also built the rung's row table staged in LDS by LDS-DMA: verified, measured at config 2
+    //  on one box at 19.1 us per iteration against 18.8 without - 8 MB of table fills per launch and a wait for every load of
+    //  the wave in front of the first barrier cost more than the L2 hits they replace - and removed in round 4.)
+    a.col = c->colmode ? 1 : 0;
+    return a;
+}
+// what FusedArgs (k_split1_pt) and IterArgs (k_iter) have in common
+template <class Args>
+void record_launch_args(hens_ctx_impl* c, Args& f) {
+    f.pool = c->pool;
+    f.wrec = c->wrec[c->cur]; f.wrecnew = c->wrec[c->cur ^ 1];
+    f.loc = c->loc[c->cur]; f.locnew = c->loc[c->cur ^ 1];
+    f.betas = c->betas[c->bcur];
+    f.accepted = c->accepted;
+    f.lo = c->lo; f.hi = c->hi; f.mu = c->mu; f.prec = c->prec; f.prec_sym = c->prec_sym;
+    f.period = c->period;
+    f.flags = c->flags;
+    f.trace = (c->tracing && c->trace_fused) ? c->d_trace : nullptr;
+    f.logp_in = c->logp_in; f.fill = c->cfg.fill_value; f.rosen_a = c->rosen_a; f.rosen_b = c->rosen_b;
+    f.iter = c->iter; f.seed = c->cfg.seed;
+    f.T = c->T; f.W = c->W; f.idx_bits = c->idx_bits;
+    f.cb = c->label_cb; f.cb_shift = c->label_cb_shift;
+}
+// the second launch (k_split1_pt): second half-step + cascade + swap counts; the caller adds where the counts go (and, on a
+// pipeline rank, the boundaries)
+FusedArgs second_launch_args(hens_ctx_impl* c, const uint32_t* keys) {
+    FusedArgs f{};
+    record_launch_args(c, f);
+    f.keys = keys;
+    f.keys_next = keys + (size_t)c->T * 8;                             // (inside the window: iteration_keys)
+    f.a = c->cfg.a; f.ndim_active = dim_active(c);
+    return f;
+}
+int launch_second(hens_ctx_impl* c, const FusedArgs& f, LaunchTimer* tm, bool pipe) {
+    const LikeKernels* lk = like_kernels(c->cfg.likelihood_kind);
+    if (!lk) return fail(c, HENS_ERR_UNSUPPORTED, "no fused kernel for likelihood kind %d", c->cfg.likelihood_kind);
+    const dim3 grid(pipe ? c->W / c->pipe.cbl : c->W / c->label_cb);
+    const int NW = fast_nw(c->D);
+    // the instantiation: column order knows neither periodic parameters nor short tiles, a pipeline rank no short tiles (step_path
+    // refuses)
+    const bool col = c->colmode, plain = !pipe && !col, per = !col && f.period, shrt = plain && c->T * c->label_cb != 2 * TILE;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    time_launch(c, tm, 2, e0, e1);
+    // (the iteration's last launch: the call's last one carries the completion signal)
+    return launch_by_ptr(c, lk->split1_pt(c->D, per, shrt, pipe, col), "k_split1_pt", grid, NW * 64, fused_lds_bytes(c->D, NW, lk->like, pipe),
+                         c->aql_last, e0, e1, f);
+}
+
+// one Philox iteration in two launches: first half-step (k_stretch_fast, carrying the pending ladder adaptation), then
+// second half-step + cascade + swap counts (k_split1_pt)
+int fused_iteration(hens_ctx_impl* c, const StepPath& path, LaunchTimer* tm) {
     if (!c->packed) {                        // (the pack kernel - first call after another entry point - runs on the HIP stream)
-        const int r = hip_interlude(c, [&] { state_to_records(c); });
+        const int r = hip_interlude(c, [&] { state_to_records(c, path.col); });
         if (r) return r;
     }
     if (c->adapt_pending && !can_fold_adapt(c)) {
@@ -1248,170 +1397,61 @@ int fused_iteration(hens_ctx_impl* c, std::vector<hipEvent_t>* evs) {
     }
     const uint32_t* keys = iteration_keys(c);
     if (c->aql_failed) { c->aql_failed = false; return HENS_ERR_HIP; }
+    // DEV PROBES (dev builds, timing only), HENS_AQL_NOBAR: bit 1 - the first launch's packet without the barrier bit; bit 0 - the
+    // second launch's (the chain is WRONG): what would it buy at most - its workgroups start as the first launch's retire, with
+    // no dependency at all (round 5, VERDICT r4 #2: the ceiling of "overlap launch 2's prologue with launch 1's drain" before
+    // anyone builds the arrival counters)
+    const int nobar = DEV_BUILD && c->aql_now ? env().aql_nobar : 0;
     {
-        StretchArgs a = base_args(c);
-        a.wrec = c->wrec[c->cur];
-        a.inplace = 1;
-        a.ikeys = keys;                                                // draws in registers (stretch_draws_at)
-        a.iseed = c->cfg.seed; a.iiter = c->iter; a.ia = c->cfg.a;
-        a.idx_bits = c->idx_bits; a.hb_shift = c->label_cb_shift - 1; a.ndim_active = dim_active(c);
-        a.split = 0;
-        a.home_off = c->parity * T * W;
-        // (column-ordered records.  Round 3 also built the rung's row table staged in LDS by LDS-DMA: verified, measured at config 2
-        //  on one box at 19.1 us per iteration against 18.8 without - 8 MB of table fills per launch and a wait for every load of
-        //  the wave in front of the first barrier cost more than the L2 hits they replace - and removed in round 4.)
-        if (c->colmode) a.col = 1;
+        StretchArgs a = inplace_first_args(c, keys);
         attach_iteration_head(c, a);
-        if (evs) {
-            c->ext_start = new_event(c);
-            c->ext_stop = new_event(c);
-            evs->push_back(c->ext_start);
-            evs->push_back(c->ext_stop);
-        }
-#ifdef HENS_DEV_BUILD
-        {   // (DEV PROBE, timing only: the first launch's packet without the barrier bit too - HENS_AQL_NOBAR bit 1)
-            static const int nobar = getenv("HENS_AQL_NOBAR") ? atoi(getenv("HENS_AQL_NOBAR")) : 0;
-            if (c->aql_now && (nobar & 2) && c->aql.windex != c->aql.call_first) c->aql.nobar_next = true;
-        }
-#endif
+        if ((nobar & 2) && c->aql.windex != c->aql.call_first) c->aql.nobar_next = true;
         c->aql.norel_next = norel_ok(c);
         c->aql.prof_kind = 0;
         a.norel = c->aql.norel_next ? 1 : 0;
-        const int r = launch_stretch<MODE_STRETCH>(c, a, (c->N0 + TILE - 1) / TILE);
-        c->ext_start = c->ext_stop = nullptr;
+        const int r = launch_stretch_timed<MODE_STRETCH>(c, a, (c->N0 + TILE - 1) / TILE, tm);
         if (r) return r;
     }
-    FusedArgs f{};
-    f.pool = c->pool;
-    f.wrec = c->wrec[c->cur]; f.wrecnew = c->wrec[c->cur ^ 1];
-    f.loc = c->loc[c->cur]; f.locnew = c->loc[c->cur ^ 1];
-    f.betas = c->betas[c->bcur];
-    f.keys = keys;
-    f.keys_next = keys + (size_t)T * 8;                                // (inside the window: iteration_keys)
-    f.a = c->cfg.a; f.ndim_active = dim_active(c);
-    f.accepted = c->accepted;
+    FusedArgs f = second_launch_args(c, keys);
     f.swap_acc = acc_take(c);
     f.acc_rows = 8 * acc_row_groups(c->T);
     acc_commit(c);
-    f.lo = c->lo; f.hi = c->hi; f.mu = c->mu; f.prec = c->prec; f.prec_sym = c->prec_sym;
-    f.period = c->period;
-    f.flags = c->flags;
-    f.trace = (c->tracing && c->trace_fused) ? c->d_trace : nullptr;
-    f.logp_in = c->logp_in; f.fill = c->cfg.fill_value; f.rosen_a = c->rosen_a; f.rosen_b = c->rosen_b;
-    f.iter = c->iter; f.seed = c->cfg.seed;
-    f.T = T; f.W = W; f.idx_bits = c->idx_bits;
-    f.cb = c->label_cb; f.cb_shift = c->label_cb_shift;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (evs) {
-        e0 = new_event(c); e1 = new_event(c);
-        evs->push_back(e0); evs->push_back(e1);
-    }
-#ifdef HENS_DEV_BUILD
-    {   // DEV PROBE, timing only (the chain is WRONG): what would the second launch's packet without the barrier bit buy at most -
-        // its workgroups start as the first launch's retire, with no dependency at all (round 5, VERDICT r4 #2: the ceiling of
-        // "overlap launch 2's prologue with launch 1's drain" before anyone builds the arrival counters)
-        static const int nobar = getenv("HENS_AQL_NOBAR") ? atoi(getenv("HENS_AQL_NOBAR")) : 0;
-        if (c->aql_now && (nobar & 1)) c->aql.nobar_next = true;
-    }
-#endif
+    if (nobar & 1) c->aql.nobar_next = true;
     c->aql.norel_next = norel_ok(c);
     c->aql.prof_kind = 2;
     f.norel = c->aql.norel_next ? 1 : 0;
-    int r;
-    switch (c->cfg.likelihood_kind) {
-        case HENS_LIKE_GAUSS_DENSE: r = launch_fused_like(c, LIKE_DENSE, f, e0, e1, false, c->colmode); break;
-#ifndef HENS_DEV_BUILD
-        case HENS_LIKE_GAUSS_DIAG: r = launch_fused_like(c, LIKE_DIAG, f, e0, e1, false, c->colmode); break;
-        case HENS_LIKE_ROSENBROCK: r = launch_fused_like(c, LIKE_ROSEN, f, e0, e1, false, c->colmode); break;
-#endif
-        default: r = fail(c, HENS_ERR_UNSUPPORTED, "no fused kernel for likelihood kind %d", c->cfg.likelihood_kind);
-    }
+    const int r = launch_second(c, f, tm, false);
     if (r) return r;
     // (no change of c->parity: the rows were updated in place, the half of the pool that the copying launches of the
     // other paths write next is still the free one)
     c->num_proposals += 1;
-#ifdef HENS_DEV_BUILD
-    static const bool noflip = getenv("HENS_DEBUG_NOFLIP") != nullptr;    // timing experiments with cut kernels (HENS_CUT_F)
-    if (!noflip)
-#endif
-    c->cur ^= 1;
-    c->adapt_pending = true;
-    c->adapt_pending_adaptive = c->cfg.adaptive != 0;
-    c->adapt_src = f.swap_acc;                     // acc_rows rows (see hens_ctx_impl::swap_acc)
-    c->adapt_nblocks = f.acc_rows;
+    cascade_ran(c, f.swap_acc, f.acc_rows, c->cfg.adaptive != 0);      // acc_rows rows (see hens_ctx_impl::swap_acc)
+    if (DEV_BUILD && env().debug_noflip) c->cur ^= 1;     // HENS_DEBUG_NOFLIP: timing experiments with cut kernels (HENS_CUT_F) - no flip
     return HENS_OK;
 }
 
-// ---- the same two launches on a rank of the ladder pipeline (round 3) -----------------------------------------------------------
-// Round 2's pipeline rank ran round 1's three copying launches (stretch x 2 -> k_pipe_walk): a config-3 shard stepped at 89 us
-// per iteration as a rank against 59 us as a ladder of its own.  Now: k_stretch_fast (first half-step, in place, draws in
-// registers, carries the adaptation and the waits for the previous sweep's arrivals) -> k_split1_pt<PIPE> (second half-step
-// + the rank's segment of the cascade + both boundaries, hand-offs per column block).  What every rank must agree on is a
-// function of (T, W, D, nranks, likelihood kind, move mix) only.
-bool pipe_fused_possible(const hens_ctx_impl* c) {
-    static const bool off = getenv("HENS_NO_FUSED") != nullptr || getenv("HENS_PIPE_NO_FUSED") != nullptr;   // A/B knob
-    if (off || !pipe_active(c) || c->pipe.staged || c->label_cb <= 0 || !has_pt(c) || !fast_path(c)) return false;
-    if (c->cfg.likelihood_kind == HENS_LIKE_HOST || c->cfg.likelihood_kind == HENS_LIKE_TEMPLATE) return false;
-    const int Tl = c->Tl;
-    if (c->T % c->pipe.nranks != 0 || Tl != c->T / c->pipe.nranks || c->cfg.rung_begin != c->pipe.rank * Tl) return false;   // equal shards
-    if (Tl < 2 || Tl > 64 || (Tl & (Tl - 1)) != 0) return false;                  // 128 / Tl columns x Tl rungs = one full tile
-    const int cbl = 2 * TILE / Tl;
-    return cbl >= c->label_cb && cbl % c->label_cb == 0 && c->W % cbl == 0;
-}
-
+// the same two launches on a rank of the ladder pipeline
 // mh: the iteration's move is the full-ensemble Metropolis-Hastings launch (in place, in the records; every guest goes home
 // in it), and the second launch is the cascade alone (FusedArgs::no_move)
-int mh_iteration(hens_ctx_impl* c, std::vector<hipEvent_t>* evs, bool inplace = false);
-int pipe_fused_iteration(hens_ctx_impl* c, std::vector<hipEvent_t>* evs, bool mh = false) {
-    const int T = c->T, W = c->W, Tl = c->Tl;
-    state_to_records(c);
+int mh_iteration(hens_ctx_impl* c, LaunchTimer* tm, bool inplace = false);
+int pipe_fused_iteration(hens_ctx_impl* c, const StepPath& path, LaunchTimer* tm, bool mh) {
+    state_to_records(c, path.col);
     const uint32_t* keys = iteration_keys(c);
     if (mh) {
-        const int r = mh_iteration(c, evs, true);
+        const int r = mh_iteration(c, tm, true);
         if (r) return r;
     } else {
-        StretchArgs a = base_args(c);
-        a.wrec = c->wrec[c->cur];
-        a.inplace = 1;
-        a.ikeys = keys;
-        a.iseed = c->cfg.seed; a.iiter = c->iter; a.ia = c->cfg.a;
-        a.idx_bits = c->idx_bits; a.hb_shift = c->label_cb_shift - 1; a.ndim_active = dim_active(c);
-        a.split = 0;
-        a.col = c->colmode ? 1 : 0;                // column-ordered records (pipe_col_ok)
-        a.home_off = c->parity * Tl * W;
+        StretchArgs a = inplace_first_args(c, keys);
         a.ghome = c->pipe.ghome;
         a.sys_all = pipe_has_top(c) ? 1 : 0;
         attach_iteration_head(c, a);               // waits for the previous sweep's arrivals, carries the pending adaptation
-        if (evs) {
-            c->ext_start = new_event(c);
-            c->ext_stop = new_event(c);
-            evs->push_back(c->ext_start);
-            evs->push_back(c->ext_stop);
-        }
-        const int r = launch_stretch<MODE_STRETCH>(c, a, (c->N0 + TILE - 1) / TILE);
-        c->ext_start = c->ext_stop = nullptr;
+        const int r = launch_stretch_timed<MODE_STRETCH>(c, a, (c->N0 + TILE - 1) / TILE, tm);
         if (r) return r;
     }
-    FusedArgs f{};
-    f.pool = c->pool;
-    f.wrec = c->wrec[c->cur]; f.wrecnew = c->wrec[c->cur ^ 1];
-    f.loc = c->loc[c->cur]; f.locnew = c->loc[c->cur ^ 1];
-    f.betas = c->betas[c->bcur];
-    f.keys = keys;
-    f.keys_next = keys + (size_t)T * 8;             // (inside the window: iteration_keys)
-    f.a = c->cfg.a; f.ndim_active = dim_active(c);
-    f.accepted = c->accepted;
-    f.lo = c->lo; f.hi = c->hi; f.mu = c->mu; f.prec = c->prec; f.prec_sym = c->prec_sym;
-    f.flags = c->flags;
-    f.trace = (c->tracing && c->trace_fused) ? c->d_trace : nullptr;
-    f.logp_in = c->logp_in; f.fill = c->cfg.fill_value; f.rosen_a = c->rosen_a; f.rosen_b = c->rosen_b;
-    f.iter = c->iter; f.seed = c->cfg.seed;
-    f.T = T; f.W = W; f.idx_bits = c->idx_bits;
-    f.cb = c->label_cb; f.cb_shift = c->label_cb_shift;
-    f.Tl = Tl; f.rung_begin = c->cfg.rung_begin;
+    FusedArgs f = second_launch_args(c, keys);      // (periodic parameters: set before hens_pipe_init, the same on every rank)
+    f.Tl = c->Tl; f.rung_begin = c->cfg.rung_begin;
     f.cbl = c->pipe.cbl; f.cbl_shift = c->pipe.cbl_shift;
     f.guest_delta = guest_delta(c);
-    f.period = c->period;                           // (periodic parameters: set before hens_pipe_init, the same on every rank)
     f.ghome = c->pipe.ghome;
     f.box = c->pipe.box;
     f.box_hot = pipe_has_top(c) ? c->pipe.boxes[c->pipe.rank + 1] : nullptr;
@@ -1426,135 +1466,52 @@ int pipe_fused_iteration(hens_ctx_impl* c, std::vector<hipEvent_t>* evs, bool mh
     f.nranks = c->pipe.nranks; f.rank = c->pipe.rank;
     f.sys_rows = pipe_has_top(c) ? 1 : 0;           // (measured on one GPU: system-scope row stores cost nothing over sc1)
     f.no_move = mh ? 1 : 0;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (evs) {
-        e0 = new_event(c); e1 = new_event(c);
-        evs->push_back(e0); evs->push_back(e1);
-    }
-    int r;
-    switch (c->cfg.likelihood_kind) {
-        case HENS_LIKE_GAUSS_DENSE: r = launch_fused_like(c, LIKE_DENSE, f, e0, e1, true, c->colmode); break;
-#ifndef HENS_DEV_BUILD
-        case HENS_LIKE_GAUSS_DIAG: r = launch_fused_like(c, LIKE_DIAG, f, e0, e1, true, c->colmode); break;
-        case HENS_LIKE_ROSENBROCK: r = launch_fused_like(c, LIKE_ROSEN, f, e0, e1, true, c->colmode); break;
-#endif
-        default: r = fail(c, HENS_ERR_UNSUPPORTED, "no fused kernel for likelihood kind %d", c->cfg.likelihood_kind);
-    }
+    const int r = launch_second(c, f, tm, true);
     if (r) return r;
     if (!mh) c->num_proposals += 1;
     pipe_finish_sweep(c);                          // queues this sweep's counts for the adaptation, flips the record buffers
     return HENS_OK;
 }
 
-// ---- one launch per iteration (k_iter, hens_iter.h) ----------------------------------------------------------------
-// the shapes of fused_ok that leave the chip half empty (latency-bound: see hens_iter.h), row widths with three tiles in
-// half a CU's LDS.  Measured on one box (tools/iter_sweep.sh, us per iteration, one launch vs two):
-//   4 x 4096 x 32  14.7 / 18.2     8 x 4096 x 32  15.5 / 18.8    16 x 2048 x 32  15.6 / 18.3    32 x 1024 x 32  17.1 / 20.1
-//   16 x 4096 x 16  16.4 / 19.7   16 x 4096 x 32 (config 2)  22.4 / 22.5     8 x 8192 x 32  22.0 / 22.7
-//   32 x 2048 x 32  23.9 / 23.8   16 x 6144 x 32  33.5 / 34.5
-// Up to one workgroup per CU at D = 32 (two at D = 16, whose workgroups are half as heavy) the single launch wins
-// 15-19 %; with two D = 32 workgroups per CU its extra gathers and likelihoods cost what the second launch did, and the
-// profiled two-launch path stays.  (Round 5's last library, same columns: 4 x 4096 x 32 11.9 / 13.1, 8 x 4096 x 32 13.3 / 13.8,
-// 16 x 2048 x 32 14.0 / 14.6, 32 x 1024 x 32 15.7 / 16.5, 16 x 4096 x 16 15.2 / 15.6; 8 x 8192 x 32 19.3 / 16.4 - the rule stands, the margin
-// is 3-12 % now.)  The grid is W / cb workgroups (short tiles of ladders that do not divide 128 included:
-// 10 x 2048 x 32 15.2 / 18.5, 6 x 4096 x 32 15.0 / 18.1).
-bool iter_ok(const hens_ctx_impl* c) {
-    static const bool off = getenv("HENS_NO_ITER") != nullptr;               // A/B knob: two launches per iteration
-    static const long per_cu = getenv("HENS_ITER_MAX") ? atol(getenv("HENS_ITER_MAX")) : 0;   // workgroups per CU allowed
-    if (off || !fused_ok(c) || !(c->D == 16 || c->D == 32) || c->T > 128 || c->W > 32768 || !c->db[0].rec1)
-        return false;
-    const long nwg = c->W / c->label_cb, allow = per_cu ? per_cu : (c->D == 16 ? 2 : 1);
-    return nwg <= allow * (long)c->num_cu;
-}
-
-// Column-ordered records (StretchArgs::col): the two-launch iteration of one GPU on full tiles - every shape of fused_ok that
-// does not take the single launch, has no periodic parameters and no MH move in the mix (those launches address the records
-// by slot).  Round 3, config 2: both launches' index phases were a round key -> permutation -> scattered record load chain
-// (4 600 / 4 700 cycles to the first barrier); in column order the records load coalesced at the head of the launch and the
-// first launch looks rows up in an LDS copy of its rung's table.
-// the same on a rank of the ladder pipeline that steps with the two in-place launches (every rank reaches the same verdict)
-bool pipe_col_ok(const hens_ctx_impl* c) {
-    static const bool off = getenv("HENS_NO_COL") != nullptr;                // A/B knob: records by slot
-    return !off && pipe_active(c) && c->pipe.fused && !c->period && c->mh_kind < 0 && (c->W & 3) == 0;
-}
-bool col_ok(const hens_ctx_impl* c) {
-    static const bool off = getenv("HENS_NO_COL") != nullptr;                // A/B knob: records by slot
-    if (off || !fused_ok(c) || iter_ok(c) || c->period || c->mh_kind >= 0) return false;
-    return c->T * c->label_cb == 2 * TILE && (c->W & 3) == 0;
-}
-
-int launch_iter_like(hens_ctx_impl* c, int like, const IterArgs& f, hipEvent_t e0, hipEvent_t e1) {
-    const dim3 grid(c->W / c->label_cb);
-    constexpr int NW = 8;
-    c->aql.norel_next = norel_ok(c);
-    IterArgs g = f;
-    g.norel = c->aql.norel_next ? 1 : 0;
-    c->aql.prof_kind = 3;
-    return launch_by_ptr(c, ktab_iter(like, c->D, g.period != nullptr), "k_iter", grid, NW * 64, iter_lds_bytes(c->D, NW), c->aql_last, e0, e1, g);
-}
-
-int iter_iteration(hens_ctx_impl* c, int which, int ib, std::vector<hipEvent_t>* evs) {
-    const int T = c->T, W = c->W;
+// one launch per iteration (k_iter) from the planned records of batch slot `ib`
+int iter_iteration(hens_ctx_impl* c, const StepPath& path, int ib, LaunchTimer* tm) {
     if (!c->packed) {
-        const int r = hip_interlude(c, [&] { state_to_records(c); });
+        const int r = hip_interlude(c, [&] { state_to_records(c, path.col); });
         if (r) return r;
     }
     if (c->adapt_pending && !(is_acc_buffer(c, c->adapt_src) && c->T <= 128)) {   // (counts of an MH iteration's cascade)
         const int r = hip_interlude(c, [&] { flush_adapt(c); });
         if (r) return r;
     }
+    const LikeKernels* lk = like_kernels(c->cfg.likelihood_kind);
+    if (!lk) return fail(c, HENS_ERR_UNSUPPORTED, "no one-launch kernel for likelihood kind %d", c->cfg.likelihood_kind);
     IterArgs f{};
-    f.pool = c->pool;
-    f.wrec = c->wrec[c->cur]; f.wrecnew = c->wrec[c->cur ^ 1];
-    f.loc = c->loc[c->cur]; f.locnew = c->loc[c->cur ^ 1];
+    record_launch_args(c, f);                    // (betas: the ladder the folded adaptation reads, before it is handed over)
     const size_t roff = (size_t)ib * rec_per_iter(c);
-    f.rec1 = c->db[which].rec1 + roff; f.rec2 = c->db[which].rec + roff; f.rec3 = c->db[which].rec3 + roff;
-    f.keys = c->db[which].keys + (size_t)ib * T * 8;
-    f.accepted = c->accepted;
-    f.betas = c->betas[c->bcur];
+    f.rec1 = c->db[0].rec1 + roff; f.rec2 = c->db[0].rec + roff; f.rec3 = c->db[0].rec3 + roff;
+    f.keys = c->db[0].keys + (size_t)ib * c->T * 8;
     f.swap_acc = acc_take(c);
     f.acc_rows = 8 * acc_row_groups(c->T);
     if (c->adapt_pending) {
         f.ad_on = 1;
         f.ad = adapt_args(c, c->adapt_pending_adaptive, c->betas[c->bcur], c->betas[c->bcur ^ 1]);
         acc_fold(c, f.ad);
-        if (c->adapt_pending_adaptive) c->adapt_time += 1;
-        c->adapt_pending = false;
-        c->adapt_src = nullptr;
-        c->bcur ^= 1;
+        adapt_taken(c, true);
     }
     acc_commit(c);
-    f.lo = c->lo; f.hi = c->hi; f.mu = c->mu; f.prec = c->prec; f.prec_sym = c->prec_sym;
-    f.period = c->period;
-    f.flags = c->flags;
-    f.trace = (c->tracing && c->trace_fused) ? c->d_trace : nullptr;
-    f.logp_in = c->logp_in; f.fill = c->cfg.fill_value; f.rosen_a = c->rosen_a; f.rosen_b = c->rosen_b;
-    f.iter = c->iter; f.seed = c->cfg.seed;
-    f.T = T; f.W = W; f.idx_bits = c->idx_bits;
-    f.cb = c->label_cb; f.cb_shift = c->label_cb_shift;
-    f.half_rows = T * W;
+    f.half_rows = c->T * c->W;
+    c->aql.norel_next = norel_ok(c);
+    f.norel = c->aql.norel_next ? 1 : 0;
+    c->aql.prof_kind = 3;
     hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (evs) {
-        e0 = new_event(c); e1 = new_event(c);
-        evs->push_back(e0); evs->push_back(e1);
-    }
-    int r;
-    switch (c->cfg.likelihood_kind) {
-        case HENS_LIKE_GAUSS_DENSE: r = launch_iter_like(c, LIKE_DENSE, f, e0, e1); break;
-#ifndef HENS_DEV_BUILD
-        case HENS_LIKE_GAUSS_DIAG: r = launch_iter_like(c, LIKE_DIAG, f, e0, e1); break;
-        case HENS_LIKE_ROSENBROCK: r = launch_iter_like(c, LIKE_ROSEN, f, e0, e1); break;
-#endif
-        default: r = fail(c, HENS_ERR_UNSUPPORTED, "no one-launch kernel for likelihood kind %d", c->cfg.likelihood_kind);
-    }
+    time_launch(c, tm, 3, e0, e1);
+    constexpr int NW = 8;
+    const int r = launch_by_ptr(c, lk->iter(c->D, f.period != nullptr), "k_iter", dim3(c->W / c->label_cb), NW * 64, iter_lds_bytes(c->D, NW),
+                                c->aql_last, e0, e1, f);
     if (r) return r;
     c->rows_mixed = true;
     c->num_proposals += 1;
-    c->cur ^= 1;
-    c->adapt_pending = true;
-    c->adapt_pending_adaptive = c->cfg.adaptive != 0;
-    c->adapt_src = f.swap_acc;
-    c->adapt_nblocks = f.acc_rows;
+    cascade_ran(c, f.swap_acc, f.acc_rows, c->cfg.adaptive != 0);
     return HENS_OK;
 }
 
@@ -1573,7 +1530,7 @@ int ensure_mh_buffers(hens_ctx_impl* c) {
 }
 
 // one full-ensemble MH proposal from the step rows / log-uniforms already in mh_step / mh_lu (mh.py:56-193)
-int mh_launch(hens_ctx_impl* c, bool want_keep, std::vector<hipEvent_t>* evs, bool inline_draws = false, bool inplace = false) {
+int mh_launch(hens_ctx_impl* c, bool want_keep, LaunchTimer* tm, bool inline_draws = false, bool inplace = false) {
     StretchArgs a = base_args(c);
     a.split = 0;
     a.home_off = c->parity * c->Tl * c->W;
@@ -1590,14 +1547,7 @@ int mh_launch(hens_ctx_impl* c, bool want_keep, std::vector<hipEvent_t>* evs, bo
     }
     attach_iteration_head(c, a);
     attach_publish(c, a, true, (c->W + TILE - 1) / TILE);
-    if (evs) {
-        c->ext_start = new_event(c);
-        c->ext_stop = new_event(c);
-        evs->push_back(c->ext_start);
-        evs->push_back(c->ext_stop);
-    }
-    const int r = launch_stretch<MODE_MH>(c, a, (c->W + TILE - 1) / TILE);
-    c->ext_start = c->ext_stop = nullptr;
+    const int r = launch_stretch_timed<MODE_MH>(c, a, (c->W + TILE - 1) / TILE, tm);
     if (r) return r;
     if (!inplace) c->parity ^= 1;                  // (in place: the free half of the pool stays the free one)
     c->num_proposals_mh += 1;
@@ -1607,7 +1557,7 @@ int mh_launch(hens_ctx_impl* c, bool want_keep, std::vector<hipEvent_t>* evs, bo
 // Philox mode: draw the iteration's steps and accept uniforms on the device, then propose.  Isotropic and
 // axis-aligned proposals on the fast row widths are drawn inside the MH launch itself (one Box-Muller pair per
 // lane); a full covariance (Cholesky product) and the generic row widths go through k_mh_draw + the step buffer.
-int mh_iteration(hens_ctx_impl* c, std::vector<hipEvent_t>* evs, bool inplace) {
+int mh_iteration(hens_ctx_impl* c, LaunchTimer* tm, bool inplace) {
     const bool inline_draws = c->mh_kind != MH_FULL && fast_path(c);
     if (!inline_draws) {
         MhDrawArgs d{};
@@ -1619,7 +1569,7 @@ int mh_iteration(hens_ctx_impl* c, std::vector<hipEvent_t>* evs, bool inplace) {
         if (d.chol_lds) lds += (size_t)c->D * (c->D + 1) * 8;
         hipLaunchKernelGGL(k_mh_draw, dim3((c->W + 63) / 64, c->Tl), dim3(256), lds, c->stream, d);
     }
-    return mh_launch(c, false, evs, inline_draws, inplace);
+    return mh_launch(c, false, tm, inline_draws, inplace);
 }
 
 // host-side move choice of hens_step (ensemble.py:971 in Philox form): one counter-based uniform per iteration
@@ -1697,8 +1647,7 @@ int rj_launch(hens_ctx_impl* c, int mode, int branch, const double* step, const 
             a.ad_fold = 1;
             a.ad_serial = ++c->rj_ad_serial;
             a.ad_flag = c->rj_ad_flag;
-            if (c->adapt_pending_adaptive) c->adapt_time += 1;               // tempering.py:596
-            c->adapt_pending = false;
+            adapt_taken(c, false);                // (same ladder buffer: no flip; adapt_src is nullptr already)
         } else {
             flush_adapt(c);
         }
@@ -1759,6 +1708,66 @@ int rj_ensure_staging(hens_ctx_impl* c) {
     return HENS_OK;
 }
 
+// The stand-alone cascade of hens_step (MH iterations of a mix, the copying launches).  Round 5: it accumulates its swap counts
+// like the fused launch does, into a handful of rows the NEXT launch's folded adaptation sums - a row per workgroup (512 x 31
+// counts at config 5) could not be folded and cost a k_adapt launch of 11.5 us per MH iteration.  HENS_PT_NO_ACC=1: A/B knob.
+void step_cascade(hens_ctx_impl* c, LaunchTimer* tm) {
+    if (!has_pt(c)) return;
+    PtArgs p = pt_args(c, nullptr, false);
+    const bool use_acc = !env().pt_no_acc && fast_path(c) && c->T <= 128;
+    if (use_acc) { p.swap_part = acc_take(c); p.acc_rows = 8 * acc_row_groups(c->T); acc_commit(c); }
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    time_launch(c, tm, 1, e0, e1);
+    if (tm) hipExtLaunchKernelGGL(k_pt_cascade<true>, dim3(pt_blocks(c)), dim3(pt_threads(c->T)), (uint32_t)pt_lds_bytes(c->T), c->stream, e0, e1, 0, p);
+    else hipLaunchKernelGGL(k_pt_cascade<true>, dim3(pt_blocks(c)), dim3(pt_threads(c->T)), pt_lds_bytes(c->T), c->stream, p);
+    cascade_ran(c, use_acc ? p.swap_part : nullptr, p.acc_rows, c->cfg.adaptive != 0);
+}
+
+// one iteration of hens_step on the call's path, from batch slot `ib` of the draw plan; an MH iteration of a mix replaces the
+// stretch move and is followed by a cascade of its own
+int run_iteration(hens_ctx_impl* c, const StepPath& path, int ib, LaunchTimer* tm) {
+    if (path.piped()) pipe_prewait(c);
+    const bool mh = iteration_is_mh(c);
+    if (path.it == Iteration::PIPE_INPLACE2) return pipe_fused_iteration(c, path, tm, mh);
+    if (!mh && path.it == Iteration::ONE_LAUNCH) return iter_iteration(c, path, ib, tm);
+    if (!mh && path.it == Iteration::INPLACE2) return fused_iteration(c, path, tm);
+    const bool inplace = !path.piped() && fast_path(c);
+    int r;
+    if (mh) {
+        // (the fast kernels and the cascade read the walker records too; other MH launches want the by-field arrays)
+        if (path.records()) state_to_records(c, path.col);
+        else state_to_fields(c);
+        r = mh_iteration(c, tm, inplace);
+    } else if (path.it == Iteration::SETS) r = stretch_sets(c, tm);
+    else r = stretch_pair(c, 0, ib, tm, inplace);
+    if (r) return r;
+    if (!path.piped()) { step_cascade(c, tm); return HENS_OK; }
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    time_launch(c, tm, 1, e0, e1);
+    if (tm) (void)hipEventRecord(e0, c->stream);
+    pipe_sweep(c);
+    if (tm) (void)hipEventRecord(e1, c->stream);
+    return HENS_OK;
+}
+
+// per-launch durations of a call into hens_timing and launch_us (begin / end of every stepping launch, us after the first begin);
+// span(k, begin_us, end_us) gives launch k's and returns its duration in ms; kind < 0: not a stepping launch
+template <class Kinds, class Span>
+void fold_timing(hens_ctx_impl* c, const Kinds& kinds, size_t n, Span span) {
+    std::vector<double> us;
+    for (size_t k = 0; k < n; ++k) {
+        if (kinds[k] < 0) continue;              // (round-key window plans)
+        double b = 0, e = 0;
+        const double ms = span(k, b, e);
+        us.push_back(b);
+        us.push_back(e);
+        if (kinds[k] == 0) { c->timing.stretch_ms += ms; c->timing.n_stretch += 1; }
+        else if (kinds[k] == 1) { c->timing.pt_ms += ms; c->timing.n_pt += 1; }
+        else { c->timing.fused_ms += ms; c->timing.n_fused += 1; }
+    }
+    c->launch_us.swap(us);
+}
+
 // the cascade + (optionally adapting) ladder update after a leaf-packing move; `key` separates the two cascades of one iteration
 void rj_cascade(hens_ctx_impl* c, uint64_t key, bool adapt) {
     if (!has_pt(c)) return;
@@ -1766,10 +1775,7 @@ void rj_cascade(hens_ctx_impl* c, uint64_t key, bool adapt) {
     PtArgs p = pt_args(c, nullptr, false);
     p.iter = key;
     hipLaunchKernelGGL(k_pt_cascade<true>, dim3(pt_blocks(c)), dim3(pt_threads(c->T)), pt_lds_bytes(c->T), c->stream, p);
-    c->cur ^= 1;
-    c->adapt_pending = true;
-    c->adapt_pending_adaptive = adapt && c->cfg.adaptive != 0;      // rj.py:381-382: swaps without adaptation after the RJ move
-    c->adapt_src = nullptr;
+    cascade_ran(c, nullptr, 0, adapt && c->cfg.adaptive != 0);     // rj.py:381-382: swaps without adaptation after the RJ move
     if (!c->rj_defer_adapt) flush_adapt(c);      // (hens_rj_step: the next k_rj launch adapts, see rj_launch)
 }
 
@@ -1926,12 +1932,11 @@ int hens_create(const hens_config* cfg, hens_ctx** out) {
     }
     c->own_stream = true;
     {   // the context's AQL queue for the stepping launches (hens_aql.h); HENS_NO_AQL=1: everything on the HIP stream
-        static const bool aql_off = getenv("HENS_NO_AQL") != nullptr;
-        if (!aql_off) {
+        if (!env().no_aql) {
             hens_aql::Device& ad = hens_aql::device(cfg->device_id);
             if (ad.ok && c->aql.create(ad)) {
                 c->aql_on = true;
-                static const int fm = getenv("HENS_AQL_FLUSH") ? atoi(getenv("HENS_AQL_FLUSH")) : -1;   // (see hens_aql::Queue::flush_mode)
+                const int fm = env().aql_flush;     // (see hens_aql::Queue::flush_mode)
                 if (fm >= 0 && fm <= 3) c->aql.flush_mode = fm;
             } else {
                 static bool warned = false;
@@ -2015,7 +2020,7 @@ int hens_create(const hens_config* cfg, hens_ctx** out) {
         const size_t nrec = c->label_cb ? (size_t)c->NB * rec_per_iter(c) : 0;   // (>= n / 2: short tiles keep their 64 places)
         if (c->label_cb) TRY(dalloc(c, &c->db[b].rec, nrec));
         if (c->label_cb && c->Tl == c->T && (c->D == 16 || c->D == 32) && c->W <= 32768 && TW <= ((size_t)1 << 20)) {
-            TRY(dalloc(c, &c->db[b].rec1, nrec));        // (one-launch iteration, see iter_ok)
+            TRY(dalloc(c, &c->db[b].rec1, nrec));        // (one-launch iteration, see step_path)
             TRY(dalloc(c, &c->db[b].rec3, nrec));
         }
         TRY(dalloc(c, &c->db[b].keys, (size_t)c->NB * c->T * 8));
@@ -2628,38 +2633,29 @@ int hens_step(hens_ctx* ctx, int64_t n_iters) {
     if (c->cfg.likelihood_kind == HENS_LIKE_HOST)
         return fail(c, HENS_ERR_UNSUPPORTED, "hens_step needs a device likelihood (host-callable likelihoods step through hens_propose_split / hens_accept_split)");
     HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    const int T = c->T, W = c->W;
-    c->N0 = (W + 1) / 2;
+    c->N0 = (c->W + 1) / 2;
     c->win_count = 0;
-    const bool pt = has_pt(c);
-    const bool fused = fused_ok(c);
-    const bool iter1 = iter_ok(c);
-    static const bool ev_env = getenv("HENS_STEP_EVENTS") != nullptr;
-    // Which queue: the two-launch iteration of one GPU goes to the context's AQL queue (hens_aql.h) unless something in this call
+    const StepPath path = step_path(c);
+    // Which queue: the in-place launches of one GPU go to the context's AQL queue (hens_aql.h) unless something in this call
     // needs the HIP stream between its launches (per-kernel events, traces, the MH move of a mix).
-    const bool aql_able = c->aql_on && fused && !piped && !c->tracing && c->mh_kind < 0 && n_iters > 0;
+    const bool aql_able = c->aql_on && path.aql_able() && !c->tracing && c->mh_kind < 0 && n_iters > 0;
     // per-launch durations: mode 1 = HIP event pairs (forces the HIP stream); mode 2 = the launches' own dispatch timestamps on
     // the queue the call would use anyway - the AQL queue's packets (hens_aql.h: set_prof), HIP events where the call steps on
     // the HIP stream whatever the mode (pipeline ranks, the MH mix)
-    const bool aprof = c->per_kernel_events == 2 && aql_able && !ev_env && n_iters <= 8192;
+    const bool aprof = c->per_kernel_events == 2 && aql_able && !env().step_events && n_iters <= 8192;
     const bool prof = c->per_kernel_events == 1 || (c->per_kernel_events == 2 && !aprof);
-    if (piped && !c->pipe.fused_decided) {         // (every rank reaches the same verdict: pipe_fused_possible)
-        c->pipe.fused = pipe_fused_possible(c);
-        c->pipe.fused_decided = true;
-    }
-    const bool pfused = piped && c->pipe.fused;
     // (the state stays in record mode between hens_step calls of the record paths - every other entry point settles it,
     //  settle_state - so a short call pays no pack / unpack)
-    if (!fused && !iter1 && !pfused) state_to_fields(c);
-    std::vector<hipEvent_t> evs;
-    std::vector<char> ev_kind;                // per event pair: 0 stretch launch, 1 cascade launch, 2 fused half-step + cascade
+    if (!path.records()) state_to_fields(c);
+    LaunchTimer timer;
+    LaunchTimer* const tm = prof ? &timer : nullptr;
     for (hipEvent_t e : c->evpool) (void)hipEventDestroy(e);
     c->evpool.clear();
     c->timing = hens_timing{};
     // (an event pair around the call - total_ms of hens_get_timing - only when timing is asked for: per-kernel profiling or
     //  HENS_STEP_EVENTS=1.  A record is a barrier packet in front of the first launch and one more behind the last: a short
     //  call - the driver times blocks of 20 iterations - pays for both.)
-    c->step_events = prof || ev_env;
+    c->step_events = prof || env().step_events;
     const bool use_aql = aql_able && !c->step_events;
     if (c->aql_on && c->aql.prof != aprof && !c->aql.set_prof(aprof)) return fail(c, HENS_ERR_HIP, "AQL dispatch timestamps: %s", c->aql.err.c_str());
     if (aprof) (void)c->aql.set_prof(true);       // (clears the last call's records)
@@ -2679,83 +2675,17 @@ int hens_step(hens_ctx* ctx, int64_t n_iters) {
     // us per iteration at 8 x 4096 x 32 without it) and, in a soak of 10^5 iterations at 32 x 1024 x 16, one chain in five parted
     // ways with its own repeats (a plan overlapping the previous batch's readers; never with the plan on the main stream: 0 of 76
     // runs).  Round 4 removed it: no code path can reach that configuration any more (tests/test_hip_repeat.py is the soak).
-    const int64_t nbatch = (n_iters + c->NB - 1) / c->NB;
-    auto batch_size = [&](int64_t b) { return (int)std::min<int64_t>(c->NB, n_iters - b * c->NB); };
-    const bool keys_only = (fused && !iter1) || pfused;   // draws in registers: iteration_keys plans the round keys, nothing else
-    for (int64_t b = 0; b < nbatch; ++b) {
-        const int which = 0, nb = batch_size(b);
-        if (!keys_only && c->nsplits == 2) {           // (more than two sets: planned iteration by iteration, stretch_sets)
-            launch_plan(c, c->stream, 0, c->iter, nb, fused, iter1);
+    const bool one = path.it == Iteration::ONE_LAUNCH;
+    for (int64_t done = 0; done < n_iters; done += c->NB) {
+        const int nb = (int)std::min<int64_t>(c->NB, n_iters - done);
+        if (!path.keys_only() && c->nsplits == 2) {    // (more than two sets: planned iteration by iteration, stretch_sets)
+            launch_plan(c, c->stream, 0, c->iter, nb, one, one);   // (k_iter reads the block-ordered records and nothing else)
             c->timing.n_plan += 1;
             if (c->aql_failed) { c->aql_failed = false; return step_failed(c, fail(c, HENS_ERR_HIP, "AQL dispatch of the draw plan: %s", c->aql.err.c_str())); }
         }
         for (int ib = 0; ib < nb; ++ib) {
-            if (piped) pipe_prewait(c);
-            const bool mh = iteration_is_mh(c);
-            if (pfused) {
-                r = pipe_fused_iteration(c, prof ? &evs : nullptr, mh);
-                if (prof) { ev_kind.push_back(0); ev_kind.push_back(2); }
-                if (r) return step_failed(c, r);
-                c->iter += 1;
-                continue;
-            }
-            if (mh) {
-                // (the fast kernels and the cascade read the walker records too; other MH launches want the by-field arrays)
-                if (fused && fast_path(c)) state_to_records(c);
-                else state_to_fields(c);
-                r = mh_iteration(c, prof ? &evs : nullptr, !piped && fast_path(c));
-                if (prof) ev_kind.push_back(0);
-            } else if (iter1) {
-                c->aql_last = c->aql_now && b + 1 == nbatch && ib + 1 == nb;
-                r = iter_iteration(c, which, ib, prof ? &evs : nullptr);
-                if (prof) ev_kind.push_back(3);
-                if (r) return step_failed(c, r);
-                c->iter += 1;
-                continue;
-            } else if (fused) {
-                c->aql_last = c->aql_now && b + 1 == nbatch && ib + 1 == nb;
-                r = fused_iteration(c, prof ? &evs : nullptr);
-                if (prof) { ev_kind.push_back(0); ev_kind.push_back(2); }
-                if (r) return step_failed(c, r);
-                c->iter += 1;
-                continue;
-            } else if (c->nsplits > 2) {
-                r = stretch_sets(c, prof ? &evs : nullptr);
-                if (prof) for (int q = 0; q < c->nsplits; ++q) ev_kind.push_back(0);
-            } else {
-                r = stretch_pair(c, which, ib, prof ? &evs : nullptr, !piped && fast_path(c));
-                if (prof) { ev_kind.push_back(0); ev_kind.push_back(0); }
-            }
-            if (r) return step_failed(c, r);
-            if (piped) {
-                if (prof) { hipEvent_t e0 = new_event(c); evs.push_back(e0); (void)hipEventRecord(e0, c->stream); }
-                pipe_sweep(c);
-                if (prof) { hipEvent_t e1 = new_event(c); evs.push_back(e1); (void)hipEventRecord(e1, c->stream); ev_kind.push_back(1); }
-            } else if (pt) {
-                PtArgs p = pt_args(c, nullptr, false);
-                // Round 5: the stand-alone cascade of hens_step (MH iterations of a mix, the copying launches) accumulates its swap
-                // counts like the fused launch does, into a handful of rows the NEXT launch's folded adaptation sums - a row per
-                // workgroup (512 x 31 counts at config 5) could not be folded and cost a k_adapt launch of 11.5 us per MH iteration
-                static const bool acc_off = getenv("HENS_PT_NO_ACC") != nullptr;             // A/B knob
-                const bool use_acc = !acc_off && fast_path(c) && c->T <= 128;
-                if (use_acc) { p.swap_part = acc_take(c); p.acc_rows = 8 * acc_row_groups(c->T); acc_commit(c); }
-                if (prof) {
-                    hipEvent_t e0 = new_event(c), e1 = new_event(c);
-                    evs.push_back(e0);
-                    evs.push_back(e1);
-                    ev_kind.push_back(1);
-                    hipExtLaunchKernelGGL(k_pt_cascade<true>, dim3(pt_blocks(c)), dim3(pt_threads(c->T)), (uint32_t)pt_lds_bytes(T),
-                                          c->stream, e0, e1, 0, p);
-                } else {
-                    hipLaunchKernelGGL(k_pt_cascade<true>, dim3(pt_blocks(c)), dim3(pt_threads(c->T)), pt_lds_bytes(T),
-                                       c->stream, p);
-                }
-                c->cur ^= 1;
-                c->adapt_pending = true;
-                c->adapt_pending_adaptive = c->cfg.adaptive != 0;
-                c->adapt_src = use_acc ? p.swap_part : nullptr;
-                if (use_acc) c->adapt_nblocks = p.acc_rows;
-            }
+            c->aql_last = c->aql_now && done + ib + 1 == n_iters;
+            if ((r = run_iteration(c, path, ib, tm))) return step_failed(c, r);
             c->iter += 1;
         }
     }
@@ -2763,12 +2693,12 @@ int hens_step(hens_ctx* ctx, int64_t n_iters) {
         c->aql.ring();
         c->aql_now = c->aql_last = false;
     }
-    if (piped && !pfused) state_to_fields(c);
-    if (pfused) pipe_fused_epilogue(c);
+    if (path.it == Iteration::PIPE_COPYING) state_to_fields(c);
+    if (path.it == Iteration::PIPE_INPLACE2) pipe_fused_epilogue(c);
     // The last cascade's ladder adaptation stays pending on one GPU: the next hens_step call folds it into its first
     // launch (no kernel of its own, ~12 us per call with its count-buffer reset), and every entry point that reads the ladder,
     // the swap counters or the state settles it first (flush_adapt at their head) - same bits either way.
-    if (piped) pipe_flush_adapt(c);
+    if (path.piped()) pipe_flush_adapt(c);
     HIPCHK(c, hipGetLastError());
     if (c->step_events) HIPCHK(c, hipEventRecord(c->ev1, c->stream));
     c->timing.n_iters = n_iters;
@@ -2777,39 +2707,26 @@ int hens_step(hens_ctx* ctx, int64_t n_iters) {
         const bool dirty = c->hip_dirty;
         if ((r = aql_settle(c))) return r;
         c->hip_dirty = dirty;
+        std::vector<double> us;
         std::vector<int> kinds;
-        if (!c->aql.collect_prof(c->launch_us, kinds)) return fail(c, HENS_ERR_HIP, "AQL dispatch timestamps: %s", c->aql.err.c_str());
-        std::vector<double> keep;
-        for (size_t k = 0; k < kinds.size(); ++k) {
-            const double ms = (c->launch_us[2 * k + 1] - c->launch_us[2 * k]) * 1e-3;
-            if (kinds[k] < 0) continue;              // (round-key window plans: not a stepping launch)
-            keep.push_back(c->launch_us[2 * k]);
-            keep.push_back(c->launch_us[2 * k + 1]);
-            if (kinds[k] == 0) { c->timing.stretch_ms += ms; c->timing.n_stretch += 1; }
-            else if (kinds[k] == 1) { c->timing.pt_ms += ms; c->timing.n_pt += 1; }
-            else { c->timing.fused_ms += ms; c->timing.n_fused += 1; }
-        }
-        if (!c->launch_us.empty()) c->timing.total_ms = (c->launch_us.back() - c->launch_us.front()) * 1e-3;
-        c->launch_us.swap(keep);
-        c->aql_prof_total = true;
+        if (!c->aql.collect_prof(us, kinds)) return fail(c, HENS_ERR_HIP, "AQL dispatch timestamps: %s", c->aql.err.c_str());
+        fold_timing(c, kinds, kinds.size(), [&](size_t k, double& b, double& e) { b = us[2 * k]; e = us[2 * k + 1]; return (e - b) * 1e-3; });
+        if (!us.empty()) c->timing.total_ms = (us.back() - us.front()) * 1e-3;
         c->timing.clock = 2;
-    } else c->aql_prof_total = false;
+    }
+    c->aql_prof_total = aprof;
     if (prof) {
         c->timing.clock = 1;
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        float ms = 0;
-        c->launch_us.clear();
-        for (size_t k = 0; k < ev_kind.size() && 2 * k + 1 < evs.size(); ++k) {
-            float b = 0, e = 0;
-            (void)hipEventElapsedTime(&b, evs[0], evs[2 * k]);
-            (void)hipEventElapsedTime(&e, evs[0], evs[2 * k + 1]);
-            c->launch_us.push_back(b * 1e3);
-            c->launch_us.push_back(e * 1e3);
+        const std::vector<hipEvent_t>& evs = timer.evs;
+        fold_timing(c, timer.kind, timer.kind.size(), [&](size_t k, double& b, double& e) {
+            float fb = 0, fe = 0, ms = 0;
+            (void)hipEventElapsedTime(&fb, evs[0], evs[2 * k]);
+            (void)hipEventElapsedTime(&fe, evs[0], evs[2 * k + 1]);
             (void)hipEventElapsedTime(&ms, evs[2 * k], evs[2 * k + 1]);
-            if (ev_kind[k] == 0) { c->timing.stretch_ms += ms; c->timing.n_stretch += 1; }
-            else if (ev_kind[k] == 1) { c->timing.pt_ms += ms; c->timing.n_pt += 1; }
-            else { c->timing.fused_ms += ms; c->timing.n_fused += 1; }
-        }
+            b = fb * 1e3; e = fe * 1e3;
+            return (double)ms;
+        });
     }
     return HENS_OK;
 }
@@ -3197,9 +3114,8 @@ int hens_rj_set_model(hens_ctx* ctx, int32_t nbranches, const int32_t* kinds, co
         HIPCHK(c, hipMemsetAsync(c->rj_acc_bd, 0, (size_t)c->Tl * c->W * 4, c->stream));
     }
     // every pool row's template, resident (birth / death by difference in hens_rj_step): 2 Tl W rows of ndata doubles
-    // (config 4: 131 MB); a lane keeps 8 points, so models of up to 512 data points
-    static const bool tm_off = getenv("HENS_RJ_NO_TEMPLATES") != nullptr;         // A/B knob
-    if (!tm_off && ndata <= 512 && (!c->rj_tm || c->rj_tm_ndata != ndata)) {
+    // (config 4: 131 MB); a lane keeps 8 points, so models of up to 512 data points; HENS_RJ_NO_TEMPLATES=1: A/B knob
+    if (!env().rj_no_templates && ndata <= 512 && (!c->rj_tm || c->rj_tm_ndata != ndata)) {
         if ((r = dalloc(c, &c->rj_tm, (size_t)2 * c->Tl * c->W * (size_t)ndata))) return r;
         c->rj_tm_ndata = ndata;
     }
@@ -3448,7 +3364,7 @@ int hens_rj_step(hens_ctx* ctx, int64_t n_iters) {
         c->rj_tm_drift = false;
         fresh = true;
     }
-    static const bool fold_off = getenv("HENS_NO_FOLD") != nullptr;           // A/B knob: k_adapt behind every cascade
+    const bool fold_off = env().no_fold;          // A/B knob: k_adapt behind every cascade
     if (!c->rj_ad_flag && !fold_off) {
         if ((r = dalloc(c, &c->rj_ad_flag, 2))) return r;
         HIPCHK(c, hipMemsetAsync(c->rj_ad_flag, 0, 8, c->stream));
@@ -3913,7 +3829,7 @@ int hens_pipe_init(hens_ctx* ctx, int32_t nranks, int32_t my_rank, void* blob_ou
     if ((r = dalloc(c, &c->pipe.d_boxes, (size_t)nranks))) return r;
     if ((r = dalloc(c, &c->pipe.tickets, (size_t)4))) return r;
     HIPCHK(c, hipMemsetAsync(c->pipe.tickets, 0, 16, c->stream));
-    {   // fused iteration (pipe_fused_possible decides at the first hens_step): guests' home rows, one row of swap counts per workgroup
+    {   // fused iteration (step_path decides at the first hens_step): guests' home rows, one row of swap counts per workgroup
         int cbl = 2 * TILE / std::max(1, std::min(c->Tl, 2 * TILE)), sh = 0;
         while ((1 << sh) < cbl) ++sh;
         c->pipe.cbl = 1 << sh; c->pipe.cbl_shift = sh;
@@ -3930,8 +3846,7 @@ int hens_pipe_init(hens_ctx* ctx, int32_t nranks, int32_t my_rank, void* blob_ou
     }
     int khz = 0;
     (void)hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, c->cfg.device_id);
-    const double secs = getenv("HENS_PIPE_TIMEOUT_S") ? atof(getenv("HENS_PIPE_TIMEOUT_S")) : 20.0;
-    c->pipe.budget = (long long)((khz > 0 ? khz : 100000) * 1000.0 * secs);
+    c->pipe.budget = (long long)((khz > 0 ? khz : 100000) * 1000.0 * env().pipe_timeout_s);
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (blob_out) {       // [mailbox handle | pool handle]
         hipIpcMemHandle_t h[2];
