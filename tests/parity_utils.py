@@ -14,8 +14,16 @@ def gaussian_problem(D, dense=True):
 
 
 def make_oracle(T, W, D, box=50.0, dense=True, seed_construct=123, seed_run=456, x0=None,
-                tempered=None, record=True, **kw):
-    mu, invcov = gaussian_problem(D, dense)
+                tempered=None, record=True, problem=None, **kw):
+    """``problem``: a tests/problems.Problem (its means, precision, per-coordinate box and start positions) in place of the default
+    Gaussian under the scalar box ``box``."""
+    if problem is not None:
+        assert problem.D == D
+        mu, invcov, lo, hi, loglike = problem.mu, problem.precision, problem.lo, problem.hi, problem.loglike
+        x0 = problem.x0(T, W) if x0 is None else x0
+    else:
+        mu, invcov = gaussian_problem(D, dense)
+        lo, hi, loglike = np.full(D, -box), np.full(D, box), (lambda x: orc.gaussian_log_like(x, mu, invcov))
     R = np.random.RandomState(seed_construct)
     G = np.random.RandomState(seed_run)
     if x0 is None:
@@ -25,15 +33,20 @@ def make_oracle(T, W, D, box=50.0, dense=True, seed_construct=123, seed_run=456,
     betas = orc.make_ladder(D, ntemps=T) if tempered else None
     if "betas" in kw:
         betas = kw.pop("betas")
-    o = orc.OracleSampler(x0, lambda x: orc.gaussian_log_like(x, mu, invcov), np.full(D, -box), np.full(D, box),
-                          R, G, betas=betas, record=record, **kw)
+    o = orc.OracleSampler(x0, loglike, lo, hi, R, G, betas=betas, record=record, **kw)
     return o, mu, invcov
 
 
-def make_engine(o, mu, invcov, dense=True, **kw):
+def device_likelihood(problem):
+    """The device likelihood of a tests/problems.Problem."""
+    from eryn_amd.likelihood import GaussianLikelihood, RosenbrockLikelihood
+    return RosenbrockLikelihood(problem.D) if problem.like_kind == "rosen" else GaussianLikelihood(problem.mu, problem.precision)
+
+
+def make_engine(o, mu, invcov, dense=True, problem=None, **kw):
     from eryn_amd.engine import HipEnsemble
     from eryn_amd.likelihood import GaussianLikelihood
-    like = GaussianLikelihood(mu, invcov if dense else np.diag(invcov).copy())
+    like = device_likelihood(problem) if problem is not None else GaussianLikelihood(mu, invcov if dense else np.diag(invcov).copy())
     return HipEnsemble(o.T, o.W, o.D, like, o.lo, o.hi, a=o.a, tempered=o.tempered, adaptive=o.adaptive,
                        adaptation_lag=o.lag, adaptation_time=o.nu, stop_adaptation=o.stop_adaptation, **kw)
 

@@ -6,7 +6,8 @@
   single <T> <W> <D> <iters> <out.npz>               the unsharded run both are compared with
 env PIPE_TEST_DELAY=1 runs everything with adaptation_delay = 1 (then "single" is a 1-rank pipeline).
   timeout                                            rank 1 never steps: rank 0 must raise, not hang
-  replay <nranks> <T> <W> <D> <iters>                N local shards against the ORACLE fed with the exported Philox draws
+  replay <nranks> <T> <W> <D> <iters> [hetero]       N local shards against the ORACLE fed with the exported Philox draws; "hetero":
+                                                     on tests/problems.hetero_problem (per-coordinate box) with its coverage asserted
   replay_from <nranks> <T> <W> <D> <start> <n,n,..>  the same after an unobserved call of <start> iterations, in calls of n
 """
 import os
@@ -38,8 +39,19 @@ DELAY = int(os.environ.get("PIPE_TEST_DELAY", "0"))      # hens_config.adaptatio
 MODEL = os.environ.get("PIPE_TEST_MODEL", "gauss")       # "rosen_mix": BASELINE config 4 in small - Rosenbrock + Stretch/Gaussian mix; "gauss_periodic"
 
 
+HETERO = None                                            # a tests/problems.Problem: "replay ... hetero"
+
+
 def make(T, W, D, rng_range=None, delay=None):
     mu, invcov, x0, betas = problem(T, W, D)
+    if HETERO is not None:
+        from tests import parity_utils as pu
+        e = HipEnsemble(T, W, D, pu.device_likelihood(HETERO), HETERO.lo, HETERO.hi, seed=SEED, rung_range=rng_range,
+                        adaptation_delay=DELAY if delay is None else delay)
+        r0, r1 = rng_range if rng_range else (0, T)
+        e.upload(HETERO.x0(T, W)[r0:r1], betas=betas)
+        e.eval_state()
+        return e
     if MODEL == "rosen_mix":
         from eryn_amd.likelihood import RosenbrockLikelihood
         like = RosenbrockLikelihood(D)
@@ -154,20 +166,26 @@ def main():
         from tests import replay_utils as ru
         nranks, T, W, D, iters = map(int, sys.argv[2:7])
         mu, invcov, x0, betas0 = problem(T, W, D)
+        fn = lambda q: orc.gaussian_log_like(q, mu, invcov)      # noqa: E731
+        lo, hi, cov = np.full(D, -6.0), np.full(D, 6.0), None
+        if len(sys.argv) > 7 and sys.argv[7] == "hetero":
+            from tests import problems as pb
+            global HETERO
+            HETERO = pb.hetero_problem(D, "dense")
+            fn, lo, hi, cov = HETERO.loglike, HETERO.lo, HETERO.hi, pb.new_coverage(D)
         _, bounds = rung_partition(T, nranks)
         engs = [make(T, W, D, b) for b in bounds]
         LadderPipeline.connect_local(engs)
         whole = make(T, W, D)                              # draws + the initial log-likelihoods the device computed
         x, L, P, betas = whole.download()
         st = ru.OracleState(x, L, P, betas)
-        fn = lambda q: orc.gaussian_log_like(q, mu, invcov)      # noqa: E731
         done = 0
         for n in (2, iters - 2):
             for e in engs:
                 e.step(n)
             for e in engs:
                 e.synchronize()
-            ru.replay(whole, st, done, n, fn, np.full(D, -6.0), np.full(D, 6.0))
+            ru.replay(whole, st, done, n, fn, lo, hi, coverage=cov)
             done += n
             snaps = [e.download() for e in engs]
             cs = [e.counters() for e in engs]
@@ -176,6 +194,11 @@ def main():
             ru.assert_state_equal(st, *[np.concatenate([s[k] for s in snaps], axis=0) for k in range(3)], snaps[0][3],
                                   counters=cnt, what=f"{nranks}-shard pipeline after {done} iterations")
         assert st.swaps_total.sum() > 0 and st.min_margin > 1e-12
+        if cov is not None:
+            from tests import tolerance_log as tol
+            assert st.accepted.sum() > 0
+            pb.assert_coverage(cov, HETERO, what=f"{nranks}-shard pipeline ({T},{W},{D})")
+            print("max_rel_L %.3e" % max([v["max_rel_L"] for v in tol.report().values()] + [0.0]))
     elif mode == "replay_from":
         # ... from iteration <start> on (tests/test_hip_counter_edges.py: the round-key window's edge, which a rank plans for
         # its rungs AND the rung below them)

@@ -19,6 +19,7 @@ import numpy as np
 
 from oracle import eryn_oracle as orc
 from tests import tolerance_log as tol
+from tests.problems import count_coverage
 
 
 def is_permutation_rows(a, W):
@@ -118,14 +119,17 @@ def _margin(st, lnpdiff, logu):
 
 
 def oracle_iteration(st, ref, loglike, lo, hi, a=2.0, adaptive=True, lag=10000, nu=100, stop_adaptation=-1,
-                     mh=None, period=None, nsplits=2):
+                     mh=None, period=None, nsplits=2, coverage=None):
     """One sampler iteration on ``st`` with the given draws (ensemble.py:965-981): the stretch move's two halves
-    (or one Metropolis-Hastings proposal when ``mh = (step, u_acc)``), the PT cascade, the ladder adaptation."""
+    (or one Metropolis-Hastings proposal when ``mh = (step, u_acc)``), the PT cascade, the ladder adaptation.
+    ``coverage``: a dict of tests/problems.new_coverage that counts what the oracle's proposals did at the prior box."""
     T, W, D = st.x.shape
     tt = np.arange(T)[:, None]
     if mh is not None:
         out = orc.mh_step(st.x, st.L, st.P, st.betas, mh[0], mh[1], lo, hi, loglike, period=period)
         st.mh_accepted += out["keep"]
+        if coverage is not None:
+            count_coverage(coverage, out["q"], out["logp"], out["keep"], lo, hi, "mh")
         with np.errstate(divide="ignore"):
             _margin(st, out["lnpdiff"], np.log(mh[1]))
     else:
@@ -135,6 +139,8 @@ def oracle_iteration(st, ref, loglike, lo, hi, a=2.0, adaptive=True, lag=10000, 
             acc = np.zeros((T, W))
             acc[tt, out["S"]] = out["keep"]
             st.accepted += acc
+            if coverage is not None:
+                count_coverage(coverage, out["q"], out["logp"], out["keep"], lo, hi, "stretch")
             with np.errstate(divide="ignore"):
                 _margin(st, out["lnpdiff"], np.log(ref[f"u_acc{sp}"]))
     if st.betas is not None and T > 1:

@@ -30,9 +30,20 @@ ROOT = os.path.dirname(HERE)
 
 
 def _engine(T, W, D, seed=5, mh=None, like_kind="dense"):
+    """``like_kind`` "hetero": tests/problems.hetero_problem (dense Gaussian, per-coordinate box, some 40 % of the first proposals
+    outside it, pinned coordinates) in place of the default problem under its scalar box."""
     from eryn_amd.engine import HipEnsemble
     from eryn_amd.likelihood import GaussianLikelihood, RosenbrockLikelihood
     mu, invcov = pu.gaussian_problem(D)
+    if like_kind == "hetero":
+        from tests import problems as pb
+        prob = pb.hetero_problem(D, "dense")
+        eng = HipEnsemble(T, W, D, pu.device_likelihood(prob), prob.lo, prob.hi, seed=seed)
+        eng.upload(prob.x0(T, W), betas=orc.make_ladder(D, ntemps=T))
+        eng.eval_state()
+        if mh is not None:
+            eng.set_mh_proposal(*(pb.mh_proposal(prob, "iso", mh[2]) if mh[0] == "iso" else mh))
+        return eng, prob.mu, prob.precision
     like = GaussianLikelihood(mu, invcov) if like_kind == "dense" else RosenbrockLikelihood(D)
     box = 50.0 if like_kind == "dense" else 5.0
     eng = HipEnsemble(T, W, D, like, -box, box, seed=seed)
@@ -127,7 +138,8 @@ np.savez(sys.argv[7], **_snapshot(eng, bool(use_mh)))
 
 
 @pytest.mark.parametrize("T,W,D,use_mh,like", [(16, 256, 32, 0, "dense"), (8, 128, 64, 1, "dense"), (32, 256, 128, 1, "rosen"),
-                                              (10, 512, 64, 1, "dense"), (12, 8192, 32, 0, "dense"), (20, 256, 128, 1, "rosen")])
+                                              (10, 512, 64, 1, "dense"), (12, 8192, 32, 0, "dense"), (20, 256, 128, 1, "rosen"),
+                                              (16, 256, 32, 0, "hetero"), (10, 512, 64, 1, "hetero")])
 def test_record_mode_equals_the_copying_three_launch_path(T, W, D, use_mh, like, tmp_path):
     outs = []
     for tag, env in (("fused", {}), ("three", {"HENS_NO_FUSED": "1"})):
@@ -152,7 +164,7 @@ def _one_launch(eng, n=3):
 
 @pytest.mark.parametrize("T,W,D,use_mh,like", [(8, 4096, 32, 0, "dense"), (16, 256, 32, 1, "dense"), (4, 1024, 16, 1, "dense"),
                                               (32, 512, 32, 0, "rosen"), (2, 128, 32, 0, "dense"), (10, 2048, 32, 1, "dense"),
-                                              (5, 512, 16, 0, "dense")])
+                                              (5, 512, 16, 0, "dense"), (8, 1024, 32, 0, "hetero"), (4, 1024, 16, 1, "hetero")])
 def test_one_launch_iteration_equals_the_two_launch_path(T, W, D, use_mh, like, tmp_path):
     """k_iter (hens_iter.h) against k_stretch_fast + k_split1_pt from the same seed: positions, log-probabilities, ladder,
     accept and swap counters bit for bit, across two calls (rows folded back into one half in between) and with the
@@ -205,6 +217,27 @@ def test_every_kept_switch_reaches_the_default_paths_state(knob, T, W, D, tmp_pa
         assert r.returncode == 0, r.stdout + r.stderr
         outs.append(dict(np.load(out)))
     _assert_same(outs[0], outs[1], f"({T},{W},{D}) default vs {knob}=1")
+
+
+@pytest.mark.parametrize("knob,T,W,D", [("HENS_NO_AQL", 16, 4096, 32), ("HENS_NO_AQL", 10, 512, 64), ("HENS_AQL_RELEASE", 16, 4096, 32),
+                                        ("HENS_AQL_RELEASE", 8, 1024, 32)])
+def test_queue_and_fence_switches_reach_the_default_paths_state_on_per_coordinate_boxes(knob, T, W, D, tmp_path):
+    """HENS_NO_AQL / HENS_AQL_RELEASE against the default path on tests/problems.hetero_problem: some 40 % of the first proposals lie
+    outside the box.  A rejected proposal stores nothing and an accepted one stores in place, so on the fence-free launches the mix
+    of the two is what the next launch's reads depend on - the default problem, whose proposals never leave its box, has no such
+    mix from the prior.  Two-launch shapes (config 2's, a short-tile ladder at D = 64) and a one-launch shape."""
+    outs = []
+    for env in ({}, {knob: "1"}):
+        out = str(tmp_path / f"{len(outs)}.npz")
+        e = dict(os.environ, **env)
+        if not env:
+            e.pop(knob, None)
+        r = subprocess.run([sys.executable, "-c", _WORKER, ROOT, str(T), str(W), str(D), "0", "hetero", out],
+                           env=e, capture_output=True, text=True, timeout=240)
+        assert r.returncode == 0, r.stdout + r.stderr
+        outs.append(dict(np.load(out)))
+    _assert_same(outs[0], outs[1], f"({T},{W},{D}) per-coordinate box: default vs {knob}=1")
+    assert outs[0]["accepted"].sum() > 0 and outs[0]["swaps_total"].sum() > 0
 
 
 @pytest.mark.parametrize("T,W,D,like", [(8, 128, 64, "dense"), (32, 256, 128, "rosen")])
@@ -326,8 +359,13 @@ T, W, D, like, n, stop = int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4]), s
 mu, invcov = pu.gaussian_problem(D)
 lk = RosenbrockLikelihood(D) if like == "rosen" else GaussianLikelihood(mu, np.diag(invcov).copy() if like == "diag" else invcov)
 box = 5.0 if like == "rosen" else 50.0
-eng = HipEnsemble(T, W, D, lk, -box, box, seed=5, adaptation_lag=50, adaptation_time=10, stop_adaptation=stop)
-eng.upload(np.clip(np.random.RandomState(11).randn(T, W, D), -0.9 * box, 0.9 * box), betas=orc.make_ladder(D, ntemps=T))
+lo, hi, x0 = -box, box, np.clip(np.random.RandomState(11).randn(T, W, D), -0.9 * box, 0.9 * box)
+if like == "hetero":               # tests/problems.py: per-coordinate box, proposals leaving it, pinned coordinates
+    from tests import problems as pb
+    prob = pb.hetero_problem(D, "dense")
+    lk, lo, hi, x0 = pu.device_likelihood(prob), prob.lo, prob.hi, prob.x0(T, W)
+eng = HipEnsemble(T, W, D, lk, lo, hi, seed=5, adaptation_lag=50, adaptation_time=10, stop_adaptation=stop)
+eng.upload(x0, betas=orc.make_ladder(D, ntemps=T))
 eng.eval_state()
 eng.step(2); eng.step(n // 2); eng.step(n - n // 2)
 x, L, P, betas = eng.download()
@@ -339,7 +377,8 @@ np.savez(sys.argv[8], x=x, L=L, P=P, betas=betas, accepted=c["accepted"], swaps_
 
 @pytest.mark.parametrize("T,W,D,like,iters,stop", [(8, 16384, 64, "dense", 60, -1), (4, 512, 64, "dense", 300, -1), (8, 2048, 64, "diag", 300, -1),
                                                     (8, 2048, 64, "rosen", 300, 40), (8, 1168, 64, "dense", 200, 30), (16, 512, 64, "dense", 200, -1),
-                                                    (2, 512, 64, "diag", 200, -1)])
+                                                    (2, 512, 64, "diag", 200, -1), (4, 512, 64, "hetero", 60, -1),
+                                                    (8, 1168, 64, "hetero", 60, 30)])
 def test_persistent_pipelined_first_launch_equals_the_rounds_of_workgroups(T, W, D, like, iters, stop, tmp_path):
     """k_stretch2 (hens_tile2.h; round 6): launches of more than one round of workgroups at D = 64 run the first half-step in
     persistent workgroups that walk two tiles, tile n + 1's phase A and part of its gathers under tile n's likelihood / accept

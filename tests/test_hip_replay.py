@@ -20,30 +20,36 @@ pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 
-def _engine(T, W, D, like, box, seed, **kw):
+def _engine(T, W, D, like, box, seed, lo=None, hi=None, **kw):
     from eryn_amd.engine import HipEnsemble
-    return HipEnsemble(T, W, D, like, -box, box, seed=seed, **kw)
+    return HipEnsemble(T, W, D, like, -box if lo is None else lo, box if hi is None else hi, seed=seed, **kw)
 
 
 def _run_case(T, W, D, like_kind="dense", box=50.0, seed=77, calls=(1, 3), x_scale=1.0, mh=None, period=None, nsplits=2,
-              start_iter=0, set_iter=None, plans=None, **kw):
+              start_iter=0, set_iter=None, plans=None, problem=None, coverage=None, **kw):
     """Replay ``calls`` of hens_step through the oracle.  ``set_iter``: the counter (and, with adaptation on, the adaptation time)
     moved on the freshly uploaded state first (hens_set_iteration: a resumed chain); ``start_iter``: an unobserved call of that many
     iterations in front of the replay, whose end state and counters the oracle starts from; ``plans``: a list that receives each
-    replayed call's (first iteration, iterations, round-key window plans inside the call, plans of the state read-back after it)."""
+    replayed call's (first iteration, iterations, round-key window plans inside the call, plans of the state read-back after it);
+    ``problem``: a tests/problems.Problem in place of the default Gaussian under the scalar box (its likelihood kind, per-coordinate
+    box, start positions and periods); ``coverage``: a dict of problems.new_coverage that counts what the oracle's proposals did at
+    the box."""
     from eryn_amd.likelihood import GaussianLikelihood, RosenbrockLikelihood
     mu, invcov = pu.gaussian_problem(D, dense=(like_kind == "dense"))
-    if like_kind == "dense":
+    if problem is not None:
+        like_kind, like, fn = problem.like_kind, pu.device_likelihood(problem), problem.loglike
+        period = problem.period if period is None else period
+    elif like_kind == "dense":
         like, fn = GaussianLikelihood(mu, invcov), (lambda x: orc.gaussian_log_like(x, mu, invcov))
     elif like_kind == "diag":
         iv = np.diag(invcov).copy()
         like, fn = GaussianLikelihood(mu, iv), (lambda x: orc.gaussian_diag_log_like(x, mu, iv))
     else:
         like, fn = RosenbrockLikelihood(D), (lambda x: orc.rosenbrock_log_like(x))
-    eng = _engine(T, W, D, like, box, seed, **kw)
-    lo, hi = np.full(D, -box), np.full(D, box)
+    lo, hi = (np.full(D, -box), np.full(D, box)) if problem is None else (problem.lo, problem.hi)
+    eng = _engine(T, W, D, like, box, seed, lo=None if problem is None else lo, hi=None if problem is None else hi, **kw)
     # inside the prior support: the reference refuses a start with an infinite log-prior (ensemble.py:930-946)
-    x0 = np.clip(x_scale * np.random.RandomState(3).randn(T, W, D), -0.95 * box, 0.95 * box)
+    x0 = np.clip(x_scale * np.random.RandomState(3).randn(T, W, D), -0.95 * box, 0.95 * box) if problem is None else problem.x0(T, W)
     tempered = T > 1
     eng.upload(x0, betas=orc.make_ladder(D, ntemps=T) if tempered else None)
     eng.eval_state()
@@ -75,7 +81,7 @@ def _run_case(T, W, D, like_kind="dense", box=50.0, seed=77, calls=(1, 3), x_sca
         eng.synchronize()
         in_call = eng.timing()["n_plan"] if plans is not None else 0
         kinds += ru.replay(eng, st, it0, n, fn, lo, hi, mh=mh is not None, period=period, nsplits=nsplits,
-                           adaptive=kw.get("adaptive", True), stop_adaptation=kw.get("stop_adaptation", -1))
+                           adaptive=kw.get("adaptive", True), stop_adaptation=kw.get("stop_adaptation", -1), coverage=coverage)
         x, L, P, betas = eng.download()
         if plans is not None:              # (the timing of a call is reset by the next call only: it goes on counting the read-back)
             plans.append((it0, n, in_call, eng.timing()["n_plan"] - in_call))

@@ -37,6 +37,18 @@ def check_logl(L, Lref, rtol=RTOL_L, what=""):
     return rel
 
 
+def note(rel, values, rtol=RTOL_L, what=""):
+    """An observation a child process made (it went through ``check_logl`` there): recorded under the running test and held to
+    the same bar."""
+    e = _seen.setdefault(_test_name(), {"max_rel_L": 0.0, "rtol": rtol, "comparisons": 0, "values": 0})
+    e["max_rel_L"] = max(e["max_rel_L"], float(rel))
+    e["rtol"] = max(e["rtol"], rtol)
+    e["comparisons"] += 1
+    e["values"] += int(values)
+    assert rel <= rtol, f"{what}: log-likelihood differs from the oracle by {rel:.3e} relative (bar {rtol:.0e})"
+    return rel
+
+
 def report():
     return dict(sorted(_seen.items()))
 
