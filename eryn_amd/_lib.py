@@ -39,6 +39,7 @@ class HensTiming(C.Structure):
 
 
 RJ_MOVE_MH, RJ_MOVE_BD, RJ_MOVE_BD_ALL, RJ_MOVE_STRETCH = 0, 1, 2, 3      # include/hipensemble.h: HENS_RJ_MOVE_*
+RJ_INMODEL_GAUSSIAN, RJ_INMODEL_STRETCH = 0, 1                           # include/hipensemble.h: HENS_RJ_INMODEL_*
 
 
 class HensRjDraws(C.Structure):
@@ -114,6 +115,7 @@ SIGNATURES = {
     "hens_rj_set_model": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, _P, C.c_int32, _P, _P, C.c_double]),
     "hens_rj_set_model_general": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, _P]),
     "hens_rj_set_mh_scale": (C.c_int, [_P, _P]),
+    "hens_rj_set_mh_chol": (C.c_int, [_P, _P]),
     "hens_rj_mh_step": (C.c_int, [_P, _P, _P, _P]),
     "hens_rj_bd_step": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P]),
     "hens_rj_step": (C.c_int, [_P, C.c_int64]),
@@ -121,6 +123,8 @@ SIGNATURES = {
     "hens_rj_debug_draws": (C.c_int, [_P, C.c_int64] + [_P] * 11),
     "hens_rj_debug_resident": (C.c_int, [_P, _P, _P]),
     "hens_rj_set_schedule": (C.c_int, [_P, C.c_int32]),
+    "hens_rj_set_in_model": (C.c_int, [_P, C.c_int32]),
+    "hens_rj_debug_draws_stretch": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P]),
     "hens_rj_bd_all_step": (C.c_int, [_P, _P, _P, _P, _P, _P]),
     "hens_rj_propose": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P]),
     "hens_rj_accept": (C.c_int, [_P, _P, _P]),

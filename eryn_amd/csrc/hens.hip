@@ -201,6 +201,8 @@ struct hens_ctx_impl {
     bool rj_general = false;                 // hens_rj_set_model_general: leaf widths other than 3 / no template likelihood - hens_rj_propose / _accept only
     bool rj_tm_drift = false;        // hens_rj_step has updated the resident templates by +- a leaf since their last full evaluation
     int rj_st_ns = 0;                       // hens_rj_stretch_split: walkers of the half being moved
+    int rj_st_split = 0;                    // hens_rj_step, stretch move: the half the next launch moves
+    int rj_in_model = HENS_RJ_INMODEL_GAUSSIAN;      // hens_rj_set_in_model: the in-model move of hens_rj_step
     unsigned* rj_ad_flag = nullptr;  // the folded adaptation's "ladder published" word (RjArgs::ad_flag), serial of the last folding launch
     uint32_t rj_ad_serial = 0;
     bool rj_defer_adapt = false;     // hens_rj_step: the adaptation behind a cascade rides in the next k_rj launch
@@ -209,7 +211,9 @@ struct hens_ctx_impl {
     bool comm_on = false;               // ... and they belong to the rows as they are (false after an upload / a parity-API move)
     int64_t rj_num_mh = 0, rj_num_bd = 0;
     bool rj_have_scale = false;
-    int rj_schedule = 0;                    // hens_rj_set_schedule: 0 "separate_branches", 1 "iterate_branches", 2 "together" (ensemble.py:414-480)
+    bool rj_have_chol = false;              // hens_rj_set_mh_chol: the in-model Gaussian step is L z per leaf (rj_chol), not scale x z
+    double rj_chol[RJ_MAX_BRANCH][RJ_ND][RJ_ND] = {};
+    int rj_schedule = 0;                    // hens_rj_set_schedule: 0 "separate_branches", 1 "iterate_branches", 2 "together" (ensemble.py:414-480), 3 no birth / death move
     const uint32_t* adapt_src = nullptr;   // pending swap counts: swap_part (nullptr) or the mailbox's reduced counts
     int adapt_nblocks = 0;
 
@@ -1597,7 +1601,7 @@ bool iteration_is_mh(const hens_ctx_impl* c) {
 // branch's leaf log-density and (branch, leaf slot, dimension, leaf kind)
 int rj_push_ctab(hens_ctx_impl* c) {
     const RjModel& M = c->rj;
-    std::vector<double> tab(4 * RJ_MAX_RW, 0.0);
+    std::vector<double> tab(RJ_CTAB_ROWS * RJ_MAX_RW, 0.0);
     std::vector<int32_t> bn(RJ_MAX_RW, 0);
     for (int b = 0; b < M.nb; ++b)
         for (int n = 0; n < M.nl[b]; ++n)
@@ -1605,6 +1609,8 @@ int rj_push_ctab(hens_ctx_impl* c) {
                 const int i = M.off[b] + n * M.nd[b] + d;
                 tab[RJ_CTAB_LO + i] = M.lo[b][d]; tab[RJ_CTAB_HI + i] = M.hi[b][d];
                 tab[RJ_CTAB_SCALE + i] = M.mh_scale[b][d]; tab[RJ_CTAB_LOGP + i] = M.leaf_logp[b];
+                if (c->rj_have_chol && d < RJ_ND)
+                    for (int j = 0; j < RJ_ND; ++j) tab[RJ_CTAB_CHOL + j * RJ_MAX_RW + i] = c->rj_chol[b][d][j];
                 bn[i] = b | (n << 4) | (d << 10) | (M.kind[b] << 12) | ((M.slot0[b] + n) << 16);
             }
     int r;
@@ -1653,7 +1659,9 @@ int rj_launch(hens_ctx_impl* c, int mode, int branch, const double* step, const 
         }
     }
     if (mode == RJ_MODE_STRETCH) {                    // (a half-step: one wavefront per position of the moving half, c->rj_st_ns of them per rung)
-        a.st_own = c->rj_st_own; a.st_cw = c->rj_st_cw; a.st_uzz = c->rj_uzz; a.st_a = c->cfg.a; a.st_ns = c->rj_st_ns;
+        a.st_a = c->cfg.a; a.st_ns = c->rj_st_ns;
+        if (u_acc) { a.st_own = c->rj_st_own; a.st_cw = c->rj_st_cw; a.st_uzz = c->rj_uzz; }      // (the caller's draws)
+        else a.st_hb = c->rj_st_split | (c->idx_bits << 8);                                       // (hens_rj_step: Philox, st_own == nullptr)
     }
     const int npr = mode == RJ_MODE_STRETCH ? c->rj_st_ns : c->W;     // waves per rung
     const dim3 grid((unsigned)((npr + RJ_WAVES - 1) / RJ_WAVES), (unsigned)c->Tl), block(RJ_WAVES * 64);
@@ -1668,10 +1676,13 @@ int rj_launch(hens_ctx_impl* c, int mode, int branch, const double* step, const 
         c->rj_h_accepted = a.accepted;
     }
 #define RJ_CASE(MODE_, TMM_) if (mode == MODE_ && tmm == TMM_) hipLaunchKernelGGL((k_rj<MODE_, TMM_>), grid, block, 0, c->stream, a); else
+    // (Philox in-model move with a full leaf covariance: the instantiations that form L z)
+    if (mode == RJ_MODE_MH && !step && c->rj_have_chol && tmm == 0) hipLaunchKernelGGL((k_rj<RJ_MODE_MH, 0, true>), grid, block, 0, c->stream, a); else
+    if (mode == RJ_MODE_MH && !step && c->rj_have_chol && tmm == -1) hipLaunchKernelGGL((k_rj<RJ_MODE_MH, -1, true>), grid, block, 0, c->stream, a); else
     RJ_CASE(RJ_MODE_EVAL, -1) RJ_CASE(RJ_MODE_EVAL, 0) RJ_CASE(RJ_MODE_EVAL, 2)
     RJ_CASE(RJ_MODE_MH, -1) RJ_CASE(RJ_MODE_MH, 0)
     RJ_CASE(RJ_MODE_BD, -1) RJ_CASE(RJ_MODE_BD, 1)
-    RJ_CASE(RJ_MODE_STRETCH, -1)
+    RJ_CASE(RJ_MODE_STRETCH, -1) RJ_CASE(RJ_MODE_STRETCH, 0)
     RJ_CASE(RJ_MODE_MH, -2) RJ_CASE(RJ_MODE_BD, -2) RJ_CASE(RJ_MODE_STRETCH, -2) RJ_CASE(RJ_MODE_EVAL, -2)
         return fail(c, HENS_ERR_INVALID, "k_rj: no instantiation for mode %d with template scheme %d", mode, tmm);
 #undef RJ_CASE
@@ -3185,6 +3196,34 @@ int hens_rj_set_mh_scale(hens_ctx* ctx, const double* scale) {
     for (int b = 0; b < c->rj.nb; ++b)
         for (int d = 0; d < RJ_ND; ++d) c->rj.mh_scale[b][d] = scale[b * RJ_ND + d];
     c->rj_have_scale = true;
+    c->rj_have_chol = false;
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    return rj_push_ctab(c);
+}
+
+// Full leaf covariances for the Philox in-model Gaussian move: chol[nbranches][3][3], the lower-triangular Cholesky factor of a
+// leaf's proposal covariance (gaussian.py:265-268 draws multivariate_normal(0, cov)); step = L z with the unit normals z the
+// diagonal path draws for the leaf's coordinates (same Philox keys)
+int hens_rj_set_mh_chol(hens_ctx* ctx, const double* chol) {
+    hens_ctx_impl* c = enter(ctx);
+    if (!c || !chol) return fail(c, HENS_ERR_INVALID, "null argument");
+    if (c->cfg.likelihood_kind != HENS_LIKE_TEMPLATE || !c->have_like) return fail(c, HENS_ERR_STATE, "hens_rj_set_model first");
+    if (c->rj_general) return fail(c, HENS_ERR_STATE, "the Philox in-model move belongs to hens_rj_step: template models only");
+    for (int b = 0; b < c->rj.nb; ++b)
+        for (int d = 0; d < RJ_ND; ++d)
+            for (int j = 0; j < RJ_ND; ++j) {
+                const double v = chol[(b * RJ_ND + d) * RJ_ND + j];
+                if (!(std::fabs(v) < INFINITY)) return fail(c, HENS_ERR_INVALID, "hens_rj_set_mh_chol: non-finite entry");
+                if (j > d && v != 0.0) return fail(c, HENS_ERR_INVALID, "hens_rj_set_mh_chol: the factor must be lower triangular");
+                if (j == d && !(v > 0.0)) return fail(c, HENS_ERR_INVALID, "hens_rj_set_mh_chol: the covariance is not positive definite (diagonal of its factor <= 0)");
+            }
+    for (int b = 0; b < c->rj.nb; ++b)
+        for (int d = 0; d < RJ_ND; ++d) {
+            for (int j = 0; j < RJ_ND; ++j) c->rj_chol[b][d][j] = chol[(b * RJ_ND + d) * RJ_ND + j];
+            c->rj.mh_scale[b][d] = c->rj_chol[b][d][d];
+        }
+    c->rj_have_scale = true;
+    c->rj_have_chol = true;
     HIPCHK(c, hipSetDevice(c->cfg.device_id));
     return rj_push_ctab(c);
 }
@@ -3341,7 +3380,11 @@ int hens_rj_step(hens_ctx* ctx, int64_t n_iters) {
     if (r) return r;
     if (n_iters < 0) return fail(c, HENS_ERR_INVALID, "n_iters < 0");
     if ((r = counter_room(c, n_iters))) return r;
-    if (!c->rj_have_scale) return fail(c, HENS_ERR_STATE, "in-model step scale not set (hens_rj_set_mh_scale)");
+    const bool stretch = c->rj_in_model == HENS_RJ_INMODEL_STRETCH;
+    if (!stretch && !c->rj_have_scale) return fail(c, HENS_ERR_STATE, "in-model step scale not set (hens_rj_set_mh_scale)");
+    if (stretch && !c->cfg.live_dangerously && c->W < 2 * c->rj.ind_off)             // red_blue.py:103-114 (every slot of every branch counts)
+        return fail(c, HENS_ERR_TOO_FEW_WALKERS, "It is unadvisable to use a red-blue move with fewer walkers than twice the number of dimensions. "
+                                                 "If you would like to do this, please set live_dangerously to True.");
     HIPCHK(c, hipSetDevice(c->cfg.device_id));
     state_to_fields(c);                       // (hens_step leaves the state in record mode)
     HIPCHK(c, hipEventRecord(c->ev0, c->stream));
@@ -3378,11 +3421,27 @@ int hens_rj_step(hens_ctx* ctx, int64_t n_iters) {
         if (c->rj_tm && c->iter % RJ_REFRESH == RJ_REFRESH - 1 && !fresh && c->rj_tm_drift)
             if ((r = rj_launch(c, RJ_MODE_EVAL, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0))) return r;
         fresh = false;
-        c->rj_tm_drift = c->rj_tm != nullptr;
-        // in-model Gaussian move on the packed leaves, then swaps + adaptation (mh.py:190-191)
-        if ((r = rj_launch(c, RJ_MODE_MH, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, tmode))) return r;
+        c->rj_tm_drift = c->rj_tm != nullptr && c->rj_schedule != 3;      // (only birth / death updates a template by +- a leaf)
+        if (stretch) {
+            // red / blue stretch move over every branch and leaf slot: two launches, a half each - the complements of a half
+            // belong to the other set, which its launch does not write (red_blue.py:148-323); ONE move (num_mh)
+            const int n0 = (c->W + 1) / 2;
+            for (int h = 0; h < 2; ++h) {
+                c->rj_st_split = h;
+                c->rj_st_ns = h == 0 ? n0 : c->W - n0;
+                if (c->rj_st_ns == 0) continue;
+                if ((r = rj_launch(c, RJ_MODE_STRETCH, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, tmode))) return r;
+            }
+        } else {
+            // in-model Gaussian move on the packed leaves (mh.py:56-193)
+            if ((r = rj_launch(c, RJ_MODE_MH, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, tmode))) return r;
+        }
         c->rj_num_mh += 1;
-        rj_cascade(c, 2 * c->iter, true);
+        rj_cascade(c, 2 * c->iter, true);         // swaps + adaptation (mh.py:190-191, red_blue.py:326-328)
+        if (c->rj_schedule == 3) {                // no reversible-jump move (EnsembleSampler without rj_moves): counter and keys as ever
+            c->iter += 1;
+            continue;
+        }
         if (c->rj_schedule == 2) {
             // "together" (ensemble.py:414-432): ONE proposal changes a leaf in every branch of the walker; one accept test
             if ((r = rj_launch(c, RJ_MODE_BD, -1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, c->rj_tm ? 1 : -1))) return r;
@@ -3478,8 +3537,77 @@ int hens_rj_set_schedule(hens_ctx* ctx, int32_t schedule) {
     hens_ctx_impl* c = enter(ctx);
     if (!c) return fail(c, HENS_ERR_INVALID, "null context");
     if (c->cfg.likelihood_kind != HENS_LIKE_TEMPLATE) return fail(c, HENS_ERR_STATE, "hens_rj_* needs a context created with HENS_LIKE_TEMPLATE");
-    if (schedule < 0 || schedule > 2) return fail(c, HENS_ERR_UNSUPPORTED, "rj schedule must be 0 (separate_branches), 1 (iterate_branches) or 2 (together)");
+    if (schedule < 0 || schedule > 3) return fail(c, HENS_ERR_UNSUPPORTED, "rj schedule must be 0 (separate_branches), 1 (iterate_branches), 2 (together) or 3 (none)");
     c->rj_schedule = schedule;
+    return HENS_OK;
+}
+
+int hens_rj_set_in_model(hens_ctx* ctx, int32_t kind) {
+    hens_ctx_impl* c = enter(ctx);
+    if (!c) return fail(c, HENS_ERR_INVALID, "null context");
+    if (c->cfg.likelihood_kind != HENS_LIKE_TEMPLATE) return fail(c, HENS_ERR_STATE, "hens_rj_* needs a context created with HENS_LIKE_TEMPLATE");
+    if (c->rj_general) return fail(c, HENS_ERR_STATE, "the Philox in-model move belongs to hens_rj_step: template models only");
+    if (kind != HENS_RJ_INMODEL_GAUSSIAN && kind != HENS_RJ_INMODEL_STRETCH)
+        return fail(c, HENS_ERR_INVALID, "in-model move must be HENS_RJ_INMODEL_GAUSSIAN or HENS_RJ_INMODEL_STRETCH");
+    c->rj_in_model = kind;
+    return HENS_OK;
+}
+
+// The stretch move's draws of iteration `iter` in the form hens_rj_stretch_split takes: k_rj_debug_stretch lists them by split
+// position; here the two sets are put in ascending walker order and a complement becomes its index in the other set's list.
+int hens_rj_debug_draws_stretch(hens_ctx* ctx, int64_t iter, uint8_t* labels, int64_t* rint, double* u_zz, double* u_acc) {
+    hens_ctx_impl* c = enter(ctx);
+    if (!c || iter < 0) return fail(c, HENS_ERR_INVALID, "null context / negative iteration");
+    if (c->cfg.likelihood_kind != HENS_LIKE_TEMPLATE || c->rj.nb <= 0) return fail(c, HENS_ERR_STATE, "hens_rj_set_model first");
+    if (!labels || !rint || !u_zz || !u_acc) return fail(c, HENS_ERR_INVALID, "null output");
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    const int Tl = c->Tl, W = c->W, nb = c->rj.nb, n0 = (W + 1) / 2;
+    const size_t TW = (size_t)Tl * W;
+    struct Scratch {
+        std::vector<void*> p;
+        ~Scratch() { for (void* q : p) (void)hipFree(q); }
+    } sc;
+    auto grab = [&](size_t bytes) -> void* {
+        void* q = nullptr;
+        if (hipMalloc(&q, std::max<size_t>(bytes, 8)) != hipSuccess) return nullptr;
+        sc.p.push_back(q);
+        return q;
+    };
+    RjDebugStretchArgs a{};
+    a.own = (int32_t*)grab(TW * 4); a.cw = (int32_t*)grab(TW * nb * 4); a.uzz = (double*)grab(TW * 8); a.uacc = (double*)grab(TW * 8);
+    if (!a.own || !a.cw || !a.uzz || !a.uacc) return fail(c, HENS_ERR_HIP, "hens_rj_debug_draws_stretch: out of device memory");
+    a.iter = (uint64_t)iter; a.seed = c->cfg.seed;
+    a.Tl = Tl; a.W = W; a.rung_begin = c->cfg.rung_begin; a.nb = nb; a.bits = c->idx_bits;
+    hipLaunchKernelGGL(k_rj_debug_stretch, dim3(grid_for((int64_t)TW)), dim3(256), 0, c->stream, a);
+    HIPCHK(c, hipGetLastError());
+    std::vector<int32_t> own(TW), cw(TW * nb);
+    std::vector<double> uz(TW), ua(TW);
+    HIPCHK(c, hipMemcpyAsync(own.data(), a.own, TW * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(cw.data(), a.cw, TW * nb * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(uz.data(), a.uzz, TW * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(ua.data(), a.uacc, TW * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    std::fill(rint, rint + (size_t)2 * nb * Tl * n0, (int64_t)0);
+    std::fill(u_zz, u_zz + (size_t)2 * Tl * n0, 0.0);
+    std::fill(u_acc, u_acc + (size_t)2 * Tl * n0, 0.0);
+    std::vector<int32_t> qof(W), rank(W);
+    for (int t = 0; t < Tl; ++t) {
+        for (int q = 0; q < W; ++q) {
+            const int w = own[(size_t)t * W + q];
+            if (w < 0 || w >= W) return fail(c, HENS_ERR_STATE, "hens_rj_debug_draws_stretch: the split is not a permutation");
+            qof[w] = q;
+            labels[(size_t)t * W + w] = q >= n0 ? 1 : 0;
+        }
+        int cnt[2] = {0, 0};
+        for (int w = 0; w < W; ++w) rank[w] = cnt[labels[(size_t)t * W + w]]++;       // index in the own set's ascending list
+        for (int w = 0; w < W; ++w) {
+            const int h = labels[(size_t)t * W + w], k = rank[w];
+            const size_t e = (size_t)t * W + qof[w];
+            for (int b = 0; b < nb; ++b) rint[(((size_t)h * nb + b) * Tl + t) * n0 + k] = rank[cw[(size_t)b * TW + e]];
+            u_zz[((size_t)h * Tl + t) * n0 + k] = uz[e];
+            u_acc[((size_t)h * Tl + t) * n0 + k] = ua[e];
+        }
+    }
     return HENS_OK;
 }
 
@@ -3488,7 +3616,8 @@ int hens_rj_debug_draws(hens_ctx* ctx, int64_t iter, double* step, double* u_mh,
     hens_ctx_impl* c = enter(ctx);
     if (!c || iter < 0) return fail(c, HENS_ERR_INVALID, "null context / negative iteration");
     if (c->cfg.likelihood_kind != HENS_LIKE_TEMPLATE || c->rj.nb <= 0) return fail(c, HENS_ERR_STATE, "hens_rj_set_model first");
-    if (!c->rj_have_scale) return fail(c, HENS_ERR_STATE, "in-model step scale not set (hens_rj_set_mh_scale)");
+    const bool stretch = c->rj_in_model == HENS_RJ_INMODEL_STRETCH;       // (its draws: hens_rj_debug_draws_stretch; step / u_mh are zeros here)
+    if (!stretch && !c->rj_have_scale) return fail(c, HENS_ERR_STATE, "in-model step scale not set (hens_rj_set_mh_scale)");
     if (!step || !u_mh || !branch || !coin || !sel || !birth || !u_bd) return fail(c, HENS_ERR_INVALID, "null output");
     HIPCHK(c, hipSetDevice(c->cfg.device_id));
     const size_t TW = (size_t)c->Tl * c->W, IO = (size_t)c->rj.ind_off;
@@ -3508,12 +3637,16 @@ int hens_rj_debug_draws(hens_ctx* ctx, int64_t iter, double* step, double* u_mh,
     a.sel = (uint32_t*)grab(TW * 4); a.birth = (double*)grab(TW * RJ_ND * 8); a.u_bd = (double*)grab(TW * 8);
     if (!a.step || !a.u_mh || !a.coin || !a.sel || !a.birth || !a.u_bd) return fail(c, HENS_ERR_HIP, "hens_rj_debug_draws: out of device memory");
     a.iter = (uint64_t)iter; a.seed = c->cfg.seed;
-    a.Tl = c->Tl; a.W = c->W; a.rung_begin = c->cfg.rung_begin;
-    // "separate_branches": the chosen branch's draws; "iterate_branches": every branch's, in order (outputs [nbranches][...])
-    const int nsub = c->rj_schedule >= 1 ? c->rj.nb : 1;
-    *branch = c->rj_schedule >= 1 ? -1 : rj_branch_of(c, (uint64_t)iter);
+    a.Tl = c->Tl; a.W = c->W; a.rung_begin = c->cfg.rung_begin; a.stretch = stretch ? 1 : 0;
+    a.use_chol = c->rj_have_chol ? 1 : 0;
+    memcpy(a.chol, c->rj_chol, sizeof(a.chol));
+    // "separate_branches" (and no birth / death move at all: what one WOULD draw): the chosen branch's draws; "iterate_branches",
+    // "together": every branch's, in order (outputs [nbranches][...])
+    const bool every = c->rj_schedule == 1 || c->rj_schedule == 2;
+    const int nsub = every ? c->rj.nb : 1;
+    *branch = every ? -1 : rj_branch_of(c, (uint64_t)iter);
     for (int k = 0; k < nsub; ++k) {
-        a.branch = c->rj_schedule >= 1 ? k : *branch;
+        a.branch = every ? k : *branch;
         a.acc_branch = c->rj_schedule == 2 ? c->rj.nb : a.branch;      // ("together": ONE accept uniform, in every row of u_bd)
         hipLaunchKernelGGL(k_rj_debug_draws, dim3(grid_for((int64_t)TW)), dim3(256), 0, c->stream, a);
         HIPCHK(c, hipGetLastError());

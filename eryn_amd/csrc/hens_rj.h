@@ -15,8 +15,10 @@
 // Gaussian pulses + sine waves, tests/test_eryn.py:38-92), everything per walker (proposal, prior over the active
 // leaves, accept test) is wave-uniform.  Modes: evaluation of the resident state, the in-model GaussianMove on all
 // active leaves (mh.py:56-193, gaussian.py:68-115), and the birth / death move of DistributionGenerateRJ on one branch
-// (distgenrj.py:35-222, rj.py:145-388 incl. edge factors and fix_logp_gibbs, move.py:368-402).  Draws come from the
-// caller (parity mode: the reference's R / G draws) or from Philox counters (production).
+// (distgenrj.py:35-222, rj.py:145-388 incl. edge factors and fix_logp_gibbs, move.py:368-402), and one half of the red / blue
+// StretchMove over every branch and leaf slot (red_blue.py:103-330, stretch.py:74-231).  Draws come from the caller (parity mode:
+// the reference's R / G draws) or from Philox counters (production: the Gaussian move with diagonal or full leaf covariances,
+// the stretch move, birth / death).
 // All file:line citations are relative to /root/reference/src/eryn unless they name tests/.
 #pragma once
 #include "hens_kernels.h"
@@ -33,9 +35,11 @@ constexpr int RJ_MAX_ND = 4;
 #define RJ_CBN_KIND(v) (((v) >> 12) & 3)
 #define RJ_CBN_SLOT(v) ((v) >> 16)
 constexpr int RJ_CTAB_LO = 0, RJ_CTAB_HI = RJ_MAX_RW, RJ_CTAB_SCALE = 2 * RJ_MAX_RW, RJ_CTAB_LOGP = 3 * RJ_MAX_RW;     // RjArgs::ctab
+constexpr int RJ_CTAB_CHOL = 4 * RJ_MAX_RW, RJ_CTAB_ROWS = 7;          // rows 4 - 6: L[d][0 .. 2] of the coordinate's dimension d (hens_rj_set_mh_chol)
 enum { RJ_KIND_PULSE = 0, RJ_KIND_SINE = 1 };
 enum { RJ_MODE_EVAL = 0, RJ_MODE_MH = 1, RJ_MODE_BD = 2, RJ_MODE_STRETCH = 3 };
-enum : uint32_t { PURPOSE_RJ_NORMAL = 20, PURPOSE_RJ_ACC = 21, PURPOSE_RJ_BD = 22, PURPOSE_RJ_BIRTH = 23, PURPOSE_RJ_BRANCH = 24 };
+enum : uint32_t { PURPOSE_RJ_NORMAL = 20, PURPOSE_RJ_ACC = 21, PURPOSE_RJ_BD = 22, PURPOSE_RJ_BIRTH = 23, PURPOSE_RJ_BRANCH = 24,
+                  PURPOSE_RJ_SPLIT = 25, PURPOSE_RJ_STRETCH = 26 };
 
 struct RjModel {
     int32_t nb, RW, ndata, ind_off;                 // branches, record width (doubles), data points, offset of the first mask
@@ -98,11 +102,14 @@ struct RjArgs {
     // RJ_MODE_STRETCH (round 5): one half of the red / blue StretchMove over EVERY branch and leaf slot of a walker (stretch.py:
     // 160-231 loops the branches: one complement walker per branch, one stretch factor per walker; red_blue.py:148-323).  One
     // wavefront per POSITION of the moving half: walker st_own[tl][k]; u_acc / keep_out are indexed by position too.
+    // Production (hens_rj_step with HENS_RJ_INMODEL_STRETCH): st_own == nullptr - walker, complements, zz and the accept uniform
+    // come from Philox in registers (rj_split_* / rj_stretch_key below), st_hb says which half moves.
     const int32_t* st_own;              // [Tl][st_ns] the moving walkers (ascending per rung: red_blue.py:150-154)
     const int32_t* st_cw;               // [nbranches][Tl][st_ns] every branch's complement walker (stretch.py:93-100, 205)
     const double* st_uzz;               // [Tl][st_ns] the uniforms behind zz (stretch.py:129-132)
     double st_a;                        // stretch scale
-    int32_t st_ns, st_pad_;
+    int32_t st_ns;
+    int32_t st_hb;                      // production: half that moves | bits of the split permutation << 8
 };
 
 // k_adapt's arithmetic (tempering.py:563-596) in one wavefront, T <= 64: lane j owns rung j; same operations in the same order
@@ -256,6 +263,25 @@ __device__ __forceinline__ double rj_accept_uniform(uint64_t seed, uint64_t it, 
     return u01(d.x, d.y);
 }
 
+// Red / blue stretch move of the production path (hens_rj_step, HENS_RJ_INMODEL_STRETCH; red_blue.py:119-154, stretch.py:93-132, 205):
+//   split       rung t's shuffled order is the keyed permutation prp(., prp_key(seed, iter, PURPOSE_RJ_SPLIT, t)): the walkers at
+//               positions [0, n0), n0 = ceil(W / 2), are set 0, the others set 1 - a uniform balanced labelling in closed form;
+//               position k of half h holds walker prp(h n0 + k): a wave finds its walker without a table
+//   complement  of branch b: word x of the call keyed (iter, wid, PURPOSE_RJ_STRETCH | h << 8 | b << 16) picks a position of the
+//               OTHER half (rj_pick: uniform on [0, Nc)) - every branch its own walker (stretch.py:205)
+//   zz          u01(words y, z) of branch 0's call (stretch.py:128-132: first branch only)
+//   accept      rj_acc_key(RJ_MODE_STRETCH, h)
+// keyed by the WALKER (wid = global rung * W + walker), so the order in which positions are enumerated does not matter.
+__device__ __forceinline__ uint32_t rj_stretch_key(int half, int branch) { return PURPOSE_RJ_STRETCH | ((uint32_t)half << 8) | ((uint32_t)branch << 16); }
+__device__ __forceinline__ int rj_split_n0(int W) { return (W + 1) >> 1; }
+__device__ __forceinline__ int rj_split_walker(const uint32_t* key, int bits, int W, int half, int k) {      // walker at position k of half `half`
+    return (int)prp((uint32_t)(half * rj_split_n0(W) + k), key, bits, (uint32_t)W);
+}
+__device__ __forceinline__ int rj_split_complement(const uint32_t* key, int bits, int W, int half, uint32_t word) {
+    const int n0 = rj_split_n0(W), Nc = half == 0 ? W - n0 : n0;
+    return rj_split_walker(key, bits, W, 1 - half, rj_pick(word, Nc));
+}
+
 #ifndef HENS_RJ_WAVES
 #define HENS_RJ_WAVES 1
 #endif
@@ -274,7 +300,9 @@ constexpr int RJ_WPE(int mode, int tmm) { return (mode == RJ_MODE_BD && tmm == 1
 // MODE, TMM: RjArgs::mode and the resident-template scheme (-1: RjArgs::tm == nullptr, else RjArgs::tm_mode) as compile-time
 // parameters - one instantiation per launch kind (hens.hip: rj_launch), so that the birth / death launch by difference does not
 // carry the registers of the full evaluation's leaf loops, nor the in-model launch those of the birth / death proposal.
-template <int MODE, int TMM>
+// CHOL (in-model move, Philox draws): the step is L z per leaf, the Cholesky factor's rows out of RjArgs::ctab (hens_rj_set_mh_chol) -
+// an instantiation of its own: as a run-time branch the extra live values cost the diagonal launch two spilled registers.
+template <int MODE, int TMM, bool CHOL = false>
 __global__ __launch_bounds__(RJ_WAVES * 64) __attribute__((amdgpu_waves_per_eu(RJ_WPE(MODE, TMM)))) void k_rj(const RjArgs A) {
     constexpr bool HAVE_TM = TMM >= 0;
     __shared__ double s_cur[RJ_WAVES][RJ_MAX_RW];
@@ -298,7 +326,24 @@ __global__ __launch_bounds__(RJ_WAVES * 64) __attribute__((amdgpu_waves_per_eu(R
     auto ndb = [&](const int b) { return GEN ? M.nd[b] : RJ_ND; };
     auto slot0 = [&](const int b) { return GEN ? M.slot0[b] : M.off[b] / RJ_ND; };
     const int bstride = GEN ? M.ndmax : RJ_ND;
-    const int64_t gw = MODE == RJ_MODE_STRETCH ? (int64_t)tl * A.W + A.st_own[slot] : slot;
+    // stretch half-step: the walker at this position - the caller's list, or (production) the split permutation's: its round keys are
+    // two Philox calls, lanes 0 and 1 one each, kept in scalar registers for the complements
+    int st_walker = 0;
+    uint32_t st_key[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+    if (MODE == RJ_MODE_STRETCH) {
+        if (A.st_own) {
+            st_walker = A.st_own[slot];
+        } else {
+            const u4 kk = rj_philox(A.seed, A.iter, (uint32_t)(A.rung_begin + tl), PURPOSE_RJ_SPLIT ^ ((lane & 1) ? 0x100u : 0u));
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                st_key[4 * j + 0] = (uint32_t)__builtin_amdgcn_readlane((int)kk.x, j); st_key[4 * j + 1] = (uint32_t)__builtin_amdgcn_readlane((int)kk.y, j);
+                st_key[4 * j + 2] = (uint32_t)__builtin_amdgcn_readlane((int)kk.z, j); st_key[4 * j + 3] = (uint32_t)__builtin_amdgcn_readlane((int)kk.w, j);
+            }
+            st_walker = rj_split_walker(st_key, A.st_hb >> 8, A.W, A.st_hb & 1, idx);
+        }
+    }
+    const int64_t gw = MODE == RJ_MODE_STRETCH ? (int64_t)tl * A.W + st_walker : slot;
     const int RW = M.RW;
 #ifdef HENS_RJ_TRACE_STRIDE        // DEV: every 64th walker instead of the first ones (all rounds of the launch)
 #define RJ_TRACE(i) do { if (A.trace && (gw & 63) == 0 && (gw >> 6) < A.trace_n && lane == 0) A.trace[(gw >> 6) * 8 + (i)] = trace_stamp(); } while (0)
@@ -365,8 +410,22 @@ __global__ __launch_bounds__(RJ_WAVES * 64) __attribute__((amdgpu_waves_per_eu(R
                 double st;
                 if (A.step) {
                     st = A.step[(size_t)gw * M.ind_off + i];
-                } else {
+                } else if constexpr (!CHOL) {
                     st = (i < 64 ? c_sc : A.ctab[RJ_CTAB_SCALE + i]) * mh_normal_from32(dr.x, dr.y).x;
+                } else {
+                    // correlated step: the leaf's lanes exchange their unit normals (a leaf's three lanes move together); where the
+                    // leaf began in the previous pass of a wide record, the lower coordinates' calls again
+                    const int d = RJ_CBN_D(bn);
+                    const double z = mh_normal_from32(dr.x, dr.y).x;
+                    double z1 = __shfl_up(z, 1), z2 = __shfl_up(z, 2);
+#pragma unroll 1
+                    for (int k = lane + 1; k <= d; ++k) {                 // (coordinates i - k of the previous pass: lanes 0 and 1 of a later pass only)
+                        const double zk = rj_unit_normal(A.seed, A.iter, wid, i - k);
+                        z1 = k == 1 ? zk : z1;
+                        z2 = k == 2 ? zk : z2;
+                    }
+                    const double l0 = A.ctab[RJ_CTAB_CHOL + i], l1 = A.ctab[RJ_CTAB_CHOL + RJ_MAX_RW + i], l2 = A.ctab[RJ_CTAB_CHOL + 2 * RJ_MAX_RW + i];
+                    st = d == 0 ? l0 * z : (d == 1 ? l0 * z1 + l1 * z : (l0 * z2 + l1 * z1) + l2 * z);
                 }
                 q[i] = cur[i] + st;
             }
@@ -376,11 +435,28 @@ __global__ __launch_bounds__(RJ_WAVES * 64) __attribute__((amdgpu_waves_per_eu(R
         // every leaf slot of every branch moves, active or not (the masks only decide what prior and likelihood see): branch b's
         // slots against branch b's complement walker, one stretch factor for the walker (stretch.py:128-145, 187-218); the Hastings
         // factor counts every slot of every branch (stretch.py:222-223; without Gibbs sampling adjust_factors changes nothing)
-        const double zz = draw_zz(A.st_uzz[slot], A.st_a);                          // stretch.py:129-132
+        double uzz;
+        int cw0 = 0, cw1 = 0, cw2 = 0, cw3 = 0;                                     // production: every branch's complement walker (wave-uniform)
+        if (A.st_own) {
+            uzz = A.st_uzz[slot];
+        } else {
+            // one Philox call for everything the walker draws: lane b branch b's complement (lane 0 the stretch factor's uniform
+            // too), lane nbranches the accept uniform
+            const int half = A.st_hb & 1;
+            const u4 dr = rj_philox(A.seed, A.iter, wid, lane < M.nb ? rj_stretch_key(half, lane) : rj_acc_key(RJ_MODE_STRETCH, half));
+            const int cwl = rj_split_complement(st_key, A.st_hb >> 8, A.W, half, dr.x);
+            cw0 = __builtin_amdgcn_readlane(cwl, 0); cw1 = __builtin_amdgcn_readlane(cwl, 1);
+            cw2 = __builtin_amdgcn_readlane(cwl, 2); cw3 = __builtin_amdgcn_readlane(cwl, 3);
+            uzz = __shfl(u01(dr.y, dr.z), 0);
+            u_drawn = __shfl(u01(dr.x, dr.y), M.nb); u_have = true;
+        }
+        const double zz = draw_zz(uzz, A.st_a);                                     // stretch.py:129-132
         const size_t TN = (size_t)A.Tl * A.st_ns;
         for (int i = lane; i < M.ind_off; i += 64) {
             const int b = RJ_CBN_B(A.cbn[i]);
-            const double c = A.pool[(size_t)A.loc[(size_t)tl * A.W + A.st_cw[(size_t)b * TN + slot]] * RW + i];
+            const int cw = A.st_own ? A.st_cw[(size_t)b * TN + slot]
+                                    : ((cw0 & -(int)(b == 0)) | (cw1 & -(int)(b == 1)) | (cw2 & -(int)(b == 2)) | (cw3 & -(int)(b == 3)));
+            const double c = A.pool[(size_t)A.loc[(size_t)tl * A.W + cw] * RW + i];
             q[i] = c - (c - cur[i]) * zz;                                           // stretch.py:141-145
         }
         factors = ((double)M.ind_off - 1.0) * log(zz);                              // stretch.py:223
@@ -935,6 +1011,9 @@ struct RjDebugArgs {
     uint64_t iter, seed;
     int32_t Tl, W, rung_begin, branch;
     int32_t acc_branch;  // branch field of the accept uniform's key: the branch, or nbranches ("together": one test for all)
+    int32_t stretch;     // the in-model move is the stretch move: step / u_mh are zeros (its draws: k_rj_debug_stretch)
+    int32_t use_chol;    // hens_rj_set_mh_chol: step_d = sum_{j <= d} chol[b][d][j] z_j, ascending j
+    double chol[RJ_MAX_BRANCH][RJ_ND][RJ_ND];
 };
 __global__ void k_rj_debug_draws(const RjDebugArgs A) {
     const int64_t gw = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -946,15 +1025,53 @@ __global__ void k_rj_debug_draws(const RjDebugArgs A) {
         int b = 0;
         while (b + 1 < M.nb && i >= M.off[b + 1]) ++b;
         const int d = (i - M.off[b]) % RJ_ND;
-        A.step[(size_t)gw * M.ind_off + i] = M.mh_scale[b][d] * rj_unit_normal(A.seed, A.iter, wid, i);
+        double st = 0.0;
+        if (A.stretch) {
+            st = 0.0;
+        } else if (!A.use_chol) {
+            st = M.mh_scale[b][d] * rj_unit_normal(A.seed, A.iter, wid, i);
+        } else {
+            for (int j = 0; j <= d; ++j) {
+                const double term = A.chol[b][d][j] * rj_unit_normal(A.seed, A.iter, wid, i - d + j);
+                st = j == 0 ? term : st + term;
+            }
+        }
+        A.step[(size_t)gw * M.ind_off + i] = st;
     }
-    A.u_mh[gw] = rj_accept_uniform(A.seed, A.iter, wid, RJ_MODE_MH, 0);
+    A.u_mh[gw] = A.stretch ? 0.0 : rj_accept_uniform(A.seed, A.iter, wid, RJ_MODE_MH, 0);
     const u4 d = rj_bd_raw(A.seed, A.iter, wid, A.branch);
     A.coin[gw] = (d.x & 1u) ? +1 : -1;
     A.sel[gw] = d.y;
     for (int k = 0; k < RJ_ND; ++k)
         A.birth[(size_t)gw * RJ_ND + k] = rj_birth_coord(A.seed, A.iter, wid, A.branch, k, M.lo[A.branch][k], M.hi[A.branch][k]);
     A.u_bd[gw] = rj_accept_uniform(A.seed, A.iter, wid, RJ_MODE_BD, A.acc_branch);
+}
+
+// hens_rj_debug_draws_stretch: the stretch move's draws of iteration `iter` by split POSITION q = half * n0 + k (one thread each):
+// the walker there, every branch's complement walker, the two uniforms - the same functions k_rj<RJ_MODE_STRETCH> evaluates
+struct RjDebugStretchArgs {
+    int32_t* own;        // [Tl][W]
+    int32_t* cw;         // [nbranches][Tl][W]
+    double* uzz;         // [Tl][W]
+    double* uacc;        // [Tl][W]
+    uint64_t iter, seed;
+    int32_t Tl, W, rung_begin, nb, bits;
+};
+__global__ void k_rj_debug_stretch(const RjDebugStretchArgs A) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= (int64_t)A.Tl * A.W) return;
+    const int tl = (int)(e / A.W), q = (int)(e - (int64_t)tl * A.W);
+    const int n0 = rj_split_n0(A.W), half = q >= n0 ? 1 : 0, k = q - half * n0;
+    const PrpKey K = prp_key(A.seed, A.iter, PURPOSE_RJ_SPLIT, (uint32_t)(A.rung_begin + tl));
+    const int own = rj_split_walker(K.k, A.bits, A.W, half, k);
+    const uint32_t wid = (uint32_t)(A.rung_begin + tl) * (uint32_t)A.W + (uint32_t)own;
+    A.own[e] = own;
+    for (int b = 0; b < A.nb; ++b) {
+        const u4 d = rj_philox(A.seed, A.iter, wid, rj_stretch_key(half, b));
+        A.cw[(size_t)b * A.Tl * A.W + e] = rj_split_complement(K.k, A.bits, A.W, half, d.x);
+        if (b == 0) A.uzz[e] = u01(d.y, d.z);
+    }
+    A.uacc[e] = rj_accept_uniform(A.seed, A.iter, wid, RJ_MODE_STRETCH, half);
 }
 
 }  // namespace hens

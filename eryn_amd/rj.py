@@ -165,6 +165,7 @@ class RJEngine:
                                device_id=device_id, a=a)
         self.lib, self.ctx = self.eng.lib, self.eng.ctx
         self.schedule = "separate_branches"
+        self.in_model = "gaussian"   # the in-model move of ``step`` (set_in_model)
         self.host_like = None        # a CallableLikelihood: every parity move = propose on the device, evaluate here, accept on the device
         nb = len(self.branches)
         kinds = np.array([b.kind for b in self.branches], dtype=np.int32)
@@ -334,14 +335,30 @@ class RJEngine:
         s = f64(scale, (len(self.branches), 3))
         check(self.lib.hens_rj_set_mh_scale(self.ctx, ptr(s)), self.ctx)
 
+    def set_mh_chol(self, chol):
+        """Lower-triangular Cholesky factors of the leaves' proposal covariances, [nbranches, 3, 3]: the in-model Gaussian step of
+        ``step`` becomes ``L @ z`` per leaf (include/hipensemble.h: hens_rj_set_mh_chol).  Not positive definite -> ValueError."""
+        L = f64(chol, (len(self.branches), 3, 3))
+        check(self.lib.hens_rj_set_mh_chol(self.ctx, ptr(L)), self.ctx)
+
+    def set_in_model(self, kind):
+        """The in-model move of ``step``: "gaussian" (``set_mh_scale`` / ``set_mh_chol``) or "stretch" (the red / blue stretch move
+        with the engine's ``a`` and ``live_dangerously``; include/hipensemble.h: hens_rj_set_in_model)."""
+        code = {"gaussian": _lib.RJ_INMODEL_GAUSSIAN, "stretch": _lib.RJ_INMODEL_STRETCH}.get(kind)
+        if code is None:
+            raise ValueError("in-model move must be 'gaussian' or 'stretch'")
+        check(self.lib.hens_rj_set_in_model(self.ctx, code), self.ctx)
+        self.in_model = kind
+
     def step(self, n_iters):
         check(self.lib.hens_rj_step(self.ctx, int(n_iters)), self.ctx)
 
     def set_schedule(self, rj_moves):
-        """The sampler's ``rj_moves`` string for ``step`` (ensemble.py:434-480): "separate_branches" | "iterate_branches"."""
-        code = {"separate_branches": 0, "iterate_branches": 1, "together": 2}.get(rj_moves)
+        """The sampler's ``rj_moves`` string for ``step`` (ensemble.py:434-480): "separate_branches" | "iterate_branches" |
+        "together", or "none": no reversible-jump move (``EnsembleSampler`` without ``rj_moves``)."""
+        code = {"separate_branches": 0, "iterate_branches": 1, "together": 2, "none": 3}.get(rj_moves)
         if code is None:
-            raise ValueError("rj_moves must be 'together', 'iterate_branches', or 'separate_branches'")
+            raise ValueError("rj_moves must be 'together', 'iterate_branches', 'separate_branches' or 'none'")
         check(self.lib.hens_rj_set_schedule(self.ctx, code), self.ctx)
         self.schedule = rj_moves
 
@@ -363,6 +380,20 @@ class RJEngine:
             for k in ("coin", "sel", "birth", "u_bd"):
                 out[k] = out[k][:1]
         return out
+
+    def debug_draws_stretch(self, it):
+        """The stretch move's draws of iteration ``it`` in the form ``stretch_split`` takes (include/hipensemble.h:
+        hens_rj_debug_draws_stretch): labels [T, W]; per half h (list index) rint [nbranches, T, Ns_h], u_zz / u_acc [T, Ns_h],
+        movers in ascending walker order, Ns_0 = ceil(W / 2), Ns_1 = W - Ns_0."""
+        T, W, nb = self.T, self.W, len(self.branches)
+        n0 = (W + 1) // 2
+        labels = np.empty((T, W), dtype=np.uint8)
+        rint = np.empty((2, nb, T, n0), dtype=np.int64)
+        u_zz, u_acc = np.empty((2, T, n0)), np.empty((2, T, n0))
+        check(self.lib.hens_rj_debug_draws_stretch(self.ctx, int(it), ptr(labels), ptr(rint), ptr(u_zz), ptr(u_acc)), self.ctx)
+        ns = (n0, W - n0)
+        return dict(labels=labels, rint=[rint[h][:, :, :ns[h]].copy() for h in range(2)],
+                    u_zz=[u_zz[h][:, :ns[h]].copy() for h in range(2)], u_acc=[u_acc[h][:, :ns[h]].copy() for h in range(2)])
 
     def debug_resident(self):
         """(x, inds, log_like) as they sit on the device, without the re-evaluation a download runs first
@@ -435,7 +466,9 @@ class RJEnsembleSampler:
     rng="numpy":  the reference's streams (the sampler-owned RandomState cloned from the global ``np.random`` at
                   construction + the global stream) are drawn on the host IN THE REFERENCE'S ORDER and handed to the device:
                   same seeds => the reference's chain (tests/test_hip_rj.py against the rj* fixtures).
-    rng="philox": device-side draws, ``thin_by`` iterations per host call (``hens_rj_step``).  The device keeps every walker's
+    rng="philox": device-side draws, ``thin_by`` iterations per host call (``hens_rj_step``), with every in-model move the class
+                  accepts: ``GaussianLeafMove`` (diagonal or full leaf covariances), ``StretchLeafMove``, with or without
+                  ``rj_moves``.  The device keeps every walker's
                   model resident and updates it by +- one leaf per accepted birth / death; the models and log-likelihoods are
                   re-evaluated from the coordinates every 64 iterations and whenever the state is downloaded (the evaluation
                   runs in front of the copy, so a stored ``State.log_like`` is exactly what the device continues with and a chain
@@ -469,10 +502,6 @@ class RJEnsembleSampler:
             raise NotImplementedError("the in-model move must be an eryn_amd.rj.GaussianLeafMove or StretchLeafMove")
         if rng not in ("numpy", "philox"):
             raise ValueError("rng must be 'numpy' or 'philox'")
-        if isinstance(moves, StretchLeafMove) and rng != "numpy":
-            raise NotImplementedError("the stretch move on leaf-packing records steps with rng='numpy' (the reference's draws)")
-        if self.rj_schedule is None and rng != "numpy":
-            raise NotImplementedError("rng='philox' steps the in-model move and the birth / death move together (hens_rj_step)")
         self.branch_names = list(branch_names if branch_names is not None else ndims.keys())
         if nbranches is not None and nbranches != len(self.branch_names):
             raise ValueError("nbranches does not match branch_names")
@@ -510,16 +539,17 @@ class RJEnsembleSampler:
                                adaptation_time=tc.adaptation_time, stop_adaptation=tc.stop_adaptation,
                                **({"a": moves.a, "live_dangerously": moves.live_dangerously} if isinstance(moves, StretchLeafMove) else {}))
         self.engine.host_like = self.host_like
-        if self.rj_schedule is not None:
-            self.engine.set_schedule(rj_moves)
-        if rng == "philox":
-            # the device draws axis-aligned steps (hens_rj_set_mh_scale: three standard deviations per branch): a covariance
-            # with off-diagonal terms is another proposal - refused rather than silently reduced to its diagonal
-            for k in self.branch_names:
-                if np.any(moves.cov[k] != np.diag(np.diag(moves.cov[k]))):
-                    raise NotImplementedError("rng='philox' takes diagonal leaf covariances (rng='numpy' runs the reference's "
-                                              "multivariate_normal draws with any covariance)")
-            self.engine.set_mh_scale(np.stack([np.sqrt(np.diag(moves.cov[k])) for k in self.branch_names]))
+        if self.rj_schedule is not None or rng == "philox":
+            self.engine.set_schedule(rj_moves or "none")
+        if rng == "philox" and isinstance(moves, StretchLeafMove):
+            self.engine.set_in_model("stretch")
+        elif rng == "philox":
+            # axis-aligned steps (hens_rj_set_mh_scale: three standard deviations per branch), or - a covariance with off-diagonal
+            # terms - the Cholesky factor of every branch's leaf covariance (hens_rj_set_mh_chol: step = L z)
+            if all(np.array_equal(moves.cov[k], np.diag(np.diag(moves.cov[k]))) for k in self.branch_names):
+                self.engine.set_mh_scale(np.stack([np.sqrt(np.diag(moves.cov[k])) for k in self.branch_names]))
+            else:
+                self.engine.set_mh_chol(np.stack([np.linalg.cholesky(moves.cov[k]) for k in self.branch_names]))
         moves.accepted = np.zeros((self.ntemps, self.nwalkers))
         nmoves = len(self.branch_names) if rj_moves == "separate_branches" else (1 if self.rj_schedule else 0)    # (rj move objects, ensemble.py:414-471)
         self.rj_accepted = [np.zeros((self.ntemps, self.nwalkers)) for _ in range(nmoves)]

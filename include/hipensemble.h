@@ -427,6 +427,13 @@ int hens_rj_set_model(hens_ctx* ctx, int32_t nbranches, const int32_t* kinds, co
 int hens_rj_set_model_general(hens_ctx* ctx, int32_t nbranches, const int32_t* ndims, const int32_t* nleaves_max,
                               const int32_t* nleaves_min, const double* lo, const double* hi, const double* leaf_logp);
 int hens_rj_set_mh_scale(hens_ctx* ctx, const double* scale);
+/* The Philox in-model Gaussian move with a FULL covariance per leaf (gaussian.py:265-268: multivariate_normal(0, cov)):
+ * chol[nbranches][3][3], the lower-triangular Cholesky factor L of a branch's leaf covariance.  A leaf's step is
+ * step_d = sum_{j <= d} L[d][j] z_j, summed in ascending j without FMA contraction, z_j the unit normals hens_rj_set_mh_scale's
+ * path draws for the leaf's coordinates (same Philox keys: chol = diag(s) is the chain of hens_rj_set_mh_scale(s) bit for bit).
+ * hens_rj_debug_draws exports the correlated step.  Entries above the diagonal must be zero; a non-finite entry or a diagonal
+ * entry <= 0 (the covariance was not positive definite) -> HENS_ERR_INVALID.  The last of the two setters called holds. */
+int hens_rj_set_mh_chol(hens_ctx* ctx, const double* chol);
 int hens_rj_mh_step(hens_ctx* ctx, const double* step, const double* u_acc, uint8_t* keep_out);
 int hens_rj_bd_step(hens_ctx* ctx, int32_t branch, const int8_t* change, const int32_t* leaf, const double* birth,
                     const double* u_acc, uint8_t* keep_out);
@@ -465,6 +472,29 @@ int hens_rj_debug_resident(hens_ctx* ctx, double* rec, double* logl);
  * With schedules 1 and 2 hens_rj_debug_draws returns branch = -1 and coin / sel / birth / u_bd for every branch in order
  * ([nbranches][Tl][W]...; the caller sizes them for nbranches either way; schedule 2: every row of u_bd is the one uniform). */
 int hens_rj_set_schedule(hens_ctx* ctx, int32_t schedule);
+
+/* The in-model move of hens_rj_step:
+ *   HENS_RJ_INMODEL_GAUSSIAN (default)  the Gaussian step of hens_rj_set_mh_scale on every active leaf (mh.py:56-193).
+ *   HENS_RJ_INMODEL_STRETCH             the red / blue StretchMove over every branch and leaf slot - the reference's default move
+ *      (ensemble.py:509-514; red_blue.py:103-330, stretch.py:74-231), two launches per iteration, a half each, with the
+ *      context's `a` and `live_dangerously` (the ones hens_rj_stretch_split uses).  No step scale is asked for; fewer than
+ *      twice as many walkers as leaf coordinates -> hens_rj_step returns HENS_ERR_TOO_FEW_WALKERS before it launches anything
+ *      (red_blue.py:103-114).  Draws (counter-based on seed, iteration, global rung, walker, half, branch): rung t's split is the
+ *      keyed permutation of purpose RJ_SPLIT - positions [0, ceil(W/2)) are set 0, the rest set 1 (red_blue.py:119-124: a
+ *      uniform balanced labelling) -; branch b's complement is a uniform position of the other half (stretch.py:93-100, 205: a
+ *      walker per branch), the stretch factor's uniform comes with branch 0's call (stretch.py:128-132), the accept uniform has
+ *      the half in its key (red_blue.py:294).  Accept counts: hens_get_counters; hens_rj_get_counters' num_mh counts one per move.
+ * Schedule 3 of hens_rj_set_schedule ("none") runs the in-model move and its cascade with adaptation alone - EnsembleSampler
+ * without rj_moves: the leaf masks never change, num_bd stays 0; the iteration counter and the cascade's key 2 iter are those of
+ * the other schedules, so a chain's in-model draws do not depend on the schedule. */
+enum { HENS_RJ_INMODEL_GAUSSIAN = 0, HENS_RJ_INMODEL_STRETCH = 1 };
+int hens_rj_set_in_model(hens_ctx* ctx, int32_t kind);
+
+/* Debug / parity: the stretch move's draws of iteration `iter` IN THE FORM hens_rj_stretch_split TAKES, n0 = ceil(W / 2):
+ * labels[Tl][W] in {0, 1}; rint[2][nbranches][Tl][n0] an index into the other set's ascending walker list; u_zz, u_acc
+ * [2][Tl][n0]; movers in ascending walker order; for odd W the second half uses the first W - n0 entries of a row (the rest
+ * are zero).  On a stretch context hens_rj_debug_draws returns zeros in step / u_mh and asks for no scale. */
+int hens_rj_debug_draws_stretch(hens_ctx* ctx, int64_t iter, uint8_t* labels, int64_t* rint, double* u_zz, double* u_acc);
 
 /* Parity-mode birth / death over ALL branches in one proposal ("together"): change / leaf [nbranches][Tl][W],
  * birth [nbranches][Tl][W][3 - max(ndims) on a hens_rj_set_model_general context], ONE u_acc [Tl][W] (rj.py:145-388 with gibbs_sampling_setup = None). */
