@@ -38,6 +38,8 @@ from eryn.prior import ProbDistContainer, uniform_dist  # noqa: E402
 from eryn.moves.tempering import make_ladder  # noqa: E402
 
 HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path[1:1] = [HERE, os.path.dirname(HERE)]   # tests/ladders.py: beside this file (a copy run elsewhere) or one directory up
+from ladders import ladder                  # noqa: E402  (NumPy only; builds on the make_ladder it is handed)
 SPLIT_ABOVE = 1 << 20          # a fixture of more bytes is written in pieces of at most PART_BYTES (tests/golden_io.py reads them)
 PART_BYTES = 1 << 19
 
@@ -199,6 +201,8 @@ def capture(name, T, W, D, nsteps, box, dense=True, vectorize=True, seed_constru
     if tc is not None:
         out["betas0"] = np.array(tc.betas, copy=True)
         out["adaptive"], out["permute"] = bool(tc.adaptive), bool(tc.permute)
+        if "adaptation_lag" in (tempering_kwargs or {}):      # (only where a fixture sets them: the others keep their keys)
+            out["adaptation_lag"], out["adaptation_time"] = float(tc.adaptation_lag), float(tc.adaptation_time)
 
     np.random.seed(seed_run)                # G for the run
     np.random.shuffle, np.random.permutation, np.random.uniform = shuffle, permutation, uniform
@@ -314,3 +318,10 @@ if __name__ == "__main__":
             tempering_kwargs=dict(Tmax=np.inf))
     # F8 three sets (RedBlueMove(nsplits=3)): uneven sets 6 / 6 / 5, the complement list = the other sets in set order
     capture("f8_nsplits3", T=3, W=17, D=4, nsteps=12, box=50.0, nsplits=3)
+    # F9 a ladder the user hands over (tests/ladders.py "user": beta_0 = 0.8, a repeated pair, a steep gap, last rung 0) under a
+    # strong adaptation (lag 50, time 10: the ladder moves in its leading digits, not its last ones)
+    strong = dict(adaptation_lag=50, adaptation_time=10)
+    capture("f9_userladder", T=6, W=24, D=5, nsteps=12, box=50.0,
+            tempering_kwargs=dict(betas=ladder("user", 6, 5, make_ladder=make_ladder), **strong))
+    # F10 a ladder of more than 64 rungs (geometric), same adaptation; proposals not stored: the file stays small
+    capture("f10_longladder", T=70, W=8, D=3, nsteps=8, box=50.0, tempering_kwargs=dict(**strong), keep_q=False)

@@ -9,6 +9,9 @@ env PIPE_TEST_DELAY=1 runs everything with adaptation_delay = 1 (then "single" i
   replay <nranks> <T> <W> <D> <iters> [hetero]       N local shards against the ORACLE fed with the exported Philox draws; "hetero":
                                                      on tests/problems.hetero_problem (per-coordinate box) with its coverage asserted
   replay_from <nranks> <T> <W> <D> <start> <n,n,..>  the same after an unobserved call of <start> iterations, in calls of n
+single, local and replay take one more, optional, LAST argument ``ladder:<family>:<box>[:<lag>:<nu>]``: a ladder of tests/ladders.py
+(its families, its start positions) on the Gaussian of tests/parity_utils.py under the box (-box, box), with the adaptation's constants
+(adaptation_lag, adaptation_time); replay then asserts the family's coverage conditions (ladders.check_coverage) on the oracle's side.
 """
 import os
 import sys
@@ -26,7 +29,16 @@ from eryn_amd.moves.tempering import make_ladder  # noqa: E402
 SEED = 11
 
 
+LADDER = None                                            # dict(family, box, lag, nu): the optional last argument (main)
+
+
 def problem(T, W, D):
+    if LADDER is not None:
+        from tests import ladders as ld
+        from tests import parity_utils as pu
+        mu, invcov = pu.gaussian_problem(D)
+        betas = ld.ladder(LADDER["family"], T, D)
+        return mu, invcov, ld.tempered_start(betas, W, D, LADDER["box"]), betas
     rng = np.random.RandomState(5)
     mu = rng.uniform(-1, 1, size=D)
     a = rng.randn(D, D)
@@ -57,8 +69,9 @@ def make(T, W, D, rng_range=None, delay=None):
         like = RosenbrockLikelihood(D)
     else:
         like = GaussianLikelihood(mu, invcov)
-    e = HipEnsemble(T, W, D, like, -6.0, 6.0, seed=SEED, rung_range=rng_range,
-                    adaptation_delay=DELAY if delay is None else delay)
+    box, kw = (6.0, {}) if LADDER is None else (LADDER["box"], dict(adaptation_lag=LADDER["lag"], adaptation_time=LADDER["nu"]))
+    e = HipEnsemble(T, W, D, like, -box, box, seed=SEED, rung_range=rng_range,
+                    adaptation_delay=DELAY if delay is None else delay, **kw)
     r0, r1 = rng_range if rng_range else (0, T)
     if MODEL == "gauss_periodic":                        # periodic parameters on every rank - before the pipeline is initialised
         period = np.zeros(D)
@@ -85,17 +98,22 @@ def snapshot(e):
 
 
 def main():
-    mode = sys.argv[1]
+    global LADDER, HETERO
+    argv = list(sys.argv)
+    if len(argv) > 2 and argv[-1].startswith("ladder:"):
+        f = argv.pop().split(":")
+        LADDER = dict(family=f[1], box=float(f[2]), lag=float(f[3]) if len(f) > 3 else 10000.0, nu=float(f[4]) if len(f) > 4 else 100.0)
+    mode = argv[1]
     if mode == "single":
-        T, W, D, iters = map(int, sys.argv[2:6])
+        T, W, D, iters = map(int, argv[2:6])
         e = make(T, W, D)
         if DELAY:                                      # the delayed schedule exists in the pipeline only: one rank of it
             LadderPipeline.connect_local([e])
         for n in (iters // 2, iters - iters // 2):     # two calls: the batch / flush logic at a call boundary
             e.step(n)
-        np.savez(sys.argv[6], **snapshot(e))
+        np.savez(argv[6], **snapshot(e))
     elif mode == "local":
-        nranks, T, W, D, iters = map(int, sys.argv[2:7])
+        nranks, T, W, D, iters = map(int, argv[2:7])
         _, bounds = rung_partition(T, nranks)
         engs = [make(T, W, D, b) for b in bounds]
         LadderPipeline.connect_local(engs)
@@ -110,10 +128,10 @@ def main():
             for s in snaps[1:]:
                 assert np.array_equal(s[k], snaps[0][k]), f"{k} differs between ranks"
             out[k] = snaps[0][k]
-        np.savez(sys.argv[7], **out)
+        np.savez(argv[7], **out)
     elif mode == "ipc":
-        rank, world, T, W, D, iters = map(int, sys.argv[2:8])
-        outdir = sys.argv[8]
+        rank, world, T, W, D, iters = map(int, argv[2:8])
+        outdir = argv[8]
         import torch.distributed as dist
         dist.init_process_group("gloo", rank=rank, world_size=world)     # only to exchange the handles
         _, bounds = rung_partition(T, world)
@@ -128,8 +146,8 @@ def main():
         dist.destroy_process_group()
     elif mode == "staged":
         # the same protocol with point-to-point messages between the stages (RCCL on a multi-GPU node; gloo here)
-        rank, world, T, W, D, iters = map(int, sys.argv[2:8])
-        outdir = sys.argv[8]
+        rank, world, T, W, D, iters = map(int, argv[2:8])
+        outdir = argv[8]
         import torch.distributed as dist
         from eryn_amd.ladder import StagedPipeline
         dist.init_process_group("gloo", rank=rank, world_size=world)
@@ -146,7 +164,7 @@ def main():
     elif mode == "rccl1":
         # the library's own RCCL transport (hens_comm_init) with ONE rank - what a one-GPU box can run of it: the communicator, a
         # ncclSend / ncclRecv round trip to myself, and hens_step(n) as one call through the staged protocol's three stages
-        T, W, D, iters = map(int, sys.argv[2:6])
+        T, W, D, iters = map(int, argv[2:6])
         from eryn_amd.ladder import RcclPipeline
         e = make(T, W, D, delay=0)
         pipe = RcclPipeline(e, 0, 1)
@@ -156,7 +174,7 @@ def main():
         for n in (iters // 2, iters - iters // 2):
             pipe.step(n)
             e.synchronize()
-        np.savez(sys.argv[6], **snapshot(e))
+        np.savez(argv[6], **snapshot(e))
         pipe.close()
         e.close()
     elif mode == "replay":
@@ -164,13 +182,17 @@ def main():
         # rung, walker), so a whole-ladder context exports them and the oracle replays the pipeline's iterations
         from oracle import eryn_oracle as orc
         from tests import replay_utils as ru
-        nranks, T, W, D, iters = map(int, sys.argv[2:7])
+        nranks, T, W, D, iters = map(int, argv[2:7])
         mu, invcov, x0, betas0 = problem(T, W, D)
         fn = lambda q: orc.gaussian_log_like(q, mu, invcov)      # noqa: E731
         lo, hi, cov = np.full(D, -6.0), np.full(D, 6.0), None
-        if len(sys.argv) > 7 and sys.argv[7] == "hetero":
+        kw = {}
+        if LADDER is not None:
+            from tests import ladders as ld
+            lo, hi = np.full(D, -LADDER["box"]), np.full(D, LADDER["box"])
+            kw = dict(lag=LADDER["lag"], nu=LADDER["nu"], rungs=ld.new_stats(T))
+        if len(argv) > 7 and argv[7] == "hetero":
             from tests import problems as pb
-            global HETERO
             HETERO = pb.hetero_problem(D, "dense")
             fn, lo, hi, cov = HETERO.loglike, HETERO.lo, HETERO.hi, pb.new_coverage(D)
         _, bounds = rung_partition(T, nranks)
@@ -185,7 +207,7 @@ def main():
                 e.step(n)
             for e in engs:
                 e.synchronize()
-            ru.replay(whole, st, done, n, fn, lo, hi, coverage=cov)
+            ru.replay(whole, st, done, n, fn, lo, hi, coverage=cov, **kw)
             done += n
             snaps = [e.download() for e in engs]
             cs = [e.counters() for e in engs]
@@ -194,6 +216,13 @@ def main():
             ru.assert_state_equal(st, *[np.concatenate([s[k] for s in snaps], axis=0) for k in range(3)], snaps[0][3],
                                   counters=cnt, what=f"{nranks}-shard pipeline after {done} iterations")
         assert st.swaps_total.sum() > 0 and st.min_margin > 1e-12
+        if LADDER is not None:
+            from tests import tolerance_log as tol
+            ld.check_coverage(LADDER["family"], T, W, betas0, snaps[0][3], st.accepted.sum(axis=1), st.swaps_total, kw["rungs"], done,
+                              what=f"{nranks}-shard pipeline ({T},{W},{D}) / {LADDER['family']}")
+            assert np.array_equal(st.betas[[0, -1]], betas0[[0, -1]])
+            rel = np.abs(snaps[0][3] - st.betas)[st.betas > 0] / st.betas[st.betas > 0]
+            print("max_rel_L %.3e max_rel_betas %.3e" % (max([v["max_rel_L"] for v in tol.report().values()] + [0.0]), rel.max()))
         if cov is not None:
             from tests import tolerance_log as tol
             assert st.accepted.sum() > 0
@@ -204,8 +233,8 @@ def main():
         # its rungs AND the rung below them)
         from oracle import eryn_oracle as orc
         from tests import replay_utils as ru
-        nranks, T, W, D, start = map(int, sys.argv[2:7])
-        calls = [int(v) for v in sys.argv[7].split(",")]
+        nranks, T, W, D, start = map(int, argv[2:7])
+        calls = [int(v) for v in argv[7].split(",")]
         mu, invcov, x0, betas0 = problem(T, W, D)
         _, bounds = rung_partition(T, nranks)
         engs = [make(T, W, D, b) for b in bounds]

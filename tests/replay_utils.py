@@ -118,11 +118,18 @@ def _margin(st, lnpdiff, logu):
         st.min_margin = min(st.min_margin, float(m.min()))
 
 
+def _count_rungs(rungs, logp):
+    if rungs is not None:
+        rungs["proposals"] = rungs.get("proposals", 0) + np.full(logp.shape[0], logp.shape[1])
+        rungs["outside"] = rungs.get("outside", 0) + np.isinf(logp).sum(axis=1)
+
+
 def oracle_iteration(st, ref, loglike, lo, hi, a=2.0, adaptive=True, lag=10000, nu=100, stop_adaptation=-1,
-                     mh=None, period=None, nsplits=2, coverage=None):
+                     mh=None, period=None, nsplits=2, coverage=None, rungs=None):
     """One sampler iteration on ``st`` with the given draws (ensemble.py:965-981): the stretch move's two halves
     (or one Metropolis-Hastings proposal when ``mh = (step, u_acc)``), the PT cascade, the ladder adaptation.
-    ``coverage``: a dict of tests/problems.new_coverage that counts what the oracle's proposals did at the prior box."""
+    ``coverage``: a dict of tests/problems.new_coverage that counts what the oracle's proposals did at the prior box;
+    ``rungs``: a dict that receives, per rung, the oracle's proposals ("proposals"[T]) and those outside the box ("outside"[T])."""
     T, W, D = st.x.shape
     tt = np.arange(T)[:, None]
     if mh is not None:
@@ -130,6 +137,7 @@ def oracle_iteration(st, ref, loglike, lo, hi, a=2.0, adaptive=True, lag=10000, 
         st.mh_accepted += out["keep"]
         if coverage is not None:
             count_coverage(coverage, out["q"], out["logp"], out["keep"], lo, hi, "mh")
+        _count_rungs(rungs, out["logp"])
         with np.errstate(divide="ignore"):
             _margin(st, out["lnpdiff"], np.log(mh[1]))
     else:
@@ -141,6 +149,7 @@ def oracle_iteration(st, ref, loglike, lo, hi, a=2.0, adaptive=True, lag=10000, 
             st.accepted += acc
             if coverage is not None:
                 count_coverage(coverage, out["q"], out["logp"], out["keep"], lo, hi, "stretch")
+            _count_rungs(rungs, out["logp"])
             with np.errstate(divide="ignore"):
                 _margin(st, out["lnpdiff"], np.log(ref[f"u_acc{sp}"]))
     if st.betas is not None and T > 1:

@@ -21,6 +21,7 @@ pytestmark = pytest.mark.skipif(not os.path.isdir("/root/reference/src/eryn"), r
 
 
 def test_generators_reproduce_every_committed_fixture(tmp_path):
+    shutil.copy(os.path.join(HERE, "ladders.py"), tmp_path / "ladders.py")     # (make_golden.py builds fixture f9's ladder with it)
     for g in GENERATORS:
         shutil.copy(os.path.join(GOLDEN, g), tmp_path / g)           # (a generator writes beside itself)
         r = subprocess.run([sys.executable, str(tmp_path / g)], cwd=str(tmp_path), capture_output=True, text=True, timeout=600,

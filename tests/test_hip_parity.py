@@ -33,13 +33,15 @@ def _fixture_oracle(fx):
         kw.update(betas=fx["betas0"], adaptive=bool(fx["adaptive"]), permute=bool(fx["permute"]))
     if "nsplits" in fx.files:
         kw["nsplits"] = int(fx["nsplits"])
+    if "adaptation_lag" in fx.files:
+        kw.update(adaptation_lag=float(fx["adaptation_lag"]), adaptation_time=float(fx["adaptation_time"]))
     o = orc.OracleSampler(fx["x0"], lambda x: orc.gaussian_log_like(x, mu, invcov), np.full(D, -box),
                           np.full(D, box), R, G, a=float(fx["a"]), record=True, **kw)
     return o, mu, invcov
 
 
 @pytest.mark.parametrize("name", ["f1_plumbing", "f2_pt", "f3_oddW", "f4_narrowbox", "f5_noadapt",
-                                  "f5_nopermute", "f6_medium", "f7_tmaxinf", "f8_nsplits3"])
+                                  "f5_nopermute", "f6_medium", "f7_tmaxinf", "f8_nsplits3", "f9_userladder", "f10_longladder"])
 def test_golden_fixture_teacher_forced(name, golden_dir):
     """Replay the reference's own recorded draws (committed fixtures) through the HIP path."""
     fx = golden_io.load(golden_dir, name)

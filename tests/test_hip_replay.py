@@ -26,15 +26,22 @@ def _engine(T, W, D, like, box, seed, lo=None, hi=None, **kw):
 
 
 def _run_case(T, W, D, like_kind="dense", box=50.0, seed=77, calls=(1, 3), x_scale=1.0, mh=None, period=None, nsplits=2,
-              start_iter=0, set_iter=None, plans=None, problem=None, coverage=None, **kw):
+              start_iter=0, set_iter=None, plans=None, problem=None, coverage=None, betas=None, lag=None, nu=None, x0=None,
+              rungs=None, probe=None, **kw):
     """Replay ``calls`` of hens_step through the oracle.  ``set_iter``: the counter (and, with adaptation on, the adaptation time)
     moved on the freshly uploaded state first (hens_set_iteration: a resumed chain); ``start_iter``: an unobserved call of that many
     iterations in front of the replay, whose end state and counters the oracle starts from; ``plans``: a list that receives each
     replayed call's (first iteration, iterations, round-key window plans inside the call, plans of the state read-back after it);
     ``problem``: a tests/problems.Problem in place of the default Gaussian under the scalar box (its likelihood kind, per-coordinate
     box, start positions and periods); ``coverage``: a dict of problems.new_coverage that counts what the oracle's proposals did at
-    the box."""
+    the box; ``betas``: the ladder to upload in place of ``make_ladder(D, ntemps=T)``; ``lag`` / ``nu``: the adaptation's constants
+    (adaptation_lag, adaptation_time) for the context and the oracle alike; ``x0``: the start positions; ``rungs``: a dict that
+    receives the oracle's per-rung proposal counts (replay_utils.oracle_iteration); ``probe``: a dict that receives the oracle's
+    state after the replay ("st"), the ladder uploaded and downloaded last ("betas0", "betas") and the launch counts of a profiled
+    call of two stretch iterations made after everything was compared ("timing": which path the context steps on)."""
     from eryn_amd.likelihood import GaussianLikelihood, RosenbrockLikelihood
+    adapt = {k: v for k, v in (("lag", lag), ("nu", nu)) if v is not None}        # (the oracle's names; the context's below)
+    kw.update({k: v for k, v in (("adaptation_lag", lag), ("adaptation_time", nu)) if v is not None})
     mu, invcov = pu.gaussian_problem(D, dense=(like_kind == "dense"))
     if problem is not None:
         like_kind, like, fn = problem.like_kind, pu.device_likelihood(problem), problem.loglike
@@ -49,9 +56,11 @@ def _run_case(T, W, D, like_kind="dense", box=50.0, seed=77, calls=(1, 3), x_sca
     lo, hi = (np.full(D, -box), np.full(D, box)) if problem is None else (problem.lo, problem.hi)
     eng = _engine(T, W, D, like, box, seed, lo=None if problem is None else lo, hi=None if problem is None else hi, **kw)
     # inside the prior support: the reference refuses a start with an infinite log-prior (ensemble.py:930-946)
-    x0 = np.clip(x_scale * np.random.RandomState(3).randn(T, W, D), -0.95 * box, 0.95 * box) if problem is None else problem.x0(T, W)
+    if x0 is None:
+        x0 = np.clip(x_scale * np.random.RandomState(3).randn(T, W, D), -0.95 * box, 0.95 * box) if problem is None else problem.x0(T, W)
     tempered = T > 1
-    eng.upload(x0, betas=orc.make_ladder(D, ntemps=T) if tempered else None)
+    betas0 = (orc.make_ladder(D, ntemps=T) if betas is None else np.array(betas, dtype=np.float64)) if tempered else None
+    eng.upload(x0, betas=betas0)
     eng.eval_state()
     if mh is not None:
         eng.set_mh_proposal(*mh)
@@ -65,8 +74,8 @@ def _run_case(T, W, D, like_kind="dense", box=50.0, seed=77, calls=(1, 3), x_sca
             eng.set_adapt_time(set_iter)
     if start_iter:
         eng.step(start_iter)
-    x, L, P, betas = eng.download()
-    st = ru.OracleState(x, L, P, betas, time=0 if (set_iter is None and not start_iter) else eng.counters()["adapt_time"])
+    x, L, P, betas_dev = eng.download()
+    st = ru.OracleState(x, L, P, betas_dev, time=0 if (set_iter is None and not start_iter) else eng.counters()["adapt_time"])
     if start_iter:                     # (the counters the unobserved call left: the oracle's go on from them)
         c0 = eng.counters()
         st.accepted, st.swaps_total, st.swaps_last = c0["accepted"].copy(), c0["swaps_total"].copy(), c0["swaps_last"].copy()
@@ -81,11 +90,12 @@ def _run_case(T, W, D, like_kind="dense", box=50.0, seed=77, calls=(1, 3), x_sca
         eng.synchronize()
         in_call = eng.timing()["n_plan"] if plans is not None else 0
         kinds += ru.replay(eng, st, it0, n, fn, lo, hi, mh=mh is not None, period=period, nsplits=nsplits,
-                           adaptive=kw.get("adaptive", True), stop_adaptation=kw.get("stop_adaptation", -1), coverage=coverage)
-        x, L, P, betas = eng.download()
+                           adaptive=kw.get("adaptive", True), stop_adaptation=kw.get("stop_adaptation", -1), coverage=coverage,
+                           **adapt, **({} if rungs is None else {"rungs": rungs}))
+        x, L, P, betas_dev = eng.download()
         if plans is not None:              # (the timing of a call is reset by the next call only: it goes on counting the read-back)
             plans.append((it0, n, in_call, eng.timing()["n_plan"] - in_call))
-        ru.assert_state_equal(st, x, L, P, betas, counters=eng.counters(),
+        ru.assert_state_equal(st, x, L, P, betas_dev, counters=eng.counters(),
                               mh_counters=eng.mh_counters() if mh is not None else None,
                               what=f"({T},{W},{D}) {like_kind} after {done + n} iterations")
         done += n
@@ -94,6 +104,14 @@ def _run_case(T, W, D, like_kind="dense", box=50.0, seed=77, calls=(1, 3), x_sca
     assert acc > 0, "nothing was ever accepted: the case does not exercise the update"
     if tempered:
         assert st.swaps_total.sum() - swaps0 > 0
+    if probe is not None:
+        probe.update(st=st, betas0=betas0, betas=betas_dev)
+        if mh is not None:
+            eng.set_mh_proposal(None, None, 0.0)
+        eng.set_profiling(True)
+        eng.step(2)
+        probe["timing"] = eng.timing()
+        eng.set_profiling(False)
     eng.close()
     return kinds
 

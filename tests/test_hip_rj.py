@@ -451,7 +451,9 @@ def _replay_oracle_class():
 
         def _pt(self, adapt, rec):
             self._casc = "mh" if adapt else "bd"                     # the cascade after the in-model move adapts (rj.py:381-382)
-            return super()._pt(adapt, rec)
+            super()._pt(adapt, rec)
+            self.swaps_sum = getattr(self, "swaps_sum", 0) + self.swaps_accepted      # accepted swaps per pair over every cascade
+            self.cascades = getattr(self, "cascades", 0) + 1
 
         def _draw_pair(self, j, W):
             slot, u = self.d["slot_" + self._casc].astype(np.int64), self.d["uswap_" + self._casc]
@@ -464,15 +466,20 @@ def _replay_oracle_class():
 
 
 def _replay_rj(T, W, nl_max, nl_min, ndata, iters, seed, start_leaves=(2, 1), calls=None, schedule="separate_branches",
-               set_iter=None, downloads=True, pulse_amp=(2.5, 3.5), inj_amp=None, start_amp=None, resident=None):
+               set_iter=None, downloads=True, pulse_amp=(2.5, 3.5), inj_amp=None, start_amp=None, resident=None, betas=None,
+               lag=None, nu=None):
     """hens_rj_step replayed through the oracle.  ``set_iter``: counter and adaptation time moved on the uploaded state first;
     ``downloads=False``: no download between calls (the resident templates are then refreshed by the counter only) - the state is
     read with hens_rj_debug_resident instead, which does not refresh; ``pulse_amp`` / ``inj_amp``: the pulse amplitude box and the
     injected amplitudes; ``start_amp``: {branch: amplitude per started slot (None: the injected one)} of the starting leaves;
     ``resident``: a dict that receives, per call end, the largest relative distance of the resident
-    log-likelihoods from the exact float64 template likelihood of the resident coordinates."""
+    log-likelihoods from the exact float64 template likelihood of the resident coordinates; ``betas``: the ladder to upload in place
+    of the geometric one; ``lag`` / ``nu``: the adaptation's constants for the context and the oracle alike.  The oracle returned
+    carries the ladder uploaded and the one downloaded last (``betas_uploaded``, ``betas_device``), the accepted proposals per rung
+    (``accepted_rung``) and the accepted swaps per pair over its ``cascades`` cascades (``swaps_sum``)."""
     from oracle import eryn_oracle_rj as orj
     from eryn_amd.moves.tempering import make_ladder
+    adapt = {k: v for k, v in (("adaptation_lag", lag), ("adaptation_time", nu)) if v is not None}
     from eryn_amd.rj import RJEngine, TemplateBranch
     rs = np.random.RandomState(seed)
     t = np.linspace(-1, 1, ndata)
@@ -488,7 +495,7 @@ def _replay_rj(T, W, nl_max, nl_min, ndata, iters, seed, start_leaves=(2, 1), ca
     scale = np.array([[1e-2, 1e-2, 1e-3], [1e-2, 1e-2, 1e-2]])
     names = ["gauss", "sine"]
     brs = [TemplateBranch(k, kinds[k], boxes[k], nl_max[i], nl_min[i]) for i, k in enumerate(names)]
-    eng = RJEngine(T, W, brs, t, y, sigma, seed=seed)
+    eng = RJEngine(T, W, brs, t, y, sigma, seed=seed, **adapt)
     x = {k: np.zeros((T, W, nl_max[i], 3)) for i, k in enumerate(names)}
     inds = {k: np.zeros((T, W, nl_max[i]), dtype=bool) for i, k in enumerate(names)}
     inj = {"gauss": gauss_inj, "sine": sine_inj}
@@ -498,7 +505,7 @@ def _replay_rj(T, W, nl_max, nl_min, ndata, iters, seed, start_leaves=(2, 1), ca
             inds[k][:, :, n] = True
             if start_amp and k in start_amp and start_amp[k][n] is not None:
                 x[k][:, :, n, 0] += start_amp[k][n] - inj[k][n % len(inj[k])][0]
-    betas0 = make_ladder(3 * sum(start_leaves), ntemps=T)
+    betas0 = make_ladder(3 * sum(start_leaves), ntemps=T) if betas is None else np.array(betas, dtype=np.float64)
     eng.upload(x, inds, betas=betas0)
     eng.eval_state()
     eng.set_mh_scale(scale)
@@ -509,7 +516,8 @@ def _replay_rj(T, W, nl_max, nl_min, ndata, iters, seed, start_leaves=(2, 1), ca
     x0, inds0, L0, P0, _ = eng.download()
     okind = {"pulse": orj.KIND_PULSE, "sine": orj.KIND_SINE}
     obr = [orj.Branch(k, okind[kinds[k]], boxes[k], nl_max[i], nl_min[i], cov=np.diag(scale[i] ** 2)) for i, k in enumerate(names)]
-    o = _replay_oracle_class()(obr, x0, inds0, t, y, sigma, None, None, betas0, schedule=schedule)
+    o = _replay_oracle_class()(obr, x0, inds0, t, y, sigma, None, None, betas0, schedule=schedule, **adapt)
+    o.betas_uploaded = betas0.copy()
     if set_iter is not None:
         o.time = set_iter
     assert np.array_equal(o.st.P, P0)
@@ -549,12 +557,14 @@ def _replay_rj(T, W, nl_max, nl_min, ndata, iters, seed, start_leaves=(2, 1), ca
         assert np.array_equal(P1, o.st.P), f"{what}: log-prior"
         tol.check_logl(L1, o.st.L, RTOL_L, what)
         np.testing.assert_allclose(betas1, o.st.betas, rtol=1e-13, atol=0, err_msg=what)
+        o.betas_device = betas1
         c = eng.counters()
         assert np.array_equal(c["accepted_mh"], mh_acc) and np.array_equal(c["accepted_bd"], bd_acc), f"{what}: accept counters"
         assert c["num_mh"] == done and c["num_bd"] == done
         assert np.array_equal(c["swaps_last"], o.swaps_accepted), f"{what}: swap counts of the last cascade"
     assert mh_acc.sum() > 0 and bd_acc.sum() > 0 and min(nbd) > 0, "both moves, both branches and both outcomes must occur"
     eng.close()
+    o.accepted_rung = (mh_acc + bd_acc).sum(axis=1)
     return o
 
 

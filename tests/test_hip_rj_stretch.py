@@ -47,9 +47,11 @@ def _oracle_branches(nl_max, nl_min):
     return [orj.Branch(k, okind[KINDS[k]], BOXES[k], nl_max[i], nl_min[i]) for i, k in enumerate(NAMES)]
 
 
-def _engine(T, W, nl_max, nl_min, ndata, seed, start_leaves, schedule, **kw):
+def _engine(T, W, nl_max, nl_min, ndata, seed, start_leaves, schedule, betas=None, **kw):
     from eryn_amd.rj import RJEngine
     brs, t, y, sigma, x, inds, betas0 = _model(T, W, nl_max, nl_min, ndata, seed, start_leaves)
+    if betas is not None:                                         # (a ladder of the caller's in place of the geometric one)
+        betas0 = np.array(betas, dtype=np.float64)
     eng = RJEngine(T, W, brs, t, y, sigma, seed=seed, **kw)
     eng.upload(x, inds, betas=betas0)
     eng.eval_state()
@@ -117,12 +119,18 @@ def test_device_stretch_draws_are_the_specification(T, W, nbranches):
 
 
 # ---- 2. production replay through the oracle -----------------------------------------------------------------------------------
-def _replay_stretch(T, W, nl_max, nl_min, ndata, schedule, iters, seed, start_leaves, downloads=True):
+def _replay_stretch(T, W, nl_max, nl_min, ndata, schedule, iters, seed, start_leaves, downloads=True, betas=None, lag=None, nu=None):
+    """``betas``: the ladder to upload in place of the geometric one; ``lag`` / ``nu``: the adaptation's constants for the context and
+    the oracle alike; the oracle returned carries the ladder uploaded and the one downloaded last (betas_uploaded, betas_device), the
+    accepted proposals per rung (accepted_rung) and the accepted swaps per pair over its cascades (swaps_sum, cascades)."""
     from oracle import eryn_oracle_rj as orj
-    eng, brs, t, y, sigma, betas0 = _engine(T, W, nl_max, nl_min, ndata, seed, start_leaves, schedule)
+    adapt = {k: v for k, v in (("adaptation_lag", lag), ("adaptation_time", nu)) if v is not None}
+    eng, brs, t, y, sigma, betas0 = _engine(T, W, nl_max, nl_min, ndata, seed, start_leaves, schedule, betas=betas, **adapt)
     x0, inds0, L0, P0, _ = eng.download()
     obr = _oracle_branches(nl_max, nl_min)
-    o = _replay_stretch_class()(obr, x0, inds0, t, y, sigma, None, None, betas0, schedule=schedule, in_model="stretch", record=True)
+    o = _replay_stretch_class()(obr, x0, inds0, t, y, sigma, None, None, betas0, schedule=schedule, in_model="stretch", record=True,
+                                **adapt)
+    o.betas_uploaded = betas0.copy()
     assert np.array_equal(o.st.P, P0)
     tol.check_logl(L0, o.st.L, RTOL_L, "template log-like")
     offsets = {b.name: eng.off[i] for i, b in enumerate(brs)}
@@ -165,6 +173,7 @@ def _replay_stretch(T, W, nl_max, nl_min, ndata, schedule, iters, seed, start_le
         assert np.array_equal(P1, o.st.P), f"{what}: log-prior"
         tol.check_logl(L1, o.st.L, RTOL_L, what)
         np.testing.assert_allclose(betas1, o.st.betas, rtol=1e-13, atol=0, err_msg=what)
+        o.betas_device = betas1
         c = eng.counters()
         assert np.array_equal(c["accepted_mh"], mh_acc) and np.array_equal(c["accepted_bd"], bd_acc), f"{what}: accept counters"
         assert c["num_mh"] == done and c["num_bd"] == (done if rj else 0)
@@ -181,6 +190,7 @@ def _replay_stretch(T, W, nl_max, nl_min, ndata, schedule, iters, seed, start_le
         assert 0 < bd_acc.sum() < bd_n, "both outcomes of the birth / death move must occur"
     else:
         assert np.array_equal(o.st.inds["gauss"], inds0["gauss"]) and np.array_equal(o.st.inds["sine"], inds0["sine"])
+    o.accepted_rung = (mh_acc + bd_acc).sum(axis=1)
     return o
 
 

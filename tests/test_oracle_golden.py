@@ -14,7 +14,7 @@ from oracle import eryn_oracle as orc
 from tests import golden_io
 
 FIXTURES = ["f1_plumbing", "f2_pt", "f3_oddW", "f4_narrowbox", "f5_noadapt",
-            "f5_nopermute", "f6_medium", "f7_tmaxinf", "f8_nsplits3"]
+            "f5_nopermute", "f6_medium", "f7_tmaxinf", "f8_nsplits3", "f9_userladder", "f10_longladder"]
 
 
 def _loglike(fx):
@@ -35,6 +35,8 @@ def build_oracle(fx, record=True):
         kw.update(betas=fx["betas0"], adaptive=bool(fx["adaptive"]), permute=bool(fx["permute"]))
     if "nsplits" in fx.files:
         kw["nsplits"] = int(fx["nsplits"])
+    if "adaptation_lag" in fx.files:
+        kw.update(adaptation_lag=float(fx["adaptation_lag"]), adaptation_time=float(fx["adaptation_time"]))
     return orc.OracleSampler(fx["x0"], _loglike(fx), np.full(D, -box), np.full(D, box), R, G,
                              a=float(fx["a"]), record=record, **kw)
 
