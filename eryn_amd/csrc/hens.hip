@@ -75,6 +75,8 @@ struct hens_ctx_impl {
     int64_t adapt_time = 0;          // tempering.py:596
     bool adapt_pending = false;      // a cascade ran and its swap counts have not been reduced yet
     bool adapt_pending_adaptive = false;
+    const uint32_t* adapt_src = nullptr;   // pending swap counts: swap_part (nullptr) or the mailbox's reduced counts
+    int adapt_nblocks = 0;
     uint32_t* swap_part = nullptr;   // [nblocks][T-1]
     double* swaps_last = nullptr;
     double* swaps_total = nullptr;
@@ -129,6 +131,9 @@ struct hens_ctx_impl {
     int32_t* d_rank_of = nullptr;    // [T]
     int64_t row_capacity = 0, n_send = 0, n_recv = 0;
     bool pt_pending = false;
+    // ladder sharding over RCCL point-to-point messages inside the library (hens_comm_init): the staged transport's exchanges
+    void* comm = nullptr;                   // ncclComm_t
+    bool comm_on = false;
 
     // ladder pipeline (neighbour exchange by one-sided puts, hens_pipe_*)
     struct Pipe {
@@ -178,44 +183,34 @@ struct hens_ctx_impl {
     int mh_kind = -1;                      // -1: hens_step runs the stretch move only
     double mh_weight = 0.0;                // probability that an iteration of hens_step is an MH proposal
     int64_t num_proposals_mh = 0;
-    // reversible-jump leaf packing (HENS_LIKE_TEMPLATE, hens_rj_*)
-    RjModel rj{};
-    double* rj_t = nullptr; double* rj_y = nullptr;        // [ndata] data of the template likelihood
-    double* rj_step = nullptr; double* rj_u = nullptr; double* rj_birth = nullptr;   // parity staging
-    int8_t* rj_change = nullptr; int32_t* rj_leaf = nullptr; uint8_t* rj_keep = nullptr;
-    int32_t* rj_st_own = nullptr; int32_t* rj_st_cw = nullptr; double* rj_uzz = nullptr;   // stretch half-step on leaf-packing records
-    double* rj_ctab = nullptr; int32_t* rj_cbn = nullptr;   // RjArgs::ctab / cbn: what a lane needs about its record coordinate (rj_push_ctab)
-    uint32_t* rj_acc_bd = nullptr;          // [Tl][W] accept counts of the birth / death move (the in-model move uses `accepted`)
-    double* rj_tm = nullptr;                // [2 Tl W][ndata] every pool row's template, resident (RjArgs::tm), or nullptr (ndata > 512)
-    int64_t rj_tm_ndata = 0;
     uint8_t* mask_buf = nullptr;     // hens_step_report: [Tl][W] accept counts of the call's last iterations
     uint32_t* report_prev = nullptr; // ... [2][Tl][W] the stretch / MH accept counters as the last report left them
     bool report_valid = false;
     uint64_t report_iter = 0, report_books = 0;
-    bool rj_tm_valid = false;
-    // host-callable likelihood on leaf-packing records (hens_rj_propose / hens_rj_accept)
-    double *rj_hq = nullptr, *rj_hlogp = nullptr, *rj_hfac = nullptr, *rj_hlu = nullptr, *rj_hlogl = nullptr;
-    uint8_t* rj_hmoved = nullptr;
-    uint32_t* rj_h_accepted = nullptr;
-    bool rj_hostlike = false, rj_accept_pending = false;
-    bool rj_general = false;                 // hens_rj_set_model_general: leaf widths other than 3 / no template likelihood - hens_rj_propose / _accept only
-    bool rj_tm_drift = false;        // hens_rj_step has updated the resident templates by +- a leaf since their last full evaluation
-    int rj_st_ns = 0;                       // hens_rj_stretch_split: walkers of the half being moved
-    int rj_st_split = 0;                    // hens_rj_step, stretch move: the half the next launch moves
-    int rj_in_model = HENS_RJ_INMODEL_GAUSSIAN;      // hens_rj_set_in_model: the in-model move of hens_rj_step
-    unsigned* rj_ad_flag = nullptr;  // the folded adaptation's "ladder published" word (RjArgs::ad_flag), serial of the last folding launch
-    uint32_t rj_ad_serial = 0;
-    bool rj_defer_adapt = false;     // hens_rj_step: the adaptation behind a cascade rides in the next k_rj launch
-    // ladder sharding over RCCL point-to-point messages inside the library (hens_comm_init): the staged transport's exchanges
-    void* comm = nullptr;                   // ncclComm_t
-    bool comm_on = false;               // ... and they belong to the rows as they are (false after an upload / a parity-API move)
-    int64_t rj_num_mh = 0, rj_num_bd = 0;
-    bool rj_have_scale = false;
-    bool rj_have_chol = false;              // hens_rj_set_mh_chol: the in-model Gaussian step is L z per leaf (rj_chol), not scale x z
-    double rj_chol[RJ_MAX_BRANCH][RJ_ND][RJ_ND] = {};
-    int rj_schedule = 0;                    // hens_rj_set_schedule: 0 "separate_branches", 1 "iterate_branches", 2 "together" (ensemble.py:414-480), 3 no birth / death move
-    const uint32_t* adapt_src = nullptr;   // pending swap counts: swap_part (nullptr) or the mailbox's reduced counts
-    int adapt_nblocks = 0;
+    // reversible-jump leaf packing (HENS_LIKE_TEMPLATE, hens_rj_*)
+    struct Rj {
+        RjModel M{};                         // the model as the kernels see it (RjArgs::M)
+        bool general = false;                // hens_rj_set_model_general: leaf widths other than 3 / no template likelihood - hens_rj_propose / _accept only
+        double* t = nullptr; double* y = nullptr;              // [ndata] data of the template likelihood
+        double* ctab = nullptr; int32_t* cbn = nullptr;        // RjArgs::ctab / cbn: what a lane needs about its record coordinate (rj_push_ctab)
+        double* step = nullptr; double* u = nullptr; double* birth = nullptr;         // the caller's draws of a teacher-forced move (rj_ensure_staging)
+        int8_t* change = nullptr; int32_t* leaf = nullptr; uint8_t* keep = nullptr;
+        int32_t* st_own = nullptr; int32_t* st_cw = nullptr; double* uzz = nullptr;   // ... of a stretch half-step
+        double *hq = nullptr, *hlogp = nullptr, *hfac = nullptr, *hlu = nullptr, *hlogl = nullptr; uint8_t* hmoved = nullptr;   // host-callable likelihood (hens_rj_propose / hens_rj_accept)
+        bool accept_pending = false;         // hens_rj_propose ran: hens_rj_accept is due ...
+        uint32_t* pending_acc = nullptr;     // ... and counts the move's accepts here (rj_accept_counter of the proposal)
+        double* tm = nullptr; int64_t tm_ndata = 0;   // [2 Tl W][ndata] every pool row's template, resident (RjArgs::tm), or nullptr (ndata > 512)
+        bool tm_valid = false;               // ... and they belong to the rows as they are (false after an upload / a teacher-forced move)
+        bool tm_drift = false;               // hens_rj_step has updated them by +- a leaf since their last full evaluation
+        int schedule = 0;                    // hens_rj_set_schedule: 0 "separate_branches", 1 "iterate_branches", 2 "together" (ensemble.py:414-480), 3 no birth / death move
+        int in_model = HENS_RJ_INMODEL_GAUSSIAN;     // hens_rj_set_in_model: the in-model move of hens_rj_step
+        bool have_scale = false, have_chol = false;  // hens_rj_set_mh_chol: the in-model Gaussian step is L z per leaf (chol), not scale x z
+        double chol[RJ_MAX_BRANCH][RJ_ND][RJ_ND] = {};
+        unsigned* ad_flag = nullptr; uint32_t ad_serial = 0;   // the folded adaptation's "ladder published" word (RjArgs::ad_flag), serial of the last folding launch
+        bool defer_adapt = false;            // hens_rj_step: the adaptation behind a cascade rides in the next k_rj launch
+        uint32_t* acc_bd = nullptr;          // [Tl][W] accept counts of the birth / death move (the in-model move uses `accepted`)
+        int64_t num_mh = 0, num_bd = 0;      // moves run
+    } rj;
 
     // debug / timing
     unsigned long long* d_trace = nullptr;
@@ -1600,7 +1595,7 @@ bool iteration_is_mh(const hens_ctx_impl* c) {
 // RjArgs::ctab / cbn from the model (hens_rj_set_model, hens_rj_set_mh_scale): per record coordinate its box, step scale, the
 // branch's leaf log-density and (branch, leaf slot, dimension, leaf kind)
 int rj_push_ctab(hens_ctx_impl* c) {
-    const RjModel& M = c->rj;
+    const RjModel& M = c->rj.M;
     std::vector<double> tab(RJ_CTAB_ROWS * RJ_MAX_RW, 0.0);
     std::vector<int32_t> bn(RJ_MAX_RW, 0);
     for (int b = 0; b < M.nb; ++b)
@@ -1609,113 +1604,150 @@ int rj_push_ctab(hens_ctx_impl* c) {
                 const int i = M.off[b] + n * M.nd[b] + d;
                 tab[RJ_CTAB_LO + i] = M.lo[b][d]; tab[RJ_CTAB_HI + i] = M.hi[b][d];
                 tab[RJ_CTAB_SCALE + i] = M.mh_scale[b][d]; tab[RJ_CTAB_LOGP + i] = M.leaf_logp[b];
-                if (c->rj_have_chol && d < RJ_ND)
-                    for (int j = 0; j < RJ_ND; ++j) tab[RJ_CTAB_CHOL + j * RJ_MAX_RW + i] = c->rj_chol[b][d][j];
+                if (c->rj.have_chol && d < RJ_ND)
+                    for (int j = 0; j < RJ_ND; ++j) tab[RJ_CTAB_CHOL + j * RJ_MAX_RW + i] = c->rj.chol[b][d][j];
                 bn[i] = b | (n << 4) | (d << 10) | (M.kind[b] << 12) | ((M.slot0[b] + n) << 16);
             }
     int r;
-    if (!c->rj_ctab) {
-        if ((r = dalloc(c, &c->rj_ctab, tab.size()))) return r;
-        if ((r = dalloc(c, &c->rj_cbn, bn.size()))) return r;
+    if (!c->rj.ctab) {
+        if ((r = dalloc(c, &c->rj.ctab, tab.size()))) return r;
+        if ((r = dalloc(c, &c->rj.cbn, bn.size()))) return r;
     }
-    HIPCHK(c, hipMemcpyAsync(c->rj_ctab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->rj_cbn, bn.data(), bn.size() * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->rj.ctab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->rj.cbn, bn.data(), bn.size() * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));          // (the vectors go out of scope)
     return HENS_OK;
 }
-// tm_mode: -1 no resident templates (parity API), else RjArgs::tm_mode
-int rj_launch(hens_ctx_impl* c, int mode, int branch, const double* step, const int8_t* change, const int32_t* leaf,
-              const double* birth, const double* u_acc, uint8_t* keep, int tm_mode = -1) {
+// One k_rj launch, said in full.  The context supplies only what is state: the walkers, the resident templates, the pending
+// ladder adaptation (and Rj::defer_adapt, whether it may ride in this launch).
+struct RjLaunch {
+    int mode = RJ_MODE_EVAL, branch = 0;
+    int tm_mode = -1;                       // RjArgs::tm_mode; -1: no resident templates (the reference's order of operations, bit for bit)
+    int ns = 0, split = 0;                  // stretch half-step: walkers of the moving half per rung; PHILOX: which half it is
+    enum Draws { PHILOX, FORCED } draws = PHILOX;      // FORCED: the caller's draws, staged on the device - u_acc and what the mode reads
+    const double* step = nullptr; const int8_t* change = nullptr; const int32_t* leaf = nullptr; const double* birth = nullptr;
+    const int32_t* st_own = nullptr; const int32_t* st_cw = nullptr; const double* st_uzz = nullptr; const double* u_acc = nullptr;
+    uint8_t* keep = nullptr;                // RjArgs::keep_out
+    bool propose = false;                   // the proposal half of a host-callable move (k_rj<MODE, -2>); k_rj_accept finishes it
+};
+RjLaunch rj_eval() { return RjLaunch{RJ_MODE_EVAL, 0, 0}; }      // every row's templates, log-likelihood and log-prior from its coordinates
+// a Philox move of hens_rj_step: on the resident templates where the model has them, birth / death by difference; `split`: that
+// half of the red / blue stretch move (red_blue.py:150-154: set k has ceil((W - k) / 2) walkers)
+RjLaunch rj_production(const hens_ctx_impl* c, int mode, int branch = 0, int split = 0) {
+    return RjLaunch{mode, branch, !c->rj.tm ? -1 : (mode == RJ_MODE_BD ? 1 : 0), split == 0 ? (c->W + 1) / 2 : c->W / 2, split};
+}
+// a teacher-forced move on the draws in the staging buffers (rj_ensure_staging); the move sets branch / ns
+RjLaunch rj_forced(const hens_ctx_impl* c, int mode, bool propose) {
+    const hens_ctx_impl::Rj& s = c->rj;
+    RjLaunch l{mode};
+    l.draws = RjLaunch::FORCED; l.propose = propose; l.u_acc = s.u; l.keep = propose ? nullptr : s.keep;
+    if (mode == RJ_MODE_MH) l.step = s.step;
+    if (mode == RJ_MODE_BD) { l.change = s.change; l.leaf = s.leaf; l.birth = s.birth; }
+    if (mode == RJ_MODE_STRETCH) { l.st_own = s.st_own; l.st_cw = s.st_cw; l.st_uzz = s.uzz; }
+    return l;
+}
+// where a move's accepts are counted.  "iterate_branches": the move's accept mask is the LAST branch's (rj.py:385-386) - in both
+// modes, so the counters of hens_rj_step and of the parity API (one hens_rj_bd_step per branch) mean the same thing
+uint32_t* rj_accept_counter(const hens_ctx_impl* c, int mode, int branch) {
+    return mode != RJ_MODE_BD ? c->accepted : (c->rj.schedule == 1 && branch != c->rj.M.nb - 1 ? nullptr : c->rj.acc_bd);
+}
+// k_rj's instantiations: (mode, template scheme or -1 none / -2 proposal half or log-prior alone, Philox in-model move that forms L z)
+struct RjInst { int mode, tmm; bool chol; void (*k)(const RjArgs); };
+#define RJ_INST(MODE_, TMM_, CHOL_) {MODE_, TMM_, CHOL_, k_rj<MODE_, TMM_, CHOL_>}
+const RjInst RJ_INSTS[] = {        // (listed in the order the code object has had them since they were an if-chain)
+    RJ_INST(RJ_MODE_MH, 0, true), RJ_INST(RJ_MODE_MH, -1, true), RJ_INST(RJ_MODE_EVAL, -1, false), RJ_INST(RJ_MODE_EVAL, 0, false), RJ_INST(RJ_MODE_EVAL, 2, false),
+    RJ_INST(RJ_MODE_MH, -1, false), RJ_INST(RJ_MODE_MH, 0, false), RJ_INST(RJ_MODE_BD, -1, false), RJ_INST(RJ_MODE_BD, 1, false),
+    RJ_INST(RJ_MODE_STRETCH, -1, false), RJ_INST(RJ_MODE_STRETCH, 0, false),
+    RJ_INST(RJ_MODE_MH, -2, false), RJ_INST(RJ_MODE_BD, -2, false), RJ_INST(RJ_MODE_STRETCH, -2, false), RJ_INST(RJ_MODE_EVAL, -2, false),
+};
+#undef RJ_INST
+
+int rj_launch(hens_ctx_impl* c, const RjLaunch& l) {
+    const int mode = l.mode;
     RjArgs a{};
     if (c->tracing && c->trace_rj == mode) { a.trace = c->d_trace; a.trace_n = (int32_t)(c->trace_words / 8); }
-    a.tm = (tm_mode >= 0) ? c->rj_tm : nullptr;
-    a.tm_mode = tm_mode >= 0 ? tm_mode : 0;
+    a.tm = (l.tm_mode >= 0) ? c->rj.tm : nullptr;
+    a.tm_mode = l.tm_mode >= 0 ? l.tm_mode : 0;
     a.pool = c->pool; a.loc = c->loc[c->cur]; a.L = c->L[c->cur]; a.P = c->P[c->cur];
     a.betas = c->cfg.tempered ? c->betas[c->bcur] : nullptr;
-    a.accepted = mode == RJ_MODE_BD ? c->rj_acc_bd : c->accepted;
-    // "iterate_branches": the move's accept mask is the LAST branch's (rj.py:385-386) - in both modes, so the counters of
-    // hens_rj_step and of the parity API (one hens_rj_bd_step per branch) mean the same thing
-    if (mode == RJ_MODE_BD && c->rj_schedule == 1 && branch != c->rj.nb - 1) a.accepted = nullptr;
-    a.keep_out = keep;
-    a.tdata = c->rj_t; a.ydata = c->rj_y;
-    a.ctab = c->rj_ctab; a.cbn = c->rj_cbn;
-    a.step = step; a.change = change; a.leaf = leaf; a.birth = birth; a.u_acc = u_acc;
-    a.flags = c->flags;
-    a.M = c->rj;
-    a.fill = c->cfg.fill_value;
-    a.iter = c->iter; a.seed = c->cfg.seed;
-    a.Tl = c->Tl; a.W = c->W; a.rung_begin = c->cfg.rung_begin; a.tempered = c->cfg.tempered; a.mode = mode; a.branch = branch;
+    a.accepted = rj_accept_counter(c, mode, l.branch); a.keep_out = l.keep;
+    a.tdata = c->rj.t; a.ydata = c->rj.y; a.ctab = c->rj.ctab; a.cbn = c->rj.cbn;
+    a.step = l.step; a.change = l.change; a.leaf = l.leaf; a.birth = l.birth; a.u_acc = l.u_acc;
+    a.flags = c->flags; a.fill = c->cfg.fill_value; a.iter = c->iter; a.seed = c->cfg.seed;
+    a.M = c->rj.M;
+    a.Tl = c->Tl; a.W = c->W; a.rung_begin = c->cfg.rung_begin; a.tempered = c->cfg.tempered; a.mode = mode; a.branch = l.branch;
     if (c->adapt_pending) {
         // the adaptation behind the last cascade: inside this launch (production launches that test against the ladder, up to 64
         // rungs: RjArgs::ad), else as a launch of its own in front of it
-        if (c->rj_defer_adapt && a.tm && mode != RJ_MODE_EVAL && c->T <= 64 && c->Tl == c->T && c->rj_ad_flag && !c->adapt_src) {
+        if (c->rj.defer_adapt && a.tm && mode != RJ_MODE_EVAL && c->T <= 64 && c->Tl == c->T && c->rj.ad_flag && !c->adapt_src) {
             a.ad = adapt_args(c, c->adapt_pending_adaptive, c->betas[c->bcur], c->betas[c->bcur]);
             a.ad_fold = 1;
-            a.ad_serial = ++c->rj_ad_serial;
-            a.ad_flag = c->rj_ad_flag;
+            a.ad_serial = ++c->rj.ad_serial;
+            a.ad_flag = c->rj.ad_flag;
             adapt_taken(c, false);                // (same ladder buffer: no flip; adapt_src is nullptr already)
         } else {
             flush_adapt(c);
         }
     }
-    if (mode == RJ_MODE_STRETCH) {                    // (a half-step: one wavefront per position of the moving half, c->rj_st_ns of them per rung)
-        a.st_a = c->cfg.a; a.st_ns = c->rj_st_ns;
-        if (u_acc) { a.st_own = c->rj_st_own; a.st_cw = c->rj_st_cw; a.st_uzz = c->rj_uzz; }      // (the caller's draws)
-        else a.st_hb = c->rj_st_split | (c->idx_bits << 8);                                       // (hens_rj_step: Philox, st_own == nullptr)
+    if (mode == RJ_MODE_STRETCH) {                    // (a half-step: one wavefront per position of the moving half, l.ns of them per rung)
+        a.st_a = c->cfg.a; a.st_ns = l.ns;
+        if (l.draws == RjLaunch::FORCED) { a.st_own = l.st_own; a.st_cw = l.st_cw; a.st_uzz = l.st_uzz; }
+        else a.st_hb = l.split | (c->idx_bits << 8);                                              // (Philox, st_own == nullptr)
     }
-    const int npr = mode == RJ_MODE_STRETCH ? c->rj_st_ns : c->W;     // waves per rung
+    const int npr = mode == RJ_MODE_STRETCH ? l.ns : c->W;            // waves per rung
     const dim3 grid((unsigned)((npr + RJ_WAVES - 1) / RJ_WAVES), (unsigned)c->Tl), block(RJ_WAVES * 64);
     int tmm = a.tm ? a.tm_mode : -1;                  // the instantiation: (mode, template scheme), see k_rj
-    if (c->rj_general && mode == RJ_MODE_EVAL && !c->rj_hostlike) tmm = -2;      // (no device likelihood: the log-prior alone)
-    else if (c->rj_general && !c->rj_hostlike) return fail(c, HENS_ERR_STATE, "a model without a device likelihood steps with hens_rj_propose / hens_rj_accept");
-    if (c->rj_hostlike) {                             // hens_rj_propose: the proposal only (k_rj<MODE, -2>), k_rj_accept finishes
-        if (a.tm || !u_acc || mode == RJ_MODE_EVAL) return fail(c, HENS_ERR_STATE, "hens_rj_propose: a teacher-forced move with its accept uniforms");
+    if (c->rj.general && mode == RJ_MODE_EVAL && !l.propose) tmm = -2;           // (no device likelihood: the log-prior alone)
+    else if (c->rj.general && !l.propose) return fail(c, HENS_ERR_STATE, "a model without a device likelihood steps with hens_rj_propose / hens_rj_accept");
+    if (l.propose) {                                  // hens_rj_propose: the proposal only, left where the host can fetch it
+        if (a.tm || l.draws != RjLaunch::FORCED || mode == RJ_MODE_EVAL) return fail(c, HENS_ERR_STATE, "hens_rj_propose: a teacher-forced move with its accept uniforms");
         tmm = -2;
-        a.hq = c->rj_hq; a.hlogp = c->rj_hlogp; a.hfac = c->rj_hfac; a.hlu = c->rj_hlu; a.hmoved = c->rj_hmoved;
-        a.keep_out = nullptr;
-        c->rj_h_accepted = a.accepted;
+        a.hq = c->rj.hq; a.hlogp = c->rj.hlogp; a.hfac = c->rj.hfac; a.hlu = c->rj.hlu; a.hmoved = c->rj.hmoved;
     }
-#define RJ_CASE(MODE_, TMM_) if (mode == MODE_ && tmm == TMM_) hipLaunchKernelGGL((k_rj<MODE_, TMM_>), grid, block, 0, c->stream, a); else
-    // (Philox in-model move with a full leaf covariance: the instantiations that form L z)
-    if (mode == RJ_MODE_MH && !step && c->rj_have_chol && tmm == 0) hipLaunchKernelGGL((k_rj<RJ_MODE_MH, 0, true>), grid, block, 0, c->stream, a); else
-    if (mode == RJ_MODE_MH && !step && c->rj_have_chol && tmm == -1) hipLaunchKernelGGL((k_rj<RJ_MODE_MH, -1, true>), grid, block, 0, c->stream, a); else
-    RJ_CASE(RJ_MODE_EVAL, -1) RJ_CASE(RJ_MODE_EVAL, 0) RJ_CASE(RJ_MODE_EVAL, 2)
-    RJ_CASE(RJ_MODE_MH, -1) RJ_CASE(RJ_MODE_MH, 0)
-    RJ_CASE(RJ_MODE_BD, -1) RJ_CASE(RJ_MODE_BD, 1)
-    RJ_CASE(RJ_MODE_STRETCH, -1) RJ_CASE(RJ_MODE_STRETCH, 0)
-    RJ_CASE(RJ_MODE_MH, -2) RJ_CASE(RJ_MODE_BD, -2) RJ_CASE(RJ_MODE_STRETCH, -2) RJ_CASE(RJ_MODE_EVAL, -2)
-        return fail(c, HENS_ERR_INVALID, "k_rj: no instantiation for mode %d with template scheme %d", mode, tmm);
-#undef RJ_CASE
+    const bool chol = mode == RJ_MODE_MH && l.draws == RjLaunch::PHILOX && c->rj.have_chol && tmm != -2;
+    const RjInst* inst = nullptr;
+    for (const RjInst& i : RJ_INSTS)
+        if (i.mode == mode && i.tmm == tmm && i.chol == chol) inst = &i;
+    if (!inst) return fail(c, HENS_ERR_INVALID, "k_rj: no instantiation for mode %d with template scheme %d", mode, tmm);
+    hipLaunchKernelGGL(inst->k, grid, block, 0, c->stream, a);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(c, HENS_ERR_HIP, "k_rj launch failed: %s", hipGetErrorString(e));
     return HENS_OK;
 }
 
-int rj_ready(hens_ctx_impl* c, bool between_halves = false) {
+// full evaluation; behind it the resident templates (where the model keeps them) are exactly those of the rows
+int rj_evaluate(hens_ctx_impl* c) {
+    const int r = rj_launch(c, rj_eval());
+    if (!r) { c->rj.tm_valid = c->rj.tm != nullptr; c->rj.tm_drift = false; }
+    return r;
+}
+
+// head of every stepping entry point.  propose: the proposal half of a host-callable move, the one way a model without a device likelihood steps
+int rj_ready(hens_ctx_impl* c, bool between_halves = false, bool propose = false) {
     int r = ready(c, true);
     if (r) return r;
     if (c->cfg.likelihood_kind != HENS_LIKE_TEMPLATE) return fail(c, HENS_ERR_STATE, "hens_rj_* needs a context created with HENS_LIKE_TEMPLATE");
     if (c->Tl != c->T) return fail(c, HENS_ERR_UNSUPPORTED, "the leaf-packing path runs on the whole ladder of one GPU");
     if ((c->expect_split != 0 && !between_halves) || c->propose_pending) return fail(c, HENS_ERR_STATE, "a half-step is pending");
-    if (c->rj_accept_pending) return fail(c, HENS_ERR_STATE, "hens_rj_accept must follow hens_rj_propose");
-    if (c->rj_general && !c->rj_hostlike)
+    if (c->rj.accept_pending) return fail(c, HENS_ERR_STATE, "hens_rj_accept must follow hens_rj_propose");
+    if (c->rj.general && !propose)
         return fail(c, HENS_ERR_STATE, "this context's model has no device likelihood (hens_rj_set_model_general): step it with hens_rj_propose / hens_rj_accept");
     return HENS_OK;
 }
 
 int rj_ensure_staging(hens_ctx_impl* c) {
-    if (c->rj_u) return HENS_OK;
+    if (c->rj.u) return HENS_OK;
     const size_t TW = (size_t)c->Tl * c->W;
     int r;
-    if ((r = dalloc(c, &c->rj_step, TW * c->D))) return r;
-    if ((r = dalloc(c, &c->rj_u, TW))) return r;
-    if ((r = dalloc(c, &c->rj_birth, TW * RJ_MAX_ND * RJ_MAX_BRANCH))) return r;      // ([nbranches][Tl][W]: hens_rj_bd_all_step)
-    if ((r = dalloc(c, &c->rj_change, TW * RJ_MAX_BRANCH))) return r;
-    if ((r = dalloc(c, &c->rj_leaf, TW * RJ_MAX_BRANCH))) return r;
-    if ((r = dalloc(c, &c->rj_keep, TW))) return r;
-    if ((r = dalloc(c, &c->rj_st_own, TW))) return r;                              // (hens_rj_stretch_split)
-    if ((r = dalloc(c, &c->rj_st_cw, TW * RJ_MAX_BRANCH))) return r;
-    if ((r = dalloc(c, &c->rj_uzz, TW))) return r;
+    if ((r = dalloc(c, &c->rj.step, TW * c->D))) return r;
+    if ((r = dalloc(c, &c->rj.u, TW))) return r;
+    if ((r = dalloc(c, &c->rj.birth, TW * RJ_MAX_ND * RJ_MAX_BRANCH))) return r;      // ([nbranches][Tl][W]: hens_rj_bd_all_step)
+    if ((r = dalloc(c, &c->rj.change, TW * RJ_MAX_BRANCH))) return r;
+    if ((r = dalloc(c, &c->rj.leaf, TW * RJ_MAX_BRANCH))) return r;
+    if ((r = dalloc(c, &c->rj.keep, TW))) return r;
+    if ((r = dalloc(c, &c->rj.st_own, TW))) return r;                              // (hens_rj_stretch_split)
+    if ((r = dalloc(c, &c->rj.st_cw, TW * RJ_MAX_BRANCH))) return r;
+    if ((r = dalloc(c, &c->rj.uzz, TW))) return r;
     return HENS_OK;
 }
 
@@ -1787,7 +1819,7 @@ void rj_cascade(hens_ctx_impl* c, uint64_t key, bool adapt) {
     p.iter = key;
     hipLaunchKernelGGL(k_pt_cascade<true>, dim3(pt_blocks(c)), dim3(pt_threads(c->T)), pt_lds_bytes(c->T), c->stream, p);
     cascade_ran(c, nullptr, 0, adapt && c->cfg.adaptive != 0);     // rj.py:381-382: swaps without adaptation after the RJ move
-    if (!c->rj_defer_adapt) flush_adapt(c);      // (hens_rj_step: the next k_rj launch adapts, see rj_launch)
+    if (!c->rj.defer_adapt) flush_adapt(c);      // (hens_rj_step: the next k_rj launch adapts, see rj_launch)
 }
 
 }  // namespace
@@ -2270,7 +2302,7 @@ int hens_upload_state(hens_ctx* ctx, const double* x, const double* logl, const 
     flush_adapt(c);
     const size_t TW = (size_t)c->Tl * c->W;
     c->cur = 0;
-    c->rj_tm_valid = false;
+    c->rj.tm_valid = false;
     c->packed = false;
     c->colmode = false;
     c->rows_mixed = false;    // (a failed hens_step call may have left these behind: step_failed)
@@ -2306,10 +2338,9 @@ int hens_download_state(hens_ctx* ctx, double* x, double* logl, double* logp, do
     // caller stores carries the very log-likelihoods the device goes on with, and the next hens_rj_step call finds its templates
     // valid (round 5 invalidated them behind the copy: the stored log_like was the +- value the device then replaced, and every
     // stored step paid the evaluation at the head of the next call instead).
-    if (c->cfg.likelihood_kind == HENS_LIKE_TEMPLATE && (x || logl) && c->rj_tm && c->rj_tm_valid && c->rj_tm_drift) {
-        int r = rj_launch(c, RJ_MODE_EVAL, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0);
+    if (c->cfg.likelihood_kind == HENS_LIKE_TEMPLATE && (x || logl) && c->rj.tm && c->rj.tm_valid && c->rj.tm_drift) {
+        int r = rj_evaluate(c);
         if (r) return r;
-        c->rj_tm_drift = false;
         if ((r = check_flags(c, true))) return r;
     }
     if (x) {
@@ -2331,10 +2362,8 @@ int hens_eval_state(hens_ctx* ctx) {
     HIPCHK(c, hipSetDevice(c->cfg.device_id));
     state_to_fields(c);                       // (hens_step leaves the state in record mode)
     if (c->cfg.likelihood_kind == HENS_LIKE_TEMPLATE) {
-        r = rj_launch(c, RJ_MODE_EVAL, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0);
+        r = rj_evaluate(c);
         if (r) return r;
-        c->rj_tm_valid = c->rj_tm != nullptr;
-        c->rj_tm_drift = false;
         r = check_flags(c, true);
         if (r) return r;
         c->have_logs = true;
@@ -2865,11 +2894,11 @@ int hens_reset_counters(hens_ctx* ctx) {
     HIPCHK(c, hipMemsetAsync(c->swaps_total, 0, (size_t)c->T * 8, c->stream));
     HIPCHK(c, hipMemsetAsync(c->swaps_last, 0, (size_t)c->T * 8, c->stream));
     if (c->accepted_mh) HIPCHK(c, hipMemsetAsync(c->accepted_mh, 0, (size_t)c->Tl * c->W * 4, c->stream));
-    if (c->rj_acc_bd) HIPCHK(c, hipMemsetAsync(c->rj_acc_bd, 0, (size_t)c->Tl * c->W * 4, c->stream));
+    if (c->rj.acc_bd) HIPCHK(c, hipMemsetAsync(c->rj.acc_bd, 0, (size_t)c->Tl * c->W * 4, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->num_proposals = 0;
     c->num_proposals_mh = 0;
-    c->rj_num_mh = c->rj_num_bd = 0;
+    c->rj.num_mh = c->rj.num_bd = 0;
     c->report_valid = false;
     return HENS_OK;
 }
@@ -3114,28 +3143,27 @@ int hens_rj_set_model(hens_ctx* ctx, int32_t nbranches, const int32_t* kinds, co
     M.ind_off = off;
     M.RW = c->D;
     if (off + nbranches > c->D) return fail(c, HENS_ERR_INVALID, "record width ndim = %d cannot hold %d coordinates + %d masks", c->D, off, nbranches);
-    c->rj = M;
-    c->rj_general = false;
+    c->rj.M = M;
+    c->rj.general = false;
     int r;
     if ((r = rj_push_ctab(c))) return r;
-    if (!c->rj_t) {
-        if ((r = dalloc(c, &c->rj_t, (size_t)ndata))) return r;
-        if ((r = dalloc(c, &c->rj_y, (size_t)ndata))) return r;
-        if ((r = dalloc(c, &c->rj_acc_bd, (size_t)c->Tl * c->W))) return r;
-        HIPCHK(c, hipMemsetAsync(c->rj_acc_bd, 0, (size_t)c->Tl * c->W * 4, c->stream));
+    if (!c->rj.t) {
+        if ((r = dalloc(c, &c->rj.t, (size_t)ndata))) return r;
+        if ((r = dalloc(c, &c->rj.y, (size_t)ndata))) return r;
+        if ((r = dalloc(c, &c->rj.acc_bd, (size_t)c->Tl * c->W))) return r;
+        HIPCHK(c, hipMemsetAsync(c->rj.acc_bd, 0, (size_t)c->Tl * c->W * 4, c->stream));
     }
     // every pool row's template, resident (birth / death by difference in hens_rj_step): 2 Tl W rows of ndata doubles
     // (config 4: 131 MB); a lane keeps 8 points, so models of up to 512 data points; HENS_RJ_NO_TEMPLATES=1: A/B knob
-    if (!env().rj_no_templates && ndata <= 512 && (!c->rj_tm || c->rj_tm_ndata != ndata)) {
-        if ((r = dalloc(c, &c->rj_tm, (size_t)2 * c->Tl * c->W * (size_t)ndata))) return r;
-        c->rj_tm_ndata = ndata;
+    if (!env().rj_no_templates && ndata <= 512 && (!c->rj.tm || c->rj.tm_ndata != ndata)) {
+        if ((r = dalloc(c, &c->rj.tm, (size_t)2 * c->Tl * c->W * (size_t)ndata))) return r;
+        c->rj.tm_ndata = ndata;
     }
-    c->rj_tm_valid = false;
-    HIPCHK(c, hipMemcpyAsync(c->rj_t, t, (size_t)ndata * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->rj_y, y, (size_t)ndata * 8, hipMemcpyHostToDevice, c->stream));
+    c->rj.tm_valid = false;
+    HIPCHK(c, hipMemcpyAsync(c->rj.t, t, (size_t)ndata * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->rj.y, y, (size_t)ndata * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->have_like = true;
-    c->have_prior = true;
+    c->have_like = c->have_prior = true;
     return HENS_OK;
 }
 
@@ -3173,18 +3201,17 @@ int hens_rj_set_model_general(hens_ctx* ctx, int32_t nbranches, const int32_t* n
     M.RW = c->D;
     if (off + nbranches > c->D || c->D > RJ_MAX_RW)
         return fail(c, HENS_ERR_INVALID, "record width ndim = %d cannot hold %d coordinates + %d masks (at most %d)", c->D, off, nbranches, RJ_MAX_RW);
-    c->rj = M;
-    c->rj_general = true;
+    c->rj.M = M;
+    c->rj.general = true;
     int r;
     if ((r = rj_push_ctab(c))) return r;
-    if (!c->rj_acc_bd) {
-        if ((r = dalloc(c, &c->rj_acc_bd, (size_t)c->Tl * c->W))) return r;
-        HIPCHK(c, hipMemsetAsync(c->rj_acc_bd, 0, (size_t)c->Tl * c->W * 4, c->stream));
+    if (!c->rj.acc_bd) {
+        if ((r = dalloc(c, &c->rj.acc_bd, (size_t)c->Tl * c->W))) return r;
+        HIPCHK(c, hipMemsetAsync(c->rj.acc_bd, 0, (size_t)c->Tl * c->W * 4, c->stream));
     }
-    c->rj_tm_valid = false;
+    c->rj.tm_valid = false;
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->have_like = true;
-    c->have_prior = true;
+    c->have_like = c->have_prior = true;
     return HENS_OK;
 }
 
@@ -3192,11 +3219,10 @@ int hens_rj_set_mh_scale(hens_ctx* ctx, const double* scale) {
     hens_ctx_impl* c = enter(ctx);
     if (!c || !scale) return fail(c, HENS_ERR_INVALID, "null argument");
     if (c->cfg.likelihood_kind != HENS_LIKE_TEMPLATE || !c->have_like) return fail(c, HENS_ERR_STATE, "hens_rj_set_model first");
-    if (c->rj_general) return fail(c, HENS_ERR_STATE, "the Philox in-model move belongs to hens_rj_step: template models only");
-    for (int b = 0; b < c->rj.nb; ++b)
-        for (int d = 0; d < RJ_ND; ++d) c->rj.mh_scale[b][d] = scale[b * RJ_ND + d];
-    c->rj_have_scale = true;
-    c->rj_have_chol = false;
+    if (c->rj.general) return fail(c, HENS_ERR_STATE, "the Philox in-model move belongs to hens_rj_step: template models only");
+    for (int b = 0; b < c->rj.M.nb; ++b)
+        for (int d = 0; d < RJ_ND; ++d) c->rj.M.mh_scale[b][d] = scale[b * RJ_ND + d];
+    c->rj.have_scale = true; c->rj.have_chol = false;
     HIPCHK(c, hipSetDevice(c->cfg.device_id));
     return rj_push_ctab(c);
 }
@@ -3208,8 +3234,8 @@ int hens_rj_set_mh_chol(hens_ctx* ctx, const double* chol) {
     hens_ctx_impl* c = enter(ctx);
     if (!c || !chol) return fail(c, HENS_ERR_INVALID, "null argument");
     if (c->cfg.likelihood_kind != HENS_LIKE_TEMPLATE || !c->have_like) return fail(c, HENS_ERR_STATE, "hens_rj_set_model first");
-    if (c->rj_general) return fail(c, HENS_ERR_STATE, "the Philox in-model move belongs to hens_rj_step: template models only");
-    for (int b = 0; b < c->rj.nb; ++b)
+    if (c->rj.general) return fail(c, HENS_ERR_STATE, "the Philox in-model move belongs to hens_rj_step: template models only");
+    for (int b = 0; b < c->rj.M.nb; ++b)
         for (int d = 0; d < RJ_ND; ++d)
             for (int j = 0; j < RJ_ND; ++j) {
                 const double v = chol[(b * RJ_ND + d) * RJ_ND + j];
@@ -3217,161 +3243,162 @@ int hens_rj_set_mh_chol(hens_ctx* ctx, const double* chol) {
                 if (j > d && v != 0.0) return fail(c, HENS_ERR_INVALID, "hens_rj_set_mh_chol: the factor must be lower triangular");
                 if (j == d && !(v > 0.0)) return fail(c, HENS_ERR_INVALID, "hens_rj_set_mh_chol: the covariance is not positive definite (diagonal of its factor <= 0)");
             }
-    for (int b = 0; b < c->rj.nb; ++b)
+    for (int b = 0; b < c->rj.M.nb; ++b)
         for (int d = 0; d < RJ_ND; ++d) {
-            for (int j = 0; j < RJ_ND; ++j) c->rj_chol[b][d][j] = chol[(b * RJ_ND + d) * RJ_ND + j];
-            c->rj.mh_scale[b][d] = c->rj_chol[b][d][d];
+            for (int j = 0; j < RJ_ND; ++j) c->rj.chol[b][d][j] = chol[(b * RJ_ND + d) * RJ_ND + j];
+            c->rj.M.mh_scale[b][d] = c->rj.chol[b][d][d];
         }
-    c->rj_have_scale = true;
-    c->rj_have_chol = true;
+    c->rj.have_scale = c->rj.have_chol = true;
     HIPCHK(c, hipSetDevice(c->cfg.device_id));
     return rj_push_ctab(c);
 }
 
-int hens_rj_mh_step(hens_ctx* ctx, const double* step, const double* u_acc, uint8_t* keep_out) {
-    hens_ctx_impl* c = enter(ctx);
-    int r = rj_ready(c);
-    if (r) return r;
-    if (!step || !u_acc) return fail(c, HENS_ERR_INVALID, "null argument");
-    if ((r = counter_room(c, 1))) return r;
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    state_to_fields(c);                       // (hens_step leaves the state in record mode)
-    flush_adapt(c);
-    if ((r = rj_ensure_staging(c))) return r;
+// ---- teacher-forced moves on leaf-packing records: the caller's draws (hens_rj_draws), the device's arithmetic ------------------
+// By HENS_RJ_MOVE_*: the in-model Gaussian move on every active leaf (mh.py:56-193); birth / death on one branch (rj.py:145-388) or,
+// "together", ONE proposal over every branch ([nbranches][...] arrays, one u_acc); one half of the red / blue StretchMove (round 5;
+// red_blue.py:103-197, 254-323 + stretch.py:160-231's loop over the branches).  A move's own argument checks,
+// staging and counter rule come first; rj_forced_move is the body they share.
+static int rj_forced_check(hens_ctx_impl* c, int move, const hens_rj_draws& d) {
+    if (move == HENS_RJ_MOVE_MH) return !d.step || !d.u_acc ? fail(c, HENS_ERR_INVALID, "null argument") : counter_room(c, 1);
+    if (move == HENS_RJ_MOVE_STRETCH) {
+        if (!d.labels || !d.rint || !d.u_zz || !d.u_acc) return fail(c, HENS_ERR_INVALID, "null argument");
+        if (d.split < 0 || d.split > 1) return fail(c, HENS_ERR_INVALID, "split must be 0 or 1 (two sets)");
+        if (d.split != c->expect_split) return fail(c, HENS_ERR_STATE, "split calls must run 0, 1 in order (expected %d)", c->expect_split);
+        if (const int r = counter_room(c, 1)) return r;
+        if (!c->cfg.live_dangerously && c->W < 2 * c->rj.M.ind_off)                 // red_blue.py:103-114 (every slot of every branch counts)
+            return fail(c, HENS_ERR_TOO_FEW_WALKERS, "It is unadvisable to use a red-blue move with fewer walkers than twice the number of dimensions. "
+                                                     "If you would like to do this, please set live_dangerously to True.");
+        return HENS_OK;
+    }
+    if (!d.change || !d.leaf || !d.birth || !d.u_acc) return fail(c, HENS_ERR_INVALID, "null argument");
+    const bool all = move == HENS_RJ_MOVE_BD_ALL;
+    if (!all && (d.branch < 0 || d.branch >= c->rj.M.nb)) return fail(c, HENS_ERR_INVALID, "branch %d out of range", d.branch);
     const size_t TW = (size_t)c->Tl * c->W;
-    HIPCHK(c, hipMemcpyAsync(c->rj_step, step, TW * c->rj.ind_off * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->rj_u, u_acc, TW * 8, hipMemcpyHostToDevice, c->stream));
-    c->rj_tm_valid = false;                   // (teacher-forced move: the reference's full evaluation, no resident templates)
-    if ((r = rj_launch(c, RJ_MODE_MH, 0, c->rj_step, nullptr, nullptr, nullptr, c->rj_u, c->rj_keep))) return r;
-    if (keep_out) HIPCHK(c, hipMemcpyAsync(keep_out, c->rj_keep, TW, hipMemcpyDeviceToHost, c->stream));
-    if ((r = check_flags(c, false))) return r;
-    c->rj_num_mh += 1;
-    if (!has_pt(c)) c->iter += 1;
+    for (int k = 0; k < (all ? c->rj.M.nb : 1); ++k)       // (k: the branch's place in the arrays)
+        for (size_t i = k * TW; i < (k + 1) * TW; ++i) {
+            if (d.change[i] < -1 || d.change[i] > 1) return fail(c, HENS_ERR_INVALID, "change must be -1, 0 or +1");
+            if (d.change[i] != 0 && (d.leaf[i] < 0 || d.leaf[i] >= c->rj.M.nl[all ? k : d.branch])) return fail(c, HENS_ERR_INVALID, "leaf slot out of range");
+        }
     return HENS_OK;
 }
 
-// One half of the red / blue StretchMove on leaf-packing records (round 5; SURVEY 8 row a4 over several branches and leaves):
-// RedBlueMove.propose's split (red_blue.py:103-197) + StretchMove.get_proposal's loop over the branches (stretch.py:160-231) +
-// priors / likelihood with inds, accept, update (red_blue.py:254-323), teacher-forced with the caller's draws.
-int hens_rj_stretch_split(hens_ctx* ctx, int32_t split, const uint8_t* labels, const int64_t* rint, const double* u_zz,
-                          const double* u_acc, uint8_t* keep_out) {
-    hens_ctx_impl* c = enter(ctx);
-    int r = rj_ready(c, split == 1);
-    if (r) return r;
-    if (!labels || !rint || !u_zz || !u_acc) return fail(c, HENS_ERR_INVALID, "null argument");
-    if (split < 0 || split > 1) return fail(c, HENS_ERR_INVALID, "split must be 0 or 1 (two sets)");
-    if (split != c->expect_split) return fail(c, HENS_ERR_STATE, "split calls must run 0, 1 in order (expected %d)", c->expect_split);
-    if ((r = counter_room(c, 1))) return r;
-    const int Tl = c->Tl, W = c->W, nb = c->rj.nb;
-    if (!c->cfg.live_dangerously && W < 2 * c->rj.ind_off)                          // red_blue.py:103-114 (every slot of every branch counts)
-        return fail(c, HENS_ERR_TOO_FEW_WALKERS, "It is unadvisable to use a red-blue move with fewer walkers than twice the number of dimensions. "
-                                                 "If you would like to do this, please set live_dangerously to True.");
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    state_to_fields(c);
-    flush_adapt(c);
-    if ((r = rj_ensure_staging(c))) return r;
+static int rj_stretch_stage(hens_ctx_impl* c, const hens_rj_draws& d, RjLaunch& l) {
+    const int Tl = c->Tl, W = c->W, nb = c->rj.M.nb, split = d.split;
     // ascending walker lists of the two sets (red_blue.py:150-154): set k has ceil((W - k) / 2) walkers (arange(W) % 2, shuffled)
     const int n0 = (W + 1) / 2, Ns = split == 0 ? n0 : W - n0, Nc = W - Ns;
     std::vector<int32_t> own((size_t)Tl * Ns), other((size_t)Tl * Nc), cw((size_t)nb * Tl * Ns);
     for (int t = 0; t < Tl; ++t) {
         int a = 0, b = 0;
         for (int w = 0; w < W; ++w) {
-            const uint8_t l = labels[(size_t)t * W + w];
-            if (l > 1) return fail(c, HENS_ERR_INVALID, "labels must be 0 or 1");
-            if (l == split) { if (a >= Ns) return fail(c, HENS_ERR_INVALID, "labels must hold ceil((W - k) / 2) walkers of set k per rung"); own[(size_t)t * Ns + a++] = w; }
+            const uint8_t lb = d.labels[(size_t)t * W + w];
+            if (lb > 1) return fail(c, HENS_ERR_INVALID, "labels must be 0 or 1");
+            if (lb == split) { if (a >= Ns) return fail(c, HENS_ERR_INVALID, "labels must hold ceil((W - k) / 2) walkers of set k per rung"); own[(size_t)t * Ns + a++] = w; }
             else { if (b >= Nc) return fail(c, HENS_ERR_INVALID, "labels must hold ceil((W - k) / 2) walkers of set k per rung"); other[(size_t)t * Nc + b++] = w; }
         }
     }
-    if (split == 0) c->labels_host.assign(labels, labels + (size_t)Tl * W);
-    else if (c->labels_host.size() != (size_t)Tl * W || memcmp(c->labels_host.data(), labels, (size_t)Tl * W) != 0)
+    if (split == 0) c->labels_host.assign(d.labels, d.labels + (size_t)Tl * W);
+    else if (c->labels_host.size() != (size_t)Tl * W || memcmp(c->labels_host.data(), d.labels, (size_t)Tl * W) != 0)
         return fail(c, HENS_ERR_INVALID, "labels differ between split 0 and split 1 of the same iteration");
     for (int b = 0; b < nb; ++b)                                                    // rint[nbranches][Tl][Ns]: an index into the other set
         for (int t = 0; t < Tl; ++t)
             for (int k = 0; k < Ns; ++k) {
-                const int64_t ri = rint[((size_t)b * Tl + t) * Ns + k];
+                const int64_t ri = d.rint[((size_t)b * Tl + t) * Ns + k];
                 if (ri < 0 || ri >= Nc) return fail(c, HENS_ERR_INVALID, "rint out of range [0, %d)", Nc);
                 cw[((size_t)b * Tl + t) * Ns + k] = other[(size_t)t * Nc + ri];
             }
     const size_t n = (size_t)Tl * Ns;
-    HIPCHK(c, hipMemcpyAsync(c->rj_st_own, own.data(), n * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->rj_st_cw, cw.data(), (size_t)nb * n * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->rj_uzz, u_zz, n * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->rj_u, u_acc, n * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->rj.st_own, own.data(), n * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->rj.st_cw, cw.data(), (size_t)nb * n * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->rj.uzz, d.u_zz, n * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->rj.u, d.u_acc, n * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));                                     // (the host vectors go out of scope)
-    c->rj_tm_valid = false;                   // (teacher-forced move: the reference's full evaluation, no resident templates)
-    c->rj_st_ns = Ns;
-    if ((r = rj_launch(c, RJ_MODE_STRETCH, 0, nullptr, nullptr, nullptr, nullptr, c->rj_u, c->rj_keep))) return r;
-    if (keep_out) HIPCHK(c, hipMemcpyAsync(keep_out, c->rj_keep, n, hipMemcpyDeviceToHost, c->stream));
-    if ((r = check_flags(c, false))) return r;
-    if (split == 1) {
-        c->rj_num_mh += 1;                    // (the in-model move's counter, whichever move it is)
-        if (!has_pt(c)) c->iter += 1;
-    }
-    c->expect_split = split ^ 1;
+    l.ns = Ns;
     return HENS_OK;
 }
-
-int hens_rj_bd_step(hens_ctx* ctx, int32_t branch, const int8_t* change, const int32_t* leaf, const double* birth,
-                    const double* u_acc, uint8_t* keep_out) {
-    hens_ctx_impl* c = enter(ctx);
-    int r = rj_ready(c);
-    if (r) return r;
-    if (!change || !leaf || !birth || !u_acc) return fail(c, HENS_ERR_INVALID, "null argument");
-    if (branch < 0 || branch >= c->rj.nb) return fail(c, HENS_ERR_INVALID, "branch %d out of range", branch);
-    const size_t TW = (size_t)c->Tl * c->W;
-    for (size_t i = 0; i < TW; ++i) {
-        if (change[i] < -1 || change[i] > 1) return fail(c, HENS_ERR_INVALID, "change must be -1, 0 or +1");
-        if (change[i] != 0 && (leaf[i] < 0 || leaf[i] >= c->rj.nl[branch])) return fail(c, HENS_ERR_INVALID, "leaf slot out of range");
+// draws -> staging buffers; the launch's branch / half
+static int rj_forced_stage(hens_ctx_impl* c, int move, const hens_rj_draws& d, RjLaunch& l) {
+    if (move == HENS_RJ_MOVE_STRETCH) return rj_stretch_stage(c, d, l);
+    const size_t TW = (size_t)c->Tl * c->W, NB = move == HENS_RJ_MOVE_BD_ALL ? (size_t)c->rj.M.nb : 1;
+    if (move == HENS_RJ_MOVE_MH) HIPCHK(c, hipMemcpyAsync(c->rj.step, d.step, TW * c->rj.M.ind_off * 8, hipMemcpyHostToDevice, c->stream));
+    else {
+        l.branch = move == HENS_RJ_MOVE_BD_ALL ? -1 : d.branch;
+        HIPCHK(c, hipMemcpyAsync(c->rj.change, d.change, NB * TW, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->rj.leaf, d.leaf, NB * TW * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->rj.birth, d.birth, NB * TW * (size_t)c->rj.M.ndmax * 8, hipMemcpyHostToDevice, c->stream));
     }
+    HIPCHK(c, hipMemcpyAsync(c->rj.u, d.u_acc, TW * 8, hipMemcpyHostToDevice, c->stream));
+    return HENS_OK;
+}
+// the counters behind a move that ran
+static void rj_forced_count(hens_ctx_impl* c, int move, const hens_rj_draws& d) {
+    if (move == HENS_RJ_MOVE_STRETCH) c->expect_split = d.split ^ 1;
+    if (move == HENS_RJ_MOVE_MH || (move == HENS_RJ_MOVE_STRETCH && d.split == 1)) {       // (ONE move; the in-model move's counter, whichever move it is)
+        c->rj.num_mh += 1;
+        if (!has_pt(c)) c->iter += 1;
+    }
+    // ("iterate_branches": one MOVE per walk through the branches)
+    if (move == HENS_RJ_MOVE_BD_ALL || (move == HENS_RJ_MOVE_BD && !(c->rj.schedule == 1 && d.branch != c->rj.M.nb - 1))) c->rj.num_bd += 1;
+}
+
+// One teacher-forced move, whole (keep_out by walker; a stretch half: by position of the moving set) - or, `propose`, its proposal
+// half up to the log-prior (hens_rj_propose).  Either way the move's counters and the order of the stretch halves advance here.
+static int rj_forced_move(hens_ctx_impl* c, int move, const hens_rj_draws& d, uint8_t* keep_out, bool propose) {
+    static const int mode_of[] = {RJ_MODE_MH, RJ_MODE_BD, RJ_MODE_BD, RJ_MODE_STRETCH};       // by HENS_RJ_MOVE_*
+    int r = rj_ready(c, move == HENS_RJ_MOVE_STRETCH && d.split == 1, propose);
+    if (r) return r;
+    if ((r = rj_forced_check(c, move, d))) return r;
     HIPCHK(c, hipSetDevice(c->cfg.device_id));
     state_to_fields(c);                       // (hens_step leaves the state in record mode)
     flush_adapt(c);
     if ((r = rj_ensure_staging(c))) return r;
-    HIPCHK(c, hipMemcpyAsync(c->rj_change, change, TW, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->rj_leaf, leaf, TW * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->rj_birth, birth, TW * (size_t)c->rj.ndmax * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->rj_u, u_acc, TW * 8, hipMemcpyHostToDevice, c->stream));
-    c->rj_tm_valid = false;                   // (teacher-forced move: the reference's full evaluation, no resident templates)
-    if ((r = rj_launch(c, RJ_MODE_BD, branch, nullptr, c->rj_change, c->rj_leaf, c->rj_birth, c->rj_u, c->rj_keep))) return r;
-    if (keep_out) HIPCHK(c, hipMemcpyAsync(keep_out, c->rj_keep, TW, hipMemcpyDeviceToHost, c->stream));
+    RjLaunch l = rj_forced(c, mode_of[move], propose);
+    if ((r = rj_forced_stage(c, move, d, l))) return r;
+    c->rj.tm_valid = false;                   // (teacher-forced move: the reference's full evaluation, no resident templates)
+    if ((r = rj_launch(c, l))) return r;
+    if (propose) c->rj.pending_acc = rj_accept_counter(c, l.mode, l.branch);
+    if (keep_out) HIPCHK(c, hipMemcpyAsync(keep_out, c->rj.keep, (size_t)c->Tl * (l.mode == RJ_MODE_STRETCH ? l.ns : c->W), hipMemcpyDeviceToHost, c->stream));
     if ((r = check_flags(c, false))) return r;
-    if (!(c->rj_schedule == 1 && branch != c->rj.nb - 1)) c->rj_num_bd += 1;    // (one MOVE per walk through the branches)
+    rj_forced_count(c, move, d);
     return HENS_OK;
 }
 
-// "together" with the caller's draws: change / leaf [nbranches][Tl][W], birth [nbranches][Tl][W][3], one u_acc [Tl][W]
+int hens_rj_mh_step(hens_ctx* ctx, const double* step, const double* u_acc, uint8_t* keep_out) {
+    hens_rj_draws d{}; d.step = step; d.u_acc = u_acc;
+    return rj_forced_move(enter(ctx), HENS_RJ_MOVE_MH, d, keep_out, false);
+}
+
+int hens_rj_stretch_split(hens_ctx* ctx, int32_t split, const uint8_t* labels, const int64_t* rint, const double* u_zz,
+                          const double* u_acc, uint8_t* keep_out) {
+    hens_rj_draws d{}; d.split = split; d.labels = labels; d.rint = rint; d.u_zz = u_zz; d.u_acc = u_acc;
+    return rj_forced_move(enter(ctx), HENS_RJ_MOVE_STRETCH, d, keep_out, false);
+}
+
+int hens_rj_bd_step(hens_ctx* ctx, int32_t branch, const int8_t* change, const int32_t* leaf, const double* birth,
+                    const double* u_acc, uint8_t* keep_out) {
+    hens_rj_draws d{}; d.branch = branch; d.change = change; d.leaf = leaf; d.birth = birth; d.u_acc = u_acc;
+    return rj_forced_move(enter(ctx), HENS_RJ_MOVE_BD, d, keep_out, false);
+}
+
 int hens_rj_bd_all_step(hens_ctx* ctx, const int8_t* change, const int32_t* leaf, const double* birth, const double* u_acc,
                         uint8_t* keep_out) {
-    hens_ctx_impl* c = enter(ctx);
-    int r = rj_ready(c);
-    if (r) return r;
-    if (!change || !leaf || !birth || !u_acc) return fail(c, HENS_ERR_INVALID, "null argument");
-    const size_t TW = (size_t)c->Tl * c->W, NB = (size_t)c->rj.nb;
-    for (size_t b = 0; b < NB; ++b)
-        for (size_t i = 0; i < TW; ++i) {
-            const int8_t ch = change[b * TW + i];
-            if (ch < -1 || ch > 1) return fail(c, HENS_ERR_INVALID, "change must be -1, 0 or +1");
-            if (ch != 0 && (leaf[b * TW + i] < 0 || leaf[b * TW + i] >= c->rj.nl[b])) return fail(c, HENS_ERR_INVALID, "leaf slot out of range");
-        }
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    state_to_fields(c);
-    flush_adapt(c);
-    if ((r = rj_ensure_staging(c))) return r;
-    HIPCHK(c, hipMemcpyAsync(c->rj_change, change, NB * TW, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->rj_leaf, leaf, NB * TW * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->rj_birth, birth, NB * TW * (size_t)c->rj.ndmax * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->rj_u, u_acc, TW * 8, hipMemcpyHostToDevice, c->stream));
-    c->rj_tm_valid = false;                   // (teacher-forced move: the reference's full evaluation, no resident templates)
-    if ((r = rj_launch(c, RJ_MODE_BD, -1, nullptr, c->rj_change, c->rj_leaf, c->rj_birth, c->rj_u, c->rj_keep))) return r;
-    if (keep_out) HIPCHK(c, hipMemcpyAsync(keep_out, c->rj_keep, TW, hipMemcpyDeviceToHost, c->stream));
-    if ((r = check_flags(c, false))) return r;
-    c->rj_num_bd += 1;
-    return HENS_OK;
+    hens_rj_draws d{}; d.change = change; d.leaf = leaf; d.birth = birth; d.u_acc = u_acc;
+    return rj_forced_move(enter(ctx), HENS_RJ_MOVE_BD_ALL, d, keep_out, false);
 }
 
 // branch of iteration `it`'s birth / death move (ensemble.py:988-990, "separate_branches"): one counter-based uniform
 static int rj_branch_of(const hens_ctx_impl* c, uint64_t it) {
-    return std::min(c->rj.nb - 1, (int)(move_uniform(c->cfg.seed ^ 0x9E3779B97F4A7C15ull, it) * c->rj.nb));
+    return std::min(c->rj.M.nb - 1, (int)(move_uniform(c->cfg.seed ^ 0x9E3779B97F4A7C15ull, it) * c->rj.M.nb));
+}
+
+// The birth / death move of hens_rj_step's iteration.  "together" (ensemble.py:414-432): ONE proposal changes a leaf in every branch of
+// the walker, one accept test; "iterate_branches" (ensemble.py:434-451, rj.py:169-388): ONE move walks through every branch - birth /
+// death, accept, update per branch -, its accept mask is the last branch's; else one branch's move (ensemble.py:988-990).
+static int rj_step_bd(hens_ctx_impl* c) {
+    if (c->rj.schedule == 2) return rj_launch(c, rj_production(c, RJ_MODE_BD, -1));
+    if (c->rj.schedule != 1) return rj_launch(c, rj_production(c, RJ_MODE_BD, rj_branch_of(c, c->iter)));
+    for (int b = 0, r; b < c->rj.M.nb; ++b)
+        if ((r = rj_launch(c, rj_production(c, RJ_MODE_BD, b)))) return r;
+    return HENS_OK;
 }
 
 int hens_rj_step(hens_ctx* ctx, int64_t n_iters) {
@@ -3380,9 +3407,9 @@ int hens_rj_step(hens_ctx* ctx, int64_t n_iters) {
     if (r) return r;
     if (n_iters < 0) return fail(c, HENS_ERR_INVALID, "n_iters < 0");
     if ((r = counter_room(c, n_iters))) return r;
-    const bool stretch = c->rj_in_model == HENS_RJ_INMODEL_STRETCH;
-    if (!stretch && !c->rj_have_scale) return fail(c, HENS_ERR_STATE, "in-model step scale not set (hens_rj_set_mh_scale)");
-    if (stretch && !c->cfg.live_dangerously && c->W < 2 * c->rj.ind_off)             // red_blue.py:103-114 (every slot of every branch counts)
+    const bool stretch = c->rj.in_model == HENS_RJ_INMODEL_STRETCH;
+    if (!stretch && !c->rj.have_scale) return fail(c, HENS_ERR_STATE, "in-model step scale not set (hens_rj_set_mh_scale)");
+    if (stretch && !c->cfg.live_dangerously && c->W < 2 * c->rj.M.ind_off)           // red_blue.py:103-114 (every slot of every branch counts)
         return fail(c, HENS_ERR_TOO_FEW_WALKERS, "It is unadvisable to use a red-blue move with fewer walkers than twice the number of dimensions. "
                                                  "If you would like to do this, please set live_dangerously to True.");
     HIPCHK(c, hipSetDevice(c->cfg.device_id));
@@ -3399,67 +3426,47 @@ int hens_rj_step(hens_ctx* ctx, int64_t n_iters) {
     // download is a function of what the download returned, so a chain is a function of (State, seed, iteration counter,
     // adaptation time): resumed in a new context it is the uninterrupted chain bit for bit (tests/test_hip_rj.py).
     constexpr int64_t RJ_REFRESH = 64;
-    const int tmode = c->rj_tm ? 0 : -1;
     bool fresh = false;
-    if (c->rj_tm && !c->rj_tm_valid && n_iters > 0) {
-        if ((r = rj_launch(c, RJ_MODE_EVAL, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0))) return r;
-        c->rj_tm_valid = true;
-        c->rj_tm_drift = false;
+    if (c->rj.tm && !c->rj.tm_valid && n_iters > 0) {
+        if ((r = rj_evaluate(c))) return r;
         fresh = true;
     }
     const bool fold_off = env().no_fold;          // A/B knob: k_adapt behind every cascade
-    if (!c->rj_ad_flag && !fold_off) {
-        if ((r = dalloc(c, &c->rj_ad_flag, 2))) return r;
-        HIPCHK(c, hipMemsetAsync(c->rj_ad_flag, 0, 8, c->stream));
+    if (!c->rj.ad_flag && !fold_off) {
+        if ((r = dalloc(c, &c->rj.ad_flag, 2))) return r;
+        HIPCHK(c, hipMemsetAsync(c->rj.ad_flag, 0, 8, c->stream));
     }
     struct Defer {                             // (every way out of the loop leaves no adaptation pending and the switch off)
         hens_ctx_impl* c;
-        ~Defer() { c->rj_defer_adapt = false; flush_adapt(c); }
+        ~Defer() { c->rj.defer_adapt = false; flush_adapt(c); }
     } defer{c};
-    c->rj_defer_adapt = !fold_off && c->rj_tm != nullptr;
+    c->rj.defer_adapt = !fold_off && c->rj.tm != nullptr;
     for (int64_t i = 0; i < n_iters; ++i) {
-        if (c->rj_tm && c->iter % RJ_REFRESH == RJ_REFRESH - 1 && !fresh && c->rj_tm_drift)
-            if ((r = rj_launch(c, RJ_MODE_EVAL, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0))) return r;
+        if (c->rj.tm && c->iter % RJ_REFRESH == RJ_REFRESH - 1 && !fresh && c->rj.tm_drift)
+            if ((r = rj_evaluate(c))) return r;
         fresh = false;
-        c->rj_tm_drift = c->rj_tm != nullptr && c->rj_schedule != 3;      // (only birth / death updates a template by +- a leaf)
+        c->rj.tm_drift = c->rj.tm != nullptr && c->rj.schedule != 3;      // (only birth / death updates a template by +- a leaf)
         if (stretch) {
             // red / blue stretch move over every branch and leaf slot: two launches, a half each - the complements of a half
             // belong to the other set, which its launch does not write (red_blue.py:148-323); ONE move (num_mh)
-            const int n0 = (c->W + 1) / 2;
-            for (int h = 0; h < 2; ++h) {
-                c->rj_st_split = h;
-                c->rj_st_ns = h == 0 ? n0 : c->W - n0;
-                if (c->rj_st_ns == 0) continue;
-                if ((r = rj_launch(c, RJ_MODE_STRETCH, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, tmode))) return r;
-            }
+            for (int h = 0; h < 2; ++h)
+                if (const RjLaunch half = rj_production(c, RJ_MODE_STRETCH, 0, h); half.ns != 0 && (r = rj_launch(c, half))) return r;
         } else {
             // in-model Gaussian move on the packed leaves (mh.py:56-193)
-            if ((r = rj_launch(c, RJ_MODE_MH, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, tmode))) return r;
+            if ((r = rj_launch(c, rj_production(c, RJ_MODE_MH)))) return r;
         }
-        c->rj_num_mh += 1;
+        c->rj.num_mh += 1;
         rj_cascade(c, 2 * c->iter, true);         // swaps + adaptation (mh.py:190-191, red_blue.py:326-328)
-        if (c->rj_schedule == 3) {                // no reversible-jump move (EnsembleSampler without rj_moves): counter and keys as ever
+        if (c->rj.schedule == 3) {                // no reversible-jump move (EnsembleSampler without rj_moves): counter and keys as ever
             c->iter += 1;
             continue;
         }
-        if (c->rj_schedule == 2) {
-            // "together" (ensemble.py:414-432): ONE proposal changes a leaf in every branch of the walker; one accept test
-            if ((r = rj_launch(c, RJ_MODE_BD, -1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, c->rj_tm ? 1 : -1))) return r;
-        } else if (c->rj_schedule == 1) {
-            // "iterate_branches" (ensemble.py:434-451, rj.py:169-388): ONE move walks through every branch - birth / death,
-            // accept, update per branch - then one sweep of swaps without adaptation; its accept mask is the last branch's
-            for (int b = 0; b < c->rj.nb; ++b)
-                if ((r = rj_launch(c, RJ_MODE_BD, b, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, c->rj_tm ? 1 : -1))) return r;
-        } else {
-            // one branch's birth / death move (ensemble.py:988-990, "separate_branches"), then swaps without adaptation
-            const int branch = rj_branch_of(c, c->iter);
-            if ((r = rj_launch(c, RJ_MODE_BD, branch, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, c->rj_tm ? 1 : -1))) return r;
-        }
-        c->rj_num_bd += 1;
+        if ((r = rj_step_bd(c))) return r;
+        c->rj.num_bd += 1;
         rj_cascade(c, 2 * c->iter + 1, false);
         c->iter += 1;
     }
-    c->rj_defer_adapt = false;
+    c->rj.defer_adapt = false;
     flush_adapt(c);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(c->ev1, c->stream));
@@ -3479,57 +3486,50 @@ int hens_rj_propose(hens_ctx* ctx, int32_t move, const hens_rj_draws* d, double*
     hens_ctx_impl* c = enter(ctx);
     if (!c || !d || !q_out || !logp_out || !moved_out) return fail(c, HENS_ERR_INVALID, "null argument");
     if (c->cfg.likelihood_kind != HENS_LIKE_TEMPLATE) return fail(c, HENS_ERR_STATE, "hens_rj_* needs a context created with HENS_LIKE_TEMPLATE");
-    if (c->rj_accept_pending) return fail(c, HENS_ERR_STATE, "hens_rj_accept must follow hens_rj_propose");
+    if (c->rj.accept_pending) return fail(c, HENS_ERR_STATE, "hens_rj_accept must follow hens_rj_propose");
     HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    const size_t TW = (size_t)c->Tl * c->W, RW = (size_t)c->rj.RW;
+    const size_t TW = (size_t)c->Tl * c->W, RW = (size_t)c->rj.M.RW;
     int r;
-    if (!c->rj_hq) {
-        if ((r = dalloc(c, &c->rj_hq, TW * RW))) return r;
-        if ((r = dalloc(c, &c->rj_hlogp, TW))) return r;
-        if ((r = dalloc(c, &c->rj_hfac, TW))) return r;
-        if ((r = dalloc(c, &c->rj_hlu, TW))) return r;
-        if ((r = dalloc(c, &c->rj_hlogl, TW))) return r;
-        if ((r = dalloc(c, &c->rj_hmoved, TW))) return r;
+    if (!c->rj.hq) {
+        if ((r = dalloc(c, &c->rj.hq, TW * RW))) return r;
+        if ((r = dalloc(c, &c->rj.hlogp, TW))) return r;
+        if ((r = dalloc(c, &c->rj.hfac, TW))) return r;
+        if ((r = dalloc(c, &c->rj.hlu, TW))) return r;
+        if ((r = dalloc(c, &c->rj.hlogl, TW))) return r;
+        if ((r = dalloc(c, &c->rj.hmoved, TW))) return r;
     }
-    HIPCHK(c, hipMemsetAsync(c->rj_hmoved, 0, TW, c->stream));
-    c->rj_hostlike = true;
-    switch (move) {
-        case HENS_RJ_MOVE_MH: r = hens_rj_mh_step(ctx, d->step, d->u_acc, nullptr); break;
-        case HENS_RJ_MOVE_BD: r = hens_rj_bd_step(ctx, d->branch, d->change, d->leaf, d->birth, d->u_acc, nullptr); break;
-        case HENS_RJ_MOVE_BD_ALL: r = hens_rj_bd_all_step(ctx, d->change, d->leaf, d->birth, d->u_acc, nullptr); break;
-        case HENS_RJ_MOVE_STRETCH: r = hens_rj_stretch_split(ctx, d->split, d->labels, d->rint, d->u_zz, d->u_acc, nullptr); break;
-        default: r = fail(c, HENS_ERR_INVALID, "hens_rj_propose: move must be HENS_RJ_MOVE_MH, _BD, _BD_ALL or _STRETCH");
-    }
-    c->rj_hostlike = false;
-    if (r) return r;
-    HIPCHK(c, hipMemcpyAsync(q_out, c->rj_hq, TW * RW * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(logp_out, c->rj_hlogp, TW * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(moved_out, c->rj_hmoved, TW, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->rj.hmoved, 0, TW, c->stream));
+    if (move < HENS_RJ_MOVE_MH || move > HENS_RJ_MOVE_STRETCH)
+        return fail(c, HENS_ERR_INVALID, "hens_rj_propose: move must be HENS_RJ_MOVE_MH, _BD, _BD_ALL or _STRETCH");
+    if ((r = rj_forced_move(c, move, *d, nullptr, true))) return r;
+    HIPCHK(c, hipMemcpyAsync(q_out, c->rj.hq, TW * RW * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(logp_out, c->rj.hlogp, TW * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(moved_out, c->rj.hmoved, TW, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->rj_accept_pending = true;
+    c->rj.accept_pending = true;
     return HENS_OK;
 }
 
 int hens_rj_accept(hens_ctx* ctx, const double* logl, uint8_t* keep_out) {
     hens_ctx_impl* c = enter(ctx);
     if (!c || !logl) return fail(c, HENS_ERR_INVALID, "null argument");
-    if (!c->rj_accept_pending) return fail(c, HENS_ERR_STATE, "hens_rj_accept must follow hens_rj_propose");
+    if (!c->rj.accept_pending) return fail(c, HENS_ERR_STATE, "hens_rj_accept must follow hens_rj_propose");
     HIPCHK(c, hipSetDevice(c->cfg.device_id));
     const size_t TW = (size_t)c->Tl * c->W;
     for (size_t i = 0; i < TW; ++i)
         if (logl[i] != logl[i]) return fail(c, HENS_ERR_NONFINITE, "The likelihood function is returning Nan.");       // ensemble.py:1542
-    HIPCHK(c, hipMemcpyAsync(c->rj_hlogl, logl, TW * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->rj.hlogl, logl, TW * 8, hipMemcpyHostToDevice, c->stream));
     RjAcceptArgs a{};
     a.pool = c->pool; a.loc = c->loc[c->cur]; a.L = c->L[c->cur]; a.P = c->P[c->cur];
     a.betas = c->cfg.tempered ? c->betas[c->bcur] : nullptr;
-    a.accepted = c->rj_h_accepted; a.keep_out = c->rj_keep;
-    a.hq = c->rj_hq; a.hlogp = c->rj_hlogp; a.hfac = c->rj_hfac; a.hlu = c->rj_hlu; a.hmoved = c->rj_hmoved; a.logl = c->rj_hlogl;
-    a.Tl = c->Tl; a.W = c->W; a.RW = c->rj.RW; a.rung_begin = c->cfg.rung_begin; a.tempered = c->cfg.tempered;
+    a.accepted = c->rj.pending_acc; a.keep_out = c->rj.keep;
+    a.hq = c->rj.hq; a.hlogp = c->rj.hlogp; a.hfac = c->rj.hfac; a.hlu = c->rj.hlu; a.hmoved = c->rj.hmoved; a.logl = c->rj.hlogl;
+    a.Tl = c->Tl; a.W = c->W; a.RW = c->rj.M.RW; a.rung_begin = c->cfg.rung_begin; a.tempered = c->cfg.tempered;
     hipLaunchKernelGGL(k_rj_accept, dim3((unsigned)((TW + 3) / 4)), dim3(256), 0, c->stream, a);
     HIPCHK(c, hipGetLastError());
-    if (keep_out) HIPCHK(c, hipMemcpyAsync(keep_out, c->rj_keep, TW, hipMemcpyDeviceToHost, c->stream));
+    if (keep_out) HIPCHK(c, hipMemcpyAsync(keep_out, c->rj.keep, TW, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->rj_accept_pending = false;
+    c->rj.accept_pending = false;
     return HENS_OK;
 }
 
@@ -3538,7 +3538,7 @@ int hens_rj_set_schedule(hens_ctx* ctx, int32_t schedule) {
     if (!c) return fail(c, HENS_ERR_INVALID, "null context");
     if (c->cfg.likelihood_kind != HENS_LIKE_TEMPLATE) return fail(c, HENS_ERR_STATE, "hens_rj_* needs a context created with HENS_LIKE_TEMPLATE");
     if (schedule < 0 || schedule > 3) return fail(c, HENS_ERR_UNSUPPORTED, "rj schedule must be 0 (separate_branches), 1 (iterate_branches), 2 (together) or 3 (none)");
-    c->rj_schedule = schedule;
+    c->rj.schedule = schedule;
     return HENS_OK;
 }
 
@@ -3546,10 +3546,10 @@ int hens_rj_set_in_model(hens_ctx* ctx, int32_t kind) {
     hens_ctx_impl* c = enter(ctx);
     if (!c) return fail(c, HENS_ERR_INVALID, "null context");
     if (c->cfg.likelihood_kind != HENS_LIKE_TEMPLATE) return fail(c, HENS_ERR_STATE, "hens_rj_* needs a context created with HENS_LIKE_TEMPLATE");
-    if (c->rj_general) return fail(c, HENS_ERR_STATE, "the Philox in-model move belongs to hens_rj_step: template models only");
+    if (c->rj.general) return fail(c, HENS_ERR_STATE, "the Philox in-model move belongs to hens_rj_step: template models only");
     if (kind != HENS_RJ_INMODEL_GAUSSIAN && kind != HENS_RJ_INMODEL_STRETCH)
         return fail(c, HENS_ERR_INVALID, "in-model move must be HENS_RJ_INMODEL_GAUSSIAN or HENS_RJ_INMODEL_STRETCH");
-    c->rj_in_model = kind;
+    c->rj.in_model = kind;
     return HENS_OK;
 }
 
@@ -3558,10 +3558,10 @@ int hens_rj_set_in_model(hens_ctx* ctx, int32_t kind) {
 int hens_rj_debug_draws_stretch(hens_ctx* ctx, int64_t iter, uint8_t* labels, int64_t* rint, double* u_zz, double* u_acc) {
     hens_ctx_impl* c = enter(ctx);
     if (!c || iter < 0) return fail(c, HENS_ERR_INVALID, "null context / negative iteration");
-    if (c->cfg.likelihood_kind != HENS_LIKE_TEMPLATE || c->rj.nb <= 0) return fail(c, HENS_ERR_STATE, "hens_rj_set_model first");
+    if (c->cfg.likelihood_kind != HENS_LIKE_TEMPLATE || c->rj.M.nb <= 0) return fail(c, HENS_ERR_STATE, "hens_rj_set_model first");
     if (!labels || !rint || !u_zz || !u_acc) return fail(c, HENS_ERR_INVALID, "null output");
     HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    const int Tl = c->Tl, W = c->W, nb = c->rj.nb, n0 = (W + 1) / 2;
+    const int Tl = c->Tl, W = c->W, nb = c->rj.M.nb, n0 = (W + 1) / 2;
     const size_t TW = (size_t)Tl * W;
     struct Scratch {
         std::vector<void*> p;
@@ -3615,12 +3615,12 @@ int hens_rj_debug_draws(hens_ctx* ctx, int64_t iter, double* step, double* u_mh,
                         double* birth, double* u_bd, int32_t* slot_mh, double* uswap_mh, int32_t* slot_bd, double* uswap_bd) {
     hens_ctx_impl* c = enter(ctx);
     if (!c || iter < 0) return fail(c, HENS_ERR_INVALID, "null context / negative iteration");
-    if (c->cfg.likelihood_kind != HENS_LIKE_TEMPLATE || c->rj.nb <= 0) return fail(c, HENS_ERR_STATE, "hens_rj_set_model first");
-    const bool stretch = c->rj_in_model == HENS_RJ_INMODEL_STRETCH;       // (its draws: hens_rj_debug_draws_stretch; step / u_mh are zeros here)
-    if (!stretch && !c->rj_have_scale) return fail(c, HENS_ERR_STATE, "in-model step scale not set (hens_rj_set_mh_scale)");
+    if (c->cfg.likelihood_kind != HENS_LIKE_TEMPLATE || c->rj.M.nb <= 0) return fail(c, HENS_ERR_STATE, "hens_rj_set_model first");
+    const bool stretch = c->rj.in_model == HENS_RJ_INMODEL_STRETCH;       // (its draws: hens_rj_debug_draws_stretch; step / u_mh are zeros here)
+    if (!stretch && !c->rj.have_scale) return fail(c, HENS_ERR_STATE, "in-model step scale not set (hens_rj_set_mh_scale)");
     if (!step || !u_mh || !branch || !coin || !sel || !birth || !u_bd) return fail(c, HENS_ERR_INVALID, "null output");
     HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    const size_t TW = (size_t)c->Tl * c->W, IO = (size_t)c->rj.ind_off;
+    const size_t TW = (size_t)c->Tl * c->W, IO = (size_t)c->rj.M.ind_off;
     struct Scratch {
         std::vector<void*> p;
         ~Scratch() { for (void* q : p) (void)hipFree(q); }
@@ -3632,22 +3632,22 @@ int hens_rj_debug_draws(hens_ctx* ctx, int64_t iter, double* step, double* u_mh,
         return q;
     };
     RjDebugArgs a{};
-    a.M = c->rj;
+    a.M = c->rj.M;
     a.step = (double*)grab(TW * IO * 8); a.u_mh = (double*)grab(TW * 8); a.coin = (int8_t*)grab(TW);
     a.sel = (uint32_t*)grab(TW * 4); a.birth = (double*)grab(TW * RJ_ND * 8); a.u_bd = (double*)grab(TW * 8);
     if (!a.step || !a.u_mh || !a.coin || !a.sel || !a.birth || !a.u_bd) return fail(c, HENS_ERR_HIP, "hens_rj_debug_draws: out of device memory");
     a.iter = (uint64_t)iter; a.seed = c->cfg.seed;
     a.Tl = c->Tl; a.W = c->W; a.rung_begin = c->cfg.rung_begin; a.stretch = stretch ? 1 : 0;
-    a.use_chol = c->rj_have_chol ? 1 : 0;
-    memcpy(a.chol, c->rj_chol, sizeof(a.chol));
+    a.use_chol = c->rj.have_chol ? 1 : 0;
+    memcpy(a.chol, c->rj.chol, sizeof(a.chol));
     // "separate_branches" (and no birth / death move at all: what one WOULD draw): the chosen branch's draws; "iterate_branches",
     // "together": every branch's, in order (outputs [nbranches][...])
-    const bool every = c->rj_schedule == 1 || c->rj_schedule == 2;
-    const int nsub = every ? c->rj.nb : 1;
+    const bool every = c->rj.schedule == 1 || c->rj.schedule == 2;
+    const int nsub = every ? c->rj.M.nb : 1;
     *branch = every ? -1 : rj_branch_of(c, (uint64_t)iter);
     for (int k = 0; k < nsub; ++k) {
         a.branch = every ? k : *branch;
-        a.acc_branch = c->rj_schedule == 2 ? c->rj.nb : a.branch;      // ("together": ONE accept uniform, in every row of u_bd)
+        a.acc_branch = c->rj.schedule == 2 ? c->rj.M.nb : a.branch;      // ("together": ONE accept uniform, in every row of u_bd)
         hipLaunchKernelGGL(k_rj_debug_draws, dim3(grid_for((int64_t)TW)), dim3(256), 0, c->stream, a);
         HIPCHK(c, hipGetLastError());
         if (k == 0) {
@@ -3680,25 +3680,25 @@ int hens_rj_debug_draws(hens_ctx* ctx, int64_t iter, double* step, double* u_mh,
 int hens_rj_get_counters(hens_ctx* ctx, double* accepted_bd, int64_t* num_mh, int64_t* num_bd) {
     hens_ctx_impl* c = enter(ctx);
     if (!c) return fail(c, HENS_ERR_INVALID, "null context");
-    if (c->cfg.likelihood_kind != HENS_LIKE_TEMPLATE || !c->rj_acc_bd) return fail(c, HENS_ERR_STATE, "hens_rj_set_model first");
+    if (c->cfg.likelihood_kind != HENS_LIKE_TEMPLATE || !c->rj.acc_bd) return fail(c, HENS_ERR_STATE, "hens_rj_set_model first");
     HIPCHK(c, hipSetDevice(c->cfg.device_id));
     state_to_fields(c);                       // (hens_step leaves the state in record mode)
     const size_t TW = (size_t)c->Tl * c->W;
     if (accepted_bd) {
         std::vector<uint32_t> acc(TW);
-        HIPCHK(c, hipMemcpyAsync(acc.data(), c->rj_acc_bd, TW * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(acc.data(), c->rj.acc_bd, TW * 4, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         for (size_t i = 0; i < TW; ++i) accepted_bd[i] = (double)acc[i];
     }
-    if (num_mh) *num_mh = c->rj_num_mh;
-    if (num_bd) *num_bd = c->rj_num_bd;
+    if (num_mh) *num_mh = c->rj.num_mh;
+    if (num_bd) *num_bd = c->rj.num_bd;
     return HENS_OK;
 }
 
 int hens_rj_debug_resident(hens_ctx* ctx, double* rec, double* logl) {
     hens_ctx_impl* c = enter(ctx);
     if (!c) return fail(c, HENS_ERR_INVALID, "null context");
-    if (c->cfg.likelihood_kind != HENS_LIKE_TEMPLATE || c->rj.nb <= 0) return fail(c, HENS_ERR_STATE, "hens_rj_set_model first");
+    if (c->cfg.likelihood_kind != HENS_LIKE_TEMPLATE || c->rj.M.nb <= 0) return fail(c, HENS_ERR_STATE, "hens_rj_set_model first");
     if (!c->have_state) return fail(c, HENS_ERR_STATE, "no state uploaded");
     HIPCHK(c, hipSetDevice(c->cfg.device_id));
     state_to_fields(c);                       // (hens_step leaves the state in record mode)
