@@ -191,6 +191,7 @@ struct hens_ctx_impl {
     struct Rj {
         RjModel M{};                         // the model as the kernels see it (RjArgs::M)
         bool general = false;                // hens_rj_set_model_general: leaf widths other than 3 / no template likelihood - hens_rj_propose / _accept only
+        bool wide = false;                   // hens_rj_set_model_kinds with a leaf kind beyond pulse / sine: the WIDE instantiations of k_rj
         double* t = nullptr; double* y = nullptr;              // [ndata] data of the template likelihood
         double* ctab = nullptr; int32_t* cbn = nullptr;        // RjArgs::ctab / cbn: what a lane needs about its record coordinate (rj_push_ctab)
         double* step = nullptr; double* u = nullptr; double* birth = nullptr;         // the caller's draws of a teacher-forced move (rj_ensure_staging)
@@ -1651,16 +1652,21 @@ RjLaunch rj_forced(const hens_ctx_impl* c, int mode, bool propose) {
 uint32_t* rj_accept_counter(const hens_ctx_impl* c, int mode, int branch) {
     return mode != RJ_MODE_BD ? c->accepted : (c->rj.schedule == 1 && branch != c->rj.M.nb - 1 ? nullptr : c->rj.acc_bd);
 }
-// k_rj's instantiations: (mode, template scheme or -1 none / -2 proposal half or log-prior alone, Philox in-model move that forms L z)
-struct RjInst { int mode, tmm; bool chol; void (*k)(const RjArgs); };
-#define RJ_INST(MODE_, TMM_, CHOL_) {MODE_, TMM_, CHOL_, k_rj<MODE_, TMM_, CHOL_>}
+// k_rj's instantiations: (mode, template scheme or -1 none / -2 proposal half or log-prior alone, Philox in-model move that forms L z,
+// a model with leaf kinds beyond pulse / sine)
+struct RjInst { int mode, tmm; bool chol, wide; void (*k)(const RjArgs); };
+#define RJ_INST(MODE_, TMM_, CHOL_) {MODE_, TMM_, CHOL_, false, k_rj<MODE_, TMM_, CHOL_>}
+#define RJ_INST_WIDE(MODE_, TMM_) {MODE_, TMM_, false, true, k_rj<MODE_, TMM_, false, true>}
 const RjInst RJ_INSTS[] = {        // (listed in the order the code object has had them since they were an if-chain)
     RJ_INST(RJ_MODE_MH, 0, true), RJ_INST(RJ_MODE_MH, -1, true), RJ_INST(RJ_MODE_EVAL, -1, false), RJ_INST(RJ_MODE_EVAL, 0, false), RJ_INST(RJ_MODE_EVAL, 2, false),
     RJ_INST(RJ_MODE_MH, -1, false), RJ_INST(RJ_MODE_MH, 0, false), RJ_INST(RJ_MODE_BD, -1, false), RJ_INST(RJ_MODE_BD, 1, false),
     RJ_INST(RJ_MODE_STRETCH, -1, false), RJ_INST(RJ_MODE_STRETCH, 0, false),
     RJ_INST(RJ_MODE_MH, -2, false), RJ_INST(RJ_MODE_BD, -2, false), RJ_INST(RJ_MODE_STRETCH, -2, false), RJ_INST(RJ_MODE_EVAL, -2, false),
+    RJ_INST_WIDE(RJ_MODE_EVAL, -1), RJ_INST_WIDE(RJ_MODE_EVAL, 0), RJ_INST_WIDE(RJ_MODE_EVAL, 2), RJ_INST_WIDE(RJ_MODE_MH, -1), RJ_INST_WIDE(RJ_MODE_MH, 0),
+    RJ_INST_WIDE(RJ_MODE_BD, -1), RJ_INST_WIDE(RJ_MODE_BD, 1), RJ_INST_WIDE(RJ_MODE_STRETCH, -1), RJ_INST_WIDE(RJ_MODE_STRETCH, 0),
 };
 #undef RJ_INST
+#undef RJ_INST_WIDE
 
 int rj_launch(hens_ctx_impl* c, const RjLaunch& l) {
     const int mode = l.mode;
@@ -1705,9 +1711,10 @@ int rj_launch(hens_ctx_impl* c, const RjLaunch& l) {
         a.hq = c->rj.hq; a.hlogp = c->rj.hlogp; a.hfac = c->rj.hfac; a.hlu = c->rj.hlu; a.hmoved = c->rj.hmoved;
     }
     const bool chol = mode == RJ_MODE_MH && l.draws == RjLaunch::PHILOX && c->rj.have_chol && tmm != -2;
+    const bool wide = c->rj.wide && tmm != -2;        // (the proposal half of a host-callable move has the widths at run time already)
     const RjInst* inst = nullptr;
     for (const RjInst& i : RJ_INSTS)
-        if (i.mode == mode && i.tmm == tmm && i.chol == chol) inst = &i;
+        if (i.mode == mode && i.tmm == tmm && i.chol == chol && i.wide == wide) inst = &i;
     if (!inst) return fail(c, HENS_ERR_INVALID, "k_rj: no instantiation for mode %d with template scheme %d", mode, tmm);
     hipLaunchKernelGGL(inst->k, grid, block, 0, c->stream, a);
     const hipError_t e = hipGetLastError();
@@ -3081,10 +3088,11 @@ int hens_debug_draws(hens_ctx* ctx, int64_t iter, int32_t* own, int32_t* cw, dou
 }
 
 // ---- reversible-jump leaf packing ----------------------------------------------------------
-int hens_rj_set_model(hens_ctx* ctx, int32_t nbranches, const int32_t* kinds, const int32_t* nleaves_max,
-                      const int32_t* nleaves_min, const double* lo, const double* hi, const double* leaf_logp,
-                      int32_t ndata, const double* t, const double* y, double sigma) {
-    hens_ctx_impl* c = enter(ctx);
+// The body of hens_rj_set_model and hens_rj_set_model_kinds: a model whose likelihood the device evaluates.  nkinds: the leaf kinds
+// the entry point takes (ids below it); lo / hi: the branches' boxes one after the other, a branch's width that of its kind.
+static int rj_set_template_model(hens_ctx_impl* c, int nkinds, int32_t nbranches, const int32_t* kinds, const int32_t* nleaves_max,
+                                 const int32_t* nleaves_min, const double* lo, const double* hi, const double* leaf_logp,
+                                 int32_t ndata, const double* t, const double* y, double sigma) {
     if (!c || !kinds || !nleaves_max || !nleaves_min || !lo || !hi || !leaf_logp || !t || !y)
         return fail(c, HENS_ERR_INVALID, "null argument");
     if (c->cfg.likelihood_kind != HENS_LIKE_TEMPLATE) return fail(c, HENS_ERR_STATE, "hens_rj_set_model needs HENS_LIKE_TEMPLATE");
@@ -3094,21 +3102,28 @@ int hens_rj_set_model(hens_ctx* ctx, int32_t nbranches, const int32_t* kinds, co
     state_to_fields(c);                       // (hens_step leaves the state in record mode)
     RjModel M{};
     M.nb = nbranches; M.ndata = ndata; M.sigma = sigma;
-    int off = 0;
+    int off = 0, slot = 0, k = 0, boff[RJ_MAX_BRANCH] = {0, 0, 0, 0};      // (boff: a branch's first entry of lo / hi)
+    bool wide = false;
     for (int b = 0; b < nbranches; ++b) {
-        if (kinds[b] != RJ_KIND_PULSE && kinds[b] != RJ_KIND_SINE) return fail(c, HENS_ERR_INVALID, "unknown leaf kind %d", kinds[b]);
+        if (kinds[b] < 0 || kinds[b] >= nkinds) return fail(c, HENS_ERR_INVALID, "unknown leaf kind %d", kinds[b]);
         if (nleaves_max[b] < 1 || nleaves_max[b] > 32 || nleaves_min[b] < 0 || nleaves_min[b] > nleaves_max[b])
             return fail(c, HENS_ERR_INVALID, "branch %d: need 0 <= nleaves_min <= nleaves_max <= 32", b);
+        const int nd = RJ_KIND_WIDTH[kinds[b]];
+        wide = wide || kinds[b] > RJ_KIND_SINE;
         M.kind[b] = kinds[b]; M.nl[b] = nleaves_max[b]; M.nlmin[b] = nleaves_min[b]; M.off[b] = off;
-        M.nd[b] = RJ_ND; M.slot0[b] = off / RJ_ND; M.ndmax = RJ_ND;
-        off += nleaves_max[b] * RJ_ND;
-        for (int d = 0; d < RJ_ND; ++d) {
-            M.lo[b][d] = lo[b * RJ_ND + d]; M.hi[b][d] = hi[b * RJ_ND + d];
+        M.nd[b] = nd; M.slot0[b] = slot; M.ndmax = std::max(M.ndmax, nd);
+        off += nleaves_max[b] * nd;
+        slot += nleaves_max[b];
+        boff[b] = k;
+        for (int d = 0; d < nd; ++d, ++k) {
+            M.lo[b][d] = lo[k]; M.hi[b][d] = hi[k];
             if (!(M.hi[b][d] > M.lo[b][d])) return fail(c, HENS_ERR_INVALID, "branch %d: empty prior box", b);
         }
         M.leaf_logp[b] = leaf_logp[b];
     }
-    {   // data points on a uniform grid (np.linspace): the sine leaves' rotation scheme of k_rj applies
+    if (wide && slot > 64) return fail(c, HENS_ERR_UNSUPPORTED, "%d leaf slots: at most 64 over all branches", slot);
+    if (wide && c->D > RJ_MAX_RW) return fail(c, HENS_ERR_INVALID, "record width ndim = %d: at most %d doubles", c->D, RJ_MAX_RW);
+    if (!wide) {   // data points on a uniform grid (np.linspace): the sine leaves' rotation scheme of k_rj applies
         const double eps = 2.220446049250313e-16;
         const double dt = ndata > 1 ? (t[ndata - 1] - t[0]) / (double)(ndata - 1) : 0.0;
         double tmax = 0.0, dev = 0.0;
@@ -3133,7 +3148,7 @@ int hens_rj_set_model(hens_ctx* ctx, int32_t nbranches, const int32_t* kinds, co
             }
             for (int b = 0; b < nbranches; ++b)
                 if (kinds[b] == RJ_KIND_PULSE) {
-                    const double clo = lo[b * RJ_ND + 2], chi = hi[b * RJ_ND + 2];
+                    const double clo = lo[boff[b] + 2], chi = hi[boff[b] + 2];
                     cmin = std::min(cmin, (clo <= 0.0 && chi >= 0.0) ? 0.0 : std::min(std::fabs(clo), std::fabs(chi)));
                 }
             uniform = d <= 128.0 * eps * cmin;           // (no pulse branch: cmin = inf)
@@ -3143,8 +3158,10 @@ int hens_rj_set_model(hens_ctx* ctx, int32_t nbranches, const int32_t* kinds, co
     M.ind_off = off;
     M.RW = c->D;
     if (off + nbranches > c->D) return fail(c, HENS_ERR_INVALID, "record width ndim = %d cannot hold %d coordinates + %d masks", c->D, off, nbranches);
+    if (wide && c->rj.have_chol) { c->rj.have_chol = c->rj.have_scale = false; memset(c->rj.chol, 0, sizeof(c->rj.chol)); }     // (full leaf covariances: pulse / sine models)
     c->rj.M = M;
     c->rj.general = false;
+    c->rj.wide = wide;
     int r;
     if ((r = rj_push_ctab(c))) return r;
     if (!c->rj.t) {
@@ -3165,6 +3182,20 @@ int hens_rj_set_model(hens_ctx* ctx, int32_t nbranches, const int32_t* kinds, co
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->have_like = c->have_prior = true;
     return HENS_OK;
+}
+
+int hens_rj_set_model(hens_ctx* ctx, int32_t nbranches, const int32_t* kinds, const int32_t* nleaves_max,
+                      const int32_t* nleaves_min, const double* lo, const double* hi, const double* leaf_logp,
+                      int32_t ndata, const double* t, const double* y, double sigma) {
+    return rj_set_template_model(enter(ctx), RJ_KIND_SINE + 1, nbranches, kinds, nleaves_max, nleaves_min, lo, hi, leaf_logp, ndata, t, y, sigma);
+}
+
+// ... with every leaf kind the device evaluates (RJ_KIND_*: one to four parameters per leaf).  A model of pulses and sines alone is
+// hens_rj_set_model's, launch for launch; any other takes the WIDE instantiations of k_rj (no uniform-grid recurrences).
+int hens_rj_set_model_kinds(hens_ctx* ctx, int32_t nbranches, const int32_t* kinds, const int32_t* nleaves_max,
+                            const int32_t* nleaves_min, const double* lo, const double* hi, const double* leaf_logp,
+                            int32_t ndata, const double* t, const double* y, double sigma) {
+    return rj_set_template_model(enter(ctx), RJ_NKINDS, nbranches, kinds, nleaves_max, nleaves_min, lo, hi, leaf_logp, ndata, t, y, sigma);
 }
 
 // A leaf-packing model WITHOUT a device likelihood: branches of 1 .. RJ_MAX_ND box-prior parameters per leaf (ensemble.py:325-329:
@@ -3203,6 +3234,7 @@ int hens_rj_set_model_general(hens_ctx* ctx, int32_t nbranches, const int32_t* n
         return fail(c, HENS_ERR_INVALID, "record width ndim = %d cannot hold %d coordinates + %d masks (at most %d)", c->D, off, nbranches, RJ_MAX_RW);
     c->rj.M = M;
     c->rj.general = true;
+    c->rj.wide = false;
     int r;
     if ((r = rj_push_ctab(c))) return r;
     if (!c->rj.acc_bd) {
@@ -3220,8 +3252,8 @@ int hens_rj_set_mh_scale(hens_ctx* ctx, const double* scale) {
     if (!c || !scale) return fail(c, HENS_ERR_INVALID, "null argument");
     if (c->cfg.likelihood_kind != HENS_LIKE_TEMPLATE || !c->have_like) return fail(c, HENS_ERR_STATE, "hens_rj_set_model first");
     if (c->rj.general) return fail(c, HENS_ERR_STATE, "the Philox in-model move belongs to hens_rj_step: template models only");
-    for (int b = 0; b < c->rj.M.nb; ++b)
-        for (int d = 0; d < RJ_ND; ++d) c->rj.M.mh_scale[b][d] = scale[b * RJ_ND + d];
+    for (int b = 0; b < c->rj.M.nb; ++b)          // [nbranches][the widest branch's parameters]: 3 on a pulse / sine model
+        for (int d = 0; d < c->rj.M.nd[b]; ++d) c->rj.M.mh_scale[b][d] = scale[b * c->rj.M.ndmax + d];
     c->rj.have_scale = true; c->rj.have_chol = false;
     HIPCHK(c, hipSetDevice(c->cfg.device_id));
     return rj_push_ctab(c);
@@ -3235,6 +3267,7 @@ int hens_rj_set_mh_chol(hens_ctx* ctx, const double* chol) {
     if (!c || !chol) return fail(c, HENS_ERR_INVALID, "null argument");
     if (c->cfg.likelihood_kind != HENS_LIKE_TEMPLATE || !c->have_like) return fail(c, HENS_ERR_STATE, "hens_rj_set_model first");
     if (c->rj.general) return fail(c, HENS_ERR_STATE, "the Philox in-model move belongs to hens_rj_step: template models only");
+    if (c->rj.wide) return fail(c, HENS_ERR_UNSUPPORTED, "full leaf covariances: models of pulses and sines only (diagonal steps: hens_rj_set_mh_scale)");
     for (int b = 0; b < c->rj.M.nb; ++b)
         for (int d = 0; d < RJ_ND; ++d)
             for (int j = 0; j < RJ_ND; ++j) {
@@ -3634,7 +3667,7 @@ int hens_rj_debug_draws(hens_ctx* ctx, int64_t iter, double* step, double* u_mh,
     RjDebugArgs a{};
     a.M = c->rj.M;
     a.step = (double*)grab(TW * IO * 8); a.u_mh = (double*)grab(TW * 8); a.coin = (int8_t*)grab(TW);
-    a.sel = (uint32_t*)grab(TW * 4); a.birth = (double*)grab(TW * RJ_ND * 8); a.u_bd = (double*)grab(TW * 8);
+    a.sel = (uint32_t*)grab(TW * 4); a.birth = (double*)grab(TW * (size_t)c->rj.M.ndmax * 8); a.u_bd = (double*)grab(TW * 8);
     if (!a.step || !a.u_mh || !a.coin || !a.sel || !a.birth || !a.u_bd) return fail(c, HENS_ERR_HIP, "hens_rj_debug_draws: out of device memory");
     a.iter = (uint64_t)iter; a.seed = c->cfg.seed;
     a.Tl = c->Tl; a.W = c->W; a.rung_begin = c->cfg.rung_begin; a.stretch = stretch ? 1 : 0;
@@ -3656,7 +3689,7 @@ int hens_rj_debug_draws(hens_ctx* ctx, int64_t iter, double* step, double* u_mh,
         }
         HIPCHK(c, hipMemcpyAsync(coin + (size_t)k * TW, a.coin, TW, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipMemcpyAsync(sel + (size_t)k * TW, a.sel, TW * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(birth + (size_t)k * TW * RJ_ND, a.birth, TW * RJ_ND * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(birth + (size_t)k * TW * c->rj.M.ndmax, a.birth, TW * (size_t)c->rj.M.ndmax * 8, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipMemcpyAsync(u_bd + (size_t)k * TW, a.u_bd, TW * 8, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }

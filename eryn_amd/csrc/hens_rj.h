@@ -26,17 +26,24 @@
 namespace hens {
 
 constexpr int RJ_MAX_BRANCH = 4, RJ_ND = 3, RJ_MAX_RW = 128;
-// leaf parameters per branch: RJ_ND = 3 for the built-in template models (pulse / sine) and everything that runs their likelihood on the
-// device; 1 .. RJ_MAX_ND per branch for models whose likelihood the host evaluates (hens_rj_set_model_general, k_rj<MODE, -2>)
+// leaf parameters per branch: RJ_ND = 3 for the pulse / sine models (hens_rj_set_model and the instantiations that carry their
+// uniform-grid recurrences); 1 .. RJ_MAX_ND per branch, a run-time property of the model, for the leaf kinds of hens_rj_set_model_kinds
+// (k_rj<.., WIDE>) and for models whose likelihood the host evaluates (hens_rj_set_model_general, k_rj<MODE, -2>)
 constexpr int RJ_MAX_ND = 4;
 #define RJ_CBN_B(v) ((v) & 15)
 #define RJ_CBN_N(v) (((v) >> 4) & 63)
 #define RJ_CBN_D(v) (((v) >> 10) & 3)
-#define RJ_CBN_KIND(v) (((v) >> 12) & 3)
+#define RJ_CBN_KIND(v) (((v) >> 12) & 15)
 #define RJ_CBN_SLOT(v) ((v) >> 16)
 constexpr int RJ_CTAB_LO = 0, RJ_CTAB_HI = RJ_MAX_RW, RJ_CTAB_SCALE = 2 * RJ_MAX_RW, RJ_CTAB_LOGP = 3 * RJ_MAX_RW;     // RjArgs::ctab
 constexpr int RJ_CTAB_CHOL = 4 * RJ_MAX_RW, RJ_CTAB_ROWS = 7;          // rows 4 - 6: L[d][0 .. 2] of the coordinate's dimension d (hens_rj_set_mh_chol)
-enum { RJ_KIND_PULSE = 0, RJ_KIND_SINE = 1 };
+// leaf kinds (hens_rj_set_model_kinds; include/hipensemble.h HENS_RJ_KIND_*): value at data point t and parameters per leaf
+//   pulse (a, b, c) a exp(-(t - b)^2 / (2 c^2))   sine (a, b, c) a sin(2 pi b t + c)   offset (a) a   ramp (a, b) a + b t
+//   lorentz (a, b, c) a / (1 + ((t - b) / c)^2)   chirp (a, b, c) a sin(2 pi b t + c t^2)
+//   burst (a, t0, w, f) a exp(-((t - t0) / w)^2) cos(2 pi f (t - t0))
+enum { RJ_KIND_PULSE = 0, RJ_KIND_SINE = 1, RJ_KIND_OFFSET = 2, RJ_KIND_RAMP = 3, RJ_KIND_LORENTZ = 4, RJ_KIND_CHIRP = 5, RJ_KIND_BURST = 6,
+       RJ_NKINDS = 7 };
+constexpr int RJ_KIND_WIDTH[RJ_NKINDS] = {3, 3, 1, 2, 3, 3, 4};
 enum { RJ_MODE_EVAL = 0, RJ_MODE_MH = 1, RJ_MODE_BD = 2, RJ_MODE_STRETCH = 3 };
 enum : uint32_t { PURPOSE_RJ_NORMAL = 20, PURPOSE_RJ_ACC = 21, PURPOSE_RJ_BD = 22, PURPOSE_RJ_BIRTH = 23, PURPOSE_RJ_BRANCH = 24,
                   PURPOSE_RJ_SPLIT = 25, PURPOSE_RJ_STRETCH = 26 };
@@ -50,7 +57,7 @@ struct RjModel {
     double sigma;
     double t_step64;                                // the data points lie on a uniform grid: 64 grid steps (else 0), see k_rj
     // leaf parameters per branch, first leaf-slot number per branch, the widest branch (= the stride of the birth arrays): 3,
-    // off / 3, 3 for the template models; read by the host-likelihood instantiations only (k_rj<MODE, -2>)
+    // off / 3, 3 for the pulse / sine models; read by the host-likelihood (k_rj<MODE, -2>) and the WIDE instantiations only
     int32_t nd[RJ_MAX_BRANCH], slot0[RJ_MAX_BRANCH], ndmax, pad_;
 };
 
@@ -62,12 +69,12 @@ struct RjArgs {
     const double* step;                 // parity in-model move: [Tl][W][ind_off] steps in record layout; nullptr: Philox
     const int8_t* change;               // parity birth / death: [Tl][W] +1 / -1 / 0 after the edge rule (distgenrj.py:69-73)
     const int32_t* leaf;                // [Tl][W] slot that is born or dies
-    const double* birth;                // [Tl][W][3] coordinates of the born leaf (generate_dist.rvs)
+    const double* birth;                // [Tl][W][M.ndmax] coordinates of the born leaf (generate_dist.rvs)
     const double* u_acc;                // [Tl][W] accept uniforms; nullptr: Philox
     unsigned* flags;
     // per record coordinate i (hens_rj_set_model / hens_rj_set_mh_scale keep it current): ctab[0][i] lo, [1][i] hi, [2][i] in-model step scale,
-    // [3][i] the branch's leaf log-density; cbn[i] = branch | slot in the branch << 4 | dimension << 10 | leaf kind << 12 | slot in the
-    // record << 16 (RJ_CBN_*) - what a LANE needs about its coordinate in one coalesced load each, instead of scalar loads from the model struct one dependent index at a time (round 5: the log-prior phase
+    // [3][i] the branch's leaf log-density; cbn[i] = branch | slot in the branch << 4 | dimension << 10 | leaf kind (4 bits) << 12 | slot
+    // in the record << 16 (RJ_CBN_*) - what a LANE needs about its coordinate in one coalesced load each, instead of scalar loads from the model struct one dependent index at a time (round 5: the log-prior phase
     // was 5 000 of a wave's 28 000 cycles, a chain of ~20 s_load + s_waitcnt)
     const double* ctab; const int32_t* cbn;
     RjModel M;
@@ -282,6 +289,33 @@ __device__ __forceinline__ int rj_split_complement(const uint32_t* key, int bits
     return rj_split_walker(key, bits, W, 1 - half, rj_pick(word, Nc));
 }
 
+// ---- the leaf kinds of the WIDE instantiations: one leaf, its kind and what does not depend on the data point; its value at t ----
+// The operation order is the oracle's (oracle/eryn_oracle_rj.py: lorentz_chirp_log_like, ramp_burst_log_like, offset_log_like; pulses
+// and sines as k_rj's strided forms have them), without FMA contraction; 2 pi is the double 2 * M_PI.
+struct RjLeaf { int kind; double a, p1, p2, p3, h; };      // h: pulse 1 / (2 c^2); sine, chirp 2 pi b; burst 2 pi f
+__device__ __forceinline__ RjLeaf rj_leaf_load(const int kind, const int nd, const double* p) {
+    RjLeaf f;
+    f.kind = kind; f.a = p[0];
+    f.p1 = nd > 1 ? p[1] : 0.0; f.p2 = nd > 2 ? p[2] : 0.0; f.p3 = nd > 3 ? p[3] : 0.0;
+    f.h = 0.0;
+    if (kind == RJ_KIND_PULSE) f.h = 1.0 / (2 * (f.p2 * f.p2));
+    else if (kind == RJ_KIND_SINE || kind == RJ_KIND_CHIRP) f.h = 2 * M_PI * f.p1;
+    else if (kind == RJ_KIND_BURST) f.h = 2 * M_PI * f.p3;
+    return f;
+}
+// leaf value at t (the kind is wave-uniform: a scalar branch)
+__device__ __forceinline__ double rj_leaf_at(const RjLeaf& f, const double t, const double* tab) {
+    switch (f.kind) {
+    case RJ_KIND_PULSE: { const double dx = t - f.p1; return f.a * rj_exp_neg(-(dx * dx) * f.h, tab); }
+    case RJ_KIND_SINE: return f.a * sin(f.h * t + f.p2);
+    case RJ_KIND_OFFSET: return f.a;
+    case RJ_KIND_RAMP: return f.a + f.p1 * t;
+    case RJ_KIND_LORENTZ: { const double z = (t - f.p1) / f.p2; return f.a / (1.0 + z * z); }
+    case RJ_KIND_CHIRP: return f.a * sin(f.h * t + f.p2 * (t * t));
+    default: { const double d = t - f.p1, z = d / f.p2; return (f.a * rj_exp_neg(-(z * z), tab)) * cos(f.h * d); }     // burst
+    }
+}
+
 #ifndef HENS_RJ_WAVES
 #define HENS_RJ_WAVES 1
 #endif
@@ -302,7 +336,11 @@ constexpr int RJ_WPE(int mode, int tmm) { return (mode == RJ_MODE_BD && tmm == 1
 // carry the registers of the full evaluation's leaf loops, nor the in-model launch those of the birth / death proposal.
 // CHOL (in-model move, Philox draws): the step is L z per leaf, the Cholesky factor's rows out of RjArgs::ctab (hens_rj_set_mh_chol) -
 // an instantiation of its own: as a run-time branch the extra live values cost the diagonal launch two spilled registers.
-template <int MODE, int TMM, bool CHOL = false>
+// WIDE: a model with a leaf kind beyond pulse / sine (hens_rj_set_model_kinds) - leaf width, first slot and birth stride of a branch
+// are the model's run-time values (as in the TMM = -2 code), every per-point site takes the leaf's value from rj_leaf_at, leaves
+// are added to ONE running template (the oracle's order), and there is no uniform-grid form.  Instantiations of their own: the
+// pulse / sine instantiations carry none of it.
+template <int MODE, int TMM, bool CHOL = false, bool WIDE = false>
 __global__ __launch_bounds__(RJ_WAVES * 64) __attribute__((amdgpu_waves_per_eu(RJ_WPE(MODE, TMM)))) void k_rj(const RjArgs A) {
     constexpr bool HAVE_TM = TMM >= 0;
     __shared__ double s_cur[RJ_WAVES][RJ_MAX_RW];
@@ -322,7 +360,8 @@ __global__ __launch_bounds__(RJ_WAVES * 64) __attribute__((amdgpu_waves_per_eu(R
     const int64_t slot = (int64_t)tl * NPR + idx;    // one wavefront per walker - stretch half-step: per position of the half
     const RjModel& M = A.M;
     // (leaf width, first slot, birth-array stride of a branch: compile-time 3 wherever the device evaluates the template likelihood)
-    constexpr bool GEN = TMM == -2;
+    constexpr bool GEN = TMM == -2 || WIDE;
+    static_assert(!(WIDE && (CHOL || TMM == -2)), "WIDE: device likelihood, diagonal in-model steps");
     auto ndb = [&](const int b) { return GEN ? M.nd[b] : RJ_ND; };
     auto slot0 = [&](const int b) { return GEN ? M.slot0[b] : M.off[b] / RJ_ND; };
     const int bstride = GEN ? M.ndmax : RJ_ND;
@@ -640,7 +679,7 @@ __global__ __launch_bounds__(RJ_WAVES * 64) __attribute__((amdgpu_waves_per_eu(R
     // pulse narrower than the grid step (|c| < h: e_0 may underflow where a later point does not) takes an exp per point, at the
     // same positions.  With |c| >= h the exponent of r_0 is below ndata in magnitude: no overflow.  The parity API (tm == nullptr)
     // and non-uniform grids keep the reference's exp / sin per point, a lane's points 64 apart (below).
-    const bool rot = HAVE_TM && M.t_step64 != 0.0;
+    const bool rot = !WIDE && HAVE_TM && M.t_step64 != 0.0;
     constexpr int NPT = 4, MAXCH = 2;                        // (strided form: template points per lane and chunk; chunks a lane keeps: ndata <= 512)
     constexpr int RJ_PPL = NPT * MAXCH;                      // (uniform grid: consecutive points per lane)
     double* tmrow = HAVE_TM ? A.tm + (size_t)A.loc[gw] * M.ndata : nullptr;
@@ -783,6 +822,13 @@ __global__ __launch_bounds__(RJ_WAVES * 64) __attribute__((amdgpu_waves_per_eu(R
                     if (ch_sign[b] == 0) continue;
                     const int n = ch_leaf[b];
                     const double* src = ch_sign[b] > 0 ? q : cur;             // (a dead leaf's coordinates stay in the record)
+                    if constexpr (WIDE) {
+                        const RjLeaf f = rj_leaf_load(M.kind[b], M.nd[b], src + M.off[b] + n * M.nd[b]);
+                        const double sgw = ch_sign[b] > 0 ? 1.0 : -1.0;
+#pragma unroll
+                        for (int k = 0; k < NPT; ++k) tmk[ch][k] += sgw * rj_leaf_at(f, ti[k], s_tab);
+                        continue;
+                    }
                     const double a = src[M.off[b] + n * RJ_ND], bb = src[M.off[b] + n * RJ_ND + 1], c = src[M.off[b] + n * RJ_ND + 2];
                     const double sg = ch_sign[b] > 0 ? 1.0 : -1.0;
                     if (M.kind[b] == RJ_KIND_PULSE) {
@@ -831,6 +877,17 @@ __global__ __launch_bounds__(RJ_WAVES * 64) __attribute__((amdgpu_waves_per_eu(R
                 tm[k] = 0.0;
             }
             for (int b = 0; b < M.nb; ++b) {
+                if constexpr (WIDE) {            // (one running template: tm + leaf, branch by branch, ascending slots)
+                    uint32_t mw = mask_of(b);
+                    while (mw) {
+                        const int n = __builtin_ctz(mw);
+                        mw &= mw - 1u;
+                        const RjLeaf f = rj_leaf_load(M.kind[b], M.nd[b], q + M.off[b] + n * M.nd[b]);
+#pragma unroll
+                        for (int k = 0; k < NPT; ++k) tm[k] += rj_leaf_at(f, ti[k], s_tab);
+                    }
+                    continue;
+                }
                 double sub[NPT];
 #pragma unroll
                 for (int k = 0; k < NPT; ++k) sub[k] = 0.0;
@@ -1006,7 +1063,7 @@ struct RjDebugArgs {
     double* u_mh;        // [Tl][W] accept uniform of the in-model move
     int8_t* coin;        // [Tl][W] +1 / -1 before the edge rule (distgenrj.py:63-66)
     uint32_t* sel;       // [Tl][W] leaf selector: the candidate of index (sel * cnt) >> 32 in ascending slot order
-    double* birth;       // [Tl][W][3] coordinates a leaf born in `branch` would get
+    double* birth;       // [Tl][W][M.ndmax] coordinates a leaf born in `branch` would get (zeros behind the branch's width)
     double* u_bd;        // [Tl][W] accept uniform of the birth / death move
     uint64_t iter, seed;
     int32_t Tl, W, rung_begin, branch;
@@ -1024,7 +1081,7 @@ __global__ void k_rj_debug_draws(const RjDebugArgs A) {
     for (int i = 0; i < M.ind_off; ++i) {
         int b = 0;
         while (b + 1 < M.nb && i >= M.off[b + 1]) ++b;
-        const int d = (i - M.off[b]) % RJ_ND;
+        const int d = (i - M.off[b]) % M.nd[b];
         double st = 0.0;
         if (A.stretch) {
             st = 0.0;
@@ -1042,8 +1099,8 @@ __global__ void k_rj_debug_draws(const RjDebugArgs A) {
     const u4 d = rj_bd_raw(A.seed, A.iter, wid, A.branch);
     A.coin[gw] = (d.x & 1u) ? +1 : -1;
     A.sel[gw] = d.y;
-    for (int k = 0; k < RJ_ND; ++k)
-        A.birth[(size_t)gw * RJ_ND + k] = rj_birth_coord(A.seed, A.iter, wid, A.branch, k, M.lo[A.branch][k], M.hi[A.branch][k]);
+    for (int k = 0; k < M.ndmax; ++k)
+        A.birth[(size_t)gw * M.ndmax + k] = k < M.nd[A.branch] ? rj_birth_coord(A.seed, A.iter, wid, A.branch, k, M.lo[A.branch][k], M.hi[A.branch][k]) : 0.0;
     A.u_bd[gw] = rj_accept_uniform(A.seed, A.iter, wid, RJ_MODE_BD, A.acc_branch);
 }
 

@@ -16,22 +16,29 @@ from ._lib import check, f64, ptr
 from .engine import HipEnsemble
 
 KIND_PULSE, KIND_SINE = 0, 1
-_KINDS = {"pulse": KIND_PULSE, "gauss": KIND_PULSE, "sine": KIND_SINE, KIND_PULSE: KIND_PULSE, KIND_SINE: KIND_SINE}
+# the leaf kinds the device evaluates, name -> (id, parameters per leaf) (include/hipensemble.h: HENS_RJ_KIND_*): value at data point t
+#   pulse (a, b, c) a exp(-(t - b)^2 / (2 c^2))   sine (a, b, c) a sin(2 pi b t + c)   offset (a) a   ramp (a, b) a + b t
+#   lorentz (a, b, c) a / (1 + ((t - b) / c)^2)   chirp (a, b, c) a sin(2 pi b t + c t^2)
+#   burst (a, t0, w, f) a exp(-((t - t0) / w)^2) cos(2 pi f (t - t0))
+LEAF_KINDS = {"pulse": (0, 3), "sine": (1, 3), "offset": (2, 1), "ramp": (3, 2), "lorentz": (4, 3), "chirp": (5, 3), "burst": (6, 4)}
+_KINDS = {**{k: v[0] for k, v in LEAF_KINDS.items()}, "gauss": KIND_PULSE, **{v[0]: v[0] for v in LEAF_KINDS.values()}}
+_WIDTH = {v[0]: v[1] for v in LEAF_KINDS.values()}
 
 
 class TemplateBranch:
-    """One model type: leaf kind ("pulse" | "sine"), a uniform box per leaf parameter, leaf budget."""
+    """One model type: leaf kind (a name of LEAF_KINDS; "gauss" is "pulse"), a uniform box per leaf parameter - as many as the kind
+    has -, leaf budget."""
 
     def __init__(self, name, kind, box, nleaves_max, nleaves_min=0):
         self.name, self.kind = str(name), _KINDS[kind]
         self.lo = f64([b[0] for b in box])
         self.hi = f64([b[1] for b in box])
-        if self.lo.shape != (3,):
-            raise ValueError("a leaf has three parameters")
-        self.ndim = 3
+        self.ndim = _WIDTH[self.kind]
+        if self.lo.shape != (self.ndim,):
+            raise ValueError(f"a leaf of this kind has {self.ndim} parameter{'s' if self.ndim != 1 else ''}: a box of {self.lo.shape[0]}")
         self.nleaves_max, self.nleaves_min = int(nleaves_max), int(nleaves_min)
         acc = np.zeros(1)                      # prior.py:364-383: sequential ``prior_vals += temp`` from 0.0
-        for d in range(3):
+        for d in range(self.ndim):
             acc += np.log(1 / (self.hi[d] - self.lo[d]))
         self.leaf_logp = float(acc[0])
 
@@ -144,12 +151,14 @@ class CallableLikelihood:
 
 class RJEngine:
     def __init__(self, ntemps, nwalkers, branches, t, y, sigma, seed=0, device_id=0, adaptive=True,
-                 adaptation_lag=10000, adaptation_time=100, stop_adaptation=-1, fill_value=-1e300, a=2.0, live_dangerously=False):
+                 adaptation_lag=10000, adaptation_time=100, stop_adaptation=-1, fill_value=-1e300, a=2.0, live_dangerously=False,
+                 kinds_entry=None):
+        # kinds_entry: hand the model to hens_rj_set_model_kinds (None: when a branch's kind is beyond pulse / sine)
         self.branches = list(branches)
         if not 1 <= len(self.branches) <= 4:
             raise NotImplementedError("1 to 4 branches")
         self.ncoord = sum(b.nleaves_max * b.ndim for b in self.branches)
-        self.ndmax = max(b.ndim for b in self.branches)          # (the stride of the birth arrays: 3 for the template models)
+        self.ndmax = max(b.ndim for b in self.branches)          # (the stride of the birth arrays: 3 for the pulse / sine models)
         # a model without a device likelihood: any LeafBranch, or no data (hens_rj_set_model_general; host_like steps it)
         self.general = t is None or any(not isinstance(b, TemplateBranch) for b in self.branches)
         rw = self.ncoord + len(self.branches)
@@ -172,18 +181,20 @@ class RJEngine:
         nlmax = np.array([b.nleaves_max for b in self.branches], dtype=np.int32)
         nlmin = np.array([b.nleaves_min for b in self.branches], dtype=np.int32)
         lp = f64([b.leaf_logp for b in self.branches])
+        self.wide = False
         if self.general:
             nds = np.array([b.ndim for b in self.branches], dtype=np.int32)
             lo, hi = f64(np.concatenate([b.lo for b in self.branches])), f64(np.concatenate([b.hi for b in self.branches]))
             check(self.lib.hens_rj_set_model_general(self.ctx, nb, ptr(nds), ptr(nlmax), ptr(nlmin), ptr(lo), ptr(hi), ptr(lp)), self.ctx)
             return
-        lo = f64(np.stack([b.lo for b in self.branches]))
-        hi = f64(np.stack([b.hi for b in self.branches]))
+        lo, hi = f64(np.concatenate([b.lo for b in self.branches])), f64(np.concatenate([b.hi for b in self.branches]))
         t, y = f64(t), f64(y)
         if t.shape != y.shape or t.ndim != 1:
             raise ValueError("t and y must be 1-D arrays of the same length")
-        check(self.lib.hens_rj_set_model(self.ctx, nb, ptr(kinds), ptr(nlmax), ptr(nlmin), ptr(lo), ptr(hi), ptr(lp),
-                                         int(t.shape[0]), ptr(t), ptr(y), float(sigma)), self.ctx)
+        self.wide = bool(np.any(kinds > KIND_SINE))              # (a leaf kind beyond pulse / sine: widths 1 to 4, no full covariances)
+        set_model = self.lib.hens_rj_set_model_kinds if (self.wide if kinds_entry is None else kinds_entry) else self.lib.hens_rj_set_model
+        check(set_model(self.ctx, nb, ptr(kinds), ptr(nlmax), ptr(nlmin), ptr(lo), ptr(hi), ptr(lp),
+                        int(t.shape[0]), ptr(t), ptr(y), float(sigma)), self.ctx)
 
     def close(self):
         self.eng.close()
@@ -331,13 +342,24 @@ class RJEngine:
 
     # -- production -------------------------------------------------------------------------------------------------
     def set_mh_scale(self, scale):
-        """Standard deviations of the in-model Gaussian step per branch and leaf parameter: [nbranches, 3] (template models)."""
-        s = f64(scale, (len(self.branches), 3))
+        """Standard deviations of the in-model Gaussian step per branch and leaf parameter: [nbranches, 3] (pulse / sine models), or one
+        row per branch, as long as its leaves have parameters (the library's rows are as long as the widest branch's)."""
+        s = np.zeros((len(self.branches), self.ndmax))
+        if len(scale) != len(self.branches):
+            raise ValueError(f"expected {len(self.branches)} rows of step scales")
+        for bi, b in enumerate(self.branches):
+            row = f64(scale[bi])
+            if row.ndim != 1 or row.shape[0] < b.ndim or np.any(row[b.ndim:] != 0.0):
+                raise ValueError(f"branch {b.name}: {b.ndim} step scales")
+            s[bi, :b.ndim] = row[:b.ndim]
         check(self.lib.hens_rj_set_mh_scale(self.ctx, ptr(s)), self.ctx)
 
     def set_mh_chol(self, chol):
         """Lower-triangular Cholesky factors of the leaves' proposal covariances, [nbranches, 3, 3]: the in-model Gaussian step of
-        ``step`` becomes ``L @ z`` per leaf (include/hipensemble.h: hens_rj_set_mh_chol).  Not positive definite -> ValueError."""
+        ``step`` becomes ``L @ z`` per leaf (include/hipensemble.h: hens_rj_set_mh_chol).  Not positive definite -> ValueError; a model
+        with a leaf kind beyond pulse / sine -> NotImplementedError."""
+        if self.wide:
+            raise NotImplementedError("full leaf covariances: models of pulses and sines only (diagonal steps: set_mh_scale)")
         L = f64(chol, (len(self.branches), 3, 3))
         check(self.lib.hens_rj_set_mh_chol(self.ctx, ptr(L)), self.ctx)
 
@@ -368,7 +390,7 @@ class RJEngine:
         T, W = self.T, self.W
         ns = len(self.branches)
         out = dict(step=np.empty((T, W, self.ncoord)), u_mh=np.empty((T, W)), coin=np.empty((ns, T, W), dtype=np.int8),
-                   sel=np.empty((ns, T, W), dtype=np.uint32), birth=np.empty((ns, T, W, 3)), u_bd=np.empty((ns, T, W)),
+                   sel=np.empty((ns, T, W), dtype=np.uint32), birth=np.empty((ns, T, W, self.ndmax)), u_bd=np.empty((ns, T, W)),
                    slot_mh=np.empty((T, W), dtype=np.int32), uswap_mh=np.empty((max(T - 1, 1), W)),
                    slot_bd=np.empty((T, W), dtype=np.int32), uswap_bd=np.empty((max(T - 1, 1), W)))
         br = C.c_int32(0)
@@ -427,7 +449,8 @@ class RJEngine:
 # ---------------------------------------------------------------------------------------------------------------------
 class TemplateLikelihood:
     """Stands where the reference takes ``log_like_fn`` + ``args=[t, y, sigma]`` (tests/test_eryn.py:79-92, 467-470):
-    the template model lives inside the kernel.  ``kinds``: ``{branch_name: "pulse" | "sine"}``."""
+    the template model lives inside the kernel.  ``kinds``: ``{branch_name: a name of LEAF_KINDS}``; a branch's ``ndims`` entry is the
+    kind's width."""
 
     def __init__(self, kinds, t, y, sigma):
         self.kinds = {k: _KINDS[v] for k, v in kinds.items()}
@@ -511,8 +534,8 @@ class RJEnsembleSampler:
         self.branches = []
         for k in self.branch_names:
             nd = int(self.ndims[k])
-            if self.host_like is None and nd != 3:
-                raise NotImplementedError("a leaf of the template model has three parameters")
+            if self.host_like is None and nd != _WIDTH[log_like_fn.kinds[k]]:
+                raise NotImplementedError(f"branch {k}: a leaf of its kind has {_WIDTH[log_like_fn.kinds[k]]} parameters, ndims says {nd}")
             if isinstance(moves, GaussianLeafMove) and moves.cov[k].shape != (nd, nd):
                 raise ValueError(f"branch {k}: the proposal covariance must be {nd} x {nd}")
             pr = priors[k]
@@ -547,7 +570,9 @@ class RJEnsembleSampler:
             # axis-aligned steps (hens_rj_set_mh_scale: three standard deviations per branch), or - a covariance with off-diagonal
             # terms - the Cholesky factor of every branch's leaf covariance (hens_rj_set_mh_chol: step = L z)
             if all(np.array_equal(moves.cov[k], np.diag(np.diag(moves.cov[k]))) for k in self.branch_names):
-                self.engine.set_mh_scale(np.stack([np.sqrt(np.diag(moves.cov[k])) for k in self.branch_names]))
+                self.engine.set_mh_scale([np.sqrt(np.diag(moves.cov[k])) for k in self.branch_names])
+            elif self.engine.wide:
+                raise NotImplementedError("rng='philox' with a leaf kind beyond pulse / sine: diagonal proposal covariances only")
             else:
                 self.engine.set_mh_chol(np.stack([np.linalg.cholesky(moves.cov[k]) for k in self.branch_names]))
         moves.accepted = np.zeros((self.ntemps, self.nwalkers))

@@ -426,6 +426,27 @@ int hens_rj_set_model(hens_ctx* ctx, int32_t nbranches, const int32_t* kinds, co
  * hens_rj_draws have a stride of max(ndims) doubles per walker. */
 int hens_rj_set_model_general(hens_ctx* ctx, int32_t nbranches, const int32_t* ndims, const int32_t* nleaves_max,
                               const int32_t* nleaves_min, const double* lo, const double* hi, const double* leaf_logp);
+/* hens_rj_set_model with every leaf kind the device evaluates - one to four parameters per leaf, the value at data point t:
+ *   HENS_RJ_KIND_PULSE   (a, b, c)      a exp(-(t - b)^2 / (2 c^2))          HENS_RJ_KIND_SINE   (a, b, c)  a sin(2 pi b t + c)
+ *   HENS_RJ_KIND_OFFSET  (a)            a                                    HENS_RJ_KIND_RAMP   (a, b)     a + b t
+ *   HENS_RJ_KIND_LORENTZ (a, b, c)      a / (1 + ((t - b) / c)^2)            HENS_RJ_KIND_CHIRP  (a, b, c)  a sin(2 pi b t + c t^2)
+ *   HENS_RJ_KIND_BURST   (a, t0, w, f)  a exp(-((t - t0) / w)^2) cos(2 pi f (t - t0))
+ * in float64 without FMA contraction, 2 pi the double 2 * M_PI; a walker's leaves are added one by one to a running template,
+ * branch by branch in ascending slot order.  lo / hi: the branches' boxes one after the other (a branch's width follows from its
+ * kind), as hens_rj_set_model_general takes them; the record holds kind-width doubles per leaf slot and the `birth` arrays have
+ * a stride of the widest branch's parameters.  Up to 64 leaf slots and 128 record doubles (else HENS_ERR_UNSUPPORTED /
+ * HENS_ERR_INVALID as hens_rj_set_model_general); an unknown kind -> HENS_ERR_INVALID.  Everything that steps or reads a
+ * hens_rj_set_model context works on such a model - hens_rj_step with every schedule and both in-model moves, the parity moves,
+ * hens_eval_state, resume by hens_set_iteration, the debug exports - except full leaf covariances: hens_rj_set_mh_chol on a
+ * model with a kind beyond pulse / sine -> HENS_ERR_UNSUPPORTED.  Such a model is evaluated point by point on every grid (no
+ * uniform-grid recurrence); resident templates for ndata <= 512 as ever.  A model of pulses and sines alone is exactly
+ * hens_rj_set_model's. */
+enum { HENS_RJ_KIND_PULSE = 0, HENS_RJ_KIND_SINE = 1, HENS_RJ_KIND_OFFSET = 2, HENS_RJ_KIND_RAMP = 3, HENS_RJ_KIND_LORENTZ = 4,
+       HENS_RJ_KIND_CHIRP = 5, HENS_RJ_KIND_BURST = 6 };
+int hens_rj_set_model_kinds(hens_ctx* ctx, int32_t nbranches, const int32_t* kinds, const int32_t* nleaves_max,
+                            const int32_t* nleaves_min, const double* lo, const double* hi, const double* leaf_logp,
+                            int32_t ndata, const double* t, const double* y, double sigma);
+/* scale[nbranches][widest branch's parameters] (3 on a hens_rj_set_model context): standard deviations of the in-model Gaussian step */
 int hens_rj_set_mh_scale(hens_ctx* ctx, const double* scale);
 /* The Philox in-model Gaussian move with a FULL covariance per leaf (gaussian.py:265-268: multivariate_normal(0, cov)):
  * chol[nbranches][3][3], the lower-triangular Cholesky factor L of a branch's leaf covariance.  A leaf's step is
