@@ -62,6 +62,12 @@ class HensDeviceBuffers(C.Structure):
     ]
 
 
+class HensChainInfo(C.Structure):
+    """struct hens_chain_info_t (include/hipensemble.h)."""
+    _fields_ = [(n, C.c_int64) for n in ("capacity", "count", "ntemps_store", "bytes", "step_bytes", "free_bytes", "n_store_timed")] + \
+               [("store_ms", C.c_double)]
+
+
 _P = C.c_void_p
 # every symbol include/hipensemble.h declares: name -> (restype, argtypes)
 SIGNATURES = {
@@ -97,6 +103,13 @@ SIGNATURES = {
     "hens_step_marked": (C.c_int, [_P, C.c_int64, C.c_int64]),
     "hens_get_marked_counters": (C.c_int, [_P, _P, _P]),
     "hens_step_report": (C.c_int, [_P, C.c_int64, C.c_int64, _P, _P, _P]),
+    "hens_chain_create": (C.c_int, [_P, C.c_int64, C.c_int32]),
+    "hens_chain_reset": (C.c_int, [_P]),
+    "hens_chain_destroy": (C.c_int, [_P]),
+    "hens_chain_info": (C.c_int, [_P, C.POINTER(HensChainInfo)]),
+    "hens_step_chain": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64]),
+    "hens_chain_download": (C.c_int, [_P, C.c_int64, C.c_int64, _P, _P, _P, _P, _P, _P]),
+    "hens_chain_totals": (C.c_int, [_P, _P, _P]),
     "hens_pipe_init": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P]),
     "hens_pipe_connect": (C.c_int, [_P, _P]),
     "hens_pipe_connect_local": (C.c_int, [_P, _P]),

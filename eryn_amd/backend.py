@@ -58,3 +58,172 @@ class Backend:
 
     def get_betas(self, discard=0, thin=1):
         return self.betas[discard:self.iteration:thin]
+
+
+class DeviceBackend:
+    """``Backend`` whose stored steps stay in device memory until somebody reads them (include/hipensemble.h: hens_chain_*).
+
+    The reference's storage contract (backends/backend.py:1014-1091 ``save_step``) on the device: ``EnsembleSampler(...,
+    backend=DeviceBackend(), rng="philox").run_mcmc(nsteps, thin_by=k)`` is one device call per chain SEGMENT - every stored step
+    is appended by a small launch between the stepping launches, the accepted / swap totals accumulate beside the chain - and an
+    accessor downloads the open segment once and keeps it until the next append.  Same accessors as ``Backend``; no array is
+    concatenated or copied per stored step.
+
+    max_bytes      device memory the open segment may take (default: a quarter of what is free at ``reset``); it fixes the
+                   capacity in stored steps.  A run that outgrows it closes the segment - one download into host arrays, the
+                   device buffers start again - and goes on.
+    ntemps_store   store rungs ``[0, ntemps_store)`` only (default: all); ``swaps_accepted`` keeps its ntemps - 1 entries.
+
+    An untempered sampler has no ladder: ``get_betas`` returns zeros there."""
+
+    FIELDS = ("x", "log_like", "log_prior", "betas", "iteration", "adapt_time")
+
+    def __init__(self, max_bytes=None, ntemps_store=None):
+        self.initialized = False
+        self.capacity = 0
+        self.max_bytes, self.ntemps_store = max_bytes, ntemps_store
+        self.engine, self.seed = None, None
+
+    @staticmethod
+    def bytes_per_step(ntemps, nwalkers, ndim, ntemps_store=None):
+        """Device bytes of one stored step: coordinates, log-likelihood and log-prior of the stored rungs, the ladder."""
+        return 8 * ((ntemps_store or ntemps) * nwalkers * (ndim + 2) + ntemps)
+
+    def attach(self, engine, seed):
+        """The engine whose context holds the chain, and the sampler's Philox seed (the checkpoint's first half)."""
+        self.engine, self.seed = engine, seed
+
+    def reset(self, nwalkers, ndims, ntemps=1, branch_names=None, **kwargs):
+        if self.engine is None:
+            raise RuntimeError("DeviceBackend.reset needs an engine (attach): EnsembleSampler(..., backend=DeviceBackend()) attaches its own")
+        self.nwalkers, self.ndims, self.ntemps = nwalkers, dict(ndims), ntemps
+        self.branch_names = list(branch_names)
+        if len(self.branch_names) != 1:
+            raise NotImplementedError("the device chain stores a single branch")
+        self.ndim = self.ndims[self.branch_names[0]]
+        self.nstore = int(self.ntemps_store or ntemps)
+        if not 1 <= self.nstore <= ntemps:
+            raise ValueError("ntemps_store must lie in [1, ntemps]")
+        budget = self.engine.chain_info()["free_bytes"] // 4 if self.max_bytes is None else int(self.max_bytes)
+        self.max_steps = max(1, budget // self.bytes_per_step(ntemps, nwalkers, self.ndim, self.nstore))
+        # (a backend that is reset for another run of the same shape keeps its device buffers: count and totals start again)
+        shape = (nwalkers, self.ndim, ntemps, self.nstore, id(self.engine))
+        keep = self.capacity if self.initialized and getattr(self, "_shape", None) == shape else 0
+        if keep:
+            self.engine.chain_reset()
+        self._shape = shape
+        self.iteration = 0
+        self.capacity = keep          # stored steps the device buffers hold (0: not created yet)
+        self.downloads = 0            # chain copies from the device so far
+        self._open = 0                # stored steps in the open (device) segment
+        self._closed = None           # everything closed so far: {field: host array}
+        self._segments = []           # ... and segments closed since somebody last read it
+        self._closed_accepted = np.zeros((self.nstore, nwalkers))
+        self._closed_swaps = np.zeros(max(ntemps - 1, 0))
+        self._cache = self._totals = None
+        self.initialized = True
+
+    # -- writing (the sampler) ---------------------------------------------------------------------
+    def grow(self, ngrow, blobs=None):
+        """Room for ``ngrow`` more stored steps, as far as ``max_bytes`` allows: the device buffers are made (or, when the
+        open segment has no room left and may be larger, closed and remade) here, never inside a run."""
+        room = self.capacity - self._open
+        if self.capacity and (room >= ngrow or self.capacity >= self.max_steps):
+            return
+        self._close_segment()
+        self.capacity = int(min(self.max_steps, max(ngrow, 1)))
+        self.engine.chain_create(self.capacity, self.nstore)
+
+    def append(self, n_store, iters_per_store, n_last):
+        """``n_store`` stored steps on the device (HipEnsemble.step_chain), closing the segment whenever it is full."""
+        if not self.capacity:
+            self.grow(n_store)
+        while n_store > 0:
+            if self._open == self.capacity:
+                self._close_segment()
+            n = min(self.capacity - self._open, n_store)
+            self._cache = self._totals = None
+            self.engine.step_chain(n, iters_per_store, n_last)
+            self._open += n
+            self.iteration += n
+            n_store -= n
+
+    def last_step(self, fields=()):
+        """The last stored step of the open segment (HipEnsemble.chain_download of one step)."""
+        return self.engine.chain_download(self._open - 1, 1, fields=fields)
+
+    def _close_segment(self):
+        if not self._open:
+            return
+        seg, (acc, swaps) = self._open_segment(), self._open_totals()
+        self._segments.append(seg)
+        self._closed_accepted = self._closed_accepted + acc
+        self._closed_swaps = self._closed_swaps + swaps
+        self.engine.chain_reset()
+        self._open = 0
+        self._cache = self._totals = None
+
+    # -- reading -----------------------------------------------------------------------------------
+    def _open_segment(self):
+        if self._cache is None:
+            self._cache = self.engine.chain_download(0, self._open)
+            self.downloads += 1
+        return self._cache
+
+    def _open_totals(self):
+        if self._totals is None:
+            self._totals = self.engine.chain_totals()
+        return self._totals
+
+    def _field(self, f, discard, thin):
+        if self._segments:            # (once per read after a closure, not per step)
+            parts = ([self._closed] if self._closed is not None else []) + self._segments
+            self._closed = {k: np.concatenate([p[k] for p in parts]) for k in self.FIELDS}
+            self._segments = []
+        parts = [self._closed[f]] if self._closed is not None else []
+        if self._open:
+            parts.append(self._open_segment()[f])
+        if not parts:
+            shape = dict(x=(self.nstore, self.nwalkers, self.ndim), betas=(self.ntemps,), iteration=(), adapt_time=())
+            return np.empty((0,) + shape.get(f, (self.nstore, self.nwalkers)))
+        full = parts[0] if len(parts) == 1 else np.concatenate(parts)
+        return full[discard:self.iteration:thin]
+
+    def get_chain(self, discard=0, thin=1):
+        return {self.branch_names[0]: self._field("x", discard, thin)[:, :, :, None, :]}
+
+    def get_log_like(self, discard=0, thin=1):
+        return self._field("log_like", discard, thin)
+
+    def get_log_prior(self, discard=0, thin=1):
+        return self._field("log_prior", discard, thin)
+
+    def get_betas(self, discard=0, thin=1):
+        return self._field("betas", discard, thin)
+
+    def get_random_states(self, discard=0, thin=1):
+        """The Philox checkpoint of every stored step - what its State carries as ``random_state``: a sampler with the same
+        seed started from stored step i (coordinates, log-likelihood, log-prior, ladder and this) continues the chain."""
+        it, tm = self._field("iteration", discard, thin), self._field("adapt_time", discard, thin)
+        return [("philox", self.seed, int(i), int(t)) for i, t in zip(it, tm)]
+
+    @property
+    def accepted(self):
+        return self._closed_accepted + self._open_totals()[0] if self._open else self._closed_accepted
+
+    @property
+    def swaps_accepted(self):
+        return self._closed_swaps + self._open_totals()[1] if self._open else self._closed_swaps
+
+    @property
+    def random_state(self):
+        """The Philox checkpoint of the last stored step: ("philox", seed, iteration counter, adaptation time)."""
+        if self._open:
+            last = self.engine.chain_download(self._open - 1, 1, fields=())      # (host-side arrays of the context: no device copy)
+        elif self._segments:
+            last = self._segments[-1]
+        elif self._closed is not None:
+            last = self._closed
+        else:
+            return None
+        return ("philox", self.seed, int(last["iteration"][-1]), int(last["adapt_time"][-1]))

@@ -7,6 +7,8 @@
 #include "hens_tile2.h"
 #include "hens_aql.h"
 #include "hens_ktable.h"
+#include "hens_chain.h"
+#include "hens_chain_host.h"
 #include <unordered_map>
 #include <hip/hip_ext.h>
 // RCCL: types only - the library is dlopen()ed (rccl_api), nothing of it is linked.  A ROCm without the RCCL development headers
@@ -236,6 +238,18 @@ struct hens_ctx_impl {
     // kernels launched by host function pointer (launch_by_ptr): dynamic-LDS attribute set on this context's device, AQL handle
     struct KernelSlot { bool attr_done = false; const hens_aql::Kernel* ak = nullptr; };
     std::unordered_map<const void*, KernelSlot> kslots;
+    // chain store (hens_chain_*, hens_step_chain): the stored steps of run_mcmc(store=True) in device memory
+    struct Chain {
+        bool on = false;
+        int64_t capacity = 0, count = 0, bytes = 0;
+        int Ts = 0;                          // rungs [0, Ts) are stored
+        double *x = nullptr, *L = nullptr, *P = nullptr, *betas = nullptr;   // [capacity] x ([Ts][W][D], [Ts][W], [Ts][W], [T])
+        uint32_t* acc_tot = nullptr;         // [Ts][W] accepted totals (backends/backend.py:1069)
+        unsigned long long* swaps_tot = nullptr;   // [T-1] swap totals (backends/backend.py:1072)
+        hens_chain::Sizes sz{};
+        std::vector<int64_t> iteration, adapt_time;   // per stored step: the Philox checkpoint of its State
+        int64_t n_timed = 0; double store_ms = 0.0;   // hens_set_profiling 1: the last call's append launches
+    } chain;
     std::vector<double> launch_us;   // per-kernel profiling: begin / end of every launch of the last hens_step call (us after the first begin)
     std::vector<void*> allocs;
 };
@@ -2104,6 +2118,7 @@ int hens_create(const hens_config* cfg, hens_ctx** out) {
     return HENS_OK;
 }
 
+static void chain_free(hens_ctx_impl* c);     // (the chain store's device buffers: below, with hens_chain_*)
 void hens_destroy(hens_ctx* ctx) {
     hens_ctx_impl* c = CTX(ctx);
     if (!c) return;
@@ -2123,6 +2138,7 @@ void hens_destroy(hens_ctx* ctx) {
     if (c->pipe.box) (void)hipFree(c->pipe.box);
     for (void* p : c->allocs)
         if (p) (void)hipFree(p);
+    chain_free(c);
     for (hipEvent_t e : c->evpool) (void)hipEventDestroy(e);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -2802,6 +2818,40 @@ int hens_step_marked(hens_ctx* ctx, int64_t n_before, int64_t n_last) {
     return n_last > 0 ? hens_step(ctx, n_last) : HENS_OK;
 }
 
+// The mark of hens_step_report and hens_step_chain: the accept counts of a call's last n_last iterations = the counters now minus
+// the counters in front of those iterations.  The "before" copy (report_prev) is kept from one call to the next - the kernel that
+// forms the difference moves it up (k_report_mask, k_chain_store) -, so the usual caller - one report / one stored step per n_last
+// iterations - pays no snapshot, and nothing here leaves record mode: the counters are read where they ride.  Anything else that
+// moved the counters in between (hens_step, a reset, another iteration counter) is noticed by the books and costs one snapshot launch.
+static uint64_t report_books(const hens_ctx_impl* c) { return (uint64_t)c->num_proposals + (uint64_t)c->num_proposals_mh; }
+static bool report_current(const hens_ctx_impl* c) {
+    return c->report_prev && c->report_valid && c->report_iter == c->iter && c->report_books == report_books(c);
+}
+static void launch_report_mask(hens_ctx_impl* c, uint8_t* out) {
+    const size_t TW = (size_t)c->Tl * c->W;
+    const bool mh = c->accepted_mh != nullptr;
+    hipLaunchKernelGGL(k_report_mask, dim3(grid_for((int64_t)TW)), dim3(256), 0, c->stream, c->packed ? c->wrec[c->cur] : nullptr, c->colmode ? 1 : 0,
+                       c->accepted, mh ? c->accepted_mh : nullptr, c->report_prev, c->report_prev + TW, out, c->Tl, c->W);
+}
+static int report_snapshot(hens_ctx_impl* c) {
+    const size_t TW = (size_t)c->Tl * c->W;
+    int r;
+    if ((r = aql_settle(c))) return r;
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    if (!c->report_prev) {
+        if ((r = dalloc(c, &c->report_prev, 2 * TW))) return r;
+        HIPCHK(c, hipMemsetAsync(c->report_prev, 0, 2 * TW * 4, c->stream));
+    }
+    launch_report_mask(c, nullptr);
+    HIPCHK(c, hipGetLastError());
+    return HENS_OK;
+}
+static void report_marked(hens_ctx_impl* c, bool valid) {
+    c->report_valid = valid;
+    c->report_iter = c->iter;
+    c->report_books = report_books(c);
+}
+
 // n_iters iterations and what a sampler loop reads after EVERY proposal (ensemble.py:974-977), in one call and one small copy: the
 // accept counts of the call's last `n_last` iterations per walker (uint8, saturating: the reference's `accepted` of one
 // sub-iteration summed over num_repeats_in_model proposals), the last cascade's swap counts and the ladder.  The walkers stay on
@@ -2813,44 +2863,235 @@ int hens_step_report(hens_ctx* ctx, int64_t n_iters, int64_t n_last, uint8_t* ac
     int r;
     if ((r = counter_room(c, n_iters))) return r;
     const size_t TW = (size_t)c->Tl * c->W;
-    // The accept counts of the last n_last iterations = the counters now minus the counters in front of those iterations.  The
-    // "before" copy is kept from report to report (report_prev: updated by the kernel that forms the difference), so the usual
-    // caller - one report per iteration - pays no snapshot, and nothing here leaves record mode: the counters are read where
-    // they ride (k_report_mask).  Anything else that moved the counters in between (hens_step, a reset, another iteration
-    // counter) is noticed by the books below and costs one snapshot launch.
-    auto books = [&] { return (uint64_t)c->num_proposals + (uint64_t)c->num_proposals_mh; };
-    const bool have_prev = c->report_prev && c->report_valid && c->report_iter == c->iter && c->report_books == books() && n_iters == n_last;
+    const bool have_prev = report_current(c) && n_iters == n_last;
     if (n_iters > n_last && (r = hens_step(ctx, n_iters - n_last))) return r;
-    auto launch_mask = [&](uint8_t* out) {
-        const bool mh = c->accepted_mh != nullptr;
-        hipLaunchKernelGGL(k_report_mask, dim3(grid_for((int64_t)TW)), dim3(256), 0, c->stream, c->packed ? c->wrec[c->cur] : nullptr, c->colmode ? 1 : 0,
-                           c->accepted, mh ? c->accepted_mh : nullptr, c->report_prev, c->report_prev + TW, out, c->Tl, c->W);
-    };
-    if (!have_prev) {
-        if ((r = aql_settle(c))) return r;
+    if (!have_prev && (r = report_snapshot(c))) return r;
+    if (!c->mask_buf) {
         HIPCHK(c, hipSetDevice(c->cfg.device_id));
-        if (!c->report_prev) {
-            if ((r = dalloc(c, &c->report_prev, 2 * TW))) return r;
-            HIPCHK(c, hipMemsetAsync(c->report_prev, 0, 2 * TW * 4, c->stream));
-        }
-        if (!c->mask_buf && (r = dalloc(c, &c->mask_buf, TW))) return r;
-        launch_mask(nullptr);
-        HIPCHK(c, hipGetLastError());
+        if ((r = dalloc(c, &c->mask_buf, TW))) return r;
     }
     if ((r = hens_step(ctx, n_last))) { c->report_valid = false; return r; }
     if ((r = aql_settle(c))) return r;
     HIPCHK(c, hipSetDevice(c->cfg.device_id));
     flush_adapt(c);                           // (swap counts and ladder of the last cascade)
-    launch_mask(c->mask_buf);
+    launch_report_mask(c, c->mask_buf);
     HIPCHK(c, hipGetLastError());
     if (accepted_last) HIPCHK(c, hipMemcpyAsync(accepted_last, c->mask_buf, TW, hipMemcpyDeviceToHost, c->stream));
     if (swaps_last && c->T > 1) HIPCHK(c, hipMemcpyAsync(swaps_last, c->swaps_last, (size_t)(c->T - 1) * 8, hipMemcpyDeviceToHost, c->stream));
     if (betas) HIPCHK(c, hipMemcpyAsync(betas, c->betas[c->bcur], (size_t)c->T * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->hip_dirty = false;
-    c->report_valid = true;
-    c->report_iter = c->iter;
-    c->report_books = books();
+    report_marked(c, true);
+    return HENS_OK;
+}
+
+// ---- chain store (include/hipensemble.h: hens_chain_*, hens_step_chain; csrc/hens_chain.h: k_chain_store) -------------------
+static void chain_free(hens_ctx_impl* c) {
+    hens_ctx_impl::Chain& ch = c->chain;
+    for (void* p : {(void*)ch.x, (void*)ch.L, (void*)ch.P, (void*)ch.betas, (void*)ch.acc_tot, (void*)ch.swaps_tot})
+        if (p) (void)hipFree(p);
+    ch = hens_ctx_impl::Chain{};
+}
+static int chain_supported(hens_ctx_impl* c) {
+    if (c->cfg.likelihood_kind == HENS_LIKE_TEMPLATE)
+        return fail(c, HENS_ERR_UNSUPPORTED, "chain store: not on a leaf-packing context (hens_rj_*: records of several branches and leaves)");
+    if (c->cfg.likelihood_kind == HENS_LIKE_HOST)
+        return fail(c, HENS_ERR_UNSUPPORTED, "chain store: needs a device likelihood (a host-callable likelihood steps through the caller)");
+    if (c->Tl != c->T) return fail(c, HENS_ERR_UNSUPPORTED, "chain store: not on a ladder shard (the whole ladder on one GPU)");
+    if (c->pipe.on) return fail(c, HENS_ERR_UNSUPPORTED, "chain store: not on a rank of the ladder pipeline");
+    return HENS_OK;
+}
+static hens_chain::Shape chain_shape(const hens_ctx_impl* c, int Ts) { return hens_chain::Shape{c->T, Ts, c->W, dim_active(c)}; }
+
+int hens_chain_create(hens_ctx* ctx, int64_t capacity, int32_t ntemps_store) {
+    hens_ctx_impl* c = enter(ctx);
+    if (!c) return fail(c, HENS_ERR_INVALID, "null context");
+    int r;
+    if ((r = chain_supported(c))) return r;
+    if (capacity < 1) return fail(c, HENS_ERR_INVALID, "hens_chain_create: capacity < 1");
+    if (ntemps_store < 0 || ntemps_store > c->T) return fail(c, HENS_ERR_INVALID, "hens_chain_create: ntemps_store outside [0, %d]", c->T);
+    const int Ts = ntemps_store ? ntemps_store : c->T;
+    hens_chain::Sizes sz{};
+    if (!hens_chain::sizes(chain_shape(c, Ts), capacity, &sz))
+        return fail(c, HENS_ERR_INVALID, "hens_chain_create: %lld stored steps of %d x %d x %d do not fit an int64 byte count", (long long)capacity, Ts, c->W, dim_active(c));
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    HIPCHK(c, hipStreamSynchronize(c->stream));     // (a chain being replaced may still be written)
+    chain_free(c);
+    hens_ctx_impl::Chain& ch = c->chain;
+    const size_t TsW = (size_t)Ts * c->W, np = (size_t)std::max(c->T - 1, 1);
+    auto get = [&](void** p, size_t bytes) { return hipMalloc(p, bytes) == hipSuccess; };
+    if (!get((void**)&ch.x, (size_t)sz.x) || !get((void**)&ch.L, (size_t)sz.lp) || !get((void**)&ch.P, (size_t)sz.lp) ||
+        !get((void**)&ch.betas, (size_t)sz.betas) || !get((void**)&ch.acc_tot, TsW * 4) || !get((void**)&ch.swaps_tot, np * 8)) {
+        const hipError_t e = hipGetLastError();     // (cleared: hens_step checks it)
+        chain_free(c);
+        return fail(c, HENS_ERR_HIP, "hens_chain_create: allocating %lld bytes of device memory for %lld stored steps failed: %s",
+                    (long long)(sz.total + TsW * 4 + np * 8), (long long)capacity, hipGetErrorString(e));
+    }
+    ch.capacity = capacity; ch.Ts = Ts; ch.sz = sz;
+    ch.bytes = sz.total + (int64_t)(TsW * 4 + np * 8);
+    ch.iteration.clear(); ch.adapt_time.clear();
+    ch.on = true;
+    return hens_chain_reset(ctx);
+}
+
+int hens_chain_reset(hens_ctx* ctx) {
+    hens_ctx_impl* c = enter(ctx);
+    if (!c) return fail(c, HENS_ERR_INVALID, "null context");
+    hens_ctx_impl::Chain& ch = c->chain;
+    if (!ch.on) return fail(c, HENS_ERR_STATE, "no chain (hens_chain_create)");
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    HIPCHK(c, hipMemsetAsync(ch.acc_tot, 0, (size_t)ch.Ts * c->W * 4, c->stream));
+    HIPCHK(c, hipMemsetAsync(ch.swaps_tot, 0, (size_t)std::max(c->T - 1, 1) * 8, c->stream));
+    ch.count = 0;
+    ch.iteration.clear(); ch.adapt_time.clear();
+    return HENS_OK;
+}
+
+int hens_chain_destroy(hens_ctx* ctx) {
+    hens_ctx_impl* c = enter(ctx);
+    if (!c) return fail(c, HENS_ERR_INVALID, "null context");
+    if (!c->chain.on) return HENS_OK;
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    chain_free(c);
+    return HENS_OK;
+}
+
+int hens_chain_info(hens_ctx* ctx, hens_chain_info_t* out) {
+    hens_ctx_impl* c = CTX(ctx);
+    if (!c || !out) return fail(c, HENS_ERR_INVALID, "null argument");
+    static_assert(sizeof(hens_chain_info_t) == 64, "hens_chain_info_t: 7 x i64 + f64 (eryn_amd/_lib.py: HensChainInfo)");
+    const hens_ctx_impl::Chain& ch = c->chain;
+    hens_chain_info_t o{};
+    hens_chain::Sizes one{};
+    (void)hens_chain::sizes(chain_shape(c, ch.on ? ch.Ts : c->T), 1, &one);
+    o.capacity = ch.capacity; o.count = ch.count; o.ntemps_store = ch.on ? ch.Ts : 0; o.bytes = ch.bytes; o.step_bytes = one.step;
+    o.n_store_timed = ch.n_timed; o.store_ms = ch.store_ms;
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    size_t fr = 0, tot = 0;
+    HIPCHK(c, hipMemGetInfo(&fr, &tot));
+    o.free_bytes = (int64_t)fr;
+    *out = o;
+    return HENS_OK;
+}
+
+// one append on the HIP stream: the state as it stands behind a hens_step call, the ladder and swap counts settled by the caller
+static void launch_chain_store(hens_ctx_impl* c, hipEvent_t e0, hipEvent_t e1) {
+    hens_ctx_impl::Chain& ch = c->chain;
+    const size_t TW = (size_t)c->Tl * c->W, TsW = (size_t)ch.Ts * c->W;
+    const int D = dim_active(c);
+    ChainArgs a{};
+    a.wrec = c->packed ? c->wrec[c->cur] : nullptr;
+    a.L = c->L[c->cur]; a.P = c->P[c->cur]; a.loc = c->loc[c->cur];
+    a.acc_fields = c->accepted;
+    a.acc_mh = c->accepted_mh;
+    a.prev = c->report_prev; a.prev_mh = c->report_prev + TW;
+    a.pool = c->pool;
+    a.betas = c->cfg.tempered ? c->betas[c->bcur] : nullptr;
+    a.swaps_last = has_pt(c) ? c->swaps_last : nullptr;
+    a.out_x = ch.x + (size_t)ch.count * TsW * D;
+    a.out_L = ch.L + (size_t)ch.count * TsW; a.out_P = ch.P + (size_t)ch.count * TsW;
+    a.out_betas = ch.betas + (size_t)ch.count * c->T;
+    a.acc_tot = ch.acc_tot; a.swaps_tot = ch.swaps_tot;
+    a.colmode = c->colmode ? 1 : 0; a.T = c->T; a.W = c->W; a.Ts = ch.Ts; a.RW = c->D; a.D = D;
+    // 16 bytes per lane where both sides' rows are 16-byte aligned, else 8; a row to the smallest power of two of lanes that covers
+    // it (at most a wave: wider rows take several rounds)
+    const int vec = (c->D % 2 == 0 && D % 2 == 0) ? 2 : 1;
+    int sh = 0;
+    while ((1 << sh) * vec < D && sh < 6) ++sh;
+    a.lpr_shift = sh;
+    const int64_t threads = (int64_t)TsW << sh;
+    const dim3 grid((unsigned)((threads + 255) / 256));
+    void* args[] = {&a};
+    const void* fn = vec == 2 ? reinterpret_cast<const void*>(k_chain_store<2>) : reinterpret_cast<const void*>(k_chain_store<1>);
+    if (e0) (void)hipExtLaunchKernel(fn, grid, dim3(256), args, 0, c->stream, e0, e1, 0);
+    else (void)hipLaunchKernel(fn, grid, dim3(256), args, 0, c->stream);
+}
+
+int hens_step_chain(hens_ctx* ctx, int64_t n_store, int64_t iters_per_store, int64_t n_last) {
+    hens_ctx_impl* c = CTX(ctx);
+    if (!c) return fail(c, HENS_ERR_INVALID, "null context");
+    int r;
+    if ((r = chain_supported(c))) return r;
+    hens_ctx_impl::Chain& ch = c->chain;
+    if (!ch.on) return fail(c, HENS_ERR_STATE, "no chain (hens_chain_create)");
+    int64_t iters = 0;
+    switch (hens_chain::append_check(ch.capacity, ch.count, n_store, iters_per_store, n_last, &iters)) {
+    case hens_chain::INVALID: return fail(c, HENS_ERR_INVALID, "hens_step_chain: n_store >= 0 and 1 <= n_last <= iters_per_store, and their product an int64");
+    case hens_chain::FULL: return fail(c, HENS_ERR_STATE, "hens_step_chain: %lld more stored steps do not fit a chain of capacity %lld that holds %lld (download and hens_chain_reset)",
+                                       (long long)n_store, (long long)ch.capacity, (long long)ch.count);
+    default: break;
+    }
+    if ((r = counter_room(c, iters))) return r;
+    const bool timed = c->per_kernel_events == 1;
+    std::vector<hipEvent_t> evs;
+    ch.n_timed = 0; ch.store_ms = 0.0;
+    for (int64_t s = 0; s < n_store; ++s) {
+        const bool have_prev = report_current(c) && iters_per_store == n_last;
+        if (iters_per_store > n_last && (r = hens_step(ctx, iters_per_store - n_last))) return r;
+        if (!have_prev && (r = report_snapshot(c))) return r;
+        if ((r = hens_step(ctx, n_last))) { c->report_valid = false; return r; }
+        if ((r = aql_settle(c))) return r;        // (the append uses the HIP stream)
+        HIPCHK(c, hipSetDevice(c->cfg.device_id));
+        flush_adapt(c);                           // (the ladder AFTER the step's adaptation - what hens_download_state returns - and its swap counts)
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        if (timed && evs.size() < 2 * 4096) {
+            HIPCHK(c, hipEventCreate(&e0)); evs.push_back(e0);
+            HIPCHK(c, hipEventCreate(&e1)); evs.push_back(e1);
+        }
+        launch_chain_store(c, e0, e1);
+        HIPCHK(c, hipGetLastError());
+        ch.iteration.push_back((int64_t)c->iter);
+        ch.adapt_time.push_back(c->adapt_time);
+        ch.count += 1;
+        report_marked(c, ch.Ts == c->Tl);         // (k_chain_store moved the mark up to now - of the rungs it stores)
+    }
+    if (!evs.empty()) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        for (size_t k = 0; k + 1 < evs.size(); k += 2) {
+            float ms = 0;
+            if (hipEventElapsedTime(&ms, evs[k], evs[k + 1]) == hipSuccess) { ch.store_ms += ms; ch.n_timed += 1; }
+        }
+        for (hipEvent_t e : evs) (void)hipEventDestroy(e);
+    }
+    return HENS_OK;
+}
+
+int hens_chain_download(hens_ctx* ctx, int64_t first, int64_t count, double* x, double* logl, double* logp, double* betas,
+                        int64_t* iteration, int64_t* adapt_time) {
+    hens_ctx_impl* c = enter(ctx);
+    if (!c) return fail(c, HENS_ERR_INVALID, "null context");
+    hens_ctx_impl::Chain& ch = c->chain;
+    if (!ch.on) return fail(c, HENS_ERR_STATE, "no chain (hens_chain_create)");
+    if (!hens_chain::range_ok(ch.count, first, count))
+        return fail(c, HENS_ERR_INVALID, "hens_chain_download: steps [%lld, %lld + %lld) outside the %lld stored", (long long)first, (long long)first, (long long)count, (long long)ch.count);
+    if (count == 0) return HENS_OK;
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    const size_t TsW = (size_t)ch.Ts * c->W, D = (size_t)dim_active(c), f = (size_t)first, n = (size_t)count;
+    if (x) HIPCHK(c, hipMemcpyAsync(x, ch.x + f * TsW * D, n * TsW * D * 8, hipMemcpyDeviceToHost, c->stream));
+    if (logl) HIPCHK(c, hipMemcpyAsync(logl, ch.L + f * TsW, n * TsW * 8, hipMemcpyDeviceToHost, c->stream));
+    if (logp) HIPCHK(c, hipMemcpyAsync(logp, ch.P + f * TsW, n * TsW * 8, hipMemcpyDeviceToHost, c->stream));
+    if (betas) HIPCHK(c, hipMemcpyAsync(betas, ch.betas + f * c->T, n * c->T * 8, hipMemcpyDeviceToHost, c->stream));
+    if (x || logl || logp || betas) HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (iteration) std::copy(ch.iteration.begin() + first, ch.iteration.begin() + first + count, iteration);
+    if (adapt_time) std::copy(ch.adapt_time.begin() + first, ch.adapt_time.begin() + first + count, adapt_time);
+    return HENS_OK;
+}
+
+int hens_chain_totals(hens_ctx* ctx, double* accepted, double* swaps_accepted) {
+    hens_ctx_impl* c = enter(ctx);
+    if (!c) return fail(c, HENS_ERR_INVALID, "null context");
+    hens_ctx_impl::Chain& ch = c->chain;
+    if (!ch.on) return fail(c, HENS_ERR_STATE, "no chain (hens_chain_create)");
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    const size_t TsW = (size_t)ch.Ts * c->W, np = (size_t)std::max(c->T - 1, 0);
+    std::vector<uint32_t> acc(accepted ? TsW : 0);
+    std::vector<unsigned long long> sw(swaps_accepted ? np : 0);
+    if (!acc.empty()) HIPCHK(c, hipMemcpyAsync(acc.data(), ch.acc_tot, TsW * 4, hipMemcpyDeviceToHost, c->stream));
+    if (!sw.empty()) HIPCHK(c, hipMemcpyAsync(sw.data(), ch.swaps_tot, np * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (size_t i = 0; i < acc.size(); ++i) accepted[i] = (double)acc[i];
+    for (size_t i = 0; i < sw.size(); ++i) swaps_accepted[i] = (double)sw[i];
     return HENS_OK;
 }
 

@@ -227,6 +227,54 @@ class HipEnsemble:
         check(self.lib.hens_step_report(self.ctx, int(n_iters), int(n_last), ptr(acc), ptr(swaps) if self.T > 1 else None, ptr(betas)), self.ctx)
         return acc, swaps, betas
 
+    # -- chain store (include/hipensemble.h: hens_chain_*, hens_step_chain) ---------------------------------
+    def chain_create(self, capacity, ntemps_store=None):
+        """Room for ``capacity`` stored steps of rungs ``[0, ntemps_store)`` (None: all) in device memory; replaces a chain
+        that exists."""
+        check(self.lib.hens_chain_create(self.ctx, int(capacity), int(ntemps_store or 0)), self.ctx)
+
+    def chain_reset(self):
+        check(self.lib.hens_chain_reset(self.ctx), self.ctx)
+
+    def chain_destroy(self):
+        check(self.lib.hens_chain_destroy(self.ctx), self.ctx)
+
+    def chain_info(self):
+        info = _lib.HensChainInfo()
+        check(self.lib.hens_chain_info(self.ctx, C.byref(info)), self.ctx)
+        return {k: getattr(info, k) for k, _ in _lib.HensChainInfo._fields_}
+
+    def step_chain(self, n_store, iters_per_store=1, n_last=1):
+        """``n_store`` stored steps of ``iters_per_store`` iterations each, appended to the chain on the device; the accepted
+        totals take the last ``n_last`` iterations of every step (ensemble.py:968-979).  Nothing is copied to the host."""
+        self.state_epoch += 1
+        check(self.lib.hens_step_chain(self.ctx, int(n_store), int(iters_per_store), int(n_last)), self.ctx)
+
+    def chain_download(self, first=0, count=None, fields=("x", "log_like", "log_prior", "betas")):
+        """Stored steps ``[first, first + count)`` (count None: to the end) as a dict: ``x[count, ntemps_store, W, D]`` (the
+        caller's D: pads are not stored), ``log_like`` / ``log_prior`` ``[count, ntemps_store, W]``, ``betas[count, T]`` - those
+        named in ``fields`` - and ``iteration`` / ``adapt_time`` ``[count]``, the Philox checkpoint of every stored step."""
+        info = self.chain_info()
+        first = int(first)
+        count = info["count"] - first if count is None else int(count)
+        Ts, n = info["ntemps_store"], max(count, 0)
+        out = dict(iteration=np.zeros(n, dtype=np.int64), adapt_time=np.zeros(n, dtype=np.int64))
+        shapes = dict(x=(n, Ts, self.W, self.D), log_like=(n, Ts, self.W), log_prior=(n, Ts, self.W), betas=(n, self.T))
+        for f in fields:
+            out[f] = np.empty(shapes[f])
+        check(self.lib.hens_chain_download(self.ctx, first, count, ptr(out.get("x")), ptr(out.get("log_like")),
+                                           ptr(out.get("log_prior")), ptr(out.get("betas")), ptr(out["iteration"]),
+                                           ptr(out["adapt_time"])), self.ctx)
+        return out
+
+    def chain_totals(self):
+        """(accepted[ntemps_store, W], swaps_accepted[T - 1]) summed over the steps stored since the last reset."""
+        Ts = self.chain_info()["ntemps_store"]
+        acc = np.zeros((Ts, self.W))
+        swaps = np.zeros(max(self.T - 1, 0))
+        check(self.lib.hens_chain_totals(self.ctx, ptr(acc), ptr(swaps) if self.T > 1 else None), self.ctx)
+        return acc, swaps
+
     def download_betas(self):
         betas = np.empty(self.T)
         check(self.lib.hens_download_state(self.ctx, None, None, None, ptr(betas)), self.ctx)

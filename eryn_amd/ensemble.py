@@ -11,13 +11,13 @@ Two RNG modes:
 """
 import numpy as np
 
-from .backend import Backend
+from .backend import Backend, DeviceBackend
 from .engine import HipEnsemble
 from .model import Model
 from .moves import DeviceMove, GaussianMove, MHMove, StretchMove, TemperatureControl
 from .periodic import PeriodicContainer, period_vector
 from .prior import ProbDistContainer
-from .state import State
+from .state import DeviceState, State
 
 
 class EnsembleSampler:
@@ -148,6 +148,12 @@ class EnsembleSampler:
 
         # -- backend + RNG (ensemble.py:593-652)
         self.backend = Backend() if backend is None else backend
+        self._device_store = isinstance(self.backend, DeviceBackend)
+        if self._device_store:
+            if rng != "philox":
+                raise NotImplementedError("DeviceBackend keeps the chain of the device-side draws: it needs rng='philox' (the walkers of "
+                                          "rng='numpy' cross the host at every proposal anyway: use Backend)")
+            self.backend.attach(self.engine, self.seed)
         if not self.backend.initialized:
             self.backend.reset(self.nwalkers, self.ndims, ntemps=self.ntemps, branch_names=self.branch_names)
         self._random = np.random.mtrand.RandomState()
@@ -207,35 +213,15 @@ class EnsembleSampler:
     # -- main loop (ensemble.py:808-1045) ------------------------------------------------------------
     def sample(self, initial_state, iterations=1, tune=False, skip_initial_state_check=True, thin_by=1,
                store=True, progress=False):
-        state = State(initial_state, copy=True)
-        name = self.branch_names[0]
-        if state.branches[name].shape != (self.ntemps, self.nwalkers, 1, self.ndim):
-            raise ValueError("incompatible input dimensions")
-        if state.log_prior is None or state.log_like is None:
-            L, P = self._eval(state.branches_coords)
-            state.log_prior = P if state.log_prior is None else state.log_prior
-            state.log_like = L if state.log_like is None else state.log_like
-        tc = self.temperature_control
-        if tc is not None:
-            if state.betas is not None:
-                if state.betas.shape[0] != self.ntemps:
-                    raise ValueError("Input state has inverse temperatures (betas), but not the correct number.")
-                tc.betas = state.betas.copy()
-            else:
-                state.betas = tc.betas.copy()
-        if np.any(np.isinf(state.log_like)):
-            raise ValueError("The initial log_like was +/- infinite")
-        if np.any(np.isinf(state.log_prior)):
-            raise ValueError("The initial log_prior was +/- infinite")
-        if np.any(np.isnan(state.log_like)) or np.any(np.isnan(state.log_prior)):
-            raise ValueError("The initial log_like / log_prior was NaN")
-        thin_by = int(thin_by)
-        if thin_by <= 0:
-            raise ValueError("Invalid thinning argument")
+        state, thin_by = self._initial_state(initial_state, thin_by)
         if store:
             self.backend.grow(iterations, None)
         model = self.get_model()
+        tc = self.temperature_control
 
+        if self.rng == "philox" and store and self._device_store:
+            yield from self._sample_chain(state, iterations, thin_by, tune)
+            return
         if self.rng == "philox":
             yield from self._sample_philox(state, iterations, thin_by, store, tune)
             return
@@ -263,6 +249,36 @@ class EnsembleSampler:
             self._previous_state = state
             yield state
 
+    def _initial_state(self, initial_state, thin_by):
+        """The checks and evaluations at the head of ``sample`` (ensemble.py:872-935): a copy of the initial state with its
+        log-prior / log-likelihood and ladder, and the thinning as an int."""
+        state = State(initial_state, copy=True)
+        name = self.branch_names[0]
+        if state.branches[name].shape != (self.ntemps, self.nwalkers, 1, self.ndim):
+            raise ValueError("incompatible input dimensions")
+        if state.log_prior is None or state.log_like is None:
+            L, P = self._eval(state.branches_coords)
+            state.log_prior = P if state.log_prior is None else state.log_prior
+            state.log_like = L if state.log_like is None else state.log_like
+        tc = self.temperature_control
+        if tc is not None:
+            if state.betas is not None:
+                if state.betas.shape[0] != self.ntemps:
+                    raise ValueError("Input state has inverse temperatures (betas), but not the correct number.")
+                tc.betas = state.betas.copy()
+            else:
+                state.betas = tc.betas.copy()
+        if np.any(np.isinf(state.log_like)):
+            raise ValueError("The initial log_like was +/- infinite")
+        if np.any(np.isinf(state.log_prior)):
+            raise ValueError("The initial log_prior was +/- infinite")
+        if np.any(np.isnan(state.log_like)) or np.any(np.isnan(state.log_prior)):
+            raise ValueError("The initial log_like / log_prior was NaN")
+        thin_by = int(thin_by)
+        if thin_by <= 0:
+            raise ValueError("Invalid thinning argument")
+        return state, thin_by
+
     def _push_mh_proposal(self, mh_move):
         """Hand the Gaussian move's proposal to the device if it differs from what the device holds (construction; a ``tune`` hook
         that rescales the move, ensemble.py:983-984 - the reference's hook mutates the move object the next proposal reads)."""
@@ -279,7 +295,8 @@ class EnsembleSampler:
         tc = self.temperature_control
         return ("philox", self.seed, int(self.engine.iteration()), 0 if tc is None else int(tc.time))
 
-    def _sample_philox(self, state, iterations, thin_by, store, tune=False):
+    def _philox_setup(self, state):
+        """The state, the resume point and the moves' settings onto the device, in front of a Philox run."""
         eng, tc, name = self.engine, self.temperature_control, self.branch_names[0]
         eng.upload(state.branches[name].coords[:, :, 0, :], state.log_like, state.log_prior,
                    None if tc is None else tc.betas)
@@ -292,7 +309,6 @@ class EnsembleSampler:
                 tc.time = int(rs[3])
         if tc is not None:
             eng.set_adapt_time(tc.time)
-        reps = self.num_repeats_in_model
         st_move, mh_move = self._philox_moves
         # one context steps both moves of the mix: they must agree on the periodic parameters
         pers = [period_vector(m.periodic, name, self.ndim) for m in (st_move, mh_move) if m is not None]
@@ -304,6 +320,12 @@ class EnsembleSampler:
             eng.set_nsplits(st_move.nsplits)
         if st_move is not None and eng.a != float(st_move.a):
             eng.set_stretch_scale(st_move.a)
+
+    def _sample_philox(self, state, iterations, thin_by, store, tune=False):
+        eng, tc, name = self.engine, self.temperature_control, self.branch_names[0]
+        self._philox_setup(state)
+        reps = self.num_repeats_in_model
+        st_move, mh_move = self._philox_moves
         prev = eng.counters()
         prev_mh = eng.mh_counters() if mh_move is not None else None
         inds = state.branches[name].inds
@@ -377,6 +399,73 @@ class EnsembleSampler:
             self._previous_state = state
             yield state
 
+    # -- stored steps kept on the device (backend=DeviceBackend(); include/hipensemble.h: hens_step_chain) -----------------------
+    def _chain_books(self, prev, prev_mh):
+        """After device-stored steps: the moves' own counters and the temperature control catch up with the device's (what
+        the host loop does per stored step, ensemble.py:974-977), from one read of the counters."""
+        eng, tc = self.engine, self.temperature_control
+        st_move, mh_move = self._philox_moves
+        c = eng.counters()
+        if st_move is not None:
+            st_move.accepted += c["accepted"] - prev["accepted"]
+            st_move.num_proposals += c["num_proposals"] - prev["num_proposals"]
+        if mh_move is not None:
+            cm = eng.mh_counters()
+            mh_move.accepted += cm["accepted"] - prev_mh["accepted"]
+            mh_move.num_proposals += cm["num_proposals"] - prev_mh["num_proposals"]
+        if tc is not None:
+            tc.time = c["adapt_time"]
+            tc.swaps_accepted = c["swaps_last"]
+
+    def _chain_checks(self, tune):
+        if tune:
+            raise NotImplementedError("tune=True calls a host hook after every proposal with that proposal's State (ensemble.py:983-984): "
+                                      "such a run crosses the host per proposal and gains nothing from a DeviceBackend - use Backend")
+
+    def _sample_chain(self, state, iterations, thin_by, tune=False):
+        """``sample`` with a DeviceBackend: one stored step per yield, appended on the device; the yielded State reads the
+        walkers from the device when somebody looks at them (eryn_amd.state.DeviceState)."""
+        self._chain_checks(tune)
+        eng, tc, name = self.engine, self.temperature_control, self.branch_names[0]
+        self._philox_setup(state)
+        reps = self.num_repeats_in_model
+        prev = eng.counters()
+        prev_mh = eng.mh_counters() if self._philox_moves[1] is not None else None
+        inds = state.branches[name].inds
+        shape = (self.ntemps, self.nwalkers, 1, self.ndim)
+        try:
+            for _ in range(iterations):
+                self.backend.append(1, thin_by * reps, reps)
+                last = self.backend.last_step(fields=("betas",) if tc is not None else ())
+                if tc is not None:
+                    tc.betas = last["betas"][0]
+                    tc.time = int(last["adapt_time"][0])
+                state = DeviceState(eng, eng.state_epoch, name, shape, inds, betas=None if tc is None else tc.betas,
+                                    random_state=("philox", self.seed, int(last["iteration"][0]), int(last["adapt_time"][0])))
+                self._previous_state = state
+                yield state
+        finally:
+            self._chain_books(prev, prev_mh)
+
+    def _run_chain(self, initial_state, nsteps, thin_by=1, tune=False, **unused):
+        """``run_mcmc(store=True)`` with a DeviceBackend: the whole run is one device call per chain segment
+        (DeviceBackend.append), the last State one download at the end."""
+        self._chain_checks(tune)
+        state, thin_by = self._initial_state(initial_state, thin_by)
+        eng, tc, name = self.engine, self.temperature_control, self.branch_names[0]
+        self.backend.grow(nsteps, None)
+        self._philox_setup(state)
+        reps = self.num_repeats_in_model
+        prev = eng.counters()
+        prev_mh = eng.mh_counters() if self._philox_moves[1] is not None else None
+        self.backend.append(nsteps, thin_by * reps, reps)
+        x, L, P, betas = eng.download()
+        self._chain_books(prev, prev_mh)
+        if tc is not None:
+            tc.betas = betas
+        return State({name: x[:, :, None, :]}, inds={name: state.branches[name].inds}, log_like=L, log_prior=P,
+                     betas=None if tc is None else betas, random_state=self.philox_checkpoint())
+
     def run_mcmc(self, initial_state, nsteps, burn=None, post_burn_update=False, **kwargs):
         """ensemble.py:1047-1125."""
         if initial_state is None:
@@ -398,6 +487,9 @@ class EnsembleSampler:
             thin = int(kw.pop("thin_by", 1))
             for results in self.sample(initial_state, iterations=1, thin_by=thin * nsteps, **kw):
                 pass
+        elif self._device_store:
+            kw = {k: v for k, v in kwargs.items() if k != "store"}
+            results = self._run_chain(initial_state, nsteps, **kw)
         else:
             for results in self.sample(initial_state, iterations=nsteps, **kwargs):
                 pass

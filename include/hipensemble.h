@@ -191,6 +191,53 @@ int hens_get_marked_counters(hens_ctx* ctx, double* accepted, double* accepted_m
  * (eryn_amd/state.py: DeviceState; SURVEY 8 b-2 "device-resident State mirror"). */
 int hens_step_report(hens_ctx* ctx, int64_t n_iters, int64_t n_last, uint8_t* accepted_last, double* swaps_last, double* betas);
 
+/* ---- Chain store: the stored steps of run_mcmc(store=True) kept in device memory ---------------------------------------------
+ * The device-side form of the reference's storage contract (backends/backend.py:1014-1091 `save_step`, called from
+ * ensemble.py:1013-1030): a chain buffer in device memory, one small launch (k_chain_store) that appends the walkers in walker
+ * order straight from where they ride - column- or slot-ordered walker records, or the by-field arrays -, the accepted / swap
+ * totals the backend keeps accumulated beside it, and ONE copy when somebody reads the chain.  Contexts of one GPU with a device
+ * likelihood only: a leaf-packing (HENS_LIKE_TEMPLATE) or host-likelihood context, a ladder shard and a pipeline rank ->
+ * HENS_ERR_UNSUPPORTED.  hens_upload_state / hens_set_iteration do not clear the chain (a resumed run appends),
+ * hens_reset_counters leaves its totals alone, hens_destroy frees it.
+ *
+ * hens_chain_create: room for `capacity` stored steps of rungs [0, ntemps_store) (0 = all): the allocation the reference makes
+ *   in Backend.grow (backends/backend.py:849-913).  A chain that exists is freed first.  Allocation failure -> HENS_ERR_HIP, the
+ *   message names the bytes asked for.
+ * hens_chain_reset: count = 0, totals = 0, buffers kept (Backend.reset, backends/backend.py:76-261, without the allocation).
+ * hens_chain_info: also valid without a chain (capacity = 0): step_bytes is what one stored step of all rungs would take.
+ * hens_step_chain: n_store times { iters_per_store - n_last iterations; the accept counters marked; n_last iterations; the
+ *   ladder adaptation settled; the state appended } - the body of the sampler's loop over stored steps, ensemble.py:965-1030,
+ *   with thin_by * num_repeats_in_model = iters_per_store and num_repeats_in_model = n_last (the reference stores the accept
+ *   counts of the LAST thinned sub-iteration, ensemble.py:968-979, and the last cascade's swap counts).  The host copies nothing
+ *   and waits for no copy; the append launch goes on the HIP stream between hens_step segments that keep their queue.  The
+ *   iteration counter and adaptation time of every stored step are kept on the host: with the seed they are the checkpoint a
+ *   stored State carries (hens_set_iteration).  Appending past the capacity -> HENS_ERR_STATE before anything is launched;
+ *   n_last < 1 or iters_per_store < n_last -> HENS_ERR_INVALID.
+ * hens_chain_download: stored steps [first, first + count) - x[count][ntemps_store][W][D] with D the REAL parameters
+ *   (hens_config::ndim_active: pads are not stored), logl / logp [count][ntemps_store][W], betas[count][T] (the ladder after
+ *   the step's adaptation, what hens_download_state returns), iteration / adapt_time [count].  Replaces Backend.get_value
+ *   (backends/backend.py:263-328).  Any pointer may be NULL; a range outside [0, count) -> HENS_ERR_INVALID.
+ * hens_chain_totals: accepted[ntemps_store][W], swaps_accepted[T-1] summed over the steps stored since the last reset
+ *   (backends/backend.py:1069-1072); kept as integers on the device. */
+typedef struct hens_chain_info_t {
+    int64_t capacity;          /* stored steps the buffers hold (0: no chain)              */
+    int64_t count;             /* stored steps appended since create / reset               */
+    int64_t ntemps_store;      /* rungs stored                                             */
+    int64_t bytes;             /* device memory the chain holds                            */
+    int64_t step_bytes;        /* ... per stored step (without a chain: of all rungs)      */
+    int64_t free_bytes;        /* free device memory now (hipMemGetInfo)                   */
+    int64_t n_store_timed;     /* appends of the last hens_step_chain call that were timed */
+    double store_ms;           /* ... and their summed duration (hens_set_profiling 1)     */
+} hens_chain_info_t;
+int hens_chain_create(hens_ctx* ctx, int64_t capacity, int32_t ntemps_store);
+int hens_chain_reset(hens_ctx* ctx);
+int hens_chain_destroy(hens_ctx* ctx);
+int hens_chain_info(hens_ctx* ctx, hens_chain_info_t* out);
+int hens_step_chain(hens_ctx* ctx, int64_t n_store, int64_t iters_per_store, int64_t n_last);
+int hens_chain_download(hens_ctx* ctx, int64_t first, int64_t count, double* x, double* logl, double* logp, double* betas,
+                        int64_t* iteration, int64_t* adapt_time);
+int hens_chain_totals(hens_ctx* ctx, double* accepted, double* swaps_accepted);
+
 /* Counters.  Replaces Move.accepted / num_proposals (move.py:404-421, red_blue.py:326-327),
  * TemperatureControl.swaps_accepted / time (tempering.py:542,596).  Any pointer may be NULL.
  *   accepted[Tl][W] f64 cumulative, swaps_last[T-1], swaps_total[T-1] f64. */
