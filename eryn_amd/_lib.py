@@ -110,6 +110,13 @@ SIGNATURES = {
     "hens_step_chain": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64]),
     "hens_chain_download": (C.c_int, [_P, C.c_int64, C.c_int64, _P, _P, _P, _P, _P, _P]),
     "hens_chain_totals": (C.c_int, [_P, _P, _P]),
+    "hens_rj_chain_create": (C.c_int, [_P, C.c_int64, C.c_int32]),
+    "hens_rj_chain_reset": (C.c_int, [_P]),
+    "hens_rj_chain_destroy": (C.c_int, [_P]),
+    "hens_rj_chain_info": (C.c_int, [_P, C.POINTER(HensChainInfo)]),
+    "hens_rj_step_chain": (C.c_int, [_P, C.c_int64, C.c_int64]),
+    "hens_rj_chain_download": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int32, _P, _P, _P, _P, _P, _P, _P]),
+    "hens_rj_chain_totals": (C.c_int, [_P, _P, _P, _P]),
     "hens_pipe_init": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P]),
     "hens_pipe_connect": (C.c_int, [_P, _P]),
     "hens_pipe_connect_local": (C.c_int, [_P, _P]),

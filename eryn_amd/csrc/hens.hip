@@ -8,6 +8,7 @@
 #include "hens_aql.h"
 #include "hens_ktable.h"
 #include "hens_chain.h"
+#include "hens_rj_chain.h"
 #include "hens_chain_host.h"
 #include <unordered_map>
 #include <hip/hip_ext.h>
@@ -250,6 +251,24 @@ struct hens_ctx_impl {
         std::vector<int64_t> iteration, adapt_time;   // per stored step: the Philox checkpoint of its State
         int64_t n_timed = 0; double store_ms = 0.0;   // hens_set_profiling 1: the last call's append launches
     } chain;
+    // ... of a leaf-packing context (hens_rj_chain_*, hens_rj_step_chain): per branch coordinates and leaf masks
+    struct RjChain {
+        bool on = false;
+        int64_t capacity = 0, count = 0, bytes = 0;
+        int Ts = 0;                          // rungs [0, Ts) are stored
+        double* x[RJ_MAX_BRANCH] = {};       // [capacity][Ts][W][nl_b][nd_b], NaN on unused leaves
+        uint8_t* inds[RJ_MAX_BRANCH] = {};   // [capacity][Ts][W][nl_b]
+        double *L = nullptr, *P = nullptr, *betas = nullptr;   // [capacity] x ([Ts][W], [Ts][W], [T])
+        uint32_t *acc_tot = nullptr, *bd_tot = nullptr;        // [Ts][W] accepted / rj_accepted totals
+        uint32_t* prev = nullptr;            // [2][Tl][W] the in-model / birth-death accept counters at the mark
+        unsigned long long* swaps_tot = nullptr;   // [T-1] in-model swap totals
+        double* swaps_step = nullptr;        // [T-1] the in-model cascade's counts of a stored step's last iteration, set aside
+        hens_chain::RjSizes sz{};
+        std::vector<int64_t> iteration, adapt_time;   // per stored step: the Philox checkpoint of its State
+        int64_t n_timed = 0; double store_ms = 0.0;   // hens_set_profiling 1: the last call's append launches
+        bool mark_valid = false;             // `prev` is the counters as they stand (the last append left it so) ...
+        int64_t mark_books = 0;              // ... as long as no move has run since: num_mh + num_bd then
+    } rjchain;
     std::vector<double> launch_us;   // per-kernel profiling: begin / end of every launch of the last hens_step call (us after the first begin)
     std::vector<void*> allocs;
 };
@@ -2119,6 +2138,8 @@ int hens_create(const hens_config* cfg, hens_ctx** out) {
 }
 
 static void chain_free(hens_ctx_impl* c);     // (the chain store's device buffers: below, with hens_chain_*)
+static void rjchain_free(hens_ctx_impl* c);   // (... a leaf-packing context's: below, with hens_rj_chain_*)
+static int rjchain_drop(hens_ctx_impl* c);
 void hens_destroy(hens_ctx* ctx) {
     hens_ctx_impl* c = CTX(ctx);
     if (!c) return;
@@ -2139,6 +2160,7 @@ void hens_destroy(hens_ctx* ctx) {
     for (void* p : c->allocs)
         if (p) (void)hipFree(p);
     chain_free(c);
+    rjchain_free(c);
     for (hipEvent_t e : c->evpool) (void)hipEventDestroy(e);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -2894,7 +2916,7 @@ static void chain_free(hens_ctx_impl* c) {
 }
 static int chain_supported(hens_ctx_impl* c) {
     if (c->cfg.likelihood_kind == HENS_LIKE_TEMPLATE)
-        return fail(c, HENS_ERR_UNSUPPORTED, "chain store: not on a leaf-packing context (hens_rj_*: records of several branches and leaves)");
+        return fail(c, HENS_ERR_UNSUPPORTED, "chain store: not on a leaf-packing context (records of several branches and leaves: hens_rj_chain_create / hens_rj_step_chain)");
     if (c->cfg.likelihood_kind == HENS_LIKE_HOST)
         return fail(c, HENS_ERR_UNSUPPORTED, "chain store: needs a device likelihood (a host-callable likelihood steps through the caller)");
     if (c->Tl != c->T) return fail(c, HENS_ERR_UNSUPPORTED, "chain store: not on a ladder shard (the whole ladder on one GPU)");
@@ -3148,6 +3170,7 @@ int hens_reset_counters(hens_ctx* ctx) {
     c->num_proposals_mh = 0;
     c->rj.num_mh = c->rj.num_bd = 0;
     c->report_valid = false;
+    c->rjchain.mark_valid = false;
     return HENS_OK;
 }
 
@@ -3341,6 +3364,7 @@ static int rj_set_template_model(hens_ctx_impl* c, int nkinds, int32_t nbranches
     if (ndata < 1 || !(sigma > 0.0)) return fail(c, HENS_ERR_INVALID, "invalid data");
     HIPCHK(c, hipSetDevice(c->cfg.device_id));
     state_to_fields(c);                       // (hens_step leaves the state in record mode)
+    if (const int rd = rjchain_drop(c)) return rd;
     RjModel M{};
     M.nb = nbranches; M.ndata = ndata; M.sigma = sigma;
     int off = 0, slot = 0, k = 0, boff[RJ_MAX_BRANCH] = {0, 0, 0, 0};      // (boff: a branch's first entry of lo / hi)
@@ -3451,6 +3475,7 @@ int hens_rj_set_model_general(hens_ctx* ctx, int32_t nbranches, const int32_t* n
     if (nbranches < 1 || nbranches > RJ_MAX_BRANCH) return fail(c, HENS_ERR_INVALID, "1..%d branches", RJ_MAX_BRANCH);
     HIPCHK(c, hipSetDevice(c->cfg.device_id));
     state_to_fields(c);
+    if (const int rd = rjchain_drop(c)) return rd;
     RjModel M{};
     M.nb = nbranches; M.ndata = 0; M.sigma = 1.0; M.t_step64 = 0.0;
     int off = 0, slot = 0, k = 0;
@@ -3675,13 +3700,21 @@ static int rj_step_bd(hens_ctx_impl* c) {
     return HENS_OK;
 }
 
-int hens_rj_step(hens_ctx* ctx, int64_t n_iters) {
-    hens_ctx_impl* c = enter(ctx);
-    int r = rj_ready(c);
-    if (r) return r;
-    if (n_iters < 0) return fail(c, HENS_ERR_INVALID, "n_iters < 0");
-    if ((r = counter_room(c, n_iters))) return r;
-    const bool stretch = c->rj.in_model == HENS_RJ_INMODEL_STRETCH;
+// What hens_rj_step and hens_rj_step_chain share: the head of a call (checks, the state by field, the first full evaluation), one
+// iteration, and the way out.
+namespace {
+struct RjStepping {
+    hens_ctx_impl* c;
+    bool stretch = false, fresh = false, armed = false;
+    explicit RjStepping(hens_ctx_impl* c_) : c(c_) {}
+    ~RjStepping() { if (armed) { c->rj.defer_adapt = false; flush_adapt(c); } }     // (every way out leaves no adaptation pending and the switch off)
+    int begin(int64_t n_iters);
+    int iteration(double* swaps_aside);
+};
+
+int RjStepping::begin(int64_t n_iters) {
+    int r;
+    stretch = c->rj.in_model == HENS_RJ_INMODEL_STRETCH;
     if (!stretch && !c->rj.have_scale) return fail(c, HENS_ERR_STATE, "in-model step scale not set (hens_rj_set_mh_scale)");
     if (stretch && !c->cfg.live_dangerously && c->W < 2 * c->rj.M.ind_off)           // red_blue.py:103-114 (every slot of every branch counts)
         return fail(c, HENS_ERR_TOO_FEW_WALKERS, "It is unadvisable to use a red-blue move with fewer walkers than twice the number of dimensions. "
@@ -3699,8 +3732,6 @@ int hens_rj_step(hens_ctx* ctx, int64_t n_iters) {
     // iterations of +- updates behind them) in the last bits of its birth / death likelihoods.  Now the resident state behind a
     // download is a function of what the download returned, so a chain is a function of (State, seed, iteration counter,
     // adaptation time): resumed in a new context it is the uninterrupted chain bit for bit (tests/test_hip_rj.py).
-    constexpr int64_t RJ_REFRESH = 64;
-    bool fresh = false;
     if (c->rj.tm && !c->rj.tm_valid && n_iters > 0) {
         if ((r = rj_evaluate(c))) return r;
         fresh = true;
@@ -3710,36 +3741,58 @@ int hens_rj_step(hens_ctx* ctx, int64_t n_iters) {
         if ((r = dalloc(c, &c->rj.ad_flag, 2))) return r;
         HIPCHK(c, hipMemsetAsync(c->rj.ad_flag, 0, 8, c->stream));
     }
-    struct Defer {                             // (every way out of the loop leaves no adaptation pending and the switch off)
-        hens_ctx_impl* c;
-        ~Defer() { c->rj.defer_adapt = false; flush_adapt(c); }
-    } defer{c};
+    armed = true;
     c->rj.defer_adapt = !fold_off && c->rj.tm != nullptr;
-    for (int64_t i = 0; i < n_iters; ++i) {
-        if (c->rj.tm && c->iter % RJ_REFRESH == RJ_REFRESH - 1 && !fresh && c->rj.tm_drift)
-            if ((r = rj_evaluate(c))) return r;
-        fresh = false;
-        c->rj.tm_drift = c->rj.tm != nullptr && c->rj.schedule != 3;      // (only birth / death updates a template by +- a leaf)
-        if (stretch) {
-            // red / blue stretch move over every branch and leaf slot: two launches, a half each - the complements of a half
-            // belong to the other set, which its launch does not write (red_blue.py:148-323); ONE move (num_mh)
-            for (int h = 0; h < 2; ++h)
-                if (const RjLaunch half = rj_production(c, RJ_MODE_STRETCH, 0, h); half.ns != 0 && (r = rj_launch(c, half))) return r;
-        } else {
-            // in-model Gaussian move on the packed leaves (mh.py:56-193)
-            if ((r = rj_launch(c, rj_production(c, RJ_MODE_MH)))) return r;
-        }
-        c->rj.num_mh += 1;
-        rj_cascade(c, 2 * c->iter, true);         // swaps + adaptation (mh.py:190-191, red_blue.py:326-328)
-        if (c->rj.schedule == 3) {                // no reversible-jump move (EnsembleSampler without rj_moves): counter and keys as ever
-            c->iter += 1;
-            continue;
-        }
-        if ((r = rj_step_bd(c))) return r;
-        c->rj.num_bd += 1;
-        rj_cascade(c, 2 * c->iter + 1, false);
-        c->iter += 1;
+    return HENS_OK;
+}
+
+// One iteration.  swaps_aside (hens_rj_step_chain, the last iteration of a stored step): the in-model cascade's swap counts, copied
+// there before the birth / death move's cascade overwrites swaps_last - its adaptation settled as a launch of its own in front of
+// the copy instead of inside the next k_rj launch (same bits: tests/test_hip_rj.py, the folded adaptation changes nothing).
+int RjStepping::iteration(double* swaps_aside) {
+    constexpr int64_t RJ_REFRESH = 64;
+    int r;
+    if (c->rj.tm && c->iter % RJ_REFRESH == RJ_REFRESH - 1 && !fresh && c->rj.tm_drift)
+        if ((r = rj_evaluate(c))) return r;
+    fresh = false;
+    c->rj.tm_drift = c->rj.tm != nullptr && c->rj.schedule != 3;      // (only birth / death updates a template by +- a leaf)
+    if (stretch) {
+        // red / blue stretch move over every branch and leaf slot: two launches, a half each - the complements of a half
+        // belong to the other set, which its launch does not write (red_blue.py:148-323); ONE move (num_mh)
+        for (int h = 0; h < 2; ++h)
+            if (const RjLaunch half = rj_production(c, RJ_MODE_STRETCH, 0, h); half.ns != 0 && (r = rj_launch(c, half))) return r;
+    } else {
+        // in-model Gaussian move on the packed leaves (mh.py:56-193)
+        if ((r = rj_launch(c, rj_production(c, RJ_MODE_MH)))) return r;
     }
+    c->rj.num_mh += 1;
+    rj_cascade(c, 2 * c->iter, true);         // swaps + adaptation (mh.py:190-191, red_blue.py:326-328)
+    if (c->rj.schedule == 3) {                // no reversible-jump move (EnsembleSampler without rj_moves): counter and keys as ever
+        c->iter += 1;
+        return HENS_OK;
+    }
+    if (swaps_aside && has_pt(c)) {
+        flush_adapt(c);
+        HIPCHK(c, hipMemcpyAsync(swaps_aside, c->swaps_last, (size_t)(c->T - 1) * 8, hipMemcpyDeviceToDevice, c->stream));
+    }
+    if ((r = rj_step_bd(c))) return r;
+    c->rj.num_bd += 1;
+    rj_cascade(c, 2 * c->iter + 1, false);
+    c->iter += 1;
+    return HENS_OK;
+}
+}  // namespace
+
+int hens_rj_step(hens_ctx* ctx, int64_t n_iters) {
+    hens_ctx_impl* c = enter(ctx);
+    int r = rj_ready(c);
+    if (r) return r;
+    if (n_iters < 0) return fail(c, HENS_ERR_INVALID, "n_iters < 0");
+    if ((r = counter_room(c, n_iters))) return r;
+    RjStepping st(c);
+    if ((r = st.begin(n_iters))) return r;
+    for (int64_t i = 0; i < n_iters; ++i)
+        if ((r = st.iteration(nullptr))) return r;
     c->rj.defer_adapt = false;
     flush_adapt(c);
     HIPCHK(c, hipGetLastError());
@@ -3748,6 +3801,261 @@ int hens_rj_step(hens_ctx* ctx, int64_t n_iters) {
     // the reference raises "The likelihood function is returning Nan." / on an infinite coordinate at once (ensemble.py:1258-
     // 1262, 1542); here once per call: the template likelihood's flags are read back with the call's last launch
     return check_flags(c, true);
+}
+
+// ---- chain store of a leaf-packing context (include/hipensemble.h: hens_rj_chain_*, hens_rj_step_chain; csrc/hens_rj_chain.h) ----
+static void rjchain_free(hens_ctx_impl* c) {
+    hens_ctx_impl::RjChain& ch = c->rjchain;
+    for (int b = 0; b < RJ_MAX_BRANCH; ++b) {
+        if (ch.x[b]) (void)hipFree(ch.x[b]);
+        if (ch.inds[b]) (void)hipFree(ch.inds[b]);
+    }
+    for (void* p : {(void*)ch.L, (void*)ch.P, (void*)ch.betas, (void*)ch.acc_tot, (void*)ch.bd_tot, (void*)ch.prev, (void*)ch.swaps_tot, (void*)ch.swaps_step})
+        if (p) (void)hipFree(p);
+    ch = hens_ctx_impl::RjChain{};
+}
+static int rjchain_supported(hens_ctx_impl* c) {
+    if (c->cfg.likelihood_kind != HENS_LIKE_TEMPLATE)
+        return fail(c, HENS_ERR_UNSUPPORTED, "hens_rj_chain_*: the chain store of a leaf-packing context (HENS_LIKE_TEMPLATE); others: hens_chain_create / hens_step_chain");
+    if (c->rj.M.nb <= 0 || !c->rj.acc_bd) return fail(c, HENS_ERR_STATE, "hens_rj_chain_*: no model (hens_rj_set_model first)");
+    if (c->rj.general)
+        return fail(c, HENS_ERR_UNSUPPORTED, "chain store: needs a device likelihood (a model of hens_rj_set_model_general steps through the caller)");
+    if (c->Tl != c->T) return fail(c, HENS_ERR_UNSUPPORTED, "chain store: not on a ladder shard (the whole ladder on one GPU)");
+    if (c->pipe.on) return fail(c, HENS_ERR_UNSUPPORTED, "chain store: not on a rank of the ladder pipeline");
+    return HENS_OK;
+}
+static hens_chain::RjShape rjchain_shape(const hens_ctx_impl* c, int Ts) {
+    hens_chain::RjShape s{c->T, Ts, c->W, c->rj.M.nb, {}, {}};
+    for (int b = 0; b < c->rj.M.nb && b < hens_chain::RJ_BRANCHES; ++b) { s.nl[b] = c->rj.M.nl[b]; s.nd[b] = c->rj.M.nd[b]; }
+    return s;
+}
+static_assert(hens_chain::RJ_BRANCHES == RJ_MAX_BRANCH, "hens_chain_host.h: branches of a record");
+// a model set anew: the chain of the old one has another shape
+static int rjchain_drop(hens_ctx_impl* c) {
+    if (!c->rjchain.on) return HENS_OK;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    rjchain_free(c);
+    return HENS_OK;
+}
+
+int hens_rj_chain_create(hens_ctx* ctx, int64_t capacity, int32_t ntemps_store) {
+    hens_ctx_impl* c = enter(ctx);
+    if (!c) return fail(c, HENS_ERR_INVALID, "null context");
+    int r;
+    if ((r = rjchain_supported(c))) return r;
+    if (capacity < 1) return fail(c, HENS_ERR_INVALID, "hens_rj_chain_create: capacity < 1");
+    if (ntemps_store < 0 || ntemps_store > c->T) return fail(c, HENS_ERR_INVALID, "hens_rj_chain_create: ntemps_store outside [0, %d]", c->T);
+    const int Ts = ntemps_store ? ntemps_store : c->T;
+    hens_chain::RjSizes sz{};
+    if (!hens_chain::rj_sizes(rjchain_shape(c, Ts), capacity, &sz))
+        return fail(c, HENS_ERR_INVALID, "hens_rj_chain_create: %lld stored steps of %d x %d x %d coordinates do not fit an int64 byte count", (long long)capacity, Ts, c->W, c->rj.M.ind_off);
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    HIPCHK(c, hipStreamSynchronize(c->stream));     // (a chain being replaced may still be written)
+    rjchain_free(c);
+    hens_ctx_impl::RjChain& ch = c->rjchain;
+    const size_t TsW = (size_t)Ts * c->W, TW = (size_t)c->Tl * c->W, np = (size_t)std::max(c->T - 1, 1);
+    auto get = [&](void** p, size_t bytes) { return hipMalloc(p, bytes) == hipSuccess; };
+    bool ok = get((void**)&ch.L, (size_t)sz.lp) && get((void**)&ch.P, (size_t)sz.lp) && get((void**)&ch.betas, (size_t)sz.betas) &&
+              get((void**)&ch.acc_tot, TsW * 4) && get((void**)&ch.bd_tot, TsW * 4) && get((void**)&ch.prev, 2 * TW * 4) &&
+              get((void**)&ch.swaps_tot, np * 8) && get((void**)&ch.swaps_step, np * 8);
+    for (int b = 0; ok && b < c->rj.M.nb; ++b) ok = get((void**)&ch.x[b], (size_t)sz.x[b]) && get((void**)&ch.inds[b], (size_t)sz.inds[b]);
+    const int64_t extra = (int64_t)(2 * TsW * 4 + 2 * TW * 4 + 2 * np * 8);
+    if (!ok) {
+        const hipError_t e = hipGetLastError();     // (cleared: the stepping calls check it)
+        rjchain_free(c);
+        return fail(c, HENS_ERR_HIP, "hens_rj_chain_create: allocating %lld bytes of device memory for %lld stored steps failed: %s",
+                    (long long)(sz.total + extra), (long long)capacity, hipGetErrorString(e));
+    }
+    ch.capacity = capacity; ch.Ts = Ts; ch.sz = sz;
+    ch.bytes = sz.total + extra;
+    ch.on = true;
+    return hens_rj_chain_reset(ctx);
+}
+
+int hens_rj_chain_reset(hens_ctx* ctx) {
+    hens_ctx_impl* c = enter(ctx);
+    if (!c) return fail(c, HENS_ERR_INVALID, "null context");
+    hens_ctx_impl::RjChain& ch = c->rjchain;
+    if (!ch.on) return fail(c, HENS_ERR_STATE, "no chain (hens_rj_chain_create)");
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    HIPCHK(c, hipMemsetAsync(ch.acc_tot, 0, (size_t)ch.Ts * c->W * 4, c->stream));
+    HIPCHK(c, hipMemsetAsync(ch.bd_tot, 0, (size_t)ch.Ts * c->W * 4, c->stream));
+    HIPCHK(c, hipMemsetAsync(ch.swaps_tot, 0, (size_t)std::max(c->T - 1, 1) * 8, c->stream));
+    ch.count = 0;
+    ch.iteration.clear(); ch.adapt_time.clear();
+    return HENS_OK;
+}
+
+int hens_rj_chain_destroy(hens_ctx* ctx) {
+    hens_ctx_impl* c = enter(ctx);
+    if (!c) return fail(c, HENS_ERR_INVALID, "null context");
+    if (!c->rjchain.on) return HENS_OK;
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    rjchain_free(c);
+    return HENS_OK;
+}
+
+int hens_rj_chain_info(hens_ctx* ctx, hens_chain_info_t* out) {
+    hens_ctx_impl* c = CTX(ctx);
+    if (!c || !out) return fail(c, HENS_ERR_INVALID, "null argument");
+    int r;
+    if ((r = rjchain_supported(c))) return r;
+    const hens_ctx_impl::RjChain& ch = c->rjchain;
+    hens_chain_info_t o{};
+    hens_chain::RjSizes one{};
+    (void)hens_chain::rj_sizes(rjchain_shape(c, ch.on ? ch.Ts : c->T), 1, &one);
+    o.capacity = ch.capacity; o.count = ch.count; o.ntemps_store = ch.on ? ch.Ts : 0; o.bytes = ch.bytes; o.step_bytes = one.step;
+    o.n_store_timed = ch.n_timed; o.store_ms = ch.store_ms;
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    size_t fr = 0, tot = 0;
+    HIPCHK(c, hipMemGetInfo(&fr, &tot));
+    o.free_bytes = (int64_t)fr;
+    *out = o;
+    return HENS_OK;
+}
+
+// one append on the HIP stream: the state by field as it stands between hens_rj_step iterations, the ladder settled by the caller
+static void launch_rj_chain_store(hens_ctx_impl* c, hipEvent_t e0, hipEvent_t e1) {
+    hens_ctx_impl::RjChain& ch = c->rjchain;
+    const RjModel& M = c->rj.M;
+    const size_t TW = (size_t)c->Tl * c->W, TsW = (size_t)ch.Ts * c->W, n = (size_t)ch.count;
+    RjChainArgs a{};
+    a.pool = c->pool; a.loc = c->loc[c->cur]; a.L = c->L[c->cur]; a.P = c->P[c->cur];
+    a.acc = c->accepted; a.acc_bd = c->rj.acc_bd;
+    a.prev = ch.prev; a.prev_bd = ch.prev + TW;
+    a.betas = c->cfg.tempered ? c->betas[c->bcur] : nullptr;
+    // the in-model cascade's counts: set aside behind it under a birth / death schedule, else swaps_last is still that cascade's
+    a.swaps = !has_pt(c) ? nullptr : (c->rj.schedule == 3 ? c->swaps_last : ch.swaps_step);
+    for (int b = 0; b < M.nb; ++b) {
+        a.off[b] = M.off[b]; a.nl[b] = M.nl[b]; a.nd[b] = M.nd[b];
+        a.out_x[b] = ch.x[b] + n * TsW * (size_t)(M.nl[b] * M.nd[b]);
+        a.out_inds[b] = ch.inds[b] + n * TsW * (size_t)M.nl[b];
+    }
+    a.out_L = ch.L + n * TsW; a.out_P = ch.P + n * TsW;
+    a.out_betas = ch.betas + n * c->T;
+    a.acc_tot = ch.acc_tot; a.bd_tot = ch.bd_tot; a.swaps_tot = ch.swaps_tot;
+    a.nb = M.nb; a.ind_off = M.ind_off; a.T = c->T; a.W = c->W; a.Ts = ch.Ts; a.RW = c->D;
+    const hens_chain::RjShape shape = rjchain_shape(c, ch.Ts);
+    const int vec = hens_chain::rj_store_vec(shape, c->D);
+    a.lpr_shift = hens_chain::rj_lane_shift(shape, vec);
+    const int64_t threads = (int64_t)TsW << a.lpr_shift;
+    const dim3 grid((unsigned)((threads + 255) / 256));
+    void* args[] = {&a};
+    const void* fn = vec == 2 ? reinterpret_cast<const void*>(k_rj_chain_store<2>) : reinterpret_cast<const void*>(k_rj_chain_store<1>);
+    if (e0) (void)hipExtLaunchKernel(fn, grid, dim3(256), args, 0, c->stream, e0, e1, 0);
+    else (void)hipLaunchKernel(fn, grid, dim3(256), args, 0, c->stream);
+}
+
+int hens_rj_step_chain(hens_ctx* ctx, int64_t n_store, int64_t iters_per_store) {
+    hens_ctx_impl* c = enter(ctx);
+    if (!c) return fail(c, HENS_ERR_INVALID, "null context");
+    int r;
+    if ((r = rjchain_supported(c))) return r;
+    hens_ctx_impl::RjChain& ch = c->rjchain;
+    if (!ch.on) return fail(c, HENS_ERR_STATE, "no chain (hens_rj_chain_create)");
+    if ((r = rj_ready(c))) return r;
+    int64_t iters = 0;
+    switch (hens_chain::rj_append_check(ch.capacity, ch.count, n_store, iters_per_store, &iters)) {
+    case hens_chain::INVALID: return fail(c, HENS_ERR_INVALID, "hens_rj_step_chain: n_store >= 0 and iters_per_store >= 1, and their product an int64");
+    case hens_chain::FULL: return fail(c, HENS_ERR_STATE, "hens_rj_step_chain: %lld more stored steps do not fit a chain of capacity %lld that holds %lld (download and hens_rj_chain_reset)",
+                                       (long long)n_store, (long long)ch.capacity, (long long)ch.count);
+    default: break;
+    }
+    if ((r = counter_room(c, iters))) return r;
+    RjStepping st(c);
+    if ((r = st.begin(iters))) return r;
+    const bool timed = c->per_kernel_events == 1;
+    const size_t TW = (size_t)c->Tl * c->W;
+    std::vector<hipEvent_t> evs;
+    ch.n_timed = 0; ch.store_ms = 0.0;
+    for (int64_t s = 0; s < n_store; ++s) {
+        for (int64_t i = 0; i + 1 < iters_per_store; ++i)
+            if ((r = st.iteration(nullptr))) return r;
+        // the mark: the two accept counters in front of the step's last iteration (the append moves it up: back-to-back stored steps
+        // of one iteration each need no copy)
+        if (!(ch.mark_valid && ch.mark_books == c->rj.num_mh + c->rj.num_bd)) {
+            HIPCHK(c, hipMemcpyAsync(ch.prev, c->accepted, TW * 4, hipMemcpyDeviceToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync(ch.prev + TW, c->rj.acc_bd, TW * 4, hipMemcpyDeviceToDevice, c->stream));
+        }
+        ch.mark_valid = false;
+        if ((r = st.iteration(ch.swaps_step))) return r;
+        flush_adapt(c);                           // (the ladder AFTER the step's adaptation - what hens_download_state returns)
+        // what hens_download_state runs in front of its copy: the stored log_like is the value the device goes on with
+        if (c->rj.tm && c->rj.tm_valid && c->rj.tm_drift && (r = rj_evaluate(c))) return r;
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        if (timed && evs.size() < 2 * 4096) {
+            HIPCHK(c, hipEventCreate(&e0)); evs.push_back(e0);
+            HIPCHK(c, hipEventCreate(&e1)); evs.push_back(e1);
+        }
+        launch_rj_chain_store(c, e0, e1);
+        HIPCHK(c, hipGetLastError());
+        ch.iteration.push_back((int64_t)c->iter);
+        ch.adapt_time.push_back(c->adapt_time);
+        ch.count += 1;
+        ch.mark_valid = true;
+        ch.mark_books = c->rj.num_mh + c->rj.num_bd;
+    }
+    c->rj.defer_adapt = false;
+    flush_adapt(c);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->ev1, c->stream));
+    c->timing.n_iters = iters;
+    r = check_flags(c, true);                     // (once per call, with the call's last launch: the host waits for nothing in between)
+    if (!evs.empty()) {
+        for (size_t k = 0; k + 1 < evs.size(); k += 2) {
+            float ms = 0;
+            if (hipEventElapsedTime(&ms, evs[k], evs[k + 1]) == hipSuccess) { ch.store_ms += ms; ch.n_timed += 1; }
+        }
+        for (hipEvent_t e : evs) (void)hipEventDestroy(e);
+    }
+    return r;
+}
+
+int hens_rj_chain_download(hens_ctx* ctx, int64_t first, int64_t count, int32_t branch, double* x, uint8_t* inds, double* logl,
+                           double* logp, double* betas, int64_t* iteration, int64_t* adapt_time) {
+    hens_ctx_impl* c = enter(ctx);
+    if (!c) return fail(c, HENS_ERR_INVALID, "null context");
+    hens_ctx_impl::RjChain& ch = c->rjchain;
+    if (!ch.on) return fail(c, HENS_ERR_STATE, "no chain (hens_rj_chain_create)");
+    if (!hens_chain::range_ok(ch.count, first, count))
+        return fail(c, HENS_ERR_INVALID, "hens_rj_chain_download: steps [%lld, %lld + %lld) outside the %lld stored", (long long)first, (long long)first, (long long)count, (long long)ch.count);
+    if (!hens_chain::rj_branch_ok(c->rj.M.nb, branch) || (branch < 0 && (x || inds)))
+        return fail(c, HENS_ERR_INVALID, "hens_rj_chain_download: branch %d of %d (-1: the shared fields, x = inds = NULL)", branch, c->rj.M.nb);
+    if (count == 0) return HENS_OK;
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    const size_t TsW = (size_t)ch.Ts * c->W, f = (size_t)first, n = (size_t)count;
+    if (branch >= 0) {
+        const size_t nl = (size_t)c->rj.M.nl[branch], seg = nl * (size_t)c->rj.M.nd[branch];
+        if (x) HIPCHK(c, hipMemcpyAsync(x, ch.x[branch] + f * TsW * seg, n * TsW * seg * 8, hipMemcpyDeviceToHost, c->stream));
+        if (inds) HIPCHK(c, hipMemcpyAsync(inds, ch.inds[branch] + f * TsW * nl, n * TsW * nl, hipMemcpyDeviceToHost, c->stream));
+    }
+    if (logl) HIPCHK(c, hipMemcpyAsync(logl, ch.L + f * TsW, n * TsW * 8, hipMemcpyDeviceToHost, c->stream));
+    if (logp) HIPCHK(c, hipMemcpyAsync(logp, ch.P + f * TsW, n * TsW * 8, hipMemcpyDeviceToHost, c->stream));
+    if (betas) HIPCHK(c, hipMemcpyAsync(betas, ch.betas + f * c->T, n * c->T * 8, hipMemcpyDeviceToHost, c->stream));
+    if (x || inds || logl || logp || betas) HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (iteration) std::copy(ch.iteration.begin() + first, ch.iteration.begin() + first + count, iteration);
+    if (adapt_time) std::copy(ch.adapt_time.begin() + first, ch.adapt_time.begin() + first + count, adapt_time);
+    return HENS_OK;
+}
+
+int hens_rj_chain_totals(hens_ctx* ctx, double* accepted, double* rj_accepted, double* swaps_accepted) {
+    hens_ctx_impl* c = enter(ctx);
+    if (!c) return fail(c, HENS_ERR_INVALID, "null context");
+    hens_ctx_impl::RjChain& ch = c->rjchain;
+    if (!ch.on) return fail(c, HENS_ERR_STATE, "no chain (hens_rj_chain_create)");
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    const size_t TsW = (size_t)ch.Ts * c->W, np = (size_t)std::max(c->T - 1, 0);
+    std::vector<uint32_t> acc(accepted ? TsW : 0), bd(rj_accepted ? TsW : 0);
+    std::vector<unsigned long long> sw(swaps_accepted ? np : 0);
+    if (!acc.empty()) HIPCHK(c, hipMemcpyAsync(acc.data(), ch.acc_tot, TsW * 4, hipMemcpyDeviceToHost, c->stream));
+    if (!bd.empty()) HIPCHK(c, hipMemcpyAsync(bd.data(), ch.bd_tot, TsW * 4, hipMemcpyDeviceToHost, c->stream));
+    if (!sw.empty()) HIPCHK(c, hipMemcpyAsync(sw.data(), ch.swaps_tot, np * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (size_t i = 0; i < acc.size(); ++i) accepted[i] = (double)acc[i];
+    for (size_t i = 0; i < bd.size(); ++i) rj_accepted[i] = (double)bd[i];
+    for (size_t i = 0; i < sw.size(); ++i) swaps_accepted[i] = (double)sw[i];
+    return HENS_OK;
 }
 
 // ---- leaf-packing moves with a HOST-CALLABLE likelihood (round 6; ensemble.py:1306-1334,1340-1545, rj.py:145-388) ---------------

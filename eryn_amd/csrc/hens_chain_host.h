@@ -1,5 +1,5 @@
-// hens_chain_host.h - the capacity / range arithmetic of the chain store (hens_chain_create, hens_step_chain, hens_chain_download) as
-// plain host functions without HIP types: hens.hip calls them, and tests/chain_host_check.cpp runs them alone under
+// hens_chain_host.h - the capacity / range arithmetic of the chain stores (hens_chain_create, hens_step_chain, hens_chain_download and
+// their hens_rj_chain_* twins) as plain host functions without HIP types: hens.hip calls them, and tools/chain_host_check.cpp runs them alone under
 // -fsanitize=address,undefined (sizes come straight from the caller: every product is overflow-checked before anything is
 // allocated, launched or copied).
 #pragma once
@@ -46,6 +46,70 @@ inline int append_check(int64_t capacity, int64_t count, int64_t n_store, int64_
 // a download range [first, first + n) inside [0, count)   (n = 0: allowed anywhere in [0, count])
 inline bool range_ok(int64_t count, int64_t first, int64_t n) {
     return first >= 0 && n >= 0 && first <= count && n <= count - first;
+}
+
+// ---- leaf-packing contexts (hens_rj_chain_*, hens_rj_step_chain) ----------------------------------------------------------------
+// what one chain of a leaf-packing context holds per stored step: per branch b x_b[Ts][W][nl_b][nd_b] doubles and inds_b[Ts][W][nl_b]
+// bytes, logl / logp [Ts][W] each, betas[T]:  step = 8 (Ts W (ncoord + 2) + T) + Ts W nslots bytes
+constexpr int RJ_BRANCHES = 4;
+struct RjShape {
+    int64_t T, Ts, W, nb;
+    int64_t nl[RJ_BRANCHES], nd[RJ_BRANCHES];
+};
+struct RjSizes {        // bytes of the device arrays of a chain of `capacity` steps, and of one step
+    int64_t x[RJ_BRANCHES], inds[RJ_BRANCHES], lp, betas, step, total;
+    int64_t ncoord, nslots;
+};
+
+// false: not a shape (a dimension < 1, more stored rungs than rungs, more branches than a record has) or a size beyond int64
+inline bool rj_sizes(const RjShape& s, int64_t capacity, RjSizes* out) {
+    if (s.T < 1 || s.W < 1 || s.Ts < 1 || s.Ts > s.T || s.nb < 1 || s.nb > RJ_BRANCHES || capacity < 0) return false;
+    int64_t tw, lp1, b1, step;
+    if (!mul(s.T, 8, &b1) || !mul(s.Ts, s.W, &tw) || !mul(tw, 8, &lp1)) return false;
+    if (!add(lp1, lp1, &step) || !add(step, b1, &step)) return false;
+    RjSizes z{};
+    for (int b = 0; b < s.nb; ++b) {
+        if (s.nl[b] < 1 || s.nd[b] < 1) return false;
+        int64_t seg, row, x1, i1;
+        if (!mul(s.nl[b], s.nd[b], &seg) || !mul(tw, seg, &row) || !mul(row, 8, &x1) || !mul(tw, s.nl[b], &i1)) return false;
+        if (!add(step, x1, &step) || !add(step, i1, &step)) return false;
+        if (!add(z.ncoord, seg, &z.ncoord) || !add(z.nslots, s.nl[b], &z.nslots)) return false;
+        if (!mul(x1, capacity, &z.x[b]) || !mul(i1, capacity, &z.inds[b])) return false;
+    }
+    z.step = step;
+    if (!mul(lp1, capacity, &z.lp) || !mul(b1, capacity, &z.betas) || !mul(step, capacity, &z.total)) return false;
+    *out = z;
+    return true;
+}
+
+// hens_rj_step_chain's arguments against the chain (a stored step's accept totals take its last iteration: n_last = 1)
+inline int rj_append_check(int64_t capacity, int64_t count, int64_t n_store, int64_t iters_per_store, int64_t* iters) {
+    return append_check(capacity, count, n_store, iters_per_store, 1, iters);
+}
+
+// hens_rj_chain_download's branch: one of the model's, or -1 (the shared fields only)
+inline bool rj_branch_ok(int64_t nb, int64_t branch) { return branch >= -1 && branch < nb; }
+
+// doubles per lane of the append launch: 2 (16-byte loads and stores) where every branch's segment starts and ends on an even
+// double on both sides - the record's rows are RW doubles apart, the destination's rows nl nd -, else 1
+inline int rj_store_vec(const RjShape& s, int64_t RW) {
+    int64_t off = 0;
+    if (RW % 2) return 1;
+    for (int b = 0; b < s.nb; ++b) {
+        const int64_t seg = s.nl[b] * s.nd[b];
+        if (off % 2 || seg % 2) return 1;
+        off += seg;
+    }
+    return 2;
+}
+
+// lanes per record as a shift: the smallest power of two that covers the widest segment, at most a wave
+inline int rj_lane_shift(const RjShape& s, int vec) {
+    int64_t widest = 1;
+    for (int b = 0; b < s.nb; ++b) widest = s.nl[b] * s.nd[b] > widest ? s.nl[b] * s.nd[b] : widest;
+    int sh = 0;
+    while (((int64_t)1 << sh) * vec < widest && sh < 6) ++sh;
+    return sh;
 }
 
 }  // namespace hens_chain

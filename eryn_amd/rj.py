@@ -375,6 +375,70 @@ class RJEngine:
     def step(self, n_iters):
         check(self.lib.hens_rj_step(self.ctx, int(n_iters)), self.ctx)
 
+    # -- chain store (include/hipensemble.h: hens_rj_chain_*, hens_rj_step_chain) ---------------------------------
+    def chain_create(self, capacity, ntemps_store=None):
+        """Room for ``capacity`` stored steps of rungs ``[0, ntemps_store)`` (None: all) in device memory; replaces a chain
+        that exists."""
+        check(self.lib.hens_rj_chain_create(self.ctx, int(capacity), int(ntemps_store or 0)), self.ctx)
+
+    def chain_reset(self):
+        check(self.lib.hens_rj_chain_reset(self.ctx), self.ctx)
+
+    def chain_destroy(self):
+        check(self.lib.hens_rj_chain_destroy(self.ctx), self.ctx)
+
+    def chain_info(self):
+        info = _lib.HensChainInfo()
+        check(self.lib.hens_rj_chain_info(self.ctx, C.byref(info)), self.ctx)
+        return {k: getattr(info, k) for k, _ in _lib.HensChainInfo._fields_}
+
+    def step_chain(self, n_store, iters_per_store=1):
+        """``n_store`` stored steps of ``iters_per_store`` iterations each, appended to the chain on the device - per stored step
+        what ``step(iters_per_store)`` + ``download(nan_fill=True)`` gives, bit for bit.  Nothing is copied to the host."""
+        self.eng.state_epoch += 1
+        check(self.lib.hens_rj_step_chain(self.ctx, int(n_store), int(iters_per_store)), self.ctx)
+
+    CHAIN_FIELDS = ("x", "inds", "log_like", "log_prior", "betas")
+
+    def chain_download(self, first=0, count=None, fields=CHAIN_FIELDS):
+        """Stored steps ``[first, first + count)`` (count None: to the end) as a dict: ``x`` / ``inds`` ``{name: [count,
+        ntemps_store, W, nl, nd] / bool [count, ntemps_store, W, nl]}`` (NaN on unused leaves), ``log_like`` / ``log_prior``
+        ``[count, ntemps_store, W]``, ``betas[count, T]`` - those named in ``fields`` - and ``iteration`` / ``adapt_time``
+        ``[count]``, the Philox checkpoint of every stored step.  One plain copy per array: nothing is reshaped on the host."""
+        info = self.chain_info()
+        first = int(first)
+        count = info["count"] - first if count is None else int(count)
+        Ts, n = info["ntemps_store"], max(count, 0)
+        out = dict(iteration=np.zeros(n, dtype=np.int64), adapt_time=np.zeros(n, dtype=np.int64))
+        shapes = dict(log_like=(n, Ts, self.W), log_prior=(n, Ts, self.W), betas=(n, self.T))
+        for f in fields:
+            if f in shapes:
+                out[f] = np.empty(shapes[f])
+        shared = [ptr(out.get("log_like")), ptr(out.get("log_prior")), ptr(out.get("betas")), ptr(out["iteration"]), ptr(out["adapt_time"])]
+        if "x" not in fields and "inds" not in fields:
+            check(self.lib.hens_rj_chain_download(self.ctx, first, count, -1, None, None, *shared), self.ctx)
+            return out
+        x, inds = {}, {}
+        for bi, b in enumerate(self.branches):
+            xb = np.empty((n, Ts, self.W, b.nleaves_max, b.ndim)) if "x" in fields else None
+            ib = np.empty((n, Ts, self.W, b.nleaves_max), dtype=np.bool_) if "inds" in fields else None      # (bytes 0 / 1)
+            check(self.lib.hens_rj_chain_download(self.ctx, first, count, bi, ptr(xb), ptr(ib), *(shared if bi == 0 else [None] * 5)), self.ctx)
+            x[b.name], inds[b.name] = xb, ib
+        if "x" in fields:
+            out["x"] = x
+        if "inds" in fields:
+            out["inds"] = inds
+        return out
+
+    def chain_totals(self):
+        """(accepted[ntemps_store, W], rj_accepted[ntemps_store, W], swaps_accepted[T - 1]) summed over the steps stored since
+        the last reset: in-model accepts, birth / death accepts and in-model swaps of every stored step's last iteration."""
+        Ts = self.chain_info()["ntemps_store"]
+        acc, bd = np.zeros((Ts, self.W)), np.zeros((Ts, self.W))
+        swaps = np.zeros(max(self.T - 1, 0))
+        check(self.lib.hens_rj_chain_totals(self.ctx, ptr(acc), ptr(bd), ptr(swaps) if self.T > 1 else None), self.ctx)
+        return acc, bd, swaps
+
     def set_schedule(self, rj_moves):
         """The sampler's ``rj_moves`` string for ``step`` (ensemble.py:434-480): "separate_branches" | "iterate_branches" |
         "together", or "none": no reversible-jump move (``EnsembleSampler`` without ``rj_moves``)."""
@@ -501,8 +565,20 @@ class RJEnsembleSampler:
 
     def __init__(self, nwalkers, ndims, log_like_fn, priors, tempering_kwargs=None, nbranches=None, branch_names=None,
                  nleaves_max=None, nleaves_min=None, moves=None, rj_moves="separate_branches", rng="numpy", seed=None,
-                 device_id=0, args=None, kwargs=None, vectorize=False, provide_groups=False, fill_zero_leaves_val=-1e300, **unused):
+                 device_id=0, args=None, kwargs=None, vectorize=False, provide_groups=False, fill_zero_leaves_val=-1e300,
+                 backend=None, **unused):
+        from .backend import RJDeviceBackend
         from .moves.tempering import TemperatureControl
+        # backend: None - the stored steps are a list of States (``self.chain``) - or an eryn_amd.backend.RJDeviceBackend: they stay
+        # in device memory until somebody reads them (one device call per chain segment, hens_rj_step_chain)
+        if backend is not None and not isinstance(backend, RJDeviceBackend):
+            raise NotImplementedError("backend: None (a list of States) or an eryn_amd.backend.RJDeviceBackend")
+        if backend is not None and rng != "philox":
+            raise NotImplementedError("RJDeviceBackend keeps the chain of the device-side draws: it needs rng='philox' (with rng='numpy' "
+                                      "every move crosses the host)")
+        if backend is not None and not isinstance(log_like_fn, TemplateLikelihood):
+            raise NotImplementedError("RJDeviceBackend needs the likelihood on the device (a TemplateLikelihood): a Python function "
+                                      "steps through the caller")
         # log_like_fn: a TemplateLikelihood (the model lives in the kernel) or - round 6 - any Python function of the packed active
         # leaves with the reference's own ``args`` / ``kwargs`` / ``vectorize`` / ``provide_groups`` (ensemble.py:211-330): the
         # device proposes, computes the prior, tests and updates, the host evaluates (CallableLikelihood)
@@ -585,6 +661,11 @@ class RJEnsembleSampler:
         self._random.set_state(np.random.get_state())          # R := snapshot of the global stream (ensemble.py:604,651-652)
         self.iteration, self.chain = 0, []
         self._previous_state = None
+        self.backend = backend
+        if backend is not None:
+            backend.attach(self.engine, seed)
+            if not backend.initialized:
+                backend.reset(self.nwalkers, self.ndims, ntemps=self.ntemps, branch_names=self.branch_names, nleaves_max=self.nleaves_max)
 
     # -- the reference's evaluation entry points, with inds (ensemble.py:1127-1217, 1219-1545) -----------------------
     def _eval(self, coords, inds):
@@ -722,7 +803,9 @@ class RJEnsembleSampler:
 
     def run_mcmc(self, initial_state, nsteps, burn=None, thin_by=1, store=True, **unused):
         """ensemble.py:1047-1125; returns the last State.  Stored steps keep the reference's NaN fill of unused leaves
-        (backends/backend.py:1049-1059) in ``self.chain`` (a list of States)."""
+        (backends/backend.py:1049-1059) in ``self.chain`` (a list of States) - or, with ``backend=RJDeviceBackend()``, in device
+        memory: ``burn`` iterations, then one device call per chain segment; ``self.chain`` stays empty and the backend's accessors
+        (``get_chain`` / ``get_inds`` / ``get_nleaves`` / ...) read the same steps bit for bit."""
         from .state import State
         tc = self.temperature_control
         if initial_state is None:
@@ -744,7 +827,14 @@ class RJEnsembleSampler:
             raise ValueError("The initial log_prior was +/- infinite")
         self.engine.upload(coords, inds, st.log_like, st.log_prior, tc.betas)
         self.engine.set_adapt_time(tc.time)
+        on_device = self.backend is not None and store
+        if on_device:
+            self.backend.grow(nsteps, None)           # (the device buffers are made here, never inside the run)
         for phase, n, keep in (("burn", burn or 0, False), ("run", nsteps, store)):
+            if on_device and phase == "run":          # one device call per chain segment; nothing crosses the host per stored step
+                self.backend.append(n, thin_by)
+                self.iteration += n
+                continue
             for _ in range(n):
                 if self.rng == "philox":
                     self.engine.step(thin_by if phase == "run" else 1)
@@ -767,4 +857,6 @@ class RJEnsembleSampler:
         return out
 
     def get_nleaves(self):
+        if self.backend is not None:
+            return self.backend.get_nleaves()
         return {b.name: np.stack([s.branches[b.name].nleaves for s in self.chain]) for b in self.branches}

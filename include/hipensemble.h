@@ -196,8 +196,8 @@ int hens_step_report(hens_ctx* ctx, int64_t n_iters, int64_t n_last, uint8_t* ac
  * ensemble.py:1013-1030): a chain buffer in device memory, one small launch (k_chain_store) that appends the walkers in walker
  * order straight from where they ride - column- or slot-ordered walker records, or the by-field arrays -, the accepted / swap
  * totals the backend keeps accumulated beside it, and ONE copy when somebody reads the chain.  Contexts of one GPU with a device
- * likelihood only: a leaf-packing (HENS_LIKE_TEMPLATE) or host-likelihood context, a ladder shard and a pipeline rank ->
- * HENS_ERR_UNSUPPORTED.  hens_upload_state / hens_set_iteration do not clear the chain (a resumed run appends),
+ * likelihood only: a leaf-packing context (HENS_LIKE_TEMPLATE: it has the hens_rj_chain_* family below) or a host-likelihood
+ * context, a ladder shard and a pipeline rank -> HENS_ERR_UNSUPPORTED.  hens_upload_state / hens_set_iteration do not clear the chain (a resumed run appends),
  * hens_reset_counters leaves its totals alone, hens_destroy frees it.
  *
  * hens_chain_create: room for `capacity` stored steps of rungs [0, ntemps_store) (0 = all): the allocation the reference makes
@@ -237,6 +237,41 @@ int hens_step_chain(hens_ctx* ctx, int64_t n_store, int64_t iters_per_store, int
 int hens_chain_download(hens_ctx* ctx, int64_t first, int64_t count, double* x, double* logl, double* logp, double* betas,
                         int64_t* iteration, int64_t* adapt_time);
 int hens_chain_totals(hens_ctx* ctx, double* accepted, double* swaps_accepted);
+
+/* ---- Chain store of a leaf-packing context (HENS_LIKE_TEMPLATE after hens_rj_set_model*) ---------------------------------------
+ * The same contract for records of several branches and leaves: the stored steps of RJEnsembleSampler.run_mcmc(store=True) stay in
+ * device memory, laid out the way the reference's backend returns them (backends/backend.py:1014-1091) - per branch b
+ * x_b[step][ntemps_store][W][nl_b][nd_b] with quiet NaN on the leaves whose mask bit is clear (:1049-1059; the resident record keeps
+ * a dead leaf's coordinates) and inds_b[step][ntemps_store][W][nl_b] as bytes 0 / 1 -, one append launch per stored step
+ * (k_rj_chain_store) straight from the resident records, one copy per branch when somebody reads.  The family is its own: on such a
+ * context hens_chain_create / hens_step_chain stay HENS_ERR_UNSUPPORTED.
+ *
+ * hens_rj_chain_create / _reset / _destroy / _info: as their hens_chain_* namesakes.  Without a model (hens_rj_set_model*) ->
+ *   HENS_ERR_STATE; a ladder shard, or a model without a device likelihood (hens_rj_set_model_general) -> HENS_ERR_UNSUPPORTED.
+ *   step_bytes = 8 (Ts W (ncoord + 2) + T) + Ts W nslots.  Setting a model anew frees the chain.
+ * hens_rj_step_chain: n_store times { iters_per_store - 1 iterations of hens_rj_step's loop; the in-model and birth / death accept
+ *   counters marked; one more iteration; the ladder adaptation settled; the full evaluation hens_download_state runs in front of its
+ *   copy, under the same rule (resident templates that have drifted); the state appended }: the chain is bit for bit what
+ *   { hens_rj_step(iters_per_store); hens_download_state } per stored step gives, and so is the state behind it.  The host waits for
+ *   nothing between stored steps; the flags (NaN likelihood, non-finite coordinate) are read once, at the end of the call.
+ *   Appending past the capacity -> HENS_ERR_STATE before anything is launched; iters_per_store < 1 -> HENS_ERR_INVALID.
+ *   Swap totals: the counts of the last iteration's IN-MODEL cascade (the reference's in_model_swaps, ensemble.py:976-979, 1026),
+ *   set aside on the device before the birth / death move's cascade overwrites them.
+ * hens_rj_chain_download: stored steps [first, first + count) of ONE branch - x[count][ntemps_store][W][nl_b][nd_b],
+ *   inds[count][ntemps_store][W][nl_b] (uint8) - and the shared fields logl / logp [count][ntemps_store][W], betas[count][T],
+ *   iteration / adapt_time [count].  branch = -1: the shared fields only (x = inds = NULL).  Any pointer may be NULL; a range
+ *   outside [0, count) or a branch the model has not -> HENS_ERR_INVALID.
+ * hens_rj_chain_totals: accepted[ntemps_store][W] (in-model move), rj_accepted[ntemps_store][W] (birth / death move: each stored
+ *   step's last iteration), swaps_accepted[T-1], summed over the steps stored since the last reset.
+ * hens_upload_state / hens_set_iteration / hens_reset_counters leave the chain and its totals alone; hens_destroy frees it. */
+int hens_rj_chain_create(hens_ctx* ctx, int64_t capacity, int32_t ntemps_store);
+int hens_rj_chain_reset(hens_ctx* ctx);
+int hens_rj_chain_destroy(hens_ctx* ctx);
+int hens_rj_chain_info(hens_ctx* ctx, hens_chain_info_t* out);
+int hens_rj_step_chain(hens_ctx* ctx, int64_t n_store, int64_t iters_per_store);
+int hens_rj_chain_download(hens_ctx* ctx, int64_t first, int64_t count, int32_t branch, double* x, uint8_t* inds, double* logl,
+                           double* logp, double* betas, int64_t* iteration, int64_t* adapt_time);
+int hens_rj_chain_totals(hens_ctx* ctx, double* accepted, double* rj_accepted, double* swaps_accepted);
 
 /* Counters.  Replaces Move.accepted / num_proposals (move.py:404-421, red_blue.py:326-327),
  * TemperatureControl.swaps_accepted / time (tempering.py:542,596).  Any pointer may be NULL.
