@@ -467,14 +467,16 @@ def _replay_oracle_class():
 
 def _replay_rj(T, W, nl_max, nl_min, ndata, iters, seed, start_leaves=(2, 1), calls=None, schedule="separate_branches",
                set_iter=None, downloads=True, pulse_amp=(2.5, 3.5), inj_amp=None, start_amp=None, resident=None, betas=None,
-               lag=None, nu=None):
+               lag=None, nu=None, start=None, on_record=None):
     """hens_rj_step replayed through the oracle.  ``set_iter``: counter and adaptation time moved on the uploaded state first;
     ``downloads=False``: no download between calls (the resident templates are then refreshed by the counter only) - the state is
     read with hens_rj_debug_resident instead, which does not refresh; ``pulse_amp`` / ``inj_amp``: the pulse amplitude box and the
     injected amplitudes; ``start_amp``: {branch: amplitude per started slot (None: the injected one)} of the starting leaves;
     ``resident``: a dict that receives, per call end, the largest relative distance of the resident
     log-likelihoods from the exact float64 template likelihood of the resident coordinates; ``betas``: the ladder to upload in place
-    of the geometric one; ``lag`` / ``nu``: the adaptation's constants for the context and the oracle alike.  The oracle returned
+    of the geometric one; ``lag`` / ``nu``: the adaptation's constants for the context and the oracle alike; ``start``:
+    dict(t, y, sigma, x, inds, betas) - data, state ({"gauss": ..., "sine": ...}) and ladder made elsewhere (tests/limit_records.py) in
+    place of the harness's own; ``on_record``: called with every iteration's trace record of the oracle.  The oracle returned
     carries the ladder uploaded and the one downloaded last (``betas_uploaded``, ``betas_device``), the accepted proposals per rung
     (``accepted_rung``) and the accepted swaps per pair over its ``cascades`` cascades (``swaps_sum``)."""
     from oracle import eryn_oracle_rj as orj
@@ -495,6 +497,8 @@ def _replay_rj(T, W, nl_max, nl_min, ndata, iters, seed, start_leaves=(2, 1), ca
     scale = np.array([[1e-2, 1e-2, 1e-3], [1e-2, 1e-2, 1e-2]])
     names = ["gauss", "sine"]
     brs = [TemplateBranch(k, kinds[k], boxes[k], nl_max[i], nl_min[i]) for i, k in enumerate(names)]
+    if start is not None:
+        t, y, sigma = start["t"], start["y"], start["sigma"]
     eng = RJEngine(T, W, brs, t, y, sigma, seed=seed, **adapt)
     x = {k: np.zeros((T, W, nl_max[i], 3)) for i, k in enumerate(names)}
     inds = {k: np.zeros((T, W, nl_max[i]), dtype=bool) for i, k in enumerate(names)}
@@ -506,6 +510,9 @@ def _replay_rj(T, W, nl_max, nl_min, ndata, iters, seed, start_leaves=(2, 1), ca
             if start_amp and k in start_amp and start_amp[k][n] is not None:
                 x[k][:, :, n, 0] += start_amp[k][n] - inj[k][n % len(inj[k])][0]
     betas0 = make_ladder(3 * sum(start_leaves), ntemps=T) if betas is None else np.array(betas, dtype=np.float64)
+    if start is not None:
+        x, inds, betas0 = start["x"], start["inds"], np.array(start["betas"], dtype=np.float64)
+        assert all(x[k].shape == (T, W, nl_max[i], 3) for i, k in enumerate(names))
     eng.upload(x, inds, betas=betas0)
     eng.eval_state()
     eng.set_mh_scale(scale)
@@ -516,7 +523,7 @@ def _replay_rj(T, W, nl_max, nl_min, ndata, iters, seed, start_leaves=(2, 1), ca
     x0, inds0, L0, P0, _ = eng.download()
     okind = {"pulse": orj.KIND_PULSE, "sine": orj.KIND_SINE}
     obr = [orj.Branch(k, okind[kinds[k]], boxes[k], nl_max[i], nl_min[i], cov=np.diag(scale[i] ** 2)) for i, k in enumerate(names)]
-    o = _replay_oracle_class()(obr, x0, inds0, t, y, sigma, None, None, betas0, schedule=schedule, **adapt)
+    o = _replay_oracle_class()(obr, x0, inds0, t, y, sigma, None, None, betas0, schedule=schedule, record=on_record is not None, **adapt)
     o.betas_uploaded = betas0.copy()
     if set_iter is not None:
         o.time = set_iter
@@ -531,6 +538,8 @@ def _replay_rj(T, W, nl_max, nl_min, ndata, iters, seed, start_leaves=(2, 1), ca
         for it in range(it0, it0 + n):
             o.load(eng.debug_draws(it), offsets)
             acc, bi, racc = o.iteration()
+            if on_record is not None:
+                on_record(o.trace.pop())
             mh_acc += acc
             bd_acc += racc                                           # ("iterate_branches": the last branch's mask, like the device)
             if schedule != "separate_branches":
@@ -603,8 +612,28 @@ def test_rj_production_step_uniform_grid_and_wide_records(T, W, nl_max, nl_min, 
     points, pulses by recurrence, sines by rotation; pulses narrower than the grid step - c < 2 / (ndata - 1) is inside the prior -
     take the exp per point) under every schedule, birth / death by difference with several branches changing at once
     ("together"), and records of more than 64 coordinates (2 x 12 leaves x 3 = 72: the second pass of the per-coordinate
-    phases) - replayed through the oracle like the small shapes above."""
-    _replay_rj(T, W, nl_max, nl_min, ndata=ndata, iters=iters, seed=19, start_leaves=(2, 2), calls=(3, iters - 3), schedule=schedule)
+    phases) - replayed through the oracle like the small shapes above.  The wide records start with sine slots 0 - 8 in use, so that
+    every sine birth goes to slot 9 (coordinates 63 - 65), 10 or 11: a sine slot wholly at or past coordinate 64 must see an accepted
+    birth and an accepted in-model move (counted from the oracle's records)."""
+    wide = 3 * sum(nl_max) > 64
+    past = [s for s in range(nl_max[1]) if 3 * nl_max[0] + 3 * s >= 64]
+    seen = dict(birth=0, inmodel=0)
+
+    def count(rec):
+        seen["inmodel"] += int((rec["pre_inds_sine"][:, :, past] & rec["mh_accepted"][:, :, None]).sum())
+        for sub in rec.get("rj_sub", [rec]):
+            if "rj_branches" in sub:
+                ch, lf = sub["rj_change_all"][1], sub["rj_leaf_all"][1]
+            elif sub["rj_branch"] == 1:
+                ch, lf = sub["rj_change"], sub["rj_leaf"]
+            else:
+                continue
+            seen["birth"] += int(((ch == +1) & np.isin(lf, past) & sub["rj_accepted"]).sum())
+    _replay_rj(T, W, nl_max, nl_min, ndata=ndata, iters=iters, seed=19, start_leaves=(2, 9) if wide else (2, 2), calls=(3, iters - 3),
+               schedule=schedule, on_record=count if wide else None)
+    if wide:
+        print(f"sine slots {past} at or past coordinate 64: accepted births {seen['birth']}, accepted in-model moves {seen['inmodel']}")
+        assert past and seen["birth"] > 0 and seen["inmodel"] > 0
 
 
 def test_rj_production_step_replayed_through_the_oracle_config4():

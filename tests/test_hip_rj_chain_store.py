@@ -33,7 +33,9 @@ CASES = {
     "one_branch_thin3": case(("pulse",), (5,), (1,), thin=3, burn=1, nsteps=5),
     # widths 1, 2, 3, 4 (the WIDE instantiations): segments 3 | 4 | 6 | 8 from offsets 0, 3, 7, 13 - every alignment; W = 33
     "four_widths_W33_together_Ts2": case(("offset", "ramp", "pulse", "burst"), (3, 2, 2, 2), W=33, rj="together", Ts=2),
-    # 64 leaf slots: mask bits up to 2^31, RW 98, every segment even: the 16-byte lanes
+    # 64 leaf slots: mask bits up to 2^31, RW 98, every segment even: the 16-byte lanes.  (This and the next case compare the device
+    # chain with the host path of the same kernels: the append at these shapes.  k_rj itself is held to the oracle at them in
+    # tests/test_hip_limit_records.py.)
     "slots64_iterate": case(("offset", "ramp"), (32, 32), rj="iterate_branches", nsteps=5),
     "pulses_RW126": case(("pulse", "pulse"), (21, 20), nsteps=4),
     "no_rj_Ts1_thin3": case(("pulse", "sine"), (3, 4), rj=None, thin=3, burn=2, Ts=1),

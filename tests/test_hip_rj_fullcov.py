@@ -14,9 +14,9 @@ UNIT_L = np.array([[[1.0, 0.0, 0.0], [0.5, 0.8, 0.0], [-0.3, 0.4, 0.7]],
 CHOL = SCALE[:, :, None] * UNIT_L                                  # lower triangular, positive diagonal
 
 
-def _engine(T, W, nl_max, nl_min, ndata, seed, start_leaves, schedule="separate_branches"):
+def _engine(T, W, nl_max, nl_min, ndata, seed, start_leaves, schedule="separate_branches", start=None):
     from eryn_amd.rj import RJEngine
-    brs, t, y, sigma, x, inds, betas0 = _model(T, W, nl_max, nl_min, ndata, seed, start_leaves)
+    brs, t, y, sigma, x, inds, betas0 = _model(T, W, nl_max, nl_min, ndata, seed, start_leaves, start=start)
     eng = RJEngine(T, W, brs, t, y, sigma, seed=seed)
     eng.upload(x, inds, betas=betas0)
     eng.eval_state()
@@ -75,10 +75,11 @@ def test_exported_step_is_L_times_the_unit_normals(T, W, nl_max):
     b.close()
 
 
-def _replay_fullcov(T, W, nl_max, nl_min, ndata, schedule, iters, seed, start_leaves):
+def _replay_fullcov(T, W, nl_max, nl_min, ndata, schedule, iters, seed, start_leaves, start=None, on_record=None):
     """hens_rj_step with hens_rj_set_mh_chol replayed through the oracle (tests/test_hip_rj.py's replay class: _draw_steps reads
-    the exported, correlated step) at the bars of DESIGN section 2."""
-    eng, brs, t, y, sigma, betas0 = _engine(T, W, nl_max, nl_min, ndata, seed, start_leaves, schedule)
+    the exported, correlated step) at the bars of DESIGN section 2.  ``start``: tests/test_hip_rj_stretch.py's _model; ``on_record``:
+    called with every iteration's trace record of the oracle."""
+    eng, brs, t, y, sigma, betas0 = _engine(T, W, nl_max, nl_min, ndata, seed, start_leaves, schedule, start=start)
     eng.set_mh_chol(CHOL)
     x0, inds0, L0, P0, _ = eng.download()
     o = _replay_oracle_class()(_oracle_branches(nl_max, nl_min), x0, inds0, t, y, sigma, None, None, betas0, schedule=schedule,
@@ -96,6 +97,8 @@ def _replay_fullcov(T, W, nl_max, nl_min, ndata, schedule, iters, seed, start_le
             acc, bi, racc = o.iteration()
             rec = o.trace.pop()
             assert not knife(rec["mh_lnpdiff"], rec["mh_u_acc"]).any(), "knife-edge accept test"
+            if on_record is not None:
+                on_record(rec)
             mh_acc += acc
             bd_acc += racc
         done += n

@@ -19,8 +19,9 @@ BOXES = {"gauss": [(2.5, 3.5), (-1.0, 1.0), (0.01, 0.21)], "sine": [(0.5, 1.5), 
 KINDS = {"gauss": "pulse", "sine": "sine"}
 
 
-def _model(T, W, nl_max, nl_min, ndata, seed, start_leaves):
-    """The model and starting state of tests/test_hip_rj.py's _replay_rj."""
+def _model(T, W, nl_max, nl_min, ndata, seed, start_leaves, start=None):
+    """The model and starting state of tests/test_hip_rj.py's _replay_rj; ``start``: dict(t, y, sigma, x, inds, betas) - data, state and
+    ladder made elsewhere (tests/limit_records.py) in their place."""
     from eryn_amd.moves.tempering import make_ladder
     from eryn_amd.rj import TemplateBranch
     rs = np.random.RandomState(seed)
@@ -38,6 +39,9 @@ def _model(T, W, nl_max, nl_min, ndata, seed, start_leaves):
         for n in range(min(start_leaves[i], nl_max[i])):
             x[k][:, :, n] = inj[k][n % len(inj[k])] + 1e-2 * rs.randn(T, W, 3) * [1, 1, 0.1 if k == "gauss" else 1]
             inds[k][:, :, n] = True
+    if start is not None:
+        assert all(start["x"][k].shape == x[k].shape for k in NAMES)
+        return brs, start["t"], start["y"], start["sigma"], start["x"], start["inds"], np.array(start["betas"], dtype=np.float64)
     return brs, t, y, sigma, x, inds, make_ladder(3 * sum(start_leaves), ntemps=T)
 
 
