@@ -1,31 +1,41 @@
-"""Log-likelihood of the library's evaluation launch against numpy (extended precision) on random states: max relative error.
-usage: [HENS_LIB=...] python tools/like_check.py T W D"""
+"""Log-likelihood of the library's evaluation launch, and after 200 production iterations, against exact arithmetic: the worst
+|L_dev - L*| / B over the walkers, L* and the float64 bound B from tests/exact_quadratic.py (the yardstick of
+tests/test_hip_likelihood_accuracy.py, which is the test of record; this is the same check at a shape of your choice).
+usage (from the repository root): [HENS_LIB=...] python tools/like_check.py T W D [family]
+family: equicorr | spectrum | scaled (default) | diag_scaled | rosen_valley"""
+import os
 import sys
+
 import numpy as np
-from eryn_amd.engine import HipEnsemble
-from eryn_amd.likelihood import GaussianLikelihood
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from eryn_amd.engine import HipEnsemble                 # noqa: E402
+from eryn_amd.moves.tempering import make_ladder        # noqa: E402
+from tests import exact_quadratic as xq                 # noqa: E402
+from tests import parity_utils as pu                    # noqa: E402
 
 T, W, D = (int(v) for v in sys.argv[1:4])
-rs = np.random.RandomState(5)
-A = rs.randn(D, D)
-mu = 0.3 * rs.randn(D)
-invcov = np.linalg.inv(A @ A.T / D + np.eye(D))
-if len(sys.argv) > 4:                      # a NON-symmetric precision matrix: the form uses A_ik + A_ki
-    invcov = invcov + 0.01 * rs.randn(D, D)
-eng = HipEnsemble(T, W, D, GaussianLikelihood(mu, invcov), -50.0, 50.0, seed=1)
-x0 = rs.randn(T, W, D) * 2.0
-x0[0, 0, 0] = 60.0                          # one walker outside the prior box
-from eryn_amd.moves.tempering import make_ladder
-eng.upload(x0, betas=make_ladder(D, ntemps=T))
-eng.eval_state()
-x, L, P, betas = eng.download()
-d = (x0 - mu).astype(np.longdouble)
-ref = -0.5 * np.einsum("twi,ij,twj->tw", d, invcov.astype(np.longdouble), d)
-inb = np.isfinite(P)
-rel = np.abs((L[inb] - ref[inb]) / ref[inb]).max()
-print(f"{T}x{W}x{D}: max relative error of log-likelihood {float(rel):.3e}; out-of-box walker L = {L[0, 0]}, P = {P[0, 0]}")
-eng.step(200); eng.synchronize()
-x, L, P, betas = eng.download()
-d = (x - mu).astype(np.longdouble)
-ref = -0.5 * np.einsum("twi,ij,twj->tw", d, invcov.astype(np.longdouble), d)
-print(f"after 200 iterations: max relative error {float(np.abs((L - ref) / ref).max()):.3e}, acceptance {eng.counters()['accepted'].mean() / 200:.3f}")
+family = sys.argv[4] if len(sys.argv) > 4 else "scaled"
+prob = xq.make_problem(family, D)
+
+
+def report(what, x, L):
+    Ls, B, canc = xq.yardstick(prob, x.reshape(-1, D))
+    dev = xq.error_ratio(L.reshape(-1), Ls, B)
+    orac = xq.error_ratio(prob.loglike(x.reshape(-1, D)), Ls, B)
+    print(f"{T}x{W}x{D} {family} {what}: worst |L_dev - L*| / B = {dev.max():.3g} (float64 NumPy: {orac.max():.3g}), "
+          f"median S / |L*| = {np.median(canc):.3g}")
+
+
+eng = HipEnsemble(T, W, D, pu.device_likelihood(prob), prob.lo, prob.hi, seed=1)
+try:
+    eng.upload(prob.x0(T, W), betas=make_ladder(D, ntemps=T) if T > 1 else None)
+    eng.eval_state()
+    x, L, P, _ = eng.download()
+    report("evaluation launch", x, L)
+    eng.step(200)
+    eng.synchronize()
+    x, L, P, _ = eng.download()
+    report(f"after 200 iterations (acceptance {eng.counters()['accepted'].mean() / 200:.3f})", x, L)
+finally:
+    eng.close()
