@@ -110,6 +110,9 @@ SIGNATURES = {
     "hens_step_chain": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64]),
     "hens_chain_download": (C.c_int, [_P, C.c_int64, C.c_int64, _P, _P, _P, _P, _P, _P]),
     "hens_chain_totals": (C.c_int, [_P, _P, _P]),
+    "hens_chain_moments": (C.c_int, [_P, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _P, _P, _P]),
+    "hens_chain_act": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P]),
+    "hens_chain_stats_ms": (C.c_int, [_P, _P, _P]),
     "hens_rj_chain_create": (C.c_int, [_P, C.c_int64, C.c_int32]),
     "hens_rj_chain_reset": (C.c_int, [_P]),
     "hens_rj_chain_destroy": (C.c_int, [_P]),

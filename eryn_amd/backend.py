@@ -1,13 +1,120 @@
-"""Minimal in-memory chain store so ``run_mcmc(store=True)`` is usable.
+"""Chain stores for ``run_mcmc(store=True)``: ``Backend`` in host memory, ``DeviceBackend`` / ``RJDeviceBackend`` in device memory.
 
-The reference's storage engine (eryn/backends, HDF5, resume, ACT/evidence accessors) is out
-of scope for this package (host-side I/O, consumes ``State`` snapshots).  This class
-keeps the accessor names the stretch + PT path's callers use.
+The reference's storage engine (eryn/backends: HDF5, resume) is out of scope for this package (host-side I/O, consumes
+``State`` snapshots).  These classes keep the accessor names the stretch + PT path's callers use, and the chain diagnostics of the
+reference's Backend (backends/backend.py:354-385, 616-817): ``get_autocorr_time``, ``get_autocorr_thin_burn``,
+``get_gelman_rubin_convergence_diagnostic`` and ``get_evidence_estimate`` on ``Backend`` and ``DeviceBackend``, computed by
+``eryn_amd.chain_stats`` on a host chain and by the library's k_chain_moments / k_chain_act where the chain sits in device memory -
+the same bits either way.  Not built: the stepping-stone evidence, diagnostics of ``RJDeviceBackend``.
 """
 import numpy as np
 
+from . import chain_stats
 
-class Backend:
+
+_TI_METHODS = ("therodynamic", "thermodynamic integration", "thermo", "ti")
+_SS_METHODS = ("stepping stone", "ss", "step", "stone", "stepping-stone")
+
+
+class _Diagnostics:
+    """The reference Backend's chain diagnostics (backends/backend.py:354-385, 616-817) over two hooks a chain store provides for
+    the kept steps ``first + j thin``, j < count, of rungs ``[0, ntemps)``:
+
+    ``_stat_act(branch, first, count, thin, ntemps, lags)``     ``tau[ntemps, W, ndim]`` (chain_stats.act with ``lags`` as window)
+    ``_stat_moments(field, first, count, thin, ntemps)``        ``(s, m2, n_finite)`` (chain_stats.moments; ``field`` a branch name,
+                                                                "log_like" or "log_prior", the latter two masked)
+    and ``_stat_rungs()``: how many rungs the chain holds.  Everything after the hooks is host arithmetic on arrays no larger
+    than one stored step, shared by every store: the answer does not depend on where the chain lives."""
+
+    def _kept(self, discard, thin):
+        discard, thin = int(discard), int(thin)
+        if discard < 0 or thin < 1:
+            raise ValueError("discard >= 0 and thin >= 1")
+        count = len(range(discard, self.iteration, thin))
+        if count < 1:
+            raise ValueError(f"no stored step is kept: {self.iteration} stored, discard={discard}")
+        return discard, count, thin
+
+    def get_autocorr_time(self, discard=0, thin=1, all_temps=False, multiply_thin=True, window=50, fast=False, average=True):
+        """Integrated autocorrelation time per parameter: ``{branch: [1 or rungs stored, ndim]}`` (``average=False``:
+        ``[..., nwalkers, ndim]``), in steps (times ``thin``) unless ``multiply_thin=False``.
+
+        A departure from the reference: its accessor raises ValueError for ntemps > 1 before its own ``all_temps`` code can run
+        (backends/backend.py:646-651), and every chain of this package is tempered.  This computes what that code computes: the
+        cold rung, or every stored rung with ``all_temps=True``."""
+        first, count, thin = self._kept(discard, thin)
+        nt = self._stat_rungs() if all_temps else 1
+        lags = chain_stats.lag_count(count, window, fast)
+        out = {}
+        for name in self.branch_names:
+            tau = self._stat_act(name, first, count, thin, nt, lags)
+            if average:
+                tau = np.average(tau, axis=1)
+            out[name] = tau * (thin if multiply_thin else 1)
+        return out
+
+    def get_autocorr_thin_burn(self):
+        """``(discard, thin)``: twice the largest and half the smallest autocorrelation time (backends/backend.py:354-384).  A
+        coordinate that never moved has tau = NaN, and ``int(NaN)`` raises ValueError here as it does in the reference."""
+        tau = self.get_autocorr_time()
+        tau_max, tau_min = 0.0, 1e10
+        for values in tau.values():
+            temp_max, temp_min = np.max(values), np.min(values)
+            tau_max = tau_max if tau_max > temp_max else temp_max
+            tau_min = tau_min if tau_min < temp_min else temp_min
+        return (int(2 * tau_max), int(0.5 * tau_min))
+
+    def get_gelman_rubin_convergence_diagnostic(self, discard=0, thin=1, doprint=True, per_walker=False):
+        """``{branch: {rung: Rhat[ndim]}}`` (utils/utility.py:279-330 ``psrf`` per stored rung), and the reference's table."""
+        first, count, thin = self._kept(discard, thin)
+        nt = self._stat_rungs()
+        r = 0 if per_walker else chain_stats.third_split(self.nwalkers, count)[2]
+        out = {}
+        for name in self.branch_names:
+            s, m2, _ = self._stat_moments(name, first, count, thin, nt)
+            head = tail = None
+            if r:
+                head = self._stat_moments(name, first, r, thin, nt)[:2]
+                tail = self._stat_moments(name, first + (count - r) * thin, r, thin, nt)[:2]
+            out[name] = {t: chain_stats.psrf_from_moments(count, s[t], m2[t], head and (head[0][t], head[1][t]),
+                                                          tail and (tail[0][t], tail[1][t]), per_walker) for t in range(nt)}
+        if doprint:
+            print("  Gelman-Rubin diagnostic \n  <R\u0302>: Mean value for all parameters\n")
+            print("  --------------")
+            for name in self.branch_names:
+                print(" Model: {}".format(name))
+                print("   T \t <R\u0302>")
+                print("  --------------")
+                for t in range(nt):
+                    print("   {:01d}\t{:3.2f}".format(t, np.mean(out[name][t])))
+                print("\n")
+        return out
+
+    def get_evidence_estimate(self, discard=0, thin=1, return_error=True, method="therodynamic"):
+        """Thermodynamic-integration estimate of log Z, ``(logZ, dlogZ)`` or ``logZ`` (backends/backend.py:664-733).  The ladder
+        must have stood still over the kept steps (``stop_adaptation``), and every rung must be stored."""
+        m = method.lower()
+        if m in _SS_METHODS:
+            raise NotImplementedError("stepping-stone evidence is not built: the reference's logls[:, order, :].reshape(-1, ntemps) "
+                                      "(utils/utility.py:255-256) mixes rungs with walkers, so there is nothing well defined to reproduce")
+        if m not in _TI_METHODS:
+            raise ValueError("Please choose only between 'thermodynamic' and 'stepping-stone' methods.")
+        first, count, thin = self._kept(discard, thin)
+        if self._stat_rungs() < self.ntemps:
+            raise ValueError(f"the evidence needs every rung: the chain stores {self._stat_rungs()} of {self.ntemps} (ntemps_store)")
+        betas_all = self._stat_betas(first, count, thin)
+        if not (betas_all == betas_all[0]).all():
+            raise ValueError("Cannot compute evidence estimation if betas are allowed to vary. Use stop_adaptation kwarg in temperature settings.")
+        s, _, nf = self._stat_moments("log_like", first, count, thin, self.ntemps)
+        logZ, dlogZ = chain_stats.thermodynamic_integration_log_evidence(betas_all[0], chain_stats.rung_means(s, nf))
+        return (logZ, dlogZ) if return_error else logZ
+
+
+def _steps(first, count, thin):
+    return slice(first, first + (count - 1) * thin + 1, thin)
+
+
+class Backend(_Diagnostics):
     def __init__(self):
         self.initialized = False
 
@@ -59,6 +166,21 @@ class Backend:
     def get_betas(self, discard=0, thin=1):
         return self.betas[discard:self.iteration:thin]
 
+    # -- diagnostics: the hooks of _Diagnostics over the host arrays --------------------------------------
+    def _stat_rungs(self):
+        return self.ntemps
+
+    def _stat_act(self, branch, first, count, thin, ntemps, lags):
+        return chain_stats.act(self.chain[branch][_steps(first, count, thin), :ntemps, :, 0, :], lags)[0]
+
+    def _stat_moments(self, field, first, count, thin, ntemps):
+        if field in self.chain:
+            return chain_stats.moments(self.chain[field][_steps(first, count, thin), :ntemps, :, 0, :])
+        return chain_stats.moments(getattr(self, field)[_steps(first, count, thin), :ntemps], mask=True)
+
+    def _stat_betas(self, first, count, thin):
+        return self.betas[_steps(first, count, thin)]
+
 
 class _DeviceChain:
     """What ``DeviceBackend`` and ``RJDeviceBackend`` share: the open segment in device memory, closed segments on the host, one
@@ -89,6 +211,7 @@ class _DeviceChain:
         self.iteration = 0
         self.capacity = keep          # stored steps the device buffers hold (0: not created yet)
         self.downloads = 0            # chain copies from the device so far
+        self.stats_launches = 0       # diagnostics launches on the device chain so far (k_chain_moments / k_chain_act)
         self._open = 0                # stored steps in the open (device) segment
         self._closed = None           # everything closed so far: {field: host array}
         self._segments = []           # ... and segments closed since somebody last read it
@@ -188,7 +311,7 @@ class _DeviceChain:
         return ("philox", self.seed, int(last["iteration"][-1]), int(last["adapt_time"][-1]))
 
 
-class DeviceBackend(_DeviceChain):
+class DeviceBackend(_DeviceChain, _Diagnostics):
     """``Backend`` whose stored steps stay in device memory until somebody reads them (include/hipensemble.h: hens_chain_*).
 
     The reference's storage contract (backends/backend.py:1014-1091 ``save_step``) on the device: ``EnsembleSampler(...,
@@ -202,7 +325,11 @@ class DeviceBackend(_DeviceChain):
                    device buffers start again - and goes on.
     ntemps_store   store rungs ``[0, ntemps_store)`` only (default: all); ``swaps_accepted`` keeps its ntemps - 1 entries.
 
-    An untempered sampler has no ladder: ``get_betas`` returns zeros there."""
+    An untempered sampler has no ladder: ``get_betas`` returns zeros there.
+
+    The diagnostics (``get_autocorr_time`` ...) run on the device - one launch, nothing downloaded but arrays the size of a stored
+    step: ``stats_launches`` counts them, ``downloads`` stays - when every kept step lies in the open segment; with closed
+    segments among them they run ``eryn_amd.chain_stats`` over the host copy.  Both give the same bits."""
 
     FIELDS = ("x", "log_like", "log_prior", "betas", "iteration", "adapt_time")
 
@@ -240,6 +367,36 @@ class DeviceBackend(_DeviceChain):
 
     def get_chain(self, discard=0, thin=1):
         return {self.branch_names[0]: self._field("x", discard, thin)[:, :, :, None, :]}
+
+    # -- diagnostics: the hooks of _Diagnostics --------------------------------------------------------------
+    def _stat_rungs(self):
+        return self.nstore
+
+    def _on_device(self, first):
+        """The kept steps from ``first`` on all lie in the open segment: its index there, else None."""
+        closed = self.iteration - self._open
+        return first - closed if first >= closed else None
+
+    def _stat_act(self, branch, first, count, thin, ntemps, lags):
+        f = self._on_device(first)
+        if f is None:
+            return chain_stats.act(self._field("x", 0, 1)[_steps(first, count, thin), :ntemps], lags)[0]
+        self.stats_launches += 1
+        return self.engine.chain_act(f, count, thin, ntemps, lags)[0]
+
+    def _stat_moments(self, field, first, count, thin, ntemps):
+        name = "x" if field == self.branch_names[0] else field
+        f = self._on_device(first)
+        if f is None:
+            return chain_stats.moments(self._field(name, 0, 1)[_steps(first, count, thin), :ntemps], mask=name != "x")
+        self.stats_launches += 1
+        return self.engine.chain_moments(name, f, count, thin, ntemps)
+
+    def _stat_betas(self, first, count, thin):
+        f = self._on_device(first)
+        if f is None:
+            return self._field("betas", 0, 1)[_steps(first, count, thin)]
+        return self.engine.chain_download(f, (count - 1) * thin + 1, fields=("betas",))["betas"][::thin]      # (count x T doubles: not a chain copy)
 
     @property
     def accepted(self):

@@ -8,6 +8,7 @@
 #include "hens_aql.h"
 #include "hens_ktable.h"
 #include "hens_chain.h"
+#include "hens_chain_stats.h"
 #include "hens_rj_chain.h"
 #include "hens_chain_host.h"
 #include <unordered_map>
@@ -250,6 +251,7 @@ struct hens_ctx_impl {
         hens_chain::Sizes sz{};
         std::vector<int64_t> iteration, adapt_time;   // per stored step: the Philox checkpoint of its State
         int64_t n_timed = 0; double store_ms = 0.0;   // hens_set_profiling 1: the last call's append launches
+        double moments_ms = -1.0, act_ms = -1.0;      // the last k_chain_moments / k_chain_act launch (hens_chain_stats_ms)
     } chain;
     // ... of a leaf-packing context (hens_rj_chain_*, hens_rj_step_chain): per branch coordinates and leaf masks
     struct RjChain {
@@ -3114,6 +3116,111 @@ int hens_chain_totals(hens_ctx* ctx, double* accepted, double* swaps_accepted) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
     for (size_t i = 0; i < acc.size(); ++i) accepted[i] = (double)acc[i];
     for (size_t i = 0; i < sw.size(); ++i) swaps_accepted[i] = (double)sw[i];
+    return HENS_OK;
+}
+
+// ---- chain diagnostics (include/hipensemble.h: hens_chain_moments, hens_chain_act; csrc/hens_chain_stats.h) -----------------
+static int chain_stats_enter(hens_ctx_impl* c, const char* who) {
+    if (c->cfg.likelihood_kind == HENS_LIKE_TEMPLATE)
+        return fail(c, HENS_ERR_UNSUPPORTED, "%s: not built for a leaf-packing context - the autocorrelation time is not defined under reversible jump "
+                    "(the reference refuses it as well) and the Gelman-Rubin diagnostic of a branch of several leaves needs the projection through the leaf masks", who);
+    if (!c->chain.on) return fail(c, HENS_ERR_STATE, "no chain (hens_chain_create)");
+    return HENS_OK;
+}
+
+// one diagnostics launch on the HIP stream between two events, its outputs (device doubles behind `dev`, `n_out` arrays of nseries
+// each) copied to the caller's arrays that are not null
+static int chain_stats_run(hens_ctx_impl* c, const void* fn, dim3 grid, dim3 block, size_t lds, ChainStatArgs& a, char* dev,
+                           void* const* host, int n_out, double* ms_out, const char* what) {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) {
+        if (e0) (void)hipEventDestroy(e0);
+        (void)hipFree(dev);
+        return fail(c, HENS_ERR_HIP, "%s: hipEventCreate failed", what);
+    }
+    void* args[] = {&a};
+    hipError_t e = hipExtLaunchKernel(fn, grid, block, args, lds, c->stream, e0, e1, 0);
+    const size_t bytes = (size_t)a.nseries * 8;
+    for (int k = 0; k < n_out && e == hipSuccess; ++k)
+        if (host[k]) e = hipMemcpyAsync(host[k], dev + (size_t)k * bytes, bytes, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    float ms = 0;
+    *ms_out = (e == hipSuccess && hipEventElapsedTime(&ms, e0, e1) == hipSuccess) ? (double)ms : -1.0;
+    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    (void)hipFree(dev);
+    if (e != hipSuccess) return fail(c, HENS_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
+    return HENS_OK;
+}
+
+int hens_chain_moments(hens_ctx* ctx, int32_t field, int64_t first, int64_t count, int64_t thin, int32_t ntemps,
+                       double* sum, double* m2, int64_t* n_finite) {
+    hens_ctx_impl* c = enter(ctx);
+    if (!c) return fail(c, HENS_ERR_INVALID, "null context");
+    int r;
+    if ((r = chain_stats_enter(c, "hens_chain_moments"))) return r;
+    hens_ctx_impl::Chain& ch = c->chain;
+    hens_chain::StatPlan pl{};
+    if (!hens_chain::stat_plan(chain_shape(c, ch.Ts), ch.count, field, first, count, thin, ntemps, &pl))
+        return fail(c, HENS_ERR_INVALID, "hens_chain_moments: field %d in [0, 2], count >= 1, thin >= 1, ntemps %d in [1, %d] and the kept steps %lld, %lld + %lld, ... (%lld of them) inside the %lld stored",
+                    field, ntemps, ch.Ts, (long long)first, (long long)first, (long long)thin, (long long)count, (long long)ch.count);
+    const int64_t blocks = hens_chain::stat_blocks(pl.nseries / pl.vec, 256);
+    if (blocks > INT32_MAX) return fail(c, HENS_ERR_UNSUPPORTED, "hens_chain_moments: %lld series are more than one launch covers", (long long)pl.nseries);
+    if (!sum && !m2 && !n_finite) return HENS_OK;
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    char* dev = nullptr;
+    HIPCHK(c, hipMalloc((void**)&dev, (size_t)pl.nseries * 8 * 3));
+    ChainStatArgs a{};
+    a.src = (field == 0 ? ch.x : field == 1 ? ch.L : ch.P) + pl.offset;
+    a.stride = pl.stride; a.count = count; a.nseries = pl.nseries;
+    a.sum = reinterpret_cast<double*>(dev);
+    a.m2 = m2 ? reinterpret_cast<double*>(dev) + pl.nseries : nullptr;
+    a.nfin = reinterpret_cast<long long*>(dev) + 2 * pl.nseries;
+    const bool mask = field != 0;
+    const void* fn = pl.vec == 2 ? (mask ? reinterpret_cast<const void*>(k_chain_moments<2, true>) : reinterpret_cast<const void*>(k_chain_moments<2, false>))
+                                 : (mask ? reinterpret_cast<const void*>(k_chain_moments<1, true>) : reinterpret_cast<const void*>(k_chain_moments<1, false>));
+    void* const host[3] = {sum, m2, n_finite};
+    return chain_stats_run(c, fn, dim3((unsigned)blocks), dim3(256), 0, a, dev, host, 3, &ch.moments_ms, "k_chain_moments");
+}
+
+int hens_chain_act(hens_ctx* ctx, int64_t first, int64_t count, int64_t thin, int32_t ntemps, int32_t window,
+                   double* tau, double* mean, double* c0) {
+    hens_ctx_impl* c = enter(ctx);
+    if (!c) return fail(c, HENS_ERR_INVALID, "null context");
+    int r;
+    if ((r = chain_stats_enter(c, "hens_chain_act"))) return r;
+    hens_ctx_impl::Chain& ch = c->chain;
+    hens_chain::StatPlan pl{};
+    if (window < 1 || !hens_chain::stat_plan(chain_shape(c, ch.Ts), ch.count, 0, first, count, thin, ntemps, &pl))
+        return fail(c, HENS_ERR_INVALID, "hens_chain_act: window >= 1, count >= 1, thin >= 1, ntemps %d in [1, %d] and the kept steps %lld, %lld + %lld, ... (%lld of them) inside the %lld stored",
+                    ntemps, ch.Ts, (long long)first, (long long)first, (long long)thin, (long long)count, (long long)ch.count);
+    const int64_t lags = hens_chain::act_lags(window, count);
+    if (!hens_chain::act_fits(lags))
+        return fail(c, HENS_ERR_UNSUPPORTED, "hens_chain_act: %lld lags (min(window, kept steps)) are more than the %d a lane's accumulators and LDS ring hold",
+                    (long long)lags, hens_chain::ACT_WINDOW_MAX);
+    static_assert(hens_chain::ACT_LANES == ACT_LANES, "hens_chain_host.h sizes the ring of k_chain_act");
+    const int64_t blocks = hens_chain::stat_blocks(pl.nseries, ACT_LANES);
+    if (blocks > INT32_MAX) return fail(c, HENS_ERR_UNSUPPORTED, "hens_chain_act: %lld series are more than one launch covers", (long long)pl.nseries);
+    if (!tau && !mean && !c0) return HENS_OK;
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    char* dev = nullptr;
+    HIPCHK(c, hipMalloc((void**)&dev, (size_t)pl.nseries * 8 * 3));
+    ChainStatArgs a{};
+    a.src = ch.x + pl.offset;
+    a.stride = pl.stride; a.count = count; a.nseries = pl.nseries;
+    a.tau = reinterpret_cast<double*>(dev); a.mean = a.tau + pl.nseries; a.c0 = a.mean + pl.nseries;
+    a.K = (int32_t)lags;
+    const int kmax = hens_chain::act_kmax(lags);
+    const void* fn = kmax == 16 ? reinterpret_cast<const void*>(k_chain_act<16>) : kmax == 32 ? reinterpret_cast<const void*>(k_chain_act<32>)
+                                                                                              : reinterpret_cast<const void*>(k_chain_act<64>);
+    void* const host[3] = {tau, mean, c0};
+    return chain_stats_run(c, fn, dim3((unsigned)blocks), dim3(ACT_LANES), (size_t)hens_chain::act_lds_bytes(lags), a, dev, host, 3, &ch.act_ms, "k_chain_act");
+}
+
+int hens_chain_stats_ms(hens_ctx* ctx, double* moments_ms, double* act_ms) {
+    hens_ctx_impl* c = CTX(ctx);
+    if (!c) return fail(c, HENS_ERR_INVALID, "null context");
+    if (moments_ms) *moments_ms = c->chain.moments_ms;
+    if (act_ms) *act_ms = c->chain.act_ms;
     return HENS_OK;
 }
 

@@ -112,4 +112,41 @@ inline int rj_lane_shift(const RjShape& s, int vec) {
     return sh;
 }
 
+// ---- chain diagnostics (hens_chain_moments, hens_chain_act; csrc/hens_chain_stats.h) ---------------------------------------------
+// The kept steps first, first + thin, ..., first + (count - 1) thin of a chain that holds `stored` steps, the rungs [0, ntemps) of
+// field 0 (x: W D doubles per rung), 1 or 2 (logl, logp: W per rung).  A series is one double of the selected head of a step's slice.
+struct StatPlan {
+    int64_t offset;     // doubles from the field's base to the first kept step's slice
+    int64_t stride;     // doubles between kept steps
+    int64_t nseries;    // ntemps x W x D, or ntemps x W
+    int vec;            // doubles per lane of k_chain_moments: 2 where every kept step's selection starts on 16 bytes and pairs up
+};
+
+inline bool stat_plan(const Shape& s, int64_t stored, int64_t field, int64_t first, int64_t count, int64_t thin, int64_t ntemps, StatPlan* out) {
+    if (s.T < 1 || s.W < 1 || s.D < 1 || s.Ts < 1 || s.Ts > s.T || stored < 0) return false;
+    if (field < 0 || field > 2 || first < 0 || count < 1 || thin < 1 || ntemps < 1 || ntemps > s.Ts) return false;
+    int64_t span, last;
+    if (!mul(count - 1, thin, &span) || !add(first, span, &last) || last >= stored) return false;
+    int64_t width = s.W, step, total;
+    if (field == 0 && !mul(s.W, s.D, &width)) return false;
+    if (!mul(s.Ts, width, &step) || !mul(step, stored, &total) || !mul(total, 8, &total)) return false;    // (every offset below is inside `total`)
+    StatPlan p{};
+    p.offset = first * step;
+    p.stride = count > 1 ? thin * step : step;          // (count > 1: thin <= last < stored; one kept step: never used)
+    p.nseries = ntemps * width;
+    p.vec = (p.nseries % 2 == 0 && step % 2 == 0) ? 2 : 1;
+    *out = p;
+    return true;
+}
+
+// k_chain_act: a workgroup is one wave of ACT_LANES series; its LDS ring holds K = min(window, count) centred values per lane, its
+// registers up to ACT_WINDOW_MAX accumulators
+constexpr int ACT_LANES = 64, ACT_WINDOW_MAX = 64;
+inline int64_t act_lags(int64_t window, int64_t count) { return window < count ? window : count; }
+inline bool act_fits(int64_t lags) { return lags >= 1 && lags <= ACT_WINDOW_MAX; }
+inline int64_t act_lds_bytes(int64_t lags) { return lags * ACT_LANES * 8; }
+// accumulators the instantiation carries: the smallest of 16 / 32 / 64 that covers the lags
+inline int act_kmax(int64_t lags) { return lags <= 16 ? 16 : lags <= 32 ? 32 : 64; }
+inline int64_t stat_blocks(int64_t lanes, int64_t per_block) { return (lanes + per_block - 1) / per_block; }
+
 }  // namespace hens_chain

@@ -275,6 +275,34 @@ class HipEnsemble:
         check(self.lib.hens_chain_totals(self.ctx, ptr(acc), ptr(swaps) if self.T > 1 else None), self.ctx)
         return acc, swaps
 
+    # -- chain diagnostics (include/hipensemble.h: hens_chain_moments, hens_chain_act) ----------------------
+    FIELD_CODES = dict(x=0, log_like=1, log_prior=2)
+
+    def chain_moments(self, field, first, count, thin=1, ntemps=None):
+        """``(sum, m2, n_finite)`` per series of ``field`` ("x": ``[ntemps, W, D]``; "log_like" / "log_prior": ``[ntemps, W]``)
+        over the kept steps ``first + j thin``, j < count, of the open chain: eryn_amd.chain_stats.moments bit for bit, computed
+        where the chain is."""
+        nt = int(self.chain_info()["ntemps_store"] if ntemps is None else ntemps)
+        shape = (max(nt, 0), self.W) + ((self.D,) if field == "x" else ())
+        s, m2, nf = np.empty(shape), np.empty(shape), np.empty(shape, dtype=np.int64)
+        check(self.lib.hens_chain_moments(self.ctx, self.FIELD_CODES[field], int(first), int(count), int(thin), nt, ptr(s), ptr(m2), ptr(nf)), self.ctx)
+        return s, m2, nf
+
+    def chain_act(self, first, count, thin=1, ntemps=None, window=50):
+        """``(tau, mean, c0)`` ``[ntemps, W, D]`` of the coordinates over the kept steps: eryn_amd.chain_stats.act bit for bit
+        with ``K = min(window, count)`` lags."""
+        nt = int(self.chain_info()["ntemps_store"] if ntemps is None else ntemps)
+        shape = (max(nt, 0), self.W, self.D)
+        tau, mean, c0 = np.empty(shape), np.empty(shape), np.empty(shape)
+        check(self.lib.hens_chain_act(self.ctx, int(first), int(count), int(thin), nt, int(window), ptr(tau), ptr(mean), ptr(c0)), self.ctx)
+        return tau, mean, c0
+
+    def chain_stats_ms(self):
+        """Durations (ms) of the last k_chain_moments and k_chain_act launches, -1 where there was none."""
+        a, b = C.c_double(-1.0), C.c_double(-1.0)
+        check(self.lib.hens_chain_stats_ms(self.ctx, C.byref(a), C.byref(b)), self.ctx)
+        return dict(moments_ms=a.value, act_ms=b.value)
+
     def download_betas(self):
         betas = np.empty(self.T)
         check(self.lib.hens_download_state(self.ctx, None, None, None, ptr(betas)), self.ctx)

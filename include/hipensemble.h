@@ -238,6 +238,30 @@ int hens_chain_download(hens_ctx* ctx, int64_t first, int64_t count, double* x, 
                         int64_t* iteration, int64_t* adapt_time);
 int hens_chain_totals(hens_ctx* ctx, double* accepted, double* swaps_accepted);
 
+/* ---- Chain diagnostics on the chain in device memory (csrc/hens_chain_stats.h: k_chain_moments, k_chain_act) -------------------
+ * The reductions over the step axis under the reference's get_autocorr_time, get_gelman_rubin_convergence_diagnostic and
+ * get_evidence_estimate (backends/backend.py:616-817, utils/utility.py:43-144, 279-330), run where the chain is: one launch reads
+ * the kept steps first, first + thin, ..., first + (count - 1) thin of rungs [0, ntemps) and returns arrays the size of one
+ * stored step.  The arithmetic and its summation order are eryn_amd/chain_stats.py's, bit for bit.  They read the chain and
+ * touch no stepping state.
+ *
+ * hens_chain_moments: per series of field 0 (x: sum / m2 / n_finite [ntemps][W][D]), 1 (logl) or 2 (logp: [ntemps][W]) the sum
+ *   over the kept steps, m2 = sum (x - sum / n)^2 in a second pass, and the entries counted.  logl / logp skip and do not count
+ *   non-finite entries (-1e300 is finite); x counts every kept step.
+ * hens_chain_act: per series of x the integrated autocorrelation time tau = 1 + 2 sum_{k=1}^{K-1} c_k / c_0 over the lags
+ *   K = min(window, count), its mean and c_0 = sum (x - mean)^2 ([ntemps][W][D] each); a constant series gives NaN.  More than 64
+ *   lags -> HENS_ERR_UNSUPPORTED (a lane's accumulators and its LDS ring).
+ * Outputs are host pointers, any may be NULL.  No chain -> HENS_ERR_STATE; count < 1, thin < 1, window < 1, a field outside
+ * [0, 2], ntemps outside [1, ntemps_store] or a kept step outside [0, count of the chain) -> HENS_ERR_INVALID before anything is
+ * launched.  A leaf-packing context -> HENS_ERR_UNSUPPORTED: not built (the autocorrelation time is not defined under reversible
+ * jump, Gelman-Rubin over several leaves needs the projection through the leaf masks).
+ * hens_chain_stats_ms: the duration in ms of the last k_chain_moments / k_chain_act launch of the chain (-1: none yet). */
+int hens_chain_moments(hens_ctx* ctx, int32_t field, int64_t first, int64_t count, int64_t thin, int32_t ntemps, double* sum,
+                       double* m2, int64_t* n_finite);
+int hens_chain_act(hens_ctx* ctx, int64_t first, int64_t count, int64_t thin, int32_t ntemps, int32_t window, double* tau,
+                   double* mean, double* c0);
+int hens_chain_stats_ms(hens_ctx* ctx, double* moments_ms, double* act_ms);
+
 /* ---- Chain store of a leaf-packing context (HENS_LIKE_TEMPLATE after hens_rj_set_model*) ---------------------------------------
  * The same contract for records of several branches and leaves: the stored steps of RJEnsembleSampler.run_mcmc(store=True) stay in
  * device memory, laid out the way the reference's backend returns them (backends/backend.py:1014-1091) - per branch b
