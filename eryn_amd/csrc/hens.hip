@@ -240,37 +240,34 @@ struct hens_ctx_impl {
     // kernels launched by host function pointer (launch_by_ptr): dynamic-LDS attribute set on this context's device, AQL handle
     struct KernelSlot { bool attr_done = false; const hens_aql::Kernel* ak = nullptr; };
     std::unordered_map<const void*, KernelSlot> kslots;
-    // chain store (hens_chain_*, hens_step_chain): the stored steps of run_mcmc(store=True) in device memory
-    struct Chain {
+    // chain store: the stored steps of run_mcmc(store=True) in device memory.  A context has one family of it - hens_chain_*,
+    // hens_step_chain, or on a leaf-packing context hens_rj_chain_*, hens_rj_step_chain (chain_supported / rjchain_supported) -
+    // and both run the host protocol of `chain store: what both families share` below.
+    struct ChainStore {
         bool on = false;
         int64_t capacity = 0, count = 0, bytes = 0;
         int Ts = 0;                          // rungs [0, Ts) are stored
-        double *x = nullptr, *L = nullptr, *P = nullptr, *betas = nullptr;   // [capacity] x ([Ts][W][D], [Ts][W], [Ts][W], [T])
+        double *L = nullptr, *P = nullptr, *betas = nullptr;   // [capacity] x ([Ts][W], [Ts][W], [T])
         uint32_t* acc_tot = nullptr;         // [Ts][W] accepted totals (backends/backend.py:1069)
-        unsigned long long* swaps_tot = nullptr;   // [T-1] swap totals (backends/backend.py:1072)
-        hens_chain::Sizes sz{};
+        unsigned long long* swaps_tot = nullptr;   // [T-1] swap totals (backends/backend.py:1072): a leaf-packing chain's in-model swaps
         std::vector<int64_t> iteration, adapt_time;   // per stored step: the Philox checkpoint of its State
         int64_t n_timed = 0; double store_ms = 0.0;   // hens_set_profiling 1: the last call's append launches
         double moments_ms = -1.0, act_ms = -1.0;      // the last k_chain_moments / k_chain_act launch (hens_chain_stats_ms)
-    } chain;
-    // ... of a leaf-packing context (hens_rj_chain_*, hens_rj_step_chain): per branch coordinates and leaf masks
-    struct RjChain {
-        bool on = false;
-        int64_t capacity = 0, count = 0, bytes = 0;
-        int Ts = 0;                          // rungs [0, Ts) are stored
+        // per family: x[0] [capacity][Ts][W][D] of a fixed-dimension chain; per branch of a leaf-packing one
         double* x[RJ_MAX_BRANCH] = {};       // [capacity][Ts][W][nl_b][nd_b], NaN on unused leaves
         uint8_t* inds[RJ_MAX_BRANCH] = {};   // [capacity][Ts][W][nl_b]
-        double *L = nullptr, *P = nullptr, *betas = nullptr;   // [capacity] x ([Ts][W], [Ts][W], [T])
-        uint32_t *acc_tot = nullptr, *bd_tot = nullptr;        // [Ts][W] accepted / rj_accepted totals
+        // ... and of a leaf-packing chain only
+        uint32_t* bd_tot = nullptr;          // [Ts][W] rj_accepted totals
         uint32_t* prev = nullptr;            // [2][Tl][W] the in-model / birth-death accept counters at the mark
-        unsigned long long* swaps_tot = nullptr;   // [T-1] in-model swap totals
         double* swaps_step = nullptr;        // [T-1] the in-model cascade's counts of a stored step's last iteration, set aside
-        hens_chain::RjSizes sz{};
-        std::vector<int64_t> iteration, adapt_time;   // per stored step: the Philox checkpoint of its State
-        int64_t n_timed = 0; double store_ms = 0.0;   // hens_set_profiling 1: the last call's append launches
         bool mark_valid = false;             // `prev` is the counters as they stand (the last append left it so) ...
         int64_t mark_books = 0;              // ... as long as no move has run since: num_mh + num_bd then
-    } rjchain;
+        std::vector<void*> owned;            // every device allocation the pointers above name
+        void release() {
+            for (void* p : owned) (void)hipFree(p);
+            *this = ChainStore{};
+        }
+    } chain;
     std::vector<double> launch_us;   // per-kernel profiling: begin / end of every launch of the last hens_step call (us after the first begin)
     std::vector<void*> allocs;
 };
@@ -2139,9 +2136,7 @@ int hens_create(const hens_config* cfg, hens_ctx** out) {
     return HENS_OK;
 }
 
-static void chain_free(hens_ctx_impl* c);     // (the chain store's device buffers: below, with hens_chain_*)
-static void rjchain_free(hens_ctx_impl* c);   // (... a leaf-packing context's: below, with hens_rj_chain_*)
-static int rjchain_drop(hens_ctx_impl* c);
+static int rjchain_drop(hens_ctx_impl* c);    // (below, with hens_rj_chain_*)
 void hens_destroy(hens_ctx* ctx) {
     hens_ctx_impl* c = CTX(ctx);
     if (!c) return;
@@ -2161,8 +2156,7 @@ void hens_destroy(hens_ctx* ctx) {
     if (c->pipe.box) (void)hipFree(c->pipe.box);
     for (void* p : c->allocs)
         if (p) (void)hipFree(p);
-    chain_free(c);
-    rjchain_free(c);
+    c->chain.release();
     for (hipEvent_t e : c->evpool) (void)hipEventDestroy(e);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -2909,13 +2903,182 @@ int hens_step_report(hens_ctx* ctx, int64_t n_iters, int64_t n_last, uint8_t* ac
     return HENS_OK;
 }
 
-// ---- chain store (include/hipensemble.h: hens_chain_*, hens_step_chain; csrc/hens_chain.h: k_chain_store) -------------------
-static void chain_free(hens_ctx_impl* c) {
-    hens_ctx_impl::Chain& ch = c->chain;
-    for (void* p : {(void*)ch.x, (void*)ch.L, (void*)ch.P, (void*)ch.betas, (void*)ch.acc_tot, (void*)ch.swaps_tot})
-        if (p) (void)hipFree(p);
-    ch = hens_ctx_impl::Chain{};
+// ---- chain store: what both families share (hens_chain_* below, hens_rj_chain_* behind hens_rj_step) ------------------------
+// The host protocol of a chain, once: an entry point of either family checks what is its own (chain_supported / rjchain_supported,
+// its arrays, its kernel's arguments) and calls these with its own name for the error texts.
+using ChainStore = hens_ctx_impl::ChainStore;
+static bool is_rj(const hens_ctx_impl* c) { return c->cfg.likelihood_kind == HENS_LIKE_TEMPLATE; }
+// the context has a chain, of the family that asks (the other family's entry points see none)
+static bool chain_is(const hens_ctx_impl* c, bool rj) { return c->chain.on && rj == is_rj(c); }
+static int chain_open(hens_ctx_impl* c, bool rj) {
+    if (!chain_is(c, rj)) return fail(c, HENS_ERR_STATE, "no chain (%s)", rj ? "hens_rj_chain_create" : "hens_chain_create");
+    return HENS_OK;
 }
+static int chain_Ts(const hens_ctx_impl* c, bool rj) { return chain_is(c, rj) ? c->chain.Ts : c->T; }   // (no chain: what one would store)
+// swap slots of a ladder: the allocations and their memsets hold at least one (T = 1), the totals copy what there is
+static size_t swap_slots(const hens_ctx_impl* c, int least) { return (size_t)std::max(c->T - 1, least); }
+
+static int chain_reset(hens_ctx_impl* c) {
+    ChainStore& ch = c->chain;
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    for (uint32_t* tot : {ch.acc_tot, ch.bd_tot})        // (bd_tot: a leaf-packing chain has it)
+        if (tot) HIPCHK(c, hipMemsetAsync(tot, 0, (size_t)ch.Ts * c->W * 4, c->stream));
+    HIPCHK(c, hipMemsetAsync(ch.swaps_tot, 0, swap_slots(c, 1) * 8, c->stream));
+    ch.count = 0;
+    ch.iteration.clear(); ch.adapt_time.clear();
+    return HENS_OK;
+}
+
+// hens_*chain_create in two halves, the family's overflow-checked sizes in between: the arguments, giving the stored rungs ...
+static int chain_create_args(hens_ctx_impl* c, const char* who, int64_t capacity, int32_t ntemps_store, int* Ts) {
+    if (capacity < 1) return fail(c, HENS_ERR_INVALID, "%s: capacity < 1", who);
+    if (ntemps_store < 0 || ntemps_store > c->T) return fail(c, HENS_ERR_INVALID, "%s: ntemps_store outside [0, %d]", who, c->T);
+    *Ts = ntemps_store ? ntemps_store : c->T;
+    return HENS_OK;
+}
+// ... and the chain itself from the family's list of (pointer in c->chain, bytes); `bytes` is the list's sum: the side arrays count
+struct ChainBuf { void* p; size_t bytes; };
+static int chain_create(hens_ctx_impl* c, const char* who, int64_t capacity, int Ts, const std::vector<ChainBuf>& bufs) {
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    HIPCHK(c, hipStreamSynchronize(c->stream));     // (a chain being replaced may still be written)
+    ChainStore& ch = c->chain;
+    ch.release();
+    int64_t bytes = 0;
+    bool ok = true;
+    for (const ChainBuf& b : bufs) {
+        bytes += (int64_t)b.bytes;
+        if (ok && (ok = hipMalloc((void**)b.p, b.bytes) == hipSuccess)) ch.owned.push_back(*(void**)b.p);
+    }
+    if (!ok) {
+        const hipError_t e = hipGetLastError();     // (cleared: the stepping calls check it)
+        ch.release();
+        return fail(c, HENS_ERR_HIP, "%s: allocating %lld bytes of device memory for %lld stored steps failed: %s",
+                    who, (long long)bytes, (long long)capacity, hipGetErrorString(e));
+    }
+    ch.capacity = capacity; ch.Ts = Ts; ch.bytes = bytes;
+    ch.on = true;
+    return chain_reset(c);
+}
+
+static int chain_destroy(hens_ctx_impl* c, bool rj) {
+    if (!chain_is(c, rj)) return HENS_OK;
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->chain.release();
+    return HENS_OK;
+}
+
+// `step_bytes`: the family's sizes of one step of chain_Ts rungs
+static int chain_info(hens_ctx_impl* c, bool rj, int64_t step_bytes, hens_chain_info_t* out) {
+    static_assert(sizeof(hens_chain_info_t) == 64, "hens_chain_info_t: 7 x i64 + f64 (eryn_amd/_lib.py: HensChainInfo)");
+    const ChainStore none{};
+    const ChainStore& ch = chain_is(c, rj) ? c->chain : none;
+    hens_chain_info_t o{};
+    o.capacity = ch.capacity; o.count = ch.count; o.ntemps_store = ch.Ts; o.bytes = ch.bytes; o.step_bytes = step_bytes;
+    o.n_store_timed = ch.n_timed; o.store_ms = ch.store_ms;
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    size_t fr = 0, tot = 0;
+    HIPCHK(c, hipMemGetInfo(&fr, &tot));
+    o.free_bytes = (int64_t)fr;
+    *out = o;
+    return HENS_OK;
+}
+
+// the event pairs around a call's append launches while hens_set_profiling is 1 (at most 4096 pairs: later appends go untimed);
+// the call's store_ms / n_timed start at zero with it, and whatever way the call ends, the events go with it
+struct ChainTimer {
+    ChainStore& ch;
+    const bool on;
+    std::vector<hipEvent_t> evs;
+    explicit ChainTimer(hens_ctx_impl* c) : ch(c->chain), on(c->per_kernel_events == 1) { ch.n_timed = 0; ch.store_ms = 0.0; }
+    ~ChainTimer() { for (hipEvent_t e : evs) (void)hipEventDestroy(e); }
+    int pair(hens_ctx_impl* c, hipEvent_t e[2]) {          // nulls: this append is not timed
+        e[0] = e[1] = nullptr;
+        if (!on || evs.size() >= 2 * 4096) return HENS_OK;
+        for (int k = 0; k < 2; ++k) { HIPCHK(c, hipEventCreate(&e[k])); evs.push_back(e[k]); }
+        return HENS_OK;
+    }
+    // after the caller's own synchronisation of the stream: hens_step_chain waits for it itself when there is a pair to read,
+    // hens_rj_step_chain has check_flags' wait behind it either way
+    void fold() {
+        for (size_t k = 0; k + 1 < evs.size(); k += 2) {
+            float ms = 0;
+            if (hipEventElapsedTime(&ms, evs[k], evs[k + 1]) == hipSuccess) { ch.store_ms += ms; ch.n_timed += 1; }
+        }
+    }
+};
+
+// one append on the HIP stream, its argument block filled by the family: Ts W records of 2^lpr_shift lanes each; then the stored
+// step's books
+static int chain_append(hens_ctx_impl* c, ChainTimer& tm, const void* fn, void* block, int lpr_shift) {
+    ChainStore& ch = c->chain;
+    hipEvent_t e[2];
+    if (const int r = tm.pair(c, e)) return r;
+    const int64_t threads = (int64_t)((size_t)ch.Ts * c->W) << lpr_shift;
+    const dim3 grid((unsigned)((threads + 255) / 256));
+    void* args[] = {block};
+    if (e[0]) (void)hipExtLaunchKernel(fn, grid, dim3(256), args, 0, c->stream, e[0], e[1], 0);
+    else (void)hipLaunchKernel(fn, grid, dim3(256), args, 0, c->stream);
+    HIPCHK(c, hipGetLastError());
+    ch.iteration.push_back((int64_t)c->iter);
+    ch.adapt_time.push_back(c->adapt_time);
+    ch.count += 1;
+    return HENS_OK;
+}
+
+// hens_*chain_download in two halves, a family's own checks in between: the open chain and the range ...
+static int chain_range(hens_ctx_impl* c, bool rj, const char* who, int64_t first, int64_t count) {
+    if (const int r = chain_open(c, rj)) return r;
+    if (!hens_chain::range_ok(c->chain.count, first, count))
+        return fail(c, HENS_ERR_INVALID, "%s: steps [%lld, %lld + %lld) outside the %lld stored", who, (long long)first, (long long)first, (long long)count, (long long)c->chain.count);
+    return HENS_OK;
+}
+// ... and the copies: the family's own fields (`step` bytes per stored step each), logl / logp / betas, one wait if anything was
+// copied, the checkpoints.  A null destination is a field not asked for.
+struct ChainCopy { void* dst; const void* src; size_t step; };
+static int chain_copy_out(hens_ctx_impl* c, int64_t first, int64_t count, std::initializer_list<ChainCopy> own, double* logl, double* logp,
+                          double* betas, int64_t* iteration, int64_t* adapt_time) {
+    if (count == 0) return HENS_OK;
+    const ChainStore& ch = c->chain;
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    const size_t lp = (size_t)ch.Ts * c->W * 8;
+    bool copied = false;
+    auto copy = [&](const ChainCopy& f) {
+        if (!f.dst) return hipSuccess;
+        copied = true;
+        return hipMemcpyAsync(f.dst, static_cast<const char*>(f.src) + (size_t)first * f.step, (size_t)count * f.step, hipMemcpyDeviceToHost, c->stream);
+    };
+    for (const ChainCopy& f : own) HIPCHK(c, copy(f));
+    for (const ChainCopy& f : {ChainCopy{logl, ch.L, lp}, ChainCopy{logp, ch.P, lp}, ChainCopy{betas, ch.betas, (size_t)c->T * 8}}) HIPCHK(c, copy(f));
+    if (copied) HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (iteration) std::copy(ch.iteration.begin() + first, ch.iteration.begin() + first + count, iteration);
+    if (adapt_time) std::copy(ch.adapt_time.begin() + first, ch.adapt_time.begin() + first + count, adapt_time);
+    return HENS_OK;
+}
+
+// hens_*chain_totals: the family's [Ts][W] counters (destination, device array) and the swap totals, widened to double
+struct ChainTotal { double* dst; const uint32_t* src; };
+static int chain_totals(hens_ctx_impl* c, std::initializer_list<ChainTotal> tots, double* swaps_accepted) {
+    const ChainStore& ch = c->chain;
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    const size_t TsW = (size_t)ch.Ts * c->W, np = swap_slots(c, 0);
+    size_t asked = 0;
+    for (const ChainTotal& t : tots) asked += t.dst != nullptr;
+    std::vector<uint32_t> acc(asked * TsW);           // (staged only where the caller asks)
+    std::vector<unsigned long long> sw(swaps_accepted ? np : 0);
+    size_t k = 0;
+    for (const ChainTotal& t : tots)
+        if (t.dst) HIPCHK(c, hipMemcpyAsync(&acc[TsW * k++], t.src, TsW * 4, hipMemcpyDeviceToHost, c->stream));
+    if (!sw.empty()) HIPCHK(c, hipMemcpyAsync(sw.data(), ch.swaps_tot, np * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    k = 0;
+    for (const ChainTotal& t : tots)
+        if (t.dst) std::copy_n(&acc[TsW * k++], TsW, t.dst);
+    std::copy(sw.begin(), sw.end(), swaps_accepted);
+    return HENS_OK;
+}
+
+// ---- chain store (include/hipensemble.h: hens_chain_*, hens_step_chain; csrc/hens_chain.h: k_chain_store) -------------------
 static int chain_supported(hens_ctx_impl* c) {
     if (c->cfg.likelihood_kind == HENS_LIKE_TEMPLATE)
         return fail(c, HENS_ERR_UNSUPPORTED, "chain store: not on a leaf-packing context (records of several branches and leaves: hens_rj_chain_create / hens_rj_step_chain)");
@@ -2930,78 +3093,41 @@ static hens_chain::Shape chain_shape(const hens_ctx_impl* c, int Ts) { return he
 int hens_chain_create(hens_ctx* ctx, int64_t capacity, int32_t ntemps_store) {
     hens_ctx_impl* c = enter(ctx);
     if (!c) return fail(c, HENS_ERR_INVALID, "null context");
-    int r;
-    if ((r = chain_supported(c))) return r;
-    if (capacity < 1) return fail(c, HENS_ERR_INVALID, "hens_chain_create: capacity < 1");
-    if (ntemps_store < 0 || ntemps_store > c->T) return fail(c, HENS_ERR_INVALID, "hens_chain_create: ntemps_store outside [0, %d]", c->T);
-    const int Ts = ntemps_store ? ntemps_store : c->T;
+    int r, Ts = 0;
+    if ((r = chain_supported(c)) || (r = chain_create_args(c, "hens_chain_create", capacity, ntemps_store, &Ts))) return r;
     hens_chain::Sizes sz{};
     if (!hens_chain::sizes(chain_shape(c, Ts), capacity, &sz))
         return fail(c, HENS_ERR_INVALID, "hens_chain_create: %lld stored steps of %d x %d x %d do not fit an int64 byte count", (long long)capacity, Ts, c->W, dim_active(c));
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    HIPCHK(c, hipStreamSynchronize(c->stream));     // (a chain being replaced may still be written)
-    chain_free(c);
-    hens_ctx_impl::Chain& ch = c->chain;
-    const size_t TsW = (size_t)Ts * c->W, np = (size_t)std::max(c->T - 1, 1);
-    auto get = [&](void** p, size_t bytes) { return hipMalloc(p, bytes) == hipSuccess; };
-    if (!get((void**)&ch.x, (size_t)sz.x) || !get((void**)&ch.L, (size_t)sz.lp) || !get((void**)&ch.P, (size_t)sz.lp) ||
-        !get((void**)&ch.betas, (size_t)sz.betas) || !get((void**)&ch.acc_tot, TsW * 4) || !get((void**)&ch.swaps_tot, np * 8)) {
-        const hipError_t e = hipGetLastError();     // (cleared: hens_step checks it)
-        chain_free(c);
-        return fail(c, HENS_ERR_HIP, "hens_chain_create: allocating %lld bytes of device memory for %lld stored steps failed: %s",
-                    (long long)(sz.total + TsW * 4 + np * 8), (long long)capacity, hipGetErrorString(e));
-    }
-    ch.capacity = capacity; ch.Ts = Ts; ch.sz = sz;
-    ch.bytes = sz.total + (int64_t)(TsW * 4 + np * 8);
-    ch.iteration.clear(); ch.adapt_time.clear();
-    ch.on = true;
-    return hens_chain_reset(ctx);
+    ChainStore& ch = c->chain;
+    return chain_create(c, "hens_chain_create", capacity, Ts, {{&ch.x[0], (size_t)sz.x}, {&ch.L, (size_t)sz.lp}, {&ch.P, (size_t)sz.lp}, {&ch.betas, (size_t)sz.betas},
+                                                               {&ch.acc_tot, (size_t)Ts * c->W * 4}, {&ch.swaps_tot, swap_slots(c, 1) * 8}});
 }
 
 int hens_chain_reset(hens_ctx* ctx) {
     hens_ctx_impl* c = enter(ctx);
     if (!c) return fail(c, HENS_ERR_INVALID, "null context");
-    hens_ctx_impl::Chain& ch = c->chain;
-    if (!ch.on) return fail(c, HENS_ERR_STATE, "no chain (hens_chain_create)");
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    HIPCHK(c, hipMemsetAsync(ch.acc_tot, 0, (size_t)ch.Ts * c->W * 4, c->stream));
-    HIPCHK(c, hipMemsetAsync(ch.swaps_tot, 0, (size_t)std::max(c->T - 1, 1) * 8, c->stream));
-    ch.count = 0;
-    ch.iteration.clear(); ch.adapt_time.clear();
-    return HENS_OK;
+    if (const int r = chain_open(c, false)) return r;
+    return chain_reset(c);
 }
 
 int hens_chain_destroy(hens_ctx* ctx) {
     hens_ctx_impl* c = enter(ctx);
     if (!c) return fail(c, HENS_ERR_INVALID, "null context");
-    if (!c->chain.on) return HENS_OK;
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    chain_free(c);
-    return HENS_OK;
+    return chain_destroy(c, false);
 }
 
+// answers on any context, with capacity 0 where there is no chain of this family (DeviceBackend asks before it creates one)
 int hens_chain_info(hens_ctx* ctx, hens_chain_info_t* out) {
     hens_ctx_impl* c = CTX(ctx);
     if (!c || !out) return fail(c, HENS_ERR_INVALID, "null argument");
-    static_assert(sizeof(hens_chain_info_t) == 64, "hens_chain_info_t: 7 x i64 + f64 (eryn_amd/_lib.py: HensChainInfo)");
-    const hens_ctx_impl::Chain& ch = c->chain;
-    hens_chain_info_t o{};
     hens_chain::Sizes one{};
-    (void)hens_chain::sizes(chain_shape(c, ch.on ? ch.Ts : c->T), 1, &one);
-    o.capacity = ch.capacity; o.count = ch.count; o.ntemps_store = ch.on ? ch.Ts : 0; o.bytes = ch.bytes; o.step_bytes = one.step;
-    o.n_store_timed = ch.n_timed; o.store_ms = ch.store_ms;
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    size_t fr = 0, tot = 0;
-    HIPCHK(c, hipMemGetInfo(&fr, &tot));
-    o.free_bytes = (int64_t)fr;
-    *out = o;
-    return HENS_OK;
+    (void)hens_chain::sizes(chain_shape(c, chain_Ts(c, false)), 1, &one);
+    return chain_info(c, false, one.step, out);
 }
 
-// one append on the HIP stream: the state as it stands behind a hens_step call, the ladder and swap counts settled by the caller
-static void launch_chain_store(hens_ctx_impl* c, hipEvent_t e0, hipEvent_t e1) {
-    hens_ctx_impl::Chain& ch = c->chain;
+// one append: the state as it stands behind a hens_step call, the ladder and swap counts settled by the caller
+static int launch_chain_store(hens_ctx_impl* c, ChainTimer& tm) {
+    ChainStore& ch = c->chain;
     const size_t TW = (size_t)c->Tl * c->W, TsW = (size_t)ch.Ts * c->W;
     const int D = dim_active(c);
     ChainArgs a{};
@@ -3013,32 +3139,26 @@ static void launch_chain_store(hens_ctx_impl* c, hipEvent_t e0, hipEvent_t e1) {
     a.pool = c->pool;
     a.betas = c->cfg.tempered ? c->betas[c->bcur] : nullptr;
     a.swaps_last = has_pt(c) ? c->swaps_last : nullptr;
-    a.out_x = ch.x + (size_t)ch.count * TsW * D;
+    a.out_x = ch.x[0] + (size_t)ch.count * TsW * D;
     a.out_L = ch.L + (size_t)ch.count * TsW; a.out_P = ch.P + (size_t)ch.count * TsW;
     a.out_betas = ch.betas + (size_t)ch.count * c->T;
     a.acc_tot = ch.acc_tot; a.swaps_tot = ch.swaps_tot;
     a.colmode = c->colmode ? 1 : 0; a.T = c->T; a.W = c->W; a.Ts = ch.Ts; a.RW = c->D; a.D = D;
-    // 16 bytes per lane where both sides' rows are 16-byte aligned, else 8; a row to the smallest power of two of lanes that covers
-    // it (at most a wave: wider rows take several rounds)
-    const int vec = (c->D % 2 == 0 && D % 2 == 0) ? 2 : 1;
-    int sh = 0;
-    while ((1 << sh) * vec < D && sh < 6) ++sh;
-    a.lpr_shift = sh;
-    const int64_t threads = (int64_t)TsW << sh;
-    const dim3 grid((unsigned)((threads + 255) / 256));
-    void* args[] = {&a};
+    // the row as one segment of D doubles: 16 bytes per lane where both sides' rows are 16-byte aligned, else 8; a row to the smallest
+    // power of two of lanes that covers it (at most a wave: wider rows take several rounds)
+    const hens_chain::RjShape row = hens_chain::one_segment(chain_shape(c, ch.Ts));
+    const int vec = hens_chain::rj_store_vec(row, c->D);
+    a.lpr_shift = hens_chain::rj_lane_shift(row, vec);
     const void* fn = vec == 2 ? reinterpret_cast<const void*>(k_chain_store<2>) : reinterpret_cast<const void*>(k_chain_store<1>);
-    if (e0) (void)hipExtLaunchKernel(fn, grid, dim3(256), args, 0, c->stream, e0, e1, 0);
-    else (void)hipLaunchKernel(fn, grid, dim3(256), args, 0, c->stream);
+    return chain_append(c, tm, fn, &a, a.lpr_shift);
 }
 
 int hens_step_chain(hens_ctx* ctx, int64_t n_store, int64_t iters_per_store, int64_t n_last) {
-    hens_ctx_impl* c = CTX(ctx);
+    hens_ctx_impl* c = CTX(ctx);              // (not `enter`, as every other chain entry point: hens_step below settles the queue itself)
     if (!c) return fail(c, HENS_ERR_INVALID, "null context");
     int r;
-    if ((r = chain_supported(c))) return r;
-    hens_ctx_impl::Chain& ch = c->chain;
-    if (!ch.on) return fail(c, HENS_ERR_STATE, "no chain (hens_chain_create)");
+    if ((r = chain_supported(c)) || (r = chain_open(c, false))) return r;
+    ChainStore& ch = c->chain;
     int64_t iters = 0;
     switch (hens_chain::append_check(ch.capacity, ch.count, n_store, iters_per_store, n_last, &iters)) {
     case hens_chain::INVALID: return fail(c, HENS_ERR_INVALID, "hens_step_chain: n_store >= 0 and 1 <= n_last <= iters_per_store, and their product an int64");
@@ -3047,9 +3167,7 @@ int hens_step_chain(hens_ctx* ctx, int64_t n_store, int64_t iters_per_store, int
     default: break;
     }
     if ((r = counter_room(c, iters))) return r;
-    const bool timed = c->per_kernel_events == 1;
-    std::vector<hipEvent_t> evs;
-    ch.n_timed = 0; ch.store_ms = 0.0;
+    ChainTimer tm(c);
     for (int64_t s = 0; s < n_store; ++s) {
         const bool have_prev = report_current(c) && iters_per_store == n_last;
         if (iters_per_store > n_last && (r = hens_step(ctx, iters_per_store - n_last))) return r;
@@ -3058,25 +3176,12 @@ int hens_step_chain(hens_ctx* ctx, int64_t n_store, int64_t iters_per_store, int
         if ((r = aql_settle(c))) return r;        // (the append uses the HIP stream)
         HIPCHK(c, hipSetDevice(c->cfg.device_id));
         flush_adapt(c);                           // (the ladder AFTER the step's adaptation - what hens_download_state returns - and its swap counts)
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (timed && evs.size() < 2 * 4096) {
-            HIPCHK(c, hipEventCreate(&e0)); evs.push_back(e0);
-            HIPCHK(c, hipEventCreate(&e1)); evs.push_back(e1);
-        }
-        launch_chain_store(c, e0, e1);
-        HIPCHK(c, hipGetLastError());
-        ch.iteration.push_back((int64_t)c->iter);
-        ch.adapt_time.push_back(c->adapt_time);
-        ch.count += 1;
+        if ((r = launch_chain_store(c, tm))) return r;
         report_marked(c, ch.Ts == c->Tl);         // (k_chain_store moved the mark up to now - of the rungs it stores)
     }
-    if (!evs.empty()) {
+    if (!tm.evs.empty()) {                        // (nothing else in this call waits for the stream)
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        for (size_t k = 0; k + 1 < evs.size(); k += 2) {
-            float ms = 0;
-            if (hipEventElapsedTime(&ms, evs[k], evs[k + 1]) == hipSuccess) { ch.store_ms += ms; ch.n_timed += 1; }
-        }
-        for (hipEvent_t e : evs) (void)hipEventDestroy(e);
+        tm.fold();
     }
     return HENS_OK;
 }
@@ -3085,38 +3190,16 @@ int hens_chain_download(hens_ctx* ctx, int64_t first, int64_t count, double* x, 
                         int64_t* iteration, int64_t* adapt_time) {
     hens_ctx_impl* c = enter(ctx);
     if (!c) return fail(c, HENS_ERR_INVALID, "null context");
-    hens_ctx_impl::Chain& ch = c->chain;
-    if (!ch.on) return fail(c, HENS_ERR_STATE, "no chain (hens_chain_create)");
-    if (!hens_chain::range_ok(ch.count, first, count))
-        return fail(c, HENS_ERR_INVALID, "hens_chain_download: steps [%lld, %lld + %lld) outside the %lld stored", (long long)first, (long long)first, (long long)count, (long long)ch.count);
-    if (count == 0) return HENS_OK;
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    const size_t TsW = (size_t)ch.Ts * c->W, D = (size_t)dim_active(c), f = (size_t)first, n = (size_t)count;
-    if (x) HIPCHK(c, hipMemcpyAsync(x, ch.x + f * TsW * D, n * TsW * D * 8, hipMemcpyDeviceToHost, c->stream));
-    if (logl) HIPCHK(c, hipMemcpyAsync(logl, ch.L + f * TsW, n * TsW * 8, hipMemcpyDeviceToHost, c->stream));
-    if (logp) HIPCHK(c, hipMemcpyAsync(logp, ch.P + f * TsW, n * TsW * 8, hipMemcpyDeviceToHost, c->stream));
-    if (betas) HIPCHK(c, hipMemcpyAsync(betas, ch.betas + f * c->T, n * c->T * 8, hipMemcpyDeviceToHost, c->stream));
-    if (x || logl || logp || betas) HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (iteration) std::copy(ch.iteration.begin() + first, ch.iteration.begin() + first + count, iteration);
-    if (adapt_time) std::copy(ch.adapt_time.begin() + first, ch.adapt_time.begin() + first + count, adapt_time);
-    return HENS_OK;
+    if (const int r = chain_range(c, false, "hens_chain_download", first, count)) return r;
+    const size_t row = (size_t)c->chain.Ts * c->W * dim_active(c) * 8;
+    return chain_copy_out(c, first, count, {{x, c->chain.x[0], row}}, logl, logp, betas, iteration, adapt_time);
 }
 
 int hens_chain_totals(hens_ctx* ctx, double* accepted, double* swaps_accepted) {
     hens_ctx_impl* c = enter(ctx);
     if (!c) return fail(c, HENS_ERR_INVALID, "null context");
-    hens_ctx_impl::Chain& ch = c->chain;
-    if (!ch.on) return fail(c, HENS_ERR_STATE, "no chain (hens_chain_create)");
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    const size_t TsW = (size_t)ch.Ts * c->W, np = (size_t)std::max(c->T - 1, 0);
-    std::vector<uint32_t> acc(accepted ? TsW : 0);
-    std::vector<unsigned long long> sw(swaps_accepted ? np : 0);
-    if (!acc.empty()) HIPCHK(c, hipMemcpyAsync(acc.data(), ch.acc_tot, TsW * 4, hipMemcpyDeviceToHost, c->stream));
-    if (!sw.empty()) HIPCHK(c, hipMemcpyAsync(sw.data(), ch.swaps_tot, np * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (size_t i = 0; i < acc.size(); ++i) accepted[i] = (double)acc[i];
-    for (size_t i = 0; i < sw.size(); ++i) swaps_accepted[i] = (double)sw[i];
-    return HENS_OK;
+    if (const int r = chain_open(c, false)) return r;
+    return chain_totals(c, {{accepted, c->chain.acc_tot}}, swaps_accepted);
 }
 
 // ---- chain diagnostics (include/hipensemble.h: hens_chain_moments, hens_chain_act; csrc/hens_chain_stats.h) -----------------
@@ -3158,7 +3241,7 @@ int hens_chain_moments(hens_ctx* ctx, int32_t field, int64_t first, int64_t coun
     if (!c) return fail(c, HENS_ERR_INVALID, "null context");
     int r;
     if ((r = chain_stats_enter(c, "hens_chain_moments"))) return r;
-    hens_ctx_impl::Chain& ch = c->chain;
+    ChainStore& ch = c->chain;
     hens_chain::StatPlan pl{};
     if (!hens_chain::stat_plan(chain_shape(c, ch.Ts), ch.count, field, first, count, thin, ntemps, &pl))
         return fail(c, HENS_ERR_INVALID, "hens_chain_moments: field %d in [0, 2], count >= 1, thin >= 1, ntemps %d in [1, %d] and the kept steps %lld, %lld + %lld, ... (%lld of them) inside the %lld stored",
@@ -3170,7 +3253,7 @@ int hens_chain_moments(hens_ctx* ctx, int32_t field, int64_t first, int64_t coun
     char* dev = nullptr;
     HIPCHK(c, hipMalloc((void**)&dev, (size_t)pl.nseries * 8 * 3));
     ChainStatArgs a{};
-    a.src = (field == 0 ? ch.x : field == 1 ? ch.L : ch.P) + pl.offset;
+    a.src = (field == 0 ? ch.x[0] : field == 1 ? ch.L : ch.P) + pl.offset;
     a.stride = pl.stride; a.count = count; a.nseries = pl.nseries;
     a.sum = reinterpret_cast<double*>(dev);
     a.m2 = m2 ? reinterpret_cast<double*>(dev) + pl.nseries : nullptr;
@@ -3188,7 +3271,7 @@ int hens_chain_act(hens_ctx* ctx, int64_t first, int64_t count, int64_t thin, in
     if (!c) return fail(c, HENS_ERR_INVALID, "null context");
     int r;
     if ((r = chain_stats_enter(c, "hens_chain_act"))) return r;
-    hens_ctx_impl::Chain& ch = c->chain;
+    ChainStore& ch = c->chain;
     hens_chain::StatPlan pl{};
     if (window < 1 || !hens_chain::stat_plan(chain_shape(c, ch.Ts), ch.count, 0, first, count, thin, ntemps, &pl))
         return fail(c, HENS_ERR_INVALID, "hens_chain_act: window >= 1, count >= 1, thin >= 1, ntemps %d in [1, %d] and the kept steps %lld, %lld + %lld, ... (%lld of them) inside the %lld stored",
@@ -3205,7 +3288,7 @@ int hens_chain_act(hens_ctx* ctx, int64_t first, int64_t count, int64_t thin, in
     char* dev = nullptr;
     HIPCHK(c, hipMalloc((void**)&dev, (size_t)pl.nseries * 8 * 3));
     ChainStatArgs a{};
-    a.src = ch.x + pl.offset;
+    a.src = ch.x[0] + pl.offset;
     a.stride = pl.stride; a.count = count; a.nseries = pl.nseries;
     a.tau = reinterpret_cast<double*>(dev); a.mean = a.tau + pl.nseries; a.c0 = a.mean + pl.nseries;
     a.K = (int32_t)lags;
@@ -3277,7 +3360,7 @@ int hens_reset_counters(hens_ctx* ctx) {
     c->num_proposals_mh = 0;
     c->rj.num_mh = c->rj.num_bd = 0;
     c->report_valid = false;
-    c->rjchain.mark_valid = false;
+    c->chain.mark_valid = false;
     return HENS_OK;
 }
 
@@ -3911,16 +3994,7 @@ int hens_rj_step(hens_ctx* ctx, int64_t n_iters) {
 }
 
 // ---- chain store of a leaf-packing context (include/hipensemble.h: hens_rj_chain_*, hens_rj_step_chain; csrc/hens_rj_chain.h) ----
-static void rjchain_free(hens_ctx_impl* c) {
-    hens_ctx_impl::RjChain& ch = c->rjchain;
-    for (int b = 0; b < RJ_MAX_BRANCH; ++b) {
-        if (ch.x[b]) (void)hipFree(ch.x[b]);
-        if (ch.inds[b]) (void)hipFree(ch.inds[b]);
-    }
-    for (void* p : {(void*)ch.L, (void*)ch.P, (void*)ch.betas, (void*)ch.acc_tot, (void*)ch.bd_tot, (void*)ch.prev, (void*)ch.swaps_tot, (void*)ch.swaps_step})
-        if (p) (void)hipFree(p);
-    ch = hens_ctx_impl::RjChain{};
-}
+// The host protocol is `chain store: what both families share` above; here what a leaf-packing chain has of its own.
 static int rjchain_supported(hens_ctx_impl* c) {
     if (c->cfg.likelihood_kind != HENS_LIKE_TEMPLATE)
         return fail(c, HENS_ERR_UNSUPPORTED, "hens_rj_chain_*: the chain store of a leaf-packing context (HENS_LIKE_TEMPLATE); others: hens_chain_create / hens_step_chain");
@@ -3939,92 +4013,54 @@ static hens_chain::RjShape rjchain_shape(const hens_ctx_impl* c, int Ts) {
 static_assert(hens_chain::RJ_BRANCHES == RJ_MAX_BRANCH, "hens_chain_host.h: branches of a record");
 // a model set anew: the chain of the old one has another shape
 static int rjchain_drop(hens_ctx_impl* c) {
-    if (!c->rjchain.on) return HENS_OK;
+    if (!c->chain.on) return HENS_OK;
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    rjchain_free(c);
+    c->chain.release();
     return HENS_OK;
 }
 
 int hens_rj_chain_create(hens_ctx* ctx, int64_t capacity, int32_t ntemps_store) {
     hens_ctx_impl* c = enter(ctx);
     if (!c) return fail(c, HENS_ERR_INVALID, "null context");
-    int r;
-    if ((r = rjchain_supported(c))) return r;
-    if (capacity < 1) return fail(c, HENS_ERR_INVALID, "hens_rj_chain_create: capacity < 1");
-    if (ntemps_store < 0 || ntemps_store > c->T) return fail(c, HENS_ERR_INVALID, "hens_rj_chain_create: ntemps_store outside [0, %d]", c->T);
-    const int Ts = ntemps_store ? ntemps_store : c->T;
+    int r, Ts = 0;
+    if ((r = rjchain_supported(c)) || (r = chain_create_args(c, "hens_rj_chain_create", capacity, ntemps_store, &Ts))) return r;
     hens_chain::RjSizes sz{};
     if (!hens_chain::rj_sizes(rjchain_shape(c, Ts), capacity, &sz))
         return fail(c, HENS_ERR_INVALID, "hens_rj_chain_create: %lld stored steps of %d x %d x %d coordinates do not fit an int64 byte count", (long long)capacity, Ts, c->W, c->rj.M.ind_off);
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    HIPCHK(c, hipStreamSynchronize(c->stream));     // (a chain being replaced may still be written)
-    rjchain_free(c);
-    hens_ctx_impl::RjChain& ch = c->rjchain;
-    const size_t TsW = (size_t)Ts * c->W, TW = (size_t)c->Tl * c->W, np = (size_t)std::max(c->T - 1, 1);
-    auto get = [&](void** p, size_t bytes) { return hipMalloc(p, bytes) == hipSuccess; };
-    bool ok = get((void**)&ch.L, (size_t)sz.lp) && get((void**)&ch.P, (size_t)sz.lp) && get((void**)&ch.betas, (size_t)sz.betas) &&
-              get((void**)&ch.acc_tot, TsW * 4) && get((void**)&ch.bd_tot, TsW * 4) && get((void**)&ch.prev, 2 * TW * 4) &&
-              get((void**)&ch.swaps_tot, np * 8) && get((void**)&ch.swaps_step, np * 8);
-    for (int b = 0; ok && b < c->rj.M.nb; ++b) ok = get((void**)&ch.x[b], (size_t)sz.x[b]) && get((void**)&ch.inds[b], (size_t)sz.inds[b]);
-    const int64_t extra = (int64_t)(2 * TsW * 4 + 2 * TW * 4 + 2 * np * 8);
-    if (!ok) {
-        const hipError_t e = hipGetLastError();     // (cleared: the stepping calls check it)
-        rjchain_free(c);
-        return fail(c, HENS_ERR_HIP, "hens_rj_chain_create: allocating %lld bytes of device memory for %lld stored steps failed: %s",
-                    (long long)(sz.total + extra), (long long)capacity, hipGetErrorString(e));
-    }
-    ch.capacity = capacity; ch.Ts = Ts; ch.sz = sz;
-    ch.bytes = sz.total + extra;
-    ch.on = true;
-    return hens_rj_chain_reset(ctx);
+    ChainStore& ch = c->chain;
+    const size_t TsW = (size_t)Ts * c->W, TW = (size_t)c->Tl * c->W, np = swap_slots(c, 1);
+    std::vector<ChainBuf> bufs = {{&ch.L, (size_t)sz.lp}, {&ch.P, (size_t)sz.lp}, {&ch.betas, (size_t)sz.betas}, {&ch.acc_tot, TsW * 4},
+                                  {&ch.bd_tot, TsW * 4}, {&ch.prev, 2 * TW * 4}, {&ch.swaps_tot, np * 8}, {&ch.swaps_step, np * 8}};
+    for (int b = 0; b < c->rj.M.nb; ++b) bufs.insert(bufs.end(), {{&ch.x[b], (size_t)sz.x[b]}, {&ch.inds[b], (size_t)sz.inds[b]}});
+    return chain_create(c, "hens_rj_chain_create", capacity, Ts, bufs);
 }
 
 int hens_rj_chain_reset(hens_ctx* ctx) {
     hens_ctx_impl* c = enter(ctx);
     if (!c) return fail(c, HENS_ERR_INVALID, "null context");
-    hens_ctx_impl::RjChain& ch = c->rjchain;
-    if (!ch.on) return fail(c, HENS_ERR_STATE, "no chain (hens_rj_chain_create)");
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    HIPCHK(c, hipMemsetAsync(ch.acc_tot, 0, (size_t)ch.Ts * c->W * 4, c->stream));
-    HIPCHK(c, hipMemsetAsync(ch.bd_tot, 0, (size_t)ch.Ts * c->W * 4, c->stream));
-    HIPCHK(c, hipMemsetAsync(ch.swaps_tot, 0, (size_t)std::max(c->T - 1, 1) * 8, c->stream));
-    ch.count = 0;
-    ch.iteration.clear(); ch.adapt_time.clear();
-    return HENS_OK;
+    if (const int r = chain_open(c, true)) return r;
+    return chain_reset(c);
 }
 
 int hens_rj_chain_destroy(hens_ctx* ctx) {
     hens_ctx_impl* c = enter(ctx);
     if (!c) return fail(c, HENS_ERR_INVALID, "null context");
-    if (!c->rjchain.on) return HENS_OK;
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    rjchain_free(c);
-    return HENS_OK;
+    return chain_destroy(c, true);
 }
 
+// refuses what rjchain_supported refuses (hens_chain_info answers on any context)
 int hens_rj_chain_info(hens_ctx* ctx, hens_chain_info_t* out) {
     hens_ctx_impl* c = CTX(ctx);
     if (!c || !out) return fail(c, HENS_ERR_INVALID, "null argument");
-    int r;
-    if ((r = rjchain_supported(c))) return r;
-    const hens_ctx_impl::RjChain& ch = c->rjchain;
-    hens_chain_info_t o{};
+    if (const int r = rjchain_supported(c)) return r;
     hens_chain::RjSizes one{};
-    (void)hens_chain::rj_sizes(rjchain_shape(c, ch.on ? ch.Ts : c->T), 1, &one);
-    o.capacity = ch.capacity; o.count = ch.count; o.ntemps_store = ch.on ? ch.Ts : 0; o.bytes = ch.bytes; o.step_bytes = one.step;
-    o.n_store_timed = ch.n_timed; o.store_ms = ch.store_ms;
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    size_t fr = 0, tot = 0;
-    HIPCHK(c, hipMemGetInfo(&fr, &tot));
-    o.free_bytes = (int64_t)fr;
-    *out = o;
-    return HENS_OK;
+    (void)hens_chain::rj_sizes(rjchain_shape(c, chain_Ts(c, true)), 1, &one);
+    return chain_info(c, true, one.step, out);
 }
 
-// one append on the HIP stream: the state by field as it stands between hens_rj_step iterations, the ladder settled by the caller
-static void launch_rj_chain_store(hens_ctx_impl* c, hipEvent_t e0, hipEvent_t e1) {
-    hens_ctx_impl::RjChain& ch = c->rjchain;
+// one append: the state by field as it stands between hens_rj_step iterations, the ladder settled by the caller
+static int launch_rj_chain_store(hens_ctx_impl* c, ChainTimer& tm) {
+    ChainStore& ch = c->chain;
     const RjModel& M = c->rj.M;
     const size_t TW = (size_t)c->Tl * c->W, TsW = (size_t)ch.Ts * c->W, n = (size_t)ch.count;
     RjChainArgs a{};
@@ -4046,22 +4082,16 @@ static void launch_rj_chain_store(hens_ctx_impl* c, hipEvent_t e0, hipEvent_t e1
     const hens_chain::RjShape shape = rjchain_shape(c, ch.Ts);
     const int vec = hens_chain::rj_store_vec(shape, c->D);
     a.lpr_shift = hens_chain::rj_lane_shift(shape, vec);
-    const int64_t threads = (int64_t)TsW << a.lpr_shift;
-    const dim3 grid((unsigned)((threads + 255) / 256));
-    void* args[] = {&a};
     const void* fn = vec == 2 ? reinterpret_cast<const void*>(k_rj_chain_store<2>) : reinterpret_cast<const void*>(k_rj_chain_store<1>);
-    if (e0) (void)hipExtLaunchKernel(fn, grid, dim3(256), args, 0, c->stream, e0, e1, 0);
-    else (void)hipLaunchKernel(fn, grid, dim3(256), args, 0, c->stream);
+    return chain_append(c, tm, fn, &a, a.lpr_shift);
 }
 
 int hens_rj_step_chain(hens_ctx* ctx, int64_t n_store, int64_t iters_per_store) {
     hens_ctx_impl* c = enter(ctx);
     if (!c) return fail(c, HENS_ERR_INVALID, "null context");
     int r;
-    if ((r = rjchain_supported(c))) return r;
-    hens_ctx_impl::RjChain& ch = c->rjchain;
-    if (!ch.on) return fail(c, HENS_ERR_STATE, "no chain (hens_rj_chain_create)");
-    if ((r = rj_ready(c))) return r;
+    if ((r = rjchain_supported(c)) || (r = chain_open(c, true)) || (r = rj_ready(c))) return r;
+    ChainStore& ch = c->chain;
     int64_t iters = 0;
     switch (hens_chain::rj_append_check(ch.capacity, ch.count, n_store, iters_per_store, &iters)) {
     case hens_chain::INVALID: return fail(c, HENS_ERR_INVALID, "hens_rj_step_chain: n_store >= 0 and iters_per_store >= 1, and their product an int64");
@@ -4072,10 +4102,8 @@ int hens_rj_step_chain(hens_ctx* ctx, int64_t n_store, int64_t iters_per_store) 
     if ((r = counter_room(c, iters))) return r;
     RjStepping st(c);
     if ((r = st.begin(iters))) return r;
-    const bool timed = c->per_kernel_events == 1;
     const size_t TW = (size_t)c->Tl * c->W;
-    std::vector<hipEvent_t> evs;
-    ch.n_timed = 0; ch.store_ms = 0.0;
+    ChainTimer tm(c);
     for (int64_t s = 0; s < n_store; ++s) {
         for (int64_t i = 0; i + 1 < iters_per_store; ++i)
             if ((r = st.iteration(nullptr))) return r;
@@ -4090,17 +4118,8 @@ int hens_rj_step_chain(hens_ctx* ctx, int64_t n_store, int64_t iters_per_store) 
         flush_adapt(c);                           // (the ladder AFTER the step's adaptation - what hens_download_state returns)
         // what hens_download_state runs in front of its copy: the stored log_like is the value the device goes on with
         if (c->rj.tm && c->rj.tm_valid && c->rj.tm_drift && (r = rj_evaluate(c))) return r;
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (timed && evs.size() < 2 * 4096) {
-            HIPCHK(c, hipEventCreate(&e0)); evs.push_back(e0);
-            HIPCHK(c, hipEventCreate(&e1)); evs.push_back(e1);
-        }
-        launch_rj_chain_store(c, e0, e1);
-        HIPCHK(c, hipGetLastError());
-        ch.iteration.push_back((int64_t)c->iter);
-        ch.adapt_time.push_back(c->adapt_time);
-        ch.count += 1;
-        ch.mark_valid = true;
+        if ((r = launch_rj_chain_store(c, tm))) return r;
+        ch.mark_valid = true;                     // (k_rj_chain_store moved the mark up to now)
         ch.mark_books = c->rj.num_mh + c->rj.num_bd;
     }
     c->rj.defer_adapt = false;
@@ -4109,13 +4128,7 @@ int hens_rj_step_chain(hens_ctx* ctx, int64_t n_store, int64_t iters_per_store) 
     HIPCHK(c, hipEventRecord(c->ev1, c->stream));
     c->timing.n_iters = iters;
     r = check_flags(c, true);                     // (once per call, with the call's last launch: the host waits for nothing in between)
-    if (!evs.empty()) {
-        for (size_t k = 0; k + 1 < evs.size(); k += 2) {
-            float ms = 0;
-            if (hipEventElapsedTime(&ms, evs[k], evs[k + 1]) == hipSuccess) { ch.store_ms += ms; ch.n_timed += 1; }
-        }
-        for (hipEvent_t e : evs) (void)hipEventDestroy(e);
-    }
+    tm.fold();                                    // (check_flags has waited for the stream; its result is the call's)
     return r;
 }
 
@@ -4123,46 +4136,20 @@ int hens_rj_chain_download(hens_ctx* ctx, int64_t first, int64_t count, int32_t 
                            double* logp, double* betas, int64_t* iteration, int64_t* adapt_time) {
     hens_ctx_impl* c = enter(ctx);
     if (!c) return fail(c, HENS_ERR_INVALID, "null context");
-    hens_ctx_impl::RjChain& ch = c->rjchain;
-    if (!ch.on) return fail(c, HENS_ERR_STATE, "no chain (hens_rj_chain_create)");
-    if (!hens_chain::range_ok(ch.count, first, count))
-        return fail(c, HENS_ERR_INVALID, "hens_rj_chain_download: steps [%lld, %lld + %lld) outside the %lld stored", (long long)first, (long long)first, (long long)count, (long long)ch.count);
+    if (const int r = chain_range(c, true, "hens_rj_chain_download", first, count)) return r;
     if (!hens_chain::rj_branch_ok(c->rj.M.nb, branch) || (branch < 0 && (x || inds)))
         return fail(c, HENS_ERR_INVALID, "hens_rj_chain_download: branch %d of %d (-1: the shared fields, x = inds = NULL)", branch, c->rj.M.nb);
-    if (count == 0) return HENS_OK;
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    const size_t TsW = (size_t)ch.Ts * c->W, f = (size_t)first, n = (size_t)count;
-    if (branch >= 0) {
-        const size_t nl = (size_t)c->rj.M.nl[branch], seg = nl * (size_t)c->rj.M.nd[branch];
-        if (x) HIPCHK(c, hipMemcpyAsync(x, ch.x[branch] + f * TsW * seg, n * TsW * seg * 8, hipMemcpyDeviceToHost, c->stream));
-        if (inds) HIPCHK(c, hipMemcpyAsync(inds, ch.inds[branch] + f * TsW * nl, n * TsW * nl, hipMemcpyDeviceToHost, c->stream));
-    }
-    if (logl) HIPCHK(c, hipMemcpyAsync(logl, ch.L + f * TsW, n * TsW * 8, hipMemcpyDeviceToHost, c->stream));
-    if (logp) HIPCHK(c, hipMemcpyAsync(logp, ch.P + f * TsW, n * TsW * 8, hipMemcpyDeviceToHost, c->stream));
-    if (betas) HIPCHK(c, hipMemcpyAsync(betas, ch.betas + f * c->T, n * c->T * 8, hipMemcpyDeviceToHost, c->stream));
-    if (x || inds || logl || logp || betas) HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (iteration) std::copy(ch.iteration.begin() + first, ch.iteration.begin() + first + count, iteration);
-    if (adapt_time) std::copy(ch.adapt_time.begin() + first, ch.adapt_time.begin() + first + count, adapt_time);
-    return HENS_OK;
+    const ChainStore& ch = c->chain;
+    const int b = std::max(branch, 0);            // (branch -1: x and inds are null, nothing of a branch is copied)
+    const size_t rows = (size_t)ch.Ts * c->W * c->rj.M.nl[b];
+    return chain_copy_out(c, first, count, {{x, ch.x[b], rows * c->rj.M.nd[b] * 8}, {inds, ch.inds[b], rows}}, logl, logp, betas, iteration, adapt_time);
 }
 
 int hens_rj_chain_totals(hens_ctx* ctx, double* accepted, double* rj_accepted, double* swaps_accepted) {
     hens_ctx_impl* c = enter(ctx);
     if (!c) return fail(c, HENS_ERR_INVALID, "null context");
-    hens_ctx_impl::RjChain& ch = c->rjchain;
-    if (!ch.on) return fail(c, HENS_ERR_STATE, "no chain (hens_rj_chain_create)");
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    const size_t TsW = (size_t)ch.Ts * c->W, np = (size_t)std::max(c->T - 1, 0);
-    std::vector<uint32_t> acc(accepted ? TsW : 0), bd(rj_accepted ? TsW : 0);
-    std::vector<unsigned long long> sw(swaps_accepted ? np : 0);
-    if (!acc.empty()) HIPCHK(c, hipMemcpyAsync(acc.data(), ch.acc_tot, TsW * 4, hipMemcpyDeviceToHost, c->stream));
-    if (!bd.empty()) HIPCHK(c, hipMemcpyAsync(bd.data(), ch.bd_tot, TsW * 4, hipMemcpyDeviceToHost, c->stream));
-    if (!sw.empty()) HIPCHK(c, hipMemcpyAsync(sw.data(), ch.swaps_tot, np * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (size_t i = 0; i < acc.size(); ++i) accepted[i] = (double)acc[i];
-    for (size_t i = 0; i < bd.size(); ++i) rj_accepted[i] = (double)bd[i];
-    for (size_t i = 0; i < sw.size(); ++i) swaps_accepted[i] = (double)sw[i];
-    return HENS_OK;
+    if (const int r = chain_open(c, true)) return r;
+    return chain_totals(c, {{accepted, c->chain.acc_tot}, {rj_accepted, c->chain.bd_tot}}, swaps_accepted);
 }
 
 // ---- leaf-packing moves with a HOST-CALLABLE likelihood (round 6; ensemble.py:1306-1334,1340-1545, rj.py:145-388) ---------------

@@ -1,16 +1,14 @@
-// hens_chain_host.h - the capacity / range arithmetic of the chain stores (hens_chain_create, hens_step_chain, hens_chain_download and
-// their hens_rj_chain_* twins) as plain host functions without HIP types: hens.hip calls them, and tools/chain_host_check.cpp runs them alone under
-// -fsanitize=address,undefined (sizes come straight from the caller: every product is overflow-checked before anything is
-// allocated, launched or copied).
+// hens_chain_host.h - the capacity / range / launch arithmetic of the chain store's two families (hens_chain_*, hens_step_chain; on a
+// leaf-packing context hens_rj_chain_*, hens_rj_step_chain: one host protocol in hens.hip) as plain host functions without HIP types:
+// hens.hip calls them, and tools/chain_host_check.cpp runs them alone under -fsanitize=address,undefined (sizes come straight from
+// the caller: every product is overflow-checked before anything is allocated, launched or copied).
 #pragma once
 #include <cstdint>
 
 namespace hens_chain {
 
 // what one chain holds, in doubles per stored step: x[Ts][W][D], logl / logp [Ts][W] each, betas[T]
-struct Shape {
-    int64_t T, Ts, W, D;
-};
+struct Shape { int64_t T, Ts, W, D; };
 struct Sizes {          // bytes of the four device arrays of a chain of `capacity` steps, and of one step
     int64_t x, lp, betas, step, total;
 };
@@ -90,8 +88,10 @@ inline int rj_append_check(int64_t capacity, int64_t count, int64_t n_store, int
 // hens_rj_chain_download's branch: one of the model's, or -1 (the shared fields only)
 inline bool rj_branch_ok(int64_t nb, int64_t branch) { return branch >= -1 && branch < nb; }
 
-// doubles per lane of the append launch: 2 (16-byte loads and stores) where every branch's segment starts and ends on an even
-// double on both sides - the record's rows are RW doubles apart, the destination's rows nl nd -, else 1
+// The append launch of BOTH families: a row is a list of segments, and a fixed-dimension chain's (k_chain_store) is the one-segment case
+inline RjShape one_segment(const Shape& s) { return RjShape{s.T, s.Ts, s.W, 1, {1}, {s.D}}; }      // D doubles at offset 0
+// doubles per lane of the append launch: 2 (16-byte loads and stores) where every segment starts and ends on an even double on both
+// sides - the source's rows are RW doubles apart, the destination's rows nl nd -, else 1   (one segment: RW and D both even)
 inline int rj_store_vec(const RjShape& s, int64_t RW) {
     int64_t off = 0;
     if (RW % 2) return 1;
@@ -103,7 +103,7 @@ inline int rj_store_vec(const RjShape& s, int64_t RW) {
     return 2;
 }
 
-// lanes per record as a shift: the smallest power of two that covers the widest segment, at most a wave
+// lanes per record as a shift: the smallest power of two that covers the widest segment, at most a wave (a wider one takes rounds)
 inline int rj_lane_shift(const RjShape& s, int vec) {
     int64_t widest = 1;
     for (int b = 0; b < s.nb; ++b) widest = s.nl[b] * s.nd[b] > widest ? s.nl[b] * s.nd[b] : widest;

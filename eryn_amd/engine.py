@@ -39,7 +39,34 @@ def padded_width(ndim, likelihood):
     return next(w for w in FAST_WIDTHS if w >= ndim)
 
 
-class HipEnsemble:
+class ChainStoreCalls:
+    """The four chain-store calls that read alike on both families, over the C entry points ``CHAIN_PREFIX + name``
+    (include/hipensemble.h: hens_chain_* of a HipEnsemble, hens_rj_chain_* of an RJEngine); needs ``self.lib`` and ``self.ctx``."""
+    CHAIN_PREFIX = None
+
+    def _chain_call(self, name, *args):
+        check(getattr(self.lib, self.CHAIN_PREFIX + name)(self.ctx, *args), self.ctx)
+
+    def chain_create(self, capacity, ntemps_store=None):
+        """Room for ``capacity`` stored steps of rungs ``[0, ntemps_store)`` (None: all) in device memory; replaces a chain
+        that exists."""
+        self._chain_call("create", int(capacity), int(ntemps_store or 0))
+
+    def chain_reset(self):
+        self._chain_call("reset")
+
+    def chain_destroy(self):
+        self._chain_call("destroy")
+
+    def chain_info(self):
+        info = _lib.HensChainInfo()
+        self._chain_call("info", C.byref(info))
+        return {k: getattr(info, k) for k, _ in _lib.HensChainInfo._fields_}
+
+
+class HipEnsemble(ChainStoreCalls):
+    CHAIN_PREFIX = "hens_chain_"
+
     def __init__(self, ntemps, nwalkers, ndim, likelihood, lo, hi, a=2.0, tempered=None,
                  adaptive=True, adaptation_lag=10000, adaptation_time=100, stop_adaptation=-1,
                  live_dangerously=False, fill_value=-1e300, seed=0, rung_range=None, device_id=0,
@@ -227,23 +254,7 @@ class HipEnsemble:
         check(self.lib.hens_step_report(self.ctx, int(n_iters), int(n_last), ptr(acc), ptr(swaps) if self.T > 1 else None, ptr(betas)), self.ctx)
         return acc, swaps, betas
 
-    # -- chain store (include/hipensemble.h: hens_chain_*, hens_step_chain) ---------------------------------
-    def chain_create(self, capacity, ntemps_store=None):
-        """Room for ``capacity`` stored steps of rungs ``[0, ntemps_store)`` (None: all) in device memory; replaces a chain
-        that exists."""
-        check(self.lib.hens_chain_create(self.ctx, int(capacity), int(ntemps_store or 0)), self.ctx)
-
-    def chain_reset(self):
-        check(self.lib.hens_chain_reset(self.ctx), self.ctx)
-
-    def chain_destroy(self):
-        check(self.lib.hens_chain_destroy(self.ctx), self.ctx)
-
-    def chain_info(self):
-        info = _lib.HensChainInfo()
-        check(self.lib.hens_chain_info(self.ctx, C.byref(info)), self.ctx)
-        return {k: getattr(info, k) for k, _ in _lib.HensChainInfo._fields_}
-
+    # -- chain store (include/hipensemble.h: hens_chain_*, hens_step_chain; chain_create / _reset / _destroy / _info: ChainStoreCalls) --
     def step_chain(self, n_store, iters_per_store=1, n_last=1):
         """``n_store`` stored steps of ``iters_per_store`` iterations each, appended to the chain on the device; the accepted
         totals take the last ``n_last`` iterations of every step (ensemble.py:968-979).  Nothing is copied to the host."""

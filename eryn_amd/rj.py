@@ -13,7 +13,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, f64, ptr
-from .engine import HipEnsemble
+from .engine import ChainStoreCalls, HipEnsemble
 
 KIND_PULSE, KIND_SINE = 0, 1
 # the leaf kinds the device evaluates, name -> (id, parameters per leaf) (include/hipensemble.h: HENS_RJ_KIND_*): value at data point t
@@ -149,7 +149,9 @@ class CallableLikelihood:
         return ll.reshape(T, W)
 
 
-class RJEngine:
+class RJEngine(ChainStoreCalls):
+    CHAIN_PREFIX = "hens_rj_chain_"
+
     def __init__(self, ntemps, nwalkers, branches, t, y, sigma, seed=0, device_id=0, adaptive=True,
                  adaptation_lag=10000, adaptation_time=100, stop_adaptation=-1, fill_value=-1e300, a=2.0, live_dangerously=False,
                  kinds_entry=None):
@@ -375,23 +377,7 @@ class RJEngine:
     def step(self, n_iters):
         check(self.lib.hens_rj_step(self.ctx, int(n_iters)), self.ctx)
 
-    # -- chain store (include/hipensemble.h: hens_rj_chain_*, hens_rj_step_chain) ---------------------------------
-    def chain_create(self, capacity, ntemps_store=None):
-        """Room for ``capacity`` stored steps of rungs ``[0, ntemps_store)`` (None: all) in device memory; replaces a chain
-        that exists."""
-        check(self.lib.hens_rj_chain_create(self.ctx, int(capacity), int(ntemps_store or 0)), self.ctx)
-
-    def chain_reset(self):
-        check(self.lib.hens_rj_chain_reset(self.ctx), self.ctx)
-
-    def chain_destroy(self):
-        check(self.lib.hens_rj_chain_destroy(self.ctx), self.ctx)
-
-    def chain_info(self):
-        info = _lib.HensChainInfo()
-        check(self.lib.hens_rj_chain_info(self.ctx, C.byref(info)), self.ctx)
-        return {k: getattr(info, k) for k, _ in _lib.HensChainInfo._fields_}
-
+    # -- chain store (include/hipensemble.h: hens_rj_chain_*, hens_rj_step_chain; chain_create / _reset / _destroy / _info: ChainStoreCalls) --
     def step_chain(self, n_store, iters_per_store=1):
         """``n_store`` stored steps of ``iters_per_store`` iterations each, appended to the chain on the device - per stored step
         what ``step(iters_per_store)`` + ``download(nan_fill=True)`` gives, bit for bit.  Nothing is copied to the host."""

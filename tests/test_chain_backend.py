@@ -2,6 +2,8 @@
 import ctypes as C
 import os
 import re
+import shutil
+import subprocess
 
 import numpy as np
 import pytest
@@ -195,3 +197,22 @@ def test_chain_code_never_mentions_the_oracle_and_the_census_stands():
         assert "oracle" not in open(os.path.join(ROOT, "eryn_amd", f)).read(), f
     from tests.test_host_logic import test_fence_free_kernels_store_census_is_the_reviewed_one as census
     census()
+
+
+def test_capacity_and_launch_arithmetic_under_a_sanitizer_build(tmp_path):
+    """tools/chain_host_check.cpp: a stand-alone program over csrc/hens_chain_host.h's capacity, range and append-launch arithmetic of
+    both chain families, built with -fsanitize=address,undefined where the compiler has the runtimes (plainly otherwise) and run on
+    the CPU."""
+    cxx = shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
+    assert cxx, "no host C++ compiler"
+    src, exe = os.path.join(ROOT, "tools", "chain_host_check.cpp"), str(tmp_path / "chain_host_check")
+    base = [cxx, "-std=c++17", "-O1", "-g", src, "-o", exe]
+    r = subprocess.run(base + ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"], capture_output=True, text=True)
+    build = "sanitizer build (address, undefined)"
+    if r.returncode != 0:
+        build = "plain build - the sanitizer build failed: " + (r.stderr.strip().splitlines() or ["no message"])[-1]
+        r = subprocess.run(base, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    print("chain_host_check:", build)                # (pytest -rA shows which build ran)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stdout + r.stderr

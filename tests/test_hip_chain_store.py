@@ -340,6 +340,21 @@ def test_error_codes():
     eng.close()
 
 
+def test_append_launches_are_timed_while_profiling_is_on():
+    """hens_set_profiling 1: an event pair around every append launch of the call, read into n_store_timed / store_ms; off again:
+    the next call's figures are zero (the leaf-packing family: tests/test_hip_rj_chain_store.py::test_protocol)."""
+    eng = engine(CASES["two_col_T8"])
+    eng.chain_create(4)
+    eng.set_profiling(1)
+    eng.step_chain(2, 2, 1)
+    info = eng.chain_info()
+    assert info["n_store_timed"] == 2 and info["store_ms"] > 0
+    eng.set_profiling(0)
+    eng.step_chain(1, 1, 1)
+    assert eng.chain_info()["n_store_timed"] == 0
+    eng.close()
+
+
 def test_contexts_without_a_chain_store():
     from eryn_amd.likelihood import HostLikelihood
     from eryn_amd.rj import _TemplateLikelihood

@@ -1,8 +1,9 @@
 // chain_host_check.cpp - the chain store's capacity / range arithmetic (eryn_amd/csrc/hens_chain_host.h) on its own, for a
 // sanitizer build on the host:
 //     c++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all tools/chain_host_check.cpp -o chain_host_check && ./chain_host_check
-// Covers the fixed-dimension chain (hens_chain_*) and the leaf-packing one (hens_rj_chain_*: sizes per branch, branch range, store
-// width and lanes per record of k_rj_chain_store).  Walks the functions over the edges of their domains (zero, one, INT64_MAX, products that pass 2^63) and over a grid of ordinary
+// (tests/test_chain_backend.py::test_capacity_and_launch_arithmetic_under_a_sanitizer_build builds and runs it so.)
+// Covers the fixed-dimension chain (hens_chain_*) and the leaf-packing one (hens_rj_chain_*: sizes per branch, branch range), and
+// the store width and lanes per record of both append kernels (k_chain_store: one segment; k_rj_chain_store).  Walks the functions over the edges of their domains (zero, one, INT64_MAX, products that pass 2^63) and over a grid of ordinary
 // shapes, and replays what hens_chain_download does with an accepted range on host arrays of exactly `count` entries, so that an
 // accepted range that reaches outside them is an AddressSanitizer report.  Exit status 0 and "ok" = every expectation held.
 #include "../eryn_amd/csrc/hens_chain_host.h"
@@ -131,6 +132,23 @@ int main() {
                         for (int64_t k = e * 8; k < (e + vec) * 8; ++k) dst[(size_t)k] += 1;
                 for (char ch : dst) EXPECT(ch == 1);                            // every byte written exactly once
             }
+        }
+    // the fixed-dimension chain is the one-segment case of the same two functions: the width and shift launch_chain_store had inline,
+    // and k_chain_store's copy loop (csrc/hens_chain.h) on a row of exactly D doubles
+    for (int64_t D : {1, 2, 3, 7, 8, 9, 63, 64, 65, 127, 128, 129, 130})
+        for (int64_t RW : {D, D + 1}) {
+            const RjShape s = one_segment(Shape{4, 3, 10, D});
+            EXPECT(s.nb == 1 && s.nl[0] * s.nd[0] == D && s.T == 4 && s.Ts == 3 && s.W == 10);
+            const int vec = rj_store_vec(s, RW), sh = rj_lane_shift(s, vec), lpr = 1 << sh;
+            EXPECT(vec == ((RW % 2 == 0 && D % 2 == 0) ? 2 : 1));
+            int want = 0;
+            while ((1 << want) * vec < D && want < 6) ++want;
+            EXPECT(sh == want);
+            std::vector<char> dst((size_t)D * 8, 0);                            // (an overrun is an ASan report)
+            for (int j = 0; j < lpr; ++j)
+                for (int64_t e = (int64_t)j * vec; e + vec <= D; e += (int64_t)lpr * vec)
+                    for (int64_t k = e * 8; k < (e + vec) * 8; ++k) dst[(size_t)k] += 1;
+            for (char ch : dst) EXPECT(ch == 1);                                // every byte written exactly once
         }
     // what hens_rj_chain_download copies for an accepted (range, branch): inside buffers of exactly the sizes rj_sizes gives
     for (int64_t count = 0; count <= 5; ++count) {
