@@ -120,6 +120,10 @@ SIGNATURES = {
     "hens_rj_step_chain": (C.c_int, [_P, C.c_int64, C.c_int64]),
     "hens_rj_chain_download": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int32, _P, _P, _P, _P, _P, _P, _P]),
     "hens_rj_chain_totals": (C.c_int, [_P, _P, _P, _P]),
+    "hens_rj_chain_leaves": (C.c_int, [_P, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _P, _P]),
+    "hens_rj_chain_leaf_moments": (C.c_int, [_P, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_int64, _P, _P, _P]),
+    "hens_rj_chain_moments": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _P, _P, _P]),
+    "hens_rj_chain_stats_ms": (C.c_int, [_P, _P, _P]),
     "hens_pipe_init": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P]),
     "hens_pipe_connect": (C.c_int, [_P, _P]),
     "hens_pipe_connect_local": (C.c_int, [_P, _P]),

@@ -5,7 +5,9 @@ The reference's storage engine (eryn/backends: HDF5, resume) is out of scope for
 reference's Backend (backends/backend.py:354-385, 616-817): ``get_autocorr_time``, ``get_autocorr_thin_burn``,
 ``get_gelman_rubin_convergence_diagnostic`` and ``get_evidence_estimate`` on ``Backend`` and ``DeviceBackend``, computed by
 ``eryn_amd.chain_stats`` on a host chain and by the library's k_chain_moments / k_chain_act where the chain sits in device memory -
-the same bits either way.  Not built: the stepping-stone evidence, diagnostics of ``RJDeviceBackend``.
+the same bits either way.  ``RJDeviceBackend`` has the ones defined under reversible jump - the Gelman-Rubin diagnostic with the
+reference's projection through the leaf masks, the evidence, and the leaf counts (``get_nleaves``, ``get_nleaves_counts``) - on
+k_rj_chain_leaves / k_rj_chain_leaf_moments / k_chain_moments.  Not built: the stepping-stone evidence.
 """
 import numpy as np
 
@@ -68,16 +70,7 @@ class _Diagnostics:
         """``{branch: {rung: Rhat[ndim]}}`` (utils/utility.py:279-330 ``psrf`` per stored rung), and the reference's table."""
         first, count, thin = self._kept(discard, thin)
         nt = self._stat_rungs()
-        r = 0 if per_walker else chain_stats.third_split(self.nwalkers, count)[2]
-        out = {}
-        for name in self.branch_names:
-            s, m2, _ = self._stat_moments(name, first, count, thin, nt)
-            head = tail = None
-            if r:
-                head = self._stat_moments(name, first, r, thin, nt)[:2]
-                tail = self._stat_moments(name, first + (count - r) * thin, r, thin, nt)[:2]
-            out[name] = {t: chain_stats.psrf_from_moments(count, s[t], m2[t], head and (head[0][t], head[1][t]),
-                                                          tail and (tail[0][t], tail[1][t]), per_walker) for t in range(nt)}
+        out = {name: self._psrf_branch(name, first, count, thin, nt, per_walker) for name in self.branch_names}
         if doprint:
             print("  Gelman-Rubin diagnostic \n  <R\u0302>: Mean value for all parameters\n")
             print("  --------------")
@@ -89,6 +82,17 @@ class _Diagnostics:
                     print("   {:01d}\t{:3.2f}".format(t, np.mean(out[name][t])))
                 print("\n")
         return out
+
+    def _psrf_branch(self, name, first, count, thin, nt, per_walker):
+        """``{rung: Rhat[ndim]}`` of one branch whose chain enters ``psrf`` as it lies (one leaf per walker)."""
+        r = 0 if per_walker else chain_stats.third_split(self.nwalkers, count)[2]
+        s, m2, _ = self._stat_moments(name, first, count, thin, nt)
+        head = tail = None
+        if r:
+            head = self._stat_moments(name, first, r, thin, nt)[:2]
+            tail = self._stat_moments(name, first + (count - r) * thin, r, thin, nt)[:2]
+        return {t: chain_stats.psrf_from_moments(count, s[t], m2[t], head and (head[0][t], head[1][t]),
+                                                 tail and (tail[0][t], tail[1][t]), per_walker) for t in range(nt)}
 
     def get_evidence_estimate(self, discard=0, thin=1, return_error=True, method="therodynamic"):
         """Thermodynamic-integration estimate of log Z, ``(logZ, dlogZ)`` or ``logZ`` (backends/backend.py:664-733).  The ladder
@@ -310,6 +314,21 @@ class _DeviceChain:
             return None
         return ("philox", self.seed, int(last["iteration"][-1]), int(last["adapt_time"][-1]))
 
+    # -- diagnostics: what the hooks of _Diagnostics share on a device chain -------------------------------
+    def _stat_rungs(self):
+        return self.nstore
+
+    def _on_device(self, first):
+        """The kept steps from ``first`` on all lie in the open segment: its index there, else None."""
+        closed = self.iteration - self._open
+        return first - closed if first >= closed else None
+
+    def _stat_betas(self, first, count, thin):
+        f = self._on_device(first)
+        if f is None:
+            return self._field("betas", 0, 1)[_steps(first, count, thin)]
+        return self.engine.chain_download(f, (count - 1) * thin + 1, fields=("betas",))["betas"][::thin]      # (count x T doubles: not a chain copy)
+
 
 class DeviceBackend(_DeviceChain, _Diagnostics):
     """``Backend`` whose stored steps stay in device memory until somebody reads them (include/hipensemble.h: hens_chain_*).
@@ -368,15 +387,7 @@ class DeviceBackend(_DeviceChain, _Diagnostics):
     def get_chain(self, discard=0, thin=1):
         return {self.branch_names[0]: self._field("x", discard, thin)[:, :, :, None, :]}
 
-    # -- diagnostics: the hooks of _Diagnostics --------------------------------------------------------------
-    def _stat_rungs(self):
-        return self.nstore
-
-    def _on_device(self, first):
-        """The kept steps from ``first`` on all lie in the open segment: its index there, else None."""
-        closed = self.iteration - self._open
-        return first - closed if first >= closed else None
-
+    # -- diagnostics: the hooks of _Diagnostics (_stat_rungs, _on_device, _stat_betas: _DeviceChain) -----------
     def _stat_act(self, branch, first, count, thin, ntemps, lags):
         f = self._on_device(first)
         if f is None:
@@ -392,12 +403,6 @@ class DeviceBackend(_DeviceChain, _Diagnostics):
         self.stats_launches += 1
         return self.engine.chain_moments(name, f, count, thin, ntemps)
 
-    def _stat_betas(self, first, count, thin):
-        f = self._on_device(first)
-        if f is None:
-            return self._field("betas", 0, 1)[_steps(first, count, thin)]
-        return self.engine.chain_download(f, (count - 1) * thin + 1, fields=("betas",))["betas"][::thin]      # (count x T doubles: not a chain copy)
-
     @property
     def accepted(self):
         return self._total(0)
@@ -407,7 +412,7 @@ class DeviceBackend(_DeviceChain, _Diagnostics):
         return self._total(1)
 
 
-class RJDeviceBackend(_DeviceChain):
+class RJDeviceBackend(_DeviceChain, _Diagnostics):
     """The chain of an ``RJEnsembleSampler`` in device memory (include/hipensemble.h: hens_rj_chain_*): ``RJEnsembleSampler(...,
     rng="philox", backend=RJDeviceBackend()).run_mcmc(state, nsteps, thin_by=k)`` is one device call per chain SEGMENT.  Every
     stored step is appended by one launch straight from the resident leaf-packing records - per branch the coordinates with the
@@ -415,7 +420,17 @@ class RJDeviceBackend(_DeviceChain):
     swaps_accepted totals the reference's backend keeps (:1069-1091) accumulate beside the chain, and an accessor downloads the
     open segment once.  ``max_bytes`` / ``ntemps_store``: as ``DeviceBackend``.
 
-    The stored steps are bit for bit the ``State`` list the sampler keeps without ``backend=``."""
+    The stored steps are bit for bit the ``State`` list the sampler keeps without ``backend=``.
+
+    Diagnostics, under the reference's names (backends/backend.py:410-434, 664-817): ``get_gelman_rubin_convergence_diagnostic``
+    (a branch of several leaves projected through its leaf masks), ``get_evidence_estimate``, ``get_nleaves(download=False)`` and
+    ``get_nleaves_counts`` run on the device chain - k_rj_chain_leaves, k_rj_chain_leaf_moments, k_chain_moments; ``stats_launches``
+    counts the launches, ``downloads`` stays - when every kept step lies in the open segment, and ``eryn_amd.chain_stats`` over the
+    host copy otherwise: the same bits either way.  ``get_autocorr_time`` / ``get_autocorr_thin_burn`` raise ValueError as the
+    reference's do under reversible jump.  Two departures from the reference's Gelman-Rubin accessor: min_leaves is taken per rung
+    from the rungs stored here (the reference's is per rung as well, but over all ``ntemps``), and where the walker with the fewest
+    leaves has too few for ``psrf`` (floor(W M / 3) < 2; ``per_walker``: M < 2) this raises ValueError naming branch and rung,
+    where the reference's ``C[-0:]`` silently takes the whole array."""
 
     @staticmethod
     def bytes_per_step(ntemps, nwalkers, ncoord, nslots, ntemps_store=None):
@@ -464,9 +479,84 @@ class RJDeviceBackend(_DeviceChain):
         """``{name: bool [nsteps, ntemps_store, W, nleaves_max]}``: which leaves are in use."""
         return {k: self._field(f"inds/{k}", discard, thin) for k in self.branch_names}
 
-    def get_nleaves(self, discard=0, thin=1):
-        """``{name: int [nsteps, ntemps_store, W]}``: leaves in use."""
-        return {k: v.sum(axis=-1, dtype=np.int64) for k, v in self.get_inds(discard, thin).items()}
+    def get_nleaves(self, discard=0, thin=1, download=True):
+        """``{name: int [nsteps, ntemps_store, W]}``: leaves in use.  ``download=False`` answers from the device chain - one byte
+        per walker and kept step (``chain_leaves``) - without copying the chain, when every kept step lies in the open segment."""
+        if download or len(range(int(discard), self.iteration, int(thin))) < 1:
+            return {k: v.sum(axis=-1, dtype=np.int64) for k, v in self.get_inds(discard, thin).items()}
+        first, count, thin = self._kept(discard, thin)
+        return {k: self._stat_leaves(k, first, count, thin, self.nstore, True)[0].astype(np.int64) for k in self.branch_names}
+
+    def get_nleaves_counts(self, discard=0, thin=1):
+        """``{name: int64 [ntemps_store, nleaves_max + 1]}``: per rung, how many (walker, kept step) pairs have k leaves in use -
+        the posterior of the model count, unnormalised."""
+        first, count, thin = self._kept(discard, thin)
+        return {k: self._stat_leaves(k, first, count, thin, self.nstore, False)[1].sum(axis=1, dtype=np.int64) for k in self.branch_names}
+
+    # -- diagnostics: the hooks of _Diagnostics, and the two of a chain with leaf masks ------------------------
+    # Every device path applies when all kept steps lie in the open segment (_on_device); else eryn_amd.chain_stats runs over
+    # the host copy.  Both give the same bits.
+    def _stat_moments(self, field, first, count, thin, ntemps):
+        """A branch's name: the coordinates as they lie, of a ONE-LEAF branch ``[ntemps, W, nd]``; "log_like" / "log_prior": masked."""
+        branch = field in self.branch_names
+        f = self._on_device(first)
+        if f is None:
+            a = self._field(f"x/{field}" if branch else field, 0, 1)[_steps(first, count, thin), :ntemps]
+            out = chain_stats.moments(a, mask=not branch)
+        else:
+            self.stats_launches += 1
+            out = self.engine.chain_moments(field, f, count, thin, ntemps)
+        return tuple(a[:, :, 0] for a in out) if branch else out
+
+    def _stat_leaves(self, name, first, count, thin, ntemps, nleaves):
+        f = self._on_device(first)
+        if f is None:
+            nle, hist = chain_stats.leaf_counts(self._field(f"inds/{name}", 0, 1)[_steps(first, count, thin), :ntemps])
+            return (nle if nleaves else None), hist
+        self.stats_launches += 1
+        return self.engine.chain_leaves(name, f, count, thin, ntemps, nleaves=nleaves)
+
+    def _stat_leaf_moments(self, name, first, count, thin, ntemps, lo, hi):
+        f = self._on_device(first)
+        if f is None:
+            sel = (_steps(first, count, thin), slice(0, ntemps))
+            return chain_stats.leaf_moments(self._field(f"x/{name}", 0, 1)[sel], self._field(f"inds/{name}", 0, 1)[sel], lo, hi)
+        self.stats_launches += 1
+        return self.engine.chain_leaf_moments(name, f, count, thin, ntemps, lo, hi)
+
+    def _psrf_branch(self, name, first, count, thin, nt, per_walker):
+        """``{rung: Rhat[ndim]}``.  A one-leaf branch enters ``psrf`` as it lies, NaN included (backends/backend.py:780-783).  A
+        branch of several leaves is projected through its masks (:786-797; eryn_amd.chain_stats.rj_psrf): one ``chain_leaves``
+        launch gives every walker's total and with it each rung's M = min_leaves; the moments of the compacted series over the
+        ordinals [0, M) - and, where third_split(W, M) leaves r != 0, over [0, r) and [M - r, M) - are ONE LAUNCH PER DISTINCT M
+        over the rungs [0, last rung with that M], whose other rows are dropped: the C entry point takes one window per launch."""
+        if self.nleaves_max[name] == 1:
+            return super()._psrf_branch(name, first, count, thin, nt, per_walker)
+        W = self.nwalkers
+        totals = chain_stats.leaf_totals(self._stat_leaves(name, first, count, thin, nt, False)[1])
+        M = [chain_stats.rj_min_leaves(totals[t], per_walker, name, t) for t in range(nt)]       # (ValueError before any moments launch)
+        out = {}
+        for m in sorted(set(M)):
+            rungs = [t for t in range(nt) if M[t] == m]
+            upto = rungs[-1] + 1
+            s, m2, n = self._stat_leaf_moments(name, first, count, thin, upto, 0, m)
+            assert (n[rungs] == m).all(), "a walker ran out of leaves below the smallest total"
+            r = 0 if per_walker else chain_stats.third_split(W, m)[2]
+            head = tail = None
+            if r:
+                head = self._stat_leaf_moments(name, first, count, thin, upto, 0, r)
+                tail = self._stat_leaf_moments(name, first, count, thin, upto, m - r, m)
+                assert (head[2][rungs] == r).all() and (tail[2][rungs] == r).all()
+            for t in rungs:
+                out[t] = chain_stats.psrf_from_moments(m, s[t], m2[t], head and (head[0][t], head[1][t]), tail and (tail[0][t], tail[1][t]), per_walker)
+        return {t: out[t] for t in range(nt)}
+
+    def get_autocorr_time(self, *args, **kwargs):
+        """Not defined under reversible jump: the reference raises (backends/backend.py:648-651), and so does this."""
+        raise ValueError("get_autocorr_time is not well-defined for number of temperatures > 1 or when using reversible jump.")
+
+    def get_autocorr_thin_burn(self):
+        return self.get_autocorr_time()
 
     @property
     def accepted(self):

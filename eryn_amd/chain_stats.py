@@ -1,5 +1,6 @@
 """Chain diagnostics, stated once in NumPy: the arithmetic the device kernels (csrc/hens_chain_stats.h: k_chain_moments,
-k_chain_act) reproduce bit for bit, and the host functions on top of it.
+k_chain_act; csrc/hens_rj_chain_stats.h: k_rj_chain_leaves, k_rj_chain_leaf_moments) reproduce bit for bit, and the host functions
+on top of it.
 
 The reference computes these in utils/utility.py (:43-144 ``get_acf`` / ``get_integrated_act``, :147-212
 ``thermodynamic_integration_log_evidence``, :279-330 ``psrf``) for its Backend's accessors (backends/backend.py:354-385, 616-817).
@@ -170,6 +171,103 @@ def psrf(C, ndims, per_walker=False):
         if r:
             head, tail = moments(x[:r])[:2], moments(x[S - r:])[:2]
     return psrf_from_moments(S, s, m2, head, tail, per_walker)
+
+
+# ---- reversible-jump chains: leaf counts and the projection through the leaf masks ------------------------------------------
+# The device twins are csrc/hens_rj_chain_stats.h: k_rj_chain_leaves, k_rj_chain_leaf_moments.  The reference projects a branch of
+# several leaves onto its model dimension before ``psrf`` (backends/backend.py:786-799): per walker the leaves in use in ascending
+# (step, slot), the first ``min_leaves`` of them, min_leaves the smallest total over the walkers.  That is a COMPACTED series per
+# (rung, walker, parameter), and the moments of it - and of its first / last r samples, ``third_split(W, min_leaves)`` - are all
+# ``psrf_from_moments`` needs.
+def leaf_counts(inds):
+    """``(nleaves[S, Ts, W] uint8, hist[Ts, W, nl + 1] uint32)`` of masks ``inds`` bool ``[S, Ts, W, nl]``: leaves in use per step,
+    and at how many steps place (t, w) has k leaves in use.  Integers: exact whatever the order."""
+    inds = np.asarray(inds, dtype=bool)
+    nl = inds.shape[-1]
+    nleaves = inds.sum(axis=-1, dtype=np.uint8)
+    hist = np.zeros(inds.shape[1:3] + (nl + 1,), dtype=np.uint32)
+    for k in range(nl + 1):
+        hist[..., k] = (nleaves == k).sum(axis=0)
+    return nleaves, hist
+
+
+def leaf_totals(hist):
+    """Leaves in use over the kept steps per place, ``sum_k k hist[..., k]`` (int64)."""
+    hist = np.asarray(hist)
+    return (hist.astype(np.int64) * np.arange(hist.shape[-1], dtype=np.int64)).sum(axis=-1)
+
+
+def leaf_moments(x, inds, lo, hi):
+    """``(s, m2)`` ``[Ts, W, nd]`` and ``n[Ts, W]`` (int64) of the compacted series of every (rung, walker, parameter):
+    ``x[j, t, w, slot, d]`` over the leaves in use (``inds[j, t, w, slot]``) in ascending (j, slot), those whose ordinal among
+    the place's leaves in use lies in ``[lo, hi)``.  The module docstring's order on that series: ``s`` sequential from 0.0,
+    ``m2`` a second sequential pass about ``s / n``; ``n`` counts the samples that entered (hi - lo unless the place runs out of
+    leaves; n = 0: mean = 0 / 0, m2 = 0)."""
+    x, inds = np.asarray(x, dtype=np.float64), np.asarray(inds, dtype=bool)
+    lo, hi = int(lo), int(hi)
+    if not 0 <= lo < hi:
+        raise ValueError("leaf_moments: 0 <= lo < hi")
+    S, nl = x.shape[0], x.shape[3]
+    place = x.shape[1:3]
+    s, m2, n = np.zeros(place + x.shape[4:]), np.zeros(place + x.shape[4:]), np.zeros(place, dtype=np.int64)
+
+    def walk(f):
+        ordinal = np.zeros(place, dtype=np.int64)
+        for j in range(S):
+            for slot in range(nl):
+                used = inds[j, :, :, slot]
+                f(used & (ordinal >= lo) & (ordinal < hi), x[j, :, :, slot, :])
+                ordinal = ordinal + used
+
+    def add(take, v):
+        nonlocal s, n
+        s = np.where(take[..., None], s + v, s)
+        n = n + take
+
+    def add_centred(take, v):
+        nonlocal m2
+        y = v - mean
+        m2 = np.where(take[..., None], m2 + y * y, m2)
+
+    with np.errstate(all="ignore"):
+        walk(add)
+        mean = s / n.astype(np.float64)[..., None]
+        walk(add_centred)
+    return s, m2, n
+
+
+def rj_min_leaves(totals, per_walker=False, branch=None, rung=None):
+    """``M``: the smallest per-walker total ``totals[W]`` - what the reference's projection keeps of every walker.  ValueError
+    where the reference has nothing defined: floor(W M / 3) < 2 (``per_walker``: M < 2) leaves ``psrf`` a group of fewer than two
+    samples, and at 0 its ``C[-0:]`` is the whole array."""
+    totals = np.asarray(totals)
+    W, M = totals.shape[0], int(totals.min())
+    if (M < 2) if per_walker else ((W * M) // 3 < 2):
+        where = "" if branch is None else f" of branch {branch!r}" + ("" if rung is None else f", rung {rung}")
+        raise ValueError(f"Gelman-Rubin{where}: the walker with the fewest leaves in use has {M} over the kept steps, too few to compare "
+                         + ("a walker's chain" if per_walker else f"thirds of {W} walkers' chains"))
+    return M
+
+
+def rj_psrf(x, inds, ndim, per_walker=False, branch=None, rung=None):
+    """Rhat[ndim] of one branch and rung of a reversible-jump chain, ``x`` ``[S, W, nl, nd]`` with masks ``inds`` ``[S, W, nl]``: the
+    reference's projection (backends/backend.py:779-799) and ``psrf``.  One leaf: the chain as it lies, NaN included."""
+    x, inds = np.asarray(x, dtype=np.float64), np.asarray(inds, dtype=bool)
+    if x.shape[3] != ndim:
+        raise ValueError("rj_psrf: x is [S, W, nl, ndim]")
+    W = x.shape[1]
+    if x.shape[2] == 1:
+        return psrf(x[:, :, 0, :].transpose(1, 0, 2), ndim, per_walker)
+    x, inds = x[:, None], inds[:, None]
+    M = rj_min_leaves(leaf_totals(leaf_counts(inds)[1])[0], per_walker, branch, rung)
+    s, m2, n = leaf_moments(x, inds, 0, M)
+    assert (n == M).all()
+    head = tail = None
+    r = 0 if per_walker else third_split(W, M)[2]
+    if r:
+        head, tail = leaf_moments(x, inds, 0, r), leaf_moments(x, inds, M - r, M)
+        head, tail = (head[0][0], head[1][0]), (tail[0][0], tail[1][0])
+    return psrf_from_moments(M, s[0], m2[0], head, tail, per_walker)
 
 
 # ---- thermodynamic integration ----------------------------------------------------------------------------------------------

@@ -10,6 +10,7 @@
 #include "hens_chain.h"
 #include "hens_chain_stats.h"
 #include "hens_rj_chain.h"
+#include "hens_rj_chain_stats.h"
 #include "hens_chain_host.h"
 #include <unordered_map>
 #include <hip/hip_ext.h>
@@ -253,6 +254,7 @@ struct hens_ctx_impl {
         std::vector<int64_t> iteration, adapt_time;   // per stored step: the Philox checkpoint of its State
         int64_t n_timed = 0; double store_ms = 0.0;   // hens_set_profiling 1: the last call's append launches
         double moments_ms = -1.0, act_ms = -1.0;      // the last k_chain_moments / k_chain_act launch (hens_chain_stats_ms)
+        double leaves_ms = -1.0, leaf_moments_ms = -1.0;   // ... k_rj_chain_leaves / k_rj_chain_leaf_moments (hens_rj_chain_stats_ms)
         // per family: x[0] [capacity][Ts][W][D] of a fixed-dimension chain; per branch of a leaf-packing one
         double* x[RJ_MAX_BRANCH] = {};       // [capacity][Ts][W][nl_b][nd_b], NaN on unused leaves
         uint8_t* inds[RJ_MAX_BRANCH] = {};   // [capacity][Ts][W][nl_b]
@@ -3211,21 +3213,21 @@ static int chain_stats_enter(hens_ctx_impl* c, const char* who) {
     return HENS_OK;
 }
 
-// one diagnostics launch on the HIP stream between two events, its outputs (device doubles behind `dev`, `n_out` arrays of nseries
-// each) copied to the caller's arrays that are not null
-static int chain_stats_run(hens_ctx_impl* c, const void* fn, dim3 grid, dim3 block, size_t lds, ChainStatArgs& a, char* dev,
-                           void* const* host, int n_out, double* ms_out, const char* what) {
+// one diagnostics launch on the HIP stream between two events, its argument block filled by the caller, its outputs (device arrays
+// inside `dev`, which is freed here) copied to the caller's arrays that are not null
+struct StatOut { void* host; const void* dev; size_t bytes; };
+static int chain_stats_run(hens_ctx_impl* c, const void* fn, dim3 grid, dim3 block, size_t lds, void* arg_block, char* dev,
+                           std::initializer_list<StatOut> outs, double* ms_out, const char* what) {
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) {
         if (e0) (void)hipEventDestroy(e0);
         (void)hipFree(dev);
         return fail(c, HENS_ERR_HIP, "%s: hipEventCreate failed", what);
     }
-    void* args[] = {&a};
+    void* args[] = {arg_block};
     hipError_t e = hipExtLaunchKernel(fn, grid, block, args, lds, c->stream, e0, e1, 0);
-    const size_t bytes = (size_t)a.nseries * 8;
-    for (int k = 0; k < n_out && e == hipSuccess; ++k)
-        if (host[k]) e = hipMemcpyAsync(host[k], dev + (size_t)k * bytes, bytes, hipMemcpyDeviceToHost, c->stream);
+    for (const StatOut& o : outs)
+        if (o.host && o.bytes && e == hipSuccess) e = hipMemcpyAsync(o.host, o.dev, o.bytes, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     float ms = 0;
     *ms_out = (e == hipSuccess && hipEventElapsedTime(&ms, e0, e1) == hipSuccess) ? (double)ms : -1.0;
@@ -3233,6 +3235,28 @@ static int chain_stats_run(hens_ctx_impl* c, const void* fn, dim3 grid, dim3 blo
     (void)hipFree(dev);
     if (e != hipSuccess) return fail(c, HENS_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
     return HENS_OK;
+}
+
+// k_chain_moments over one array of a chain of either family: `base` the field's array, `pl` its plan (hens_chain_host.h)
+static int chain_moments_run(hens_ctx_impl* c, const double* base, const hens_chain::StatPlan& pl, int64_t count, bool mask, double* sum,
+                             double* m2, int64_t* n_finite, const char* who) {
+    const int64_t blocks = hens_chain::stat_blocks(pl.nseries / pl.vec, 256);
+    if (blocks > INT32_MAX) return fail(c, HENS_ERR_UNSUPPORTED, "%s: %lld series are more than one launch covers", who, (long long)pl.nseries);
+    if (!sum && !m2 && !n_finite) return HENS_OK;
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    char* dev = nullptr;
+    const size_t bytes = (size_t)pl.nseries * 8;
+    HIPCHK(c, hipMalloc((void**)&dev, bytes * 3));
+    ChainStatArgs a{};
+    a.src = base + pl.offset;
+    a.stride = pl.stride; a.count = count; a.nseries = pl.nseries;
+    a.sum = reinterpret_cast<double*>(dev);
+    a.m2 = m2 ? reinterpret_cast<double*>(dev) + pl.nseries : nullptr;
+    a.nfin = reinterpret_cast<long long*>(dev) + 2 * pl.nseries;
+    const void* fn = pl.vec == 2 ? (mask ? reinterpret_cast<const void*>(k_chain_moments<2, true>) : reinterpret_cast<const void*>(k_chain_moments<2, false>))
+                                 : (mask ? reinterpret_cast<const void*>(k_chain_moments<1, true>) : reinterpret_cast<const void*>(k_chain_moments<1, false>));
+    return chain_stats_run(c, fn, dim3((unsigned)blocks), dim3(256), 0, &a, dev, {{sum, dev, bytes}, {m2, dev + bytes, bytes}, {n_finite, dev + 2 * bytes, bytes}},
+                           &c->chain.moments_ms, "k_chain_moments");
 }
 
 int hens_chain_moments(hens_ctx* ctx, int32_t field, int64_t first, int64_t count, int64_t thin, int32_t ntemps,
@@ -3246,23 +3270,7 @@ int hens_chain_moments(hens_ctx* ctx, int32_t field, int64_t first, int64_t coun
     if (!hens_chain::stat_plan(chain_shape(c, ch.Ts), ch.count, field, first, count, thin, ntemps, &pl))
         return fail(c, HENS_ERR_INVALID, "hens_chain_moments: field %d in [0, 2], count >= 1, thin >= 1, ntemps %d in [1, %d] and the kept steps %lld, %lld + %lld, ... (%lld of them) inside the %lld stored",
                     field, ntemps, ch.Ts, (long long)first, (long long)first, (long long)thin, (long long)count, (long long)ch.count);
-    const int64_t blocks = hens_chain::stat_blocks(pl.nseries / pl.vec, 256);
-    if (blocks > INT32_MAX) return fail(c, HENS_ERR_UNSUPPORTED, "hens_chain_moments: %lld series are more than one launch covers", (long long)pl.nseries);
-    if (!sum && !m2 && !n_finite) return HENS_OK;
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    char* dev = nullptr;
-    HIPCHK(c, hipMalloc((void**)&dev, (size_t)pl.nseries * 8 * 3));
-    ChainStatArgs a{};
-    a.src = (field == 0 ? ch.x[0] : field == 1 ? ch.L : ch.P) + pl.offset;
-    a.stride = pl.stride; a.count = count; a.nseries = pl.nseries;
-    a.sum = reinterpret_cast<double*>(dev);
-    a.m2 = m2 ? reinterpret_cast<double*>(dev) + pl.nseries : nullptr;
-    a.nfin = reinterpret_cast<long long*>(dev) + 2 * pl.nseries;
-    const bool mask = field != 0;
-    const void* fn = pl.vec == 2 ? (mask ? reinterpret_cast<const void*>(k_chain_moments<2, true>) : reinterpret_cast<const void*>(k_chain_moments<2, false>))
-                                 : (mask ? reinterpret_cast<const void*>(k_chain_moments<1, true>) : reinterpret_cast<const void*>(k_chain_moments<1, false>));
-    void* const host[3] = {sum, m2, n_finite};
-    return chain_stats_run(c, fn, dim3((unsigned)blocks), dim3(256), 0, a, dev, host, 3, &ch.moments_ms, "k_chain_moments");
+    return chain_moments_run(c, field == 0 ? ch.x[0] : field == 1 ? ch.L : ch.P, pl, count, field != 0, sum, m2, n_finite, "hens_chain_moments");
 }
 
 int hens_chain_act(hens_ctx* ctx, int64_t first, int64_t count, int64_t thin, int32_t ntemps, int32_t window,
@@ -3295,8 +3303,9 @@ int hens_chain_act(hens_ctx* ctx, int64_t first, int64_t count, int64_t thin, in
     const int kmax = hens_chain::act_kmax(lags);
     const void* fn = kmax == 16 ? reinterpret_cast<const void*>(k_chain_act<16>) : kmax == 32 ? reinterpret_cast<const void*>(k_chain_act<32>)
                                                                                               : reinterpret_cast<const void*>(k_chain_act<64>);
-    void* const host[3] = {tau, mean, c0};
-    return chain_stats_run(c, fn, dim3((unsigned)blocks), dim3(ACT_LANES), (size_t)hens_chain::act_lds_bytes(lags), a, dev, host, 3, &ch.act_ms, "k_chain_act");
+    const size_t bytes = (size_t)pl.nseries * 8;
+    return chain_stats_run(c, fn, dim3((unsigned)blocks), dim3(ACT_LANES), (size_t)hens_chain::act_lds_bytes(lags), &a, dev,
+                           {{tau, dev, bytes}, {mean, dev + bytes, bytes}, {c0, dev + 2 * bytes, bytes}}, &ch.act_ms, "k_chain_act");
 }
 
 int hens_chain_stats_ms(hens_ctx* ctx, double* moments_ms, double* act_ms) {
@@ -4150,6 +4159,111 @@ int hens_rj_chain_totals(hens_ctx* ctx, double* accepted, double* rj_accepted, d
     if (!c) return fail(c, HENS_ERR_INVALID, "null context");
     if (const int r = chain_open(c, true)) return r;
     return chain_totals(c, {{accepted, c->chain.acc_tot}, {rj_accepted, c->chain.bd_tot}}, swaps_accepted);
+}
+
+// ---- chain diagnostics of a leaf-packing context (include/hipensemble.h: hens_rj_chain_leaves, hens_rj_chain_leaf_moments,
+// hens_rj_chain_moments; csrc/hens_rj_chain_stats.h) ------------------------------------------------------------------------------
+static int rj_stats_enter(hens_ctx_impl* c) {
+    if (const int r = rjchain_supported(c)) return r;
+    return chain_open(c, true);
+}
+// the selection's plan, or HENS_ERR_INVALID with the offending values
+static int rj_stats_plan(hens_ctx_impl* c, const char* who, int32_t branch, int64_t first, int64_t count, int64_t thin, int32_t ntemps,
+                         hens_chain::RjStatPlan* pl) {
+    const ChainStore& ch = c->chain;
+    if (!hens_chain::rj_stat_plan(rjchain_shape(c, ch.Ts), ch.count, branch, first, count, thin, ntemps, pl))
+        return fail(c, HENS_ERR_INVALID, "%s: branch %d in [0, %d), 1 <= count <= 2^31, thin >= 1, ntemps %d in [1, %d] and the kept steps %lld, %lld + %lld, ... (%lld of them) inside the %lld stored",
+                    who, branch, c->rj.M.nb, ntemps, ch.Ts, (long long)first, (long long)first, (long long)thin, (long long)count, (long long)ch.count);
+    static_assert(hens_chain::RJ_STAT_LANES == RJ_STAT_LANES, "hens_chain_host.h sizes the table of k_rj_chain_leaves");
+    return HENS_OK;
+}
+static RjStatArgs rj_stat_args(const ChainStore& ch, int32_t branch, const hens_chain::RjStatPlan& pl, int64_t count) {
+    RjStatArgs a{};
+    a.inds = ch.inds[branch] + pl.inds_offset; a.x = ch.x[branch] + pl.x_offset;
+    a.inds_stride = pl.inds_stride; a.x_stride = pl.x_stride;
+    a.count = count; a.nplaces = pl.nplaces;
+    a.nl = (int32_t)pl.nl; a.nd = (int32_t)pl.nd;
+    return a;
+}
+
+int hens_rj_chain_leaves(hens_ctx* ctx, int32_t branch, int64_t first, int64_t count, int64_t thin, int32_t ntemps, uint8_t* nleaves,
+                         uint32_t* hist) {
+    hens_ctx_impl* c = enter(ctx);
+    if (!c) return fail(c, HENS_ERR_INVALID, "null context");
+    int r;
+    hens_chain::RjStatPlan pl{};
+    if ((r = rj_stats_enter(c)) || (r = rj_stats_plan(c, "hens_rj_chain_leaves", branch, first, count, thin, ntemps, &pl))) return r;
+    ChainStore& ch = c->chain;
+    const int64_t blocks = hens_chain::stat_blocks(pl.nplaces, RJ_STAT_LANES);
+    int64_t nbytes = 0;
+    if (blocks > INT32_MAX || !hens_chain::mul(count, pl.nplaces, &nbytes))
+        return fail(c, HENS_ERR_UNSUPPORTED, "hens_rj_chain_leaves: %lld places over %lld kept steps are more than one launch covers", (long long)pl.nplaces, (long long)count);
+    if (!nleaves && !hist) return HENS_OK;
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    const size_t hbytes = (size_t)pl.nplaces * (size_t)(pl.nl + 1) * 4;
+    char* dev = nullptr;
+    HIPCHK(c, hipMalloc((void**)&dev, hbytes + (nleaves ? (size_t)nbytes : 0)));
+    RjStatArgs a = rj_stat_args(ch, branch, pl, count);
+    a.hist = reinterpret_cast<uint32_t*>(dev);
+    a.nleaves = nleaves ? reinterpret_cast<uint8_t*>(dev + hbytes) : nullptr;
+    const void* fn = pl.vec == 4 ? reinterpret_cast<const void*>(k_rj_chain_leaves<4>) : reinterpret_cast<const void*>(k_rj_chain_leaves<1>);
+    return chain_stats_run(c, fn, dim3((unsigned)blocks), dim3(RJ_STAT_LANES), (size_t)pl.lds_bytes, &a, dev,
+                           {{hist, dev, hbytes}, {nleaves, dev + hbytes, (size_t)nbytes}}, &ch.leaves_ms, "k_rj_chain_leaves");
+}
+
+int hens_rj_chain_leaf_moments(hens_ctx* ctx, int32_t branch, int64_t first, int64_t count, int64_t thin, int32_t ntemps, int64_t lo,
+                               int64_t hi, double* sum, double* m2, int64_t* n) {
+    hens_ctx_impl* c = enter(ctx);
+    if (!c) return fail(c, HENS_ERR_INVALID, "null context");
+    int r;
+    hens_chain::RjStatPlan pl{};
+    if ((r = rj_stats_enter(c)) || (r = rj_stats_plan(c, "hens_rj_chain_leaf_moments", branch, first, count, thin, ntemps, &pl))) return r;
+    if (!hens_chain::rj_window_ok(lo, hi))
+        return fail(c, HENS_ERR_INVALID, "hens_rj_chain_leaf_moments: the ordinal window [%lld, %lld) needs 0 <= lo < hi", (long long)lo, (long long)hi);
+    ChainStore& ch = c->chain;
+    const int64_t blocks = hens_chain::stat_blocks(pl.nseries, RJ_STAT_LANES);
+    if (blocks > INT32_MAX) return fail(c, HENS_ERR_UNSUPPORTED, "hens_rj_chain_leaf_moments: %lld series are more than one launch covers", (long long)pl.nseries);
+    if (!sum && !m2 && !n) return HENS_OK;
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    const size_t sbytes = (size_t)pl.nseries * 8, pbytes = (size_t)pl.nplaces * 8;
+    char* dev = nullptr;
+    HIPCHK(c, hipMalloc((void**)&dev, 2 * sbytes + pbytes));
+    RjStatArgs a = rj_stat_args(ch, branch, pl, count);
+    a.lo = lo; a.hi = hi;
+    a.sum = reinterpret_cast<double*>(dev);
+    a.m2 = m2 ? reinterpret_cast<double*>(dev + sbytes) : nullptr;
+    a.n = reinterpret_cast<long long*>(dev + 2 * sbytes);
+    const void* fn = pl.vec == 4 ? reinterpret_cast<const void*>(k_rj_chain_leaf_moments<4>) : reinterpret_cast<const void*>(k_rj_chain_leaf_moments<1>);
+    return chain_stats_run(c, fn, dim3((unsigned)blocks), dim3(RJ_STAT_LANES), 0, &a, dev,
+                           {{sum, dev, sbytes}, {m2, dev + sbytes, sbytes}, {n, dev + 2 * sbytes, pbytes}}, &ch.leaf_moments_ms, "k_rj_chain_leaf_moments");
+}
+
+// the chain as it lies - a one-leaf branch's coordinates (NaN where the leaf is unused: it propagates, as in the reference), logl /
+// logp masked - through k_chain_moments unchanged
+int hens_rj_chain_moments(hens_ctx* ctx, int32_t field, int32_t branch, int64_t first, int64_t count, int64_t thin, int32_t ntemps,
+                          double* sum, double* m2, int64_t* n_finite) {
+    hens_ctx_impl* c = enter(ctx);
+    if (!c) return fail(c, HENS_ERR_INVALID, "null context");
+    if (const int r = rj_stats_enter(c)) return r;
+    ChainStore& ch = c->chain;
+    hens_chain::StatPlan pl{};
+    if (!hens_chain::rj_plain_plan(rjchain_shape(c, ch.Ts), ch.count, field, branch, first, count, thin, ntemps, &pl))
+        return fail(c, HENS_ERR_INVALID, "hens_rj_chain_moments: field %d in [0, 2], branch %d in [0, %d) (field 0), count >= 1, thin >= 1, ntemps %d in [1, %d] and the kept steps %lld, %lld + %lld, ... (%lld of them) inside the %lld stored",
+                    field, branch, c->rj.M.nb, ntemps, ch.Ts, (long long)first, (long long)first, (long long)thin, (long long)count, (long long)ch.count);
+    const int r = chain_moments_run(c, field == 0 ? ch.x[branch] : field == 1 ? ch.L : ch.P, pl, count, field != 0, sum, m2, n_finite, "hens_rj_chain_moments");
+    if (r == HENS_OK && (sum || m2 || n_finite)) ch.leaf_moments_ms = ch.moments_ms;
+    return r;
+}
+
+// leaves_ms: the last k_rj_chain_leaves launch; moments_ms: the last k_rj_chain_leaf_moments or k_chain_moments launch, whichever
+// ran later (-1: none yet)
+int hens_rj_chain_stats_ms(hens_ctx* ctx, double* leaves_ms, double* moments_ms) {
+    hens_ctx_impl* c = CTX(ctx);
+    if (!c) return fail(c, HENS_ERR_INVALID, "null context");
+    if (const int r = rjchain_supported(c)) return r;
+    if (leaves_ms) *leaves_ms = c->chain.leaves_ms;
+    if (moments_ms) *moments_ms = c->chain.leaf_moments_ms;
+    return HENS_OK;
 }
 
 // ---- leaf-packing moves with a HOST-CALLABLE likelihood (round 6; ensemble.py:1306-1334,1340-1545, rj.py:145-388) ---------------

@@ -1,7 +1,8 @@
 // hens_chain_host.h - the capacity / range / launch arithmetic of the chain store's two families (hens_chain_*, hens_step_chain; on a
 // leaf-packing context hens_rj_chain_*, hens_rj_step_chain: one host protocol in hens.hip) as plain host functions without HIP types:
-// hens.hip calls them, and tools/chain_host_check.cpp runs them alone under -fsanitize=address,undefined (sizes come straight from
-// the caller: every product is overflow-checked before anything is allocated, launched or copied).
+// hens.hip calls them, and tools/chain_host_check.cpp, tools/chain_stats_host_check.cpp and tools/rj_chain_stats_host_check.cpp run
+// them alone under -fsanitize=address,undefined (sizes come straight from the caller: every product is overflow-checked before
+// anything is allocated, launched or copied).
 #pragma once
 #include <cstdint>
 
@@ -148,5 +149,60 @@ inline int64_t act_lds_bytes(int64_t lags) { return lags * ACT_LANES * 8; }
 // accumulators the instantiation carries: the smallest of 16 / 32 / 64 that covers the lags
 inline int act_kmax(int64_t lags) { return lags <= 16 ? 16 : lags <= 32 ? 32 : 64; }
 inline int64_t stat_blocks(int64_t lanes, int64_t per_block) { return (lanes + per_block - 1) / per_block; }
+
+// ---- chain diagnostics of a leaf-packing context (hens_rj_chain_leaves, hens_rj_chain_leaf_moments; csrc/hens_rj_chain_stats.h) ----
+// The kept steps first, first + thin, ... of branch `branch` of a chain that holds `stored` steps, the rungs [0, ntemps): a PLACE is
+// one (rung, walker) of the selection, a series one (place, parameter).  Place i's nl mask bytes sit at byte i nl of a step's mask
+// slice, its coordinates at double i nl nd of the step's coordinate slice.
+constexpr int RJ_STAT_LANES = 256, RJ_STAT_NL_MAX = 32, RJ_STAT_ND_MAX = 4;
+constexpr int64_t RJ_STAT_COUNT_MAX = (int64_t)1 << 31;      // kept steps: a u32 histogram bin cannot wrap
+struct RjStatPlan {
+    int64_t inds_offset, inds_stride;   // bytes from inds_b's base to the first kept step's slice / between kept steps
+    int64_t x_offset, x_stride;         // doubles, of x_b
+    int64_t nplaces, nseries;           // ntemps x W, ntemps x W x nd
+    int64_t nl, nd;
+    int64_t lds_bytes;                  // k_rj_chain_leaves' table [nl + 1][RJ_STAT_LANES] of u32
+    int vec;                            // mask bytes per load: 4 where nl is a multiple of 4 (every place starts on a dword), else 1
+};
+
+inline bool rj_stat_plan(const RjShape& s, int64_t stored, int64_t branch, int64_t first, int64_t count, int64_t thin, int64_t ntemps,
+                         RjStatPlan* out) {
+    RjSizes sz{};
+    if (stored < 0 || !rj_sizes(s, stored, &sz)) return false;                  // (the shape, and every buffer size inside int64)
+    if (branch < 0 || branch >= s.nb) return false;
+    const int64_t nl = s.nl[branch], nd = s.nd[branch];
+    if (nl > RJ_STAT_NL_MAX || nd > RJ_STAT_ND_MAX) return false;
+    if (first < 0 || count < 1 || count > RJ_STAT_COUNT_MAX || thin < 1 || ntemps < 1 || ntemps > s.Ts) return false;
+    int64_t span, last;
+    if (!mul(count - 1, thin, &span) || !add(first, span, &last) || last >= stored) return false;
+    int64_t tw, istep, xstep;
+    if (!mul(s.Ts, s.W, &tw) || !mul(tw, nl, &istep) || !mul(istep, nd, &xstep)) return false;
+    RjStatPlan p{};
+    p.nl = nl; p.nd = nd;
+    p.inds_offset = first * istep;                       // (first <= last < stored, and stored x istep = sz.inds fits)
+    p.x_offset = first * xstep;
+    p.inds_stride = count > 1 ? thin * istep : istep;    // (count > 1: thin <= last < stored; one kept step: never used)
+    p.x_stride = count > 1 ? thin * xstep : xstep;
+    p.nplaces = ntemps * s.W;
+    p.nseries = p.nplaces * nd;
+    p.lds_bytes = (nl + 1) * RJ_STAT_LANES * 4;
+    p.vec = nl % 4 == 0 ? 4 : 1;
+    *out = p;
+    return true;
+}
+
+// k_rj_chain_leaf_moments' ordinal window [lo, hi)
+inline bool rj_window_ok(int64_t lo, int64_t hi) { return lo >= 0 && lo < hi; }
+
+// hens_rj_chain_moments: the fixed-dimension plan over a leaf-packing chain's own arrays - field 0: x of `branch` as stored, a
+// "coordinate" row the nl nd doubles of a walker; 1 / 2: logl / logp
+inline bool rj_plain_plan(const RjShape& s, int64_t stored, int64_t field, int64_t branch, int64_t first, int64_t count, int64_t thin,
+                          int64_t ntemps, StatPlan* out) {
+    RjSizes sz{};
+    if (stored < 0 || !rj_sizes(s, stored, &sz)) return false;
+    if (field == 0 && (branch < 0 || branch >= s.nb)) return false;
+    const int64_t D = field == 0 ? s.nl[branch] * s.nd[branch] : 1;             // (rj_sizes multiplied them)
+    return stat_plan(Shape{s.T, s.Ts, s.W, D}, stored, field, first, count, thin, ntemps, out);
+}
 
 }  // namespace hens_chain

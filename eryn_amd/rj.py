@@ -425,6 +425,58 @@ class RJEngine(ChainStoreCalls):
         check(self.lib.hens_rj_chain_totals(self.ctx, ptr(acc), ptr(bd), ptr(swaps) if self.T > 1 else None), self.ctx)
         return acc, bd, swaps
 
+    # -- chain diagnostics (include/hipensemble.h: hens_rj_chain_leaves, hens_rj_chain_leaf_moments, hens_rj_chain_moments) ----------
+    def _branch_index(self, branch):
+        names = [b.name for b in self.branches]
+        return names.index(branch) if branch in names else int(branch)
+
+    def _stat_rungs(self, ntemps):
+        return int(self.chain_info()["ntemps_store"] if ntemps is None else ntemps)
+
+    def chain_leaves(self, branch, first, count, thin=1, ntemps=None, nleaves=True):
+        """``(nleaves, hist)`` of branch ``branch`` (name or index) over the kept steps ``first + j thin``, j < count, of the open
+        chain: leaves in use ``uint8 [count, ntemps, W]`` (None with ``nleaves=False``: nothing the size of the range is copied) and
+        ``hist uint32 [ntemps, W, nl + 1]``, at how many kept steps a walker has k leaves in use: eryn_amd.chain_stats.leaf_counts,
+        computed where the chain is."""
+        bi, nt = self._branch_index(branch), self._stat_rungs(ntemps)
+        nl = self.branches[bi].nleaves_max if 0 <= bi < len(self.branches) else 0
+        nle = np.empty((max(int(count), 0), max(nt, 0), self.W), dtype=np.uint8) if nleaves else None
+        hist = np.empty((max(nt, 0), self.W, nl + 1), dtype=np.uint32)
+        check(self.lib.hens_rj_chain_leaves(self.ctx, bi, int(first), int(count), int(thin), nt, ptr(nle), ptr(hist)), self.ctx)
+        return nle, hist
+
+    def chain_leaf_moments(self, branch, first, count, thin, ntemps, lo, hi):
+        """``(sum, m2, n)`` - ``[ntemps, W, nd]``, ``[ntemps, W, nd]``, ``int64 [ntemps, W]`` - of every (rung, walker, parameter)'s
+        series of the leaves in use in ascending (kept step, slot) whose ordinal lies in ``[lo, hi)``:
+        eryn_amd.chain_stats.leaf_moments bit for bit."""
+        bi, nt = self._branch_index(branch), self._stat_rungs(ntemps)
+        nd = self.branches[bi].ndim if 0 <= bi < len(self.branches) else 1
+        s, m2, n = np.empty((max(nt, 0), self.W, nd)), np.empty((max(nt, 0), self.W, nd)), np.empty((max(nt, 0), self.W), dtype=np.int64)
+        check(self.lib.hens_rj_chain_leaf_moments(self.ctx, bi, int(first), int(count), int(thin), nt, int(lo), int(hi), ptr(s), ptr(m2), ptr(n)), self.ctx)
+        return s, m2, n
+
+    def chain_moments(self, field, first, count, thin=1, ntemps=None):
+        """``(sum, m2, n_finite)`` per series of ``field`` - a branch's name: its coordinates as stored, ``[ntemps, W, nl, nd]``, NaN
+        of an unused leaf propagating; "log_like" / "log_prior": ``[ntemps, W]``, non-finite entries skipped - over the kept steps:
+        eryn_amd.chain_stats.moments bit for bit."""
+        nt = self._stat_rungs(ntemps)
+        if field in ("log_like", "log_prior"):
+            code, bi, shape = (1 if field == "log_like" else 2), 0, (max(nt, 0), self.W)
+        else:
+            code, bi = 0, self._branch_index(field)
+            b = self.branches[bi] if 0 <= bi < len(self.branches) else None
+            shape = (max(nt, 0), self.W) + ((b.nleaves_max, b.ndim) if b else (1, 1))
+        s, m2, nf = np.empty(shape), np.empty(shape), np.empty(shape, dtype=np.int64)
+        check(self.lib.hens_rj_chain_moments(self.ctx, code, bi, int(first), int(count), int(thin), nt, ptr(s), ptr(m2), ptr(nf)), self.ctx)
+        return s, m2, nf
+
+    def chain_stats_ms(self):
+        """Durations (ms) of the last k_rj_chain_leaves launch and of the last moments launch (k_rj_chain_leaf_moments or
+        k_chain_moments), -1 where there was none."""
+        a, b = C.c_double(-1.0), C.c_double(-1.0)
+        check(self.lib.hens_rj_chain_stats_ms(self.ctx, C.byref(a), C.byref(b)), self.ctx)
+        return dict(leaves_ms=a.value, moments_ms=b.value)
+
     def set_schedule(self, rj_moves):
         """The sampler's ``rj_moves`` string for ``step`` (ensemble.py:434-480): "separate_branches" | "iterate_branches" |
         "together", or "none": no reversible-jump move (``EnsembleSampler`` without ``rj_moves``)."""

@@ -253,8 +253,9 @@ int hens_chain_totals(hens_ctx* ctx, double* accepted, double* swaps_accepted);
  *   lags -> HENS_ERR_UNSUPPORTED (a lane's accumulators and its LDS ring).
  * Outputs are host pointers, any may be NULL.  No chain -> HENS_ERR_STATE; count < 1, thin < 1, window < 1, a field outside
  * [0, 2], ntemps outside [1, ntemps_store] or a kept step outside [0, count of the chain) -> HENS_ERR_INVALID before anything is
- * launched.  A leaf-packing context -> HENS_ERR_UNSUPPORTED: not built (the autocorrelation time is not defined under reversible
- * jump, Gelman-Rubin over several leaves needs the projection through the leaf masks).
+ * launched.  A leaf-packing context -> HENS_ERR_UNSUPPORTED: the autocorrelation time is not defined under reversible jump, and
+ * Gelman-Rubin over several leaves needs the projection through the leaf masks - hens_rj_chain_leaves / _leaf_moments / _moments
+ * below are that family's own.
  * hens_chain_stats_ms: the duration in ms of the last k_chain_moments / k_chain_act launch of the chain (-1: none yet). */
 int hens_chain_moments(hens_ctx* ctx, int32_t field, int64_t first, int64_t count, int64_t thin, int32_t ntemps, double* sum,
                        double* m2, int64_t* n_finite);
@@ -296,6 +297,37 @@ int hens_rj_step_chain(hens_ctx* ctx, int64_t n_store, int64_t iters_per_store);
 int hens_rj_chain_download(hens_ctx* ctx, int64_t first, int64_t count, int32_t branch, double* x, uint8_t* inds, double* logl,
                            double* logp, double* betas, int64_t* iteration, int64_t* adapt_time);
 int hens_rj_chain_totals(hens_ctx* ctx, double* accepted, double* rj_accepted, double* swaps_accepted);
+
+/* ---- Chain diagnostics of a leaf-packing context's chain (csrc/hens_rj_chain_stats.h: k_rj_chain_leaves, k_rj_chain_leaf_moments) --
+ * What one asks of a reversible-jump run - how many leaves, have the walkers converged, the evidence - as reductions over the step
+ * axis where the chain is: the reference's get_nleaves, the projection through the leaf masks of its
+ * get_gelman_rubin_convergence_diagnostic and its get_evidence_estimate (backends/backend.py:410-434, 664-817).  One launch reads the
+ * kept steps first, first + thin, ..., first + (count - 1) thin of rungs [0, ntemps) of one branch and returns arrays no larger than
+ * one stored step (nleaves: one byte per place and kept step).  The arithmetic and its order are eryn_amd/chain_stats.py's
+ * (leaf_counts, leaf_moments, moments), bit for bit.  They read the chain and touch no stepping state.
+ *
+ * hens_rj_chain_leaves: nleaves[count][ntemps][W] the leaves in use per kept step, hist[ntemps][W][nl_b + 1] at how many kept steps
+ *   walker (t, w) has k leaves in use.  Per-walker totals are sum_k k hist, the model-count posterior of a rung sum_w hist.
+ * hens_rj_chain_leaf_moments: per (rung, walker, parameter) the series of the leaves in use in ascending (kept step, slot), those
+ *   whose ordinal among the walker's leaves in use lies in [lo, hi): sum and m2 = sum (x - sum / n)^2 in a second pass
+ *   [ntemps][W][nd_b], and n[ntemps][W] the samples that entered (hi - lo unless the walker runs out of leaves; n = 0 gives
+ *   m2 = 0).  The projected chain of the reference's Gelman-Rubin diagnostic is the window [0, min_leaves).
+ * hens_rj_chain_moments: hens_chain_moments over this chain's own arrays - field 0: x of `branch` as stored
+ *   ([ntemps][W][nl_b][nd_b], NaN of an unused leaf propagates: what the reference does with a one-leaf branch), 1: logl, 2: logp
+ *   ([ntemps][W], non-finite entries skipped and not counted; `branch` unused).
+ * hens_rj_chain_stats_ms: the duration in ms of the last k_rj_chain_leaves launch and of the last moments launch of either kind
+ *   (-1: none yet).
+ * Outputs are host pointers, any may be NULL (all NULL: HENS_OK after the checks, nothing launched).  No chain -> HENS_ERR_STATE; a
+ * branch the model has not, count outside [1, 2^31], thin < 1, ntemps outside [1, ntemps_store], a kept step outside the stored
+ * ones, lo < 0 or lo >= hi -> HENS_ERR_INVALID with the values in the text, before anything is launched.  A context of the
+ * fixed-dimension family -> HENS_ERR_UNSUPPORTED (hens_chain_moments / hens_chain_act are its own, and stay closed to this one). */
+int hens_rj_chain_leaves(hens_ctx* ctx, int32_t branch, int64_t first, int64_t count, int64_t thin, int32_t ntemps, uint8_t* nleaves,
+                         uint32_t* hist);
+int hens_rj_chain_leaf_moments(hens_ctx* ctx, int32_t branch, int64_t first, int64_t count, int64_t thin, int32_t ntemps, int64_t lo,
+                               int64_t hi, double* sum, double* m2, int64_t* n);
+int hens_rj_chain_moments(hens_ctx* ctx, int32_t field, int32_t branch, int64_t first, int64_t count, int64_t thin, int32_t ntemps,
+                          double* sum, double* m2, int64_t* n_finite);
+int hens_rj_chain_stats_ms(hens_ctx* ctx, double* leaves_ms, double* moments_ms);
 
 /* Counters.  Replaces Move.accepted / num_proposals (move.py:404-421, red_blue.py:326-327),
  * TemperatureControl.swaps_accepted / time (tempering.py:542,596).  Any pointer may be NULL.
