@@ -286,6 +286,7 @@ int fail(hens_ctx_impl* c, int code, const char* fmt, ...) {
     g_last_error = buf;
     return code;
 }
+int no_context() { return fail(nullptr, HENS_ERR_INVALID, "null context"); }
 
 #define HIPCHK(c, expr)                                                                            \
     do {                                                                                           \
@@ -753,8 +754,54 @@ int check_flags(hens_ctx_impl* c, bool nan_logl_is_error) {
     return HENS_OK;
 }
 
+// device scratch of one call (the debug exports): plain allocations of at least 8 bytes, all freed on every way out
+struct DeviceScratch {
+    std::vector<void*> p;
+    ~DeviceScratch() { for (void* q : p) (void)hipFree(q); }
+    template <class Tp>
+    Tp* grab(size_t n) {                     // nullptr: out of device memory (the caller's text names its entry point)
+        void* q = nullptr;
+        if (hipMalloc(&q, std::max<size_t>(n * sizeof(Tp), 8)) != hipSuccess) return nullptr;
+        p.push_back(q);
+        return static_cast<Tp*>(q);
+    }
+};
+
+// the draws of the cascade keyed `key_iter` (k_debug_pt) through the scratch ds / du [T][W] into the caller's arrays that are not null
+int export_pt_draws(hens_ctx_impl* c, int32_t* ds, double* du, uint64_t key_iter, int32_t* slot_out, double* u_out) {
+    const size_t n = (size_t)c->T * c->W;
+    hipLaunchKernelGGL(k_debug_pt, dim3(grid_for((int64_t)n)), dim3(256), 0, c->stream, ds, du, c->T, c->W, c->idx_bits, c->cfg.seed, key_iter);
+    HIPCHK(c, hipGetLastError());
+    if (slot_out) HIPCHK(c, hipMemcpyAsync(slot_out, ds, n * 4, hipMemcpyDeviceToHost, c->stream));
+    if (u_out) HIPCHK(c, hipMemcpyAsync(u_out, du, (size_t)(c->T - 1) * c->W * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return HENS_OK;
+}
+
+// Device counter arrays of n uint32 each into the caller's double arrays (a null destination is not asked for and not copied):
+// the copies, whatever `also` queues on the stream besides, ONE wait for all of it, the conversions.
+struct CounterOut { double* dst; const uint32_t* src; };
+template <class Also>
+int read_counters(hens_ctx_impl* c, size_t n, std::initializer_list<CounterOut> outs, Also&& also) {
+    size_t asked = 0;
+    for (const CounterOut& o : outs) asked += o.dst != nullptr;
+    std::vector<uint32_t> h(asked * n);               // (staged only where the caller asks)
+    size_t k = 0;
+    for (const CounterOut& o : outs)
+        if (o.dst) HIPCHK(c, hipMemcpyAsync(&h[n * k++], o.src, n * 4, hipMemcpyDeviceToHost, c->stream));
+    if (const int r = also()) return r;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    k = 0;
+    for (const CounterOut& o : outs)
+        if (o.dst) std::copy_n(&h[n * k++], n, o.dst);
+    return HENS_OK;
+}
+int read_counters(hens_ctx_impl* c, size_t n, std::initializer_list<CounterOut> outs) {
+    return read_counters(c, n, outs, [] { return (int)HENS_OK; });
+}
+
 int ready(hens_ctx_impl* c, bool need_logs) {
-    if (!c) return fail(nullptr, HENS_ERR_INVALID, "null context");
+    if (!c) return no_context();
     if (!c->have_prior) return fail(c, HENS_ERR_STATE, "prior box not set (hens_set_prior_box)");
     if (!c->have_like) return fail(c, HENS_ERR_STATE, "likelihood constants not set");
     if (!c->have_state) return fail(c, HENS_ERR_STATE, "no state uploaded (hens_upload_state)");
@@ -1332,6 +1379,32 @@ void state_to_fields(hens_ctx_impl* c) {
     }
 }
 
+// ---- the gate of the C entry points -----------------------------------------------------------------------------------------------
+// hens_step leaves the walkers as packed records (slot or column order, after k_iter with rows in both halves of the pool) and the
+// last cascade's ladder adaptation pending: a short call pays no pack / unpack and no k_adapt launch.  Every other entry point
+// states here what it is about to use - the context's device, the by-field arrays L / P / loc / accepted, the ladder with its swap
+// counts - behind its argument and state checks (a refused call settles nothing), and nothing else calls state_to_fields or
+// flush_adapt but the stepping internals.
+enum : unsigned { NEED_DEVICE = 1, NEED_FIELDS = 2, NEED_LADDER = 4 };
+int settle(hens_ctx_impl* c, unsigned need) {
+    if (need & NEED_DEVICE) HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    if (need & NEED_FIELDS) state_to_fields(c);
+    if (need & NEED_LADDER) flush_adapt(c);
+    return HENS_OK;
+}
+#define SETTLE(c, need)                                     \
+    do {                                                    \
+        if (const int s_ = settle(c, need)) return s_;      \
+    } while (0)
+
+// preconditions of the leaf-packing entry points, one spelling each: the context's kind; a model set on it
+bool is_rj(const hens_ctx_impl* c) { return c->cfg.likelihood_kind == HENS_LIKE_TEMPLATE; }
+int need_rj_context(hens_ctx_impl* c) {
+    return is_rj(c) ? HENS_OK : fail(c, HENS_ERR_STATE, "hens_rj_* needs a context created with HENS_LIKE_TEMPLATE");
+}
+bool rj_has_model(const hens_ctx_impl* c) { return is_rj(c) && c->have_like && c->rj.M.nb > 0 && c->rj.acc_bd; }
+int need_rj_model(hens_ctx_impl* c) { return rj_has_model(c) ? HENS_OK : fail(c, HENS_ERR_STATE, "hens_rj_set_model first"); }
+
 // round keys of iteration c->iter (planning a new window if the chain has left the current one)
 const uint32_t* iteration_keys(hens_ctx_impl* c) {
     // (the window must hold the NEXT iteration's keys too: column-ordered records are written in its order)
@@ -1767,7 +1840,7 @@ int rj_evaluate(hens_ctx_impl* c) {
 int rj_ready(hens_ctx_impl* c, bool between_halves = false, bool propose = false) {
     int r = ready(c, true);
     if (r) return r;
-    if (c->cfg.likelihood_kind != HENS_LIKE_TEMPLATE) return fail(c, HENS_ERR_STATE, "hens_rj_* needs a context created with HENS_LIKE_TEMPLATE");
+    if (const int rk = need_rj_context(c)) return rk;
     if (c->Tl != c->T) return fail(c, HENS_ERR_UNSUPPORTED, "the leaf-packing path runs on the whole ladder of one GPU");
     if ((c->expect_split != 0 && !between_halves) || c->propose_pending) return fail(c, HENS_ERR_STATE, "a half-step is pending");
     if (c->rj.accept_pending) return fail(c, HENS_ERR_STATE, "hens_rj_accept must follow hens_rj_propose");
@@ -2168,7 +2241,7 @@ void hens_destroy(hens_ctx* ctx) {
 
 int hens_synchronize(hens_ctx* ctx) {
     hens_ctx_impl* c = CTX(ctx);
-    if (!c) return fail(nullptr, HENS_ERR_INVALID, "null context");
+    if (!c) return no_context();
     if (c->aql_on) {              // the AQL queue first (a spin on its completion signal); the HIP stream only if it may hold work
         const bool dirty = c->hip_dirty;
         const int r = aql_settle(c);
@@ -2185,7 +2258,7 @@ int hens_synchronize(hens_ctx* ctx) {
 
 int hens_set_stream(hens_ctx* ctx, void* s) {
     hens_ctx_impl* c = enter(ctx);
-    if (!c) return fail(nullptr, HENS_ERR_INVALID, "null context");
+    if (!c) return no_context();
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (c->own_stream) (void)hipStreamDestroy(c->stream);
     c->stream = reinterpret_cast<hipStream_t>(s);
@@ -2198,8 +2271,7 @@ int hens_set_prior_box(hens_ctx* ctx, const double* lo, const double* hi, double
     if (!c || !lo || !hi) return fail(c, HENS_ERR_INVALID, "null argument");
     for (int d = 0; d < c->D; ++d)
         if (!(lo[d] < hi[d])) return fail(c, HENS_ERR_INVALID, "prior box needs lo < hi in every dimension (dim %d)", d);
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    state_to_fields(c);                       // (hens_step leaves the state in record mode)
+    SETTLE(c, NEED_DEVICE | NEED_FIELDS);
     HIPCHK(c, hipMemcpyAsync(c->lo, lo, c->D * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->hi, hi, c->D * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2210,8 +2282,8 @@ int hens_set_prior_box(hens_ctx* ctx, const double* lo, const double* hi, double
 
 int hens_set_periodic(hens_ctx* ctx, const double* period) {
     hens_ctx_impl* c = enter(ctx);
-    if (!c) return fail(c, HENS_ERR_INVALID, "null context");
-    if (c->cfg.likelihood_kind == HENS_LIKE_TEMPLATE)
+    if (!c) return no_context();
+    if (is_rj(c))
         return fail(c, HENS_ERR_UNSUPPORTED, "periodic parameters are not defined on leaf-packing records");
     bool any = false;
     if (period)
@@ -2223,9 +2295,7 @@ int hens_set_periodic(hens_ctx* ctx, const double* period) {
         if (!any && !c->period) return HENS_OK;
         return fail(c, HENS_ERR_STATE, "set the periodic parameters before hens_pipe_init");
     }
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    state_to_fields(c);                       // (hens_step leaves the state in record mode)
-    flush_adapt(c);
+    SETTLE(c, NEED_DEVICE | NEED_FIELDS | NEED_LADDER);
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (!any) {                       // back to the compile-time-width kernels
         c->period = nullptr;
@@ -2247,8 +2317,7 @@ int hens_set_gaussian(hens_ctx* ctx, const double* mu, const double* prec) {
     if (c->cfg.likelihood_kind != HENS_LIKE_GAUSS_DENSE && c->cfg.likelihood_kind != HENS_LIKE_GAUSS_DIAG)
         return fail(c, HENS_ERR_STATE, "context was not created with a Gaussian likelihood kind");
     const size_t n = c->cfg.likelihood_kind == HENS_LIKE_GAUSS_DENSE ? (size_t)c->D * c->D : (size_t)c->D;
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    state_to_fields(c);                       // (hens_step leaves the state in record mode)
+    SETTLE(c, NEED_DEVICE | NEED_FIELDS);
     HIPCHK(c, hipMemcpyAsync(c->mu, mu, c->D * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->prec, prec, n * 8, hipMemcpyHostToDevice, c->stream));
     std::vector<double> sym;
@@ -2327,7 +2396,7 @@ int hens_set_gaussian(hens_ctx* ctx, const double* mu, const double* prec) {
 
 int hens_set_rosenbrock(hens_ctx* ctx, double a, double b) {
     hens_ctx_impl* c = enter(ctx);
-    if (!c) return fail(c, HENS_ERR_INVALID, "null context");
+    if (!c) return no_context();
     if (c->cfg.likelihood_kind != HENS_LIKE_ROSENBROCK)
         return fail(c, HENS_ERR_STATE, "context was not created with HENS_LIKE_ROSENBROCK");
     c->rosen_a = a; c->rosen_b = b;
@@ -2340,9 +2409,7 @@ int hens_upload_state(hens_ctx* ctx, const double* x, const double* logl, const 
     if (!c || !x) return fail(c, HENS_ERR_INVALID, "null argument");
     if (c->cfg.tempered && !betas) return fail(c, HENS_ERR_INVALID, "betas required for a tempered context");
     if ((logl == nullptr) != (logp == nullptr)) return fail(c, HENS_ERR_INVALID, "give both logl and logp or neither");
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    state_to_fields(c);                       // (hens_step leaves the state in record mode)
-    flush_adapt(c);
+    SETTLE(c, NEED_DEVICE | NEED_FIELDS | NEED_LADDER);
     const size_t TW = (size_t)c->Tl * c->W;
     c->cur = 0;
     c->rj.tm_valid = false;
@@ -2368,12 +2435,10 @@ int hens_upload_state(hens_ctx* ctx, const double* x, const double* logl, const 
 
 int hens_download_state(hens_ctx* ctx, double* x, double* logl, double* logp, double* betas) {
     hens_ctx_impl* c = enter(ctx);
-    if (!c) return fail(c, HENS_ERR_INVALID, "null context");
+    if (!c) return no_context();
     if (!c->have_state) return fail(c, HENS_ERR_STATE, "no state uploaded");
     if (c->pt_pending) return fail(c, HENS_ERR_STATE, "sharded PT exchange in flight (call hens_pt_finish_sharded)");
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    state_to_fields(c);                       // (hens_step leaves the state in record mode)
-    flush_adapt(c);
+    SETTLE(c, NEED_DEVICE | NEED_FIELDS | NEED_LADDER);
     const size_t TW = (size_t)c->Tl * c->W;
     // Leaf-packing contexts with resident templates (round 6): what the caller is about to hold is what a resumed chain
     // would start from - exact templates and log-likelihoods, a function of the coordinates.  If hens_rj_step has updated the
@@ -2381,7 +2446,7 @@ int hens_download_state(hens_ctx* ctx, double* x, double* logl, double* logp, do
     // caller stores carries the very log-likelihoods the device goes on with, and the next hens_rj_step call finds its templates
     // valid (round 5 invalidated them behind the copy: the stored log_like was the +- value the device then replaced, and every
     // stored step paid the evaluation at the head of the next call instead).
-    if (c->cfg.likelihood_kind == HENS_LIKE_TEMPLATE && (x || logl) && c->rj.tm && c->rj.tm_valid && c->rj.tm_drift) {
+    if (is_rj(c) && (x || logl) && c->rj.tm && c->rj.tm_valid && c->rj.tm_drift) {
         int r = rj_evaluate(c);
         if (r) return r;
         if ((r = check_flags(c, true))) return r;
@@ -2402,9 +2467,8 @@ int hens_eval_state(hens_ctx* ctx) {
     hens_ctx_impl* c = enter(ctx);
     int r = ready(c, false);
     if (r) return r;
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    state_to_fields(c);                       // (hens_step leaves the state in record mode)
-    if (c->cfg.likelihood_kind == HENS_LIKE_TEMPLATE) {
+    SETTLE(c, NEED_DEVICE | NEED_FIELDS);
+    if (is_rj(c)) {
         r = rj_evaluate(c);
         if (r) return r;
         r = check_flags(c, true);
@@ -2444,8 +2508,7 @@ static int prepare_split(hens_ctx_impl* c, int32_t split, const uint8_t* labels,
     if (c->propose_pending) return fail(c, HENS_ERR_STATE, "hens_propose_split without its hens_accept_split");
     int r;
     if ((r = counter_room(c, 1))) return r;          // (the iteration's last half-step, or its cascade, advances the counter)
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    flush_adapt(c);
+    SETTLE(c, NEED_DEVICE | NEED_LADDER);
     const int Tl = c->Tl, W = c->W;
     if (split == 0) {
         // ascending index lists per label (red_blue.py:150-154): order = [label 0 ... | label 1 ... | ...]
@@ -2504,8 +2567,7 @@ int hens_stretch_split(hens_ctx* ctx, int32_t split, const uint8_t* labels, cons
     hens_ctx_impl* c = enter(ctx);
     int r = ready(c, true);
     if (r) return r;
-    (void)hipSetDevice(c->cfg.device_id);
-    state_to_fields(c);                       // (hens_step leaves the state in record mode)
+    SETTLE(c, NEED_DEVICE | NEED_FIELDS);
     if (c->cfg.likelihood_kind == HENS_LIKE_HOST)
         return fail(c, HENS_ERR_STATE, "host-likelihood context: use hens_propose_split / hens_accept_split");
     if (!u_acc) return fail(c, HENS_ERR_INVALID, "null argument");
@@ -2549,7 +2611,7 @@ static HostLikeArgs hostlike_args(hens_ctx_impl* c, int32_t split) {
 // (utils/updates.py:130-175 mutates move.a; stretch.py:37,129-132 reads it per proposal): the scale of every LATER proposal.
 int hens_set_stretch_scale(hens_ctx* ctx, double a) {
     hens_ctx_impl* c = enter(ctx);
-    if (!c) return fail(c, HENS_ERR_INVALID, "null context");
+    if (!c) return no_context();
     if (!(a > 1.0) || !(a < INFINITY)) return fail(c, HENS_ERR_INVALID, "stretch scale a must be finite and > 1");
     if (c->expect_split != 0 || c->propose_pending) return fail(c, HENS_ERR_STATE, "a half-step is pending");
     c->cfg.a = a;                              // (every launch reads it from the context when it is built)
@@ -2559,7 +2621,7 @@ int hens_set_stretch_scale(hens_ctx* ctx, double a) {
 
 int hens_set_nsplits(hens_ctx* ctx, int32_t nsplits) {
     hens_ctx_impl* c = enter(ctx);
-    if (!c) return fail(c, HENS_ERR_INVALID, "null context");
+    if (!c) return no_context();
     if (nsplits < 2 || nsplits > 8) return fail(c, HENS_ERR_INVALID, "nsplits must be in [2, 8]");
     if (nsplits > c->W) return fail(c, HENS_ERR_INVALID, "more sets than walkers");
     if (c->expect_split != 0 || c->propose_pending) return fail(c, HENS_ERR_STATE, "a red-blue move is under way");
@@ -2573,8 +2635,7 @@ int hens_propose_split(hens_ctx* ctx, int32_t split, const uint8_t* labels, cons
     hens_ctx_impl* c = enter(ctx);
     int r = ready(c, true);
     if (r) return r;
-    (void)hipSetDevice(c->cfg.device_id);
-    state_to_fields(c);                       // (hens_step leaves the state in record mode)
+    SETTLE(c, NEED_DEVICE | NEED_FIELDS);
     if (c->cfg.likelihood_kind != HENS_LIKE_HOST)
         return fail(c, HENS_ERR_STATE, "hens_propose_split needs a context created with HENS_LIKE_HOST");
     if (!q_out || !inbox_out) return fail(c, HENS_ERR_INVALID, "null argument");
@@ -2604,8 +2665,7 @@ int hens_accept_split(hens_ctx* ctx, int32_t split, const double* logl, const do
     if (!c->propose_pending || split != c->expect_split)
         return fail(c, HENS_ERR_STATE, "hens_accept_split must follow hens_propose_split of the same split");
     if (!logl || !u_acc) return fail(c, HENS_ERR_INVALID, "null argument");
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    state_to_fields(c);                       // (hens_step leaves the state in record mode)
+    SETTLE(c, NEED_DEVICE | NEED_FIELDS);
     const int Ns = c->seg_off[split + 1] - c->seg_off[split];
     const size_t n = (size_t)c->Tl * Ns;
     const HostLikeArgs h = hostlike_args(c, split);
@@ -2632,11 +2692,10 @@ int hens_pt_sweep(hens_ctx* ctx, const int64_t* iperm, const int64_t* i1perm, co
     if (c->expect_split != 0) return fail(c, HENS_ERR_STATE, "PT sweep between split 0 and split 1");
     if ((r = counter_room(c, 1))) return r;
     if (!iperm || !i1perm || !u_swap) return fail(c, HENS_ERR_INVALID, "null argument");
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    state_to_fields(c);                       // (hens_step leaves the state in record mode)
+    SETTLE(c, NEED_DEVICE | NEED_FIELDS);
     const int T = c->T, W = c->W;
     if (T < 2) return HENS_OK;
-    flush_adapt(c);
+    SETTLE(c, NEED_LADDER);
     r = ensure_pt_buffers(c);
     if (r) return r;
     const size_t PW = (size_t)(T - 1) * W;
@@ -2664,7 +2723,7 @@ int hens_pt_sweep(hens_ctx* ctx, const int64_t* iperm, const int64_t* i1perm, co
     hipLaunchKernelGGL(k_pt_cascade<false>, dim3(pt_blocks(c)), dim3(pt_threads(c->T)), pt_lds_bytes(T), c->stream, p);
     c->adapt_pending = true;
     c->adapt_pending_adaptive = adapt && c->cfg.adaptive;
-    flush_adapt(c);
+    SETTLE(c, NEED_LADDER);                   // (this sweep's own counts)
     hipLaunchKernelGGL(k_pt_sel_to_korder, dim3(grid_for(PW)), dim3(256), 0, c->stream, c->selcol, c->colk, c->selk,
                        T - 1, W);
     HIPCHK(c, hipGetLastError());
@@ -2728,7 +2787,7 @@ int hens_step(hens_ctx* ctx, int64_t n_iters) {
     const bool aprof = c->per_kernel_events == 2 && aql_able && !env().step_events && n_iters <= 8192;
     const bool prof = c->per_kernel_events == 1 || (c->per_kernel_events == 2 && !aprof);
     // (the state stays in record mode between hens_step calls of the record paths - every other entry point settles it,
-    //  settle_state - so a short call pays no pack / unpack)
+    //  settle - so a short call pays no pack / unpack)
     if (!path.records()) state_to_fields(c);
     LaunchTimer timer;
     LaunchTimer* const tm = prof ? &timer : nullptr;
@@ -2780,7 +2839,7 @@ int hens_step(hens_ctx* ctx, int64_t n_iters) {
     if (path.it == Iteration::PIPE_INPLACE2) pipe_fused_epilogue(c);
     // The last cascade's ladder adaptation stays pending on one GPU: the next hens_step call folds it into its first
     // launch (no kernel of its own, ~12 us per call with its count-buffer reset), and every entry point that reads the ladder,
-    // the swap counters or the state settles it first (flush_adapt at their head) - same bits either way.
+    // the swap counters or the state settles it first (settle, NEED_LADDER) - same bits either way.
     if (path.piped()) pipe_flush_adapt(c);
     HIPCHK(c, hipGetLastError());
     if (c->step_events) HIPCHK(c, hipEventRecord(c->ev1, c->stream));
@@ -2820,17 +2879,16 @@ int hens_step(hens_ctx* ctx, int64_t n_iters) {
 // copies and their synchronisations per stored sample).
 int hens_step_marked(hens_ctx* ctx, int64_t n_before, int64_t n_last) {
     hens_ctx_impl* c = enter(ctx);
-    if (!c) return fail(c, HENS_ERR_INVALID, "null context");
+    if (!c) return no_context();
     if (n_before < 0 || n_last < 0) return fail(c, HENS_ERR_INVALID, "negative iteration count");
     int r;
     if (n_before > INT64_MAX - n_last) return fail(c, HENS_ERR_INVALID, "iteration count past INT64_MAX");
     if ((r = counter_room(c, n_before + n_last))) return r;
     if (n_before > 0 && (r = hens_step(ctx, n_before))) return r;
     if ((r = aql_settle(c))) return r;        // (what follows uses the HIP stream)
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    SETTLE(c, NEED_DEVICE | NEED_FIELDS);     // (the counters ride in the walker records during a hens_step call)
     const size_t TW = (size_t)c->Tl * c->W;
     if (!c->accepted_mark && (r = dalloc(c, &c->accepted_mark, 2 * TW))) return r;
-    state_to_fields(c);                       // (the counters ride in the walker records during a hens_step call)
     HIPCHK(c, hipMemcpyAsync(c->accepted_mark, c->accepted, TW * 4, hipMemcpyDeviceToDevice, c->stream));
     c->mark_mh = c->accepted_mh != nullptr;
     if (c->mark_mh) HIPCHK(c, hipMemcpyAsync(c->accepted_mark + TW, c->accepted_mh, TW * 4, hipMemcpyDeviceToDevice, c->stream));
@@ -2857,7 +2915,7 @@ static int report_snapshot(hens_ctx_impl* c) {
     const size_t TW = (size_t)c->Tl * c->W;
     int r;
     if ((r = aql_settle(c))) return r;
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    SETTLE(c, NEED_DEVICE);
     if (!c->report_prev) {
         if ((r = dalloc(c, &c->report_prev, 2 * TW))) return r;
         HIPCHK(c, hipMemsetAsync(c->report_prev, 0, 2 * TW * 4, c->stream));
@@ -2872,44 +2930,54 @@ static void report_marked(hens_ctx_impl* c, bool valid) {
     c->report_books = report_books(c);
 }
 
+// What a report and a stored step share: n - n_last iterations, the mark in front of the last n_last (kept from the last call where
+// the books allow: report_current), those iterations, the ladder and the swap counts of their last cascade settled, then the
+// consumer's launch - it reads the counters against the mark and moves the mark up, for every rung (`marks_all`) or for some.
+extern "C++" {                                // (a template, in the middle of the C ABI)
+template <class Consume>
+static int step_to_mark(hens_ctx* ctx, int64_t n, int64_t n_last, bool marks_all, Consume&& consume) {
+    hens_ctx_impl* c = CTX(ctx);
+    int r;
+    const bool have_prev = report_current(c) && n == n_last;
+    if (n > n_last && (r = hens_step(ctx, n - n_last))) return r;
+    if (!have_prev && (r = report_snapshot(c))) return r;
+    if ((r = hens_step(ctx, n_last))) { c->report_valid = false; return r; }
+    if ((r = aql_settle(c))) return r;        // (the consumer uses the HIP stream)
+    SETTLE(c, NEED_DEVICE | NEED_LADDER);     // (the ladder AFTER the step's adaptation - what hens_download_state returns - and its swap counts)
+    if ((r = consume())) return r;
+    report_marked(c, marks_all);
+    return HENS_OK;
+}
+}  // extern "C++"
+
 // n_iters iterations and what a sampler loop reads after EVERY proposal (ensemble.py:974-977), in one call and one small copy: the
 // accept counts of the call's last `n_last` iterations per walker (uint8, saturating: the reference's `accepted` of one
 // sub-iteration summed over num_repeats_in_model proposals), the last cascade's swap counts and the ladder.  The walkers stay on
 // the device: the drop-in moves' lazy State (eryn_amd/state.py: DeviceState) downloads them when somebody reads them.
 int hens_step_report(hens_ctx* ctx, int64_t n_iters, int64_t n_last, uint8_t* accepted_last, double* swaps_last, double* betas) {
     hens_ctx_impl* c = CTX(ctx);
-    if (!c) return fail(c, HENS_ERR_INVALID, "null context");
+    if (!c) return no_context();
     if (n_last < 1 || n_iters < n_last) return fail(c, HENS_ERR_INVALID, "hens_step_report: 1 <= n_last <= n_iters");
-    int r;
-    if ((r = counter_room(c, n_iters))) return r;
+    if (const int r = counter_room(c, n_iters)) return r;
     const size_t TW = (size_t)c->Tl * c->W;
-    const bool have_prev = report_current(c) && n_iters == n_last;
-    if (n_iters > n_last && (r = hens_step(ctx, n_iters - n_last))) return r;
-    if (!have_prev && (r = report_snapshot(c))) return r;
-    if (!c->mask_buf) {
-        HIPCHK(c, hipSetDevice(c->cfg.device_id));
-        if ((r = dalloc(c, &c->mask_buf, TW))) return r;
-    }
-    if ((r = hens_step(ctx, n_last))) { c->report_valid = false; return r; }
-    if ((r = aql_settle(c))) return r;
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    flush_adapt(c);                           // (swap counts and ladder of the last cascade)
-    launch_report_mask(c, c->mask_buf);
-    HIPCHK(c, hipGetLastError());
-    if (accepted_last) HIPCHK(c, hipMemcpyAsync(accepted_last, c->mask_buf, TW, hipMemcpyDeviceToHost, c->stream));
-    if (swaps_last && c->T > 1) HIPCHK(c, hipMemcpyAsync(swaps_last, c->swaps_last, (size_t)(c->T - 1) * 8, hipMemcpyDeviceToHost, c->stream));
-    if (betas) HIPCHK(c, hipMemcpyAsync(betas, c->betas[c->bcur], (size_t)c->T * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->hip_dirty = false;
-    report_marked(c, true);
-    return HENS_OK;
+    return step_to_mark(ctx, n_iters, n_last, true, [&]() -> int {
+        if (!c->mask_buf)
+            if (const int r = dalloc(c, &c->mask_buf, TW)) return r;
+        launch_report_mask(c, c->mask_buf);
+        HIPCHK(c, hipGetLastError());
+        if (accepted_last) HIPCHK(c, hipMemcpyAsync(accepted_last, c->mask_buf, TW, hipMemcpyDeviceToHost, c->stream));
+        if (swaps_last && c->T > 1) HIPCHK(c, hipMemcpyAsync(swaps_last, c->swaps_last, (size_t)(c->T - 1) * 8, hipMemcpyDeviceToHost, c->stream));
+        if (betas) HIPCHK(c, hipMemcpyAsync(betas, c->betas[c->bcur], (size_t)c->T * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        c->hip_dirty = false;
+        return HENS_OK;
+    });
 }
 
 // ---- chain store: what both families share (hens_chain_* below, hens_rj_chain_* behind hens_rj_step) ------------------------
 // The host protocol of a chain, once: an entry point of either family checks what is its own (chain_supported / rjchain_supported,
 // its arrays, its kernel's arguments) and calls these with its own name for the error texts.
 using ChainStore = hens_ctx_impl::ChainStore;
-static bool is_rj(const hens_ctx_impl* c) { return c->cfg.likelihood_kind == HENS_LIKE_TEMPLATE; }
 // the context has a chain, of the family that asks (the other family's entry points see none)
 static bool chain_is(const hens_ctx_impl* c, bool rj) { return c->chain.on && rj == is_rj(c); }
 static int chain_open(hens_ctx_impl* c, bool rj) {
@@ -2922,7 +2990,7 @@ static size_t swap_slots(const hens_ctx_impl* c, int least) { return (size_t)std
 
 static int chain_reset(hens_ctx_impl* c) {
     ChainStore& ch = c->chain;
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    SETTLE(c, NEED_DEVICE);
     for (uint32_t* tot : {ch.acc_tot, ch.bd_tot})        // (bd_tot: a leaf-packing chain has it)
         if (tot) HIPCHK(c, hipMemsetAsync(tot, 0, (size_t)ch.Ts * c->W * 4, c->stream));
     HIPCHK(c, hipMemsetAsync(ch.swaps_tot, 0, swap_slots(c, 1) * 8, c->stream));
@@ -2941,7 +3009,7 @@ static int chain_create_args(hens_ctx_impl* c, const char* who, int64_t capacity
 // ... and the chain itself from the family's list of (pointer in c->chain, bytes); `bytes` is the list's sum: the side arrays count
 struct ChainBuf { void* p; size_t bytes; };
 static int chain_create(hens_ctx_impl* c, const char* who, int64_t capacity, int Ts, const std::vector<ChainBuf>& bufs) {
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    SETTLE(c, NEED_DEVICE);
     HIPCHK(c, hipStreamSynchronize(c->stream));     // (a chain being replaced may still be written)
     ChainStore& ch = c->chain;
     ch.release();
@@ -2964,7 +3032,7 @@ static int chain_create(hens_ctx_impl* c, const char* who, int64_t capacity, int
 
 static int chain_destroy(hens_ctx_impl* c, bool rj) {
     if (!chain_is(c, rj)) return HENS_OK;
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    SETTLE(c, NEED_DEVICE);
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->chain.release();
     return HENS_OK;
@@ -2978,7 +3046,7 @@ static int chain_info(hens_ctx_impl* c, bool rj, int64_t step_bytes, hens_chain_
     hens_chain_info_t o{};
     o.capacity = ch.capacity; o.count = ch.count; o.ntemps_store = ch.Ts; o.bytes = ch.bytes; o.step_bytes = step_bytes;
     o.n_store_timed = ch.n_timed; o.store_ms = ch.store_ms;
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    SETTLE(c, NEED_DEVICE);
     size_t fr = 0, tot = 0;
     HIPCHK(c, hipMemGetInfo(&fr, &tot));
     o.free_bytes = (int64_t)fr;
@@ -3042,7 +3110,7 @@ static int chain_copy_out(hens_ctx_impl* c, int64_t first, int64_t count, std::i
                           double* betas, int64_t* iteration, int64_t* adapt_time) {
     if (count == 0) return HENS_OK;
     const ChainStore& ch = c->chain;
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    SETTLE(c, NEED_DEVICE);
     const size_t lp = (size_t)ch.Ts * c->W * 8;
     bool copied = false;
     auto copy = [&](const ChainCopy& f) {
@@ -3059,30 +3127,23 @@ static int chain_copy_out(hens_ctx_impl* c, int64_t first, int64_t count, std::i
 }
 
 // hens_*chain_totals: the family's [Ts][W] counters (destination, device array) and the swap totals, widened to double
-struct ChainTotal { double* dst; const uint32_t* src; };
-static int chain_totals(hens_ctx_impl* c, std::initializer_list<ChainTotal> tots, double* swaps_accepted) {
+static int chain_totals(hens_ctx_impl* c, std::initializer_list<CounterOut> tots, double* swaps_accepted) {
     const ChainStore& ch = c->chain;
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    const size_t TsW = (size_t)ch.Ts * c->W, np = swap_slots(c, 0);
-    size_t asked = 0;
-    for (const ChainTotal& t : tots) asked += t.dst != nullptr;
-    std::vector<uint32_t> acc(asked * TsW);           // (staged only where the caller asks)
+    SETTLE(c, NEED_DEVICE);
+    const size_t np = swap_slots(c, 0);
     std::vector<unsigned long long> sw(swaps_accepted ? np : 0);
-    size_t k = 0;
-    for (const ChainTotal& t : tots)
-        if (t.dst) HIPCHK(c, hipMemcpyAsync(&acc[TsW * k++], t.src, TsW * 4, hipMemcpyDeviceToHost, c->stream));
-    if (!sw.empty()) HIPCHK(c, hipMemcpyAsync(sw.data(), ch.swaps_tot, np * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    k = 0;
-    for (const ChainTotal& t : tots)
-        if (t.dst) std::copy_n(&acc[TsW * k++], TsW, t.dst);
+    const int r = read_counters(c, (size_t)ch.Ts * c->W, tots, [&]() -> int {
+        if (!sw.empty()) HIPCHK(c, hipMemcpyAsync(sw.data(), ch.swaps_tot, np * 8, hipMemcpyDeviceToHost, c->stream));
+        return HENS_OK;
+    });
+    if (r) return r;
     std::copy(sw.begin(), sw.end(), swaps_accepted);
     return HENS_OK;
 }
 
 // ---- chain store (include/hipensemble.h: hens_chain_*, hens_step_chain; csrc/hens_chain.h: k_chain_store) -------------------
 static int chain_supported(hens_ctx_impl* c) {
-    if (c->cfg.likelihood_kind == HENS_LIKE_TEMPLATE)
+    if (is_rj(c))
         return fail(c, HENS_ERR_UNSUPPORTED, "chain store: not on a leaf-packing context (records of several branches and leaves: hens_rj_chain_create / hens_rj_step_chain)");
     if (c->cfg.likelihood_kind == HENS_LIKE_HOST)
         return fail(c, HENS_ERR_UNSUPPORTED, "chain store: needs a device likelihood (a host-callable likelihood steps through the caller)");
@@ -3094,7 +3155,7 @@ static hens_chain::Shape chain_shape(const hens_ctx_impl* c, int Ts) { return he
 
 int hens_chain_create(hens_ctx* ctx, int64_t capacity, int32_t ntemps_store) {
     hens_ctx_impl* c = enter(ctx);
-    if (!c) return fail(c, HENS_ERR_INVALID, "null context");
+    if (!c) return no_context();
     int r, Ts = 0;
     if ((r = chain_supported(c)) || (r = chain_create_args(c, "hens_chain_create", capacity, ntemps_store, &Ts))) return r;
     hens_chain::Sizes sz{};
@@ -3107,14 +3168,14 @@ int hens_chain_create(hens_ctx* ctx, int64_t capacity, int32_t ntemps_store) {
 
 int hens_chain_reset(hens_ctx* ctx) {
     hens_ctx_impl* c = enter(ctx);
-    if (!c) return fail(c, HENS_ERR_INVALID, "null context");
+    if (!c) return no_context();
     if (const int r = chain_open(c, false)) return r;
     return chain_reset(c);
 }
 
 int hens_chain_destroy(hens_ctx* ctx) {
     hens_ctx_impl* c = enter(ctx);
-    if (!c) return fail(c, HENS_ERR_INVALID, "null context");
+    if (!c) return no_context();
     return chain_destroy(c, false);
 }
 
@@ -3157,7 +3218,7 @@ static int launch_chain_store(hens_ctx_impl* c, ChainTimer& tm) {
 
 int hens_step_chain(hens_ctx* ctx, int64_t n_store, int64_t iters_per_store, int64_t n_last) {
     hens_ctx_impl* c = CTX(ctx);              // (not `enter`, as every other chain entry point: hens_step below settles the queue itself)
-    if (!c) return fail(c, HENS_ERR_INVALID, "null context");
+    if (!c) return no_context();
     int r;
     if ((r = chain_supported(c)) || (r = chain_open(c, false))) return r;
     ChainStore& ch = c->chain;
@@ -3170,17 +3231,8 @@ int hens_step_chain(hens_ctx* ctx, int64_t n_store, int64_t iters_per_store, int
     }
     if ((r = counter_room(c, iters))) return r;
     ChainTimer tm(c);
-    for (int64_t s = 0; s < n_store; ++s) {
-        const bool have_prev = report_current(c) && iters_per_store == n_last;
-        if (iters_per_store > n_last && (r = hens_step(ctx, iters_per_store - n_last))) return r;
-        if (!have_prev && (r = report_snapshot(c))) return r;
-        if ((r = hens_step(ctx, n_last))) { c->report_valid = false; return r; }
-        if ((r = aql_settle(c))) return r;        // (the append uses the HIP stream)
-        HIPCHK(c, hipSetDevice(c->cfg.device_id));
-        flush_adapt(c);                           // (the ladder AFTER the step's adaptation - what hens_download_state returns - and its swap counts)
-        if ((r = launch_chain_store(c, tm))) return r;
-        report_marked(c, ch.Ts == c->Tl);         // (k_chain_store moved the mark up to now - of the rungs it stores)
-    }
+    for (int64_t s = 0; s < n_store; ++s)         // (k_chain_store moves the mark up to now - of the rungs it stores)
+        if ((r = step_to_mark(ctx, iters_per_store, n_last, ch.Ts == c->Tl, [&] { return launch_chain_store(c, tm); }))) return r;
     if (!tm.evs.empty()) {                        // (nothing else in this call waits for the stream)
         HIPCHK(c, hipStreamSynchronize(c->stream));
         tm.fold();
@@ -3191,7 +3243,7 @@ int hens_step_chain(hens_ctx* ctx, int64_t n_store, int64_t iters_per_store, int
 int hens_chain_download(hens_ctx* ctx, int64_t first, int64_t count, double* x, double* logl, double* logp, double* betas,
                         int64_t* iteration, int64_t* adapt_time) {
     hens_ctx_impl* c = enter(ctx);
-    if (!c) return fail(c, HENS_ERR_INVALID, "null context");
+    if (!c) return no_context();
     if (const int r = chain_range(c, false, "hens_chain_download", first, count)) return r;
     const size_t row = (size_t)c->chain.Ts * c->W * dim_active(c) * 8;
     return chain_copy_out(c, first, count, {{x, c->chain.x[0], row}}, logl, logp, betas, iteration, adapt_time);
@@ -3199,14 +3251,14 @@ int hens_chain_download(hens_ctx* ctx, int64_t first, int64_t count, double* x, 
 
 int hens_chain_totals(hens_ctx* ctx, double* accepted, double* swaps_accepted) {
     hens_ctx_impl* c = enter(ctx);
-    if (!c) return fail(c, HENS_ERR_INVALID, "null context");
+    if (!c) return no_context();
     if (const int r = chain_open(c, false)) return r;
     return chain_totals(c, {{accepted, c->chain.acc_tot}}, swaps_accepted);
 }
 
 // ---- chain diagnostics (include/hipensemble.h: hens_chain_moments, hens_chain_act; csrc/hens_chain_stats.h) -----------------
 static int chain_stats_enter(hens_ctx_impl* c, const char* who) {
-    if (c->cfg.likelihood_kind == HENS_LIKE_TEMPLATE)
+    if (is_rj(c))
         return fail(c, HENS_ERR_UNSUPPORTED, "%s: not built for a leaf-packing context - the autocorrelation time is not defined under reversible jump "
                     "(the reference refuses it as well) and the Gelman-Rubin diagnostic of a branch of several leaves needs the projection through the leaf masks", who);
     if (!c->chain.on) return fail(c, HENS_ERR_STATE, "no chain (hens_chain_create)");
@@ -3243,7 +3295,7 @@ static int chain_moments_run(hens_ctx_impl* c, const double* base, const hens_ch
     const int64_t blocks = hens_chain::stat_blocks(pl.nseries / pl.vec, 256);
     if (blocks > INT32_MAX) return fail(c, HENS_ERR_UNSUPPORTED, "%s: %lld series are more than one launch covers", who, (long long)pl.nseries);
     if (!sum && !m2 && !n_finite) return HENS_OK;
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    SETTLE(c, NEED_DEVICE);
     char* dev = nullptr;
     const size_t bytes = (size_t)pl.nseries * 8;
     HIPCHK(c, hipMalloc((void**)&dev, bytes * 3));
@@ -3262,7 +3314,7 @@ static int chain_moments_run(hens_ctx_impl* c, const double* base, const hens_ch
 int hens_chain_moments(hens_ctx* ctx, int32_t field, int64_t first, int64_t count, int64_t thin, int32_t ntemps,
                        double* sum, double* m2, int64_t* n_finite) {
     hens_ctx_impl* c = enter(ctx);
-    if (!c) return fail(c, HENS_ERR_INVALID, "null context");
+    if (!c) return no_context();
     int r;
     if ((r = chain_stats_enter(c, "hens_chain_moments"))) return r;
     ChainStore& ch = c->chain;
@@ -3276,7 +3328,7 @@ int hens_chain_moments(hens_ctx* ctx, int32_t field, int64_t first, int64_t coun
 int hens_chain_act(hens_ctx* ctx, int64_t first, int64_t count, int64_t thin, int32_t ntemps, int32_t window,
                    double* tau, double* mean, double* c0) {
     hens_ctx_impl* c = enter(ctx);
-    if (!c) return fail(c, HENS_ERR_INVALID, "null context");
+    if (!c) return no_context();
     int r;
     if ((r = chain_stats_enter(c, "hens_chain_act"))) return r;
     ChainStore& ch = c->chain;
@@ -3292,7 +3344,7 @@ int hens_chain_act(hens_ctx* ctx, int64_t first, int64_t count, int64_t thin, in
     const int64_t blocks = hens_chain::stat_blocks(pl.nseries, ACT_LANES);
     if (blocks > INT32_MAX) return fail(c, HENS_ERR_UNSUPPORTED, "hens_chain_act: %lld series are more than one launch covers", (long long)pl.nseries);
     if (!tau && !mean && !c0) return HENS_OK;
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    SETTLE(c, NEED_DEVICE);
     char* dev = nullptr;
     HIPCHK(c, hipMalloc((void**)&dev, (size_t)pl.nseries * 8 * 3));
     ChainStatArgs a{};
@@ -3310,7 +3362,7 @@ int hens_chain_act(hens_ctx* ctx, int64_t first, int64_t count, int64_t thin, in
 
 int hens_chain_stats_ms(hens_ctx* ctx, double* moments_ms, double* act_ms) {
     hens_ctx_impl* c = CTX(ctx);
-    if (!c) return fail(c, HENS_ERR_INVALID, "null context");
+    if (!c) return no_context();
     if (moments_ms) *moments_ms = c->chain.moments_ms;
     if (act_ms) *act_ms = c->chain.act_ms;
     return HENS_OK;
@@ -3319,35 +3371,28 @@ int hens_chain_stats_ms(hens_ctx* ctx, double* moments_ms, double* act_ms) {
 // the counters kept by the last hens_step_marked call ([Tl][W] each; accepted_mh may be null; zeros if there is no MH move)
 int hens_get_marked_counters(hens_ctx* ctx, double* accepted, double* accepted_mh) {
     hens_ctx_impl* c = enter(ctx);
-    if (!c) return fail(c, HENS_ERR_INVALID, "null context");
+    if (!c) return no_context();
     if (!c->mark_valid) return fail(c, HENS_ERR_STATE, "hens_get_marked_counters without hens_step_marked");
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    SETTLE(c, NEED_DEVICE);
     const size_t TW = (size_t)c->Tl * c->W;
-    std::vector<uint32_t> h(2 * TW, 0u);
-    HIPCHK(c, hipMemcpyAsync(h.data(), c->accepted_mark, (c->mark_mh ? 2 : 1) * TW * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (accepted) for (size_t i = 0; i < TW; ++i) accepted[i] = (double)h[i];
-    if (accepted_mh) for (size_t i = 0; i < TW; ++i) accepted_mh[i] = (double)h[TW + i];
+    std::vector<double> both(2 * TW, 0.0);                // (one copy of the mark: [stretch | MH, where there is an MH move])
+    if (const int r = read_counters(c, (c->mark_mh ? 2 : 1) * TW, {{both.data(), c->accepted_mark}})) return r;
+    if (accepted) std::copy_n(both.data(), TW, accepted);
+    if (accepted_mh) std::copy_n(both.data() + TW, TW, accepted_mh);
     return HENS_OK;
 }
 
 int hens_get_counters(hens_ctx* ctx, double* accepted, int64_t* num_proposals, double* swaps_last, double* swaps_total,
                       int64_t* adapt_time) {
     hens_ctx_impl* c = enter(ctx);
-    if (!c) return fail(c, HENS_ERR_INVALID, "null context");
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    state_to_fields(c);                       // (hens_step leaves the state in record mode)
-    flush_adapt(c);
-    const size_t TW = (size_t)c->Tl * c->W;
-    std::vector<uint32_t> acc;
-    if (accepted) {
-        acc.resize(TW);
-        HIPCHK(c, hipMemcpyAsync(acc.data(), c->accepted, TW * 4, hipMemcpyDeviceToHost, c->stream));
-    }
-    if (swaps_last && c->T > 1) HIPCHK(c, hipMemcpyAsync(swaps_last, c->swaps_last, (size_t)(c->T - 1) * 8, hipMemcpyDeviceToHost, c->stream));
-    if (swaps_total && c->T > 1) HIPCHK(c, hipMemcpyAsync(swaps_total, c->swaps_total, (size_t)(c->T - 1) * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (accepted) for (size_t i = 0; i < TW; ++i) accepted[i] = (double)acc[i];
+    if (!c) return no_context();
+    SETTLE(c, NEED_DEVICE | NEED_FIELDS | NEED_LADDER);
+    const int r = read_counters(c, (size_t)c->Tl * c->W, {{accepted, c->accepted}}, [&]() -> int {      // (the swap arrays under the same wait)
+        if (swaps_last && c->T > 1) HIPCHK(c, hipMemcpyAsync(swaps_last, c->swaps_last, (size_t)(c->T - 1) * 8, hipMemcpyDeviceToHost, c->stream));
+        if (swaps_total && c->T > 1) HIPCHK(c, hipMemcpyAsync(swaps_total, c->swaps_total, (size_t)(c->T - 1) * 8, hipMemcpyDeviceToHost, c->stream));
+        return HENS_OK;
+    });
+    if (r) return r;
     if (num_proposals) *num_proposals = c->num_proposals;
     if (adapt_time) *adapt_time = c->adapt_time;
     return HENS_OK;
@@ -3355,10 +3400,8 @@ int hens_get_counters(hens_ctx* ctx, double* accepted, int64_t* num_proposals, d
 
 int hens_reset_counters(hens_ctx* ctx) {
     hens_ctx_impl* c = enter(ctx);
-    if (!c) return fail(c, HENS_ERR_INVALID, "null context");
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    state_to_fields(c);                       // (hens_step leaves the state in record mode)
-    flush_adapt(c);
+    if (!c) return no_context();
+    SETTLE(c, NEED_DEVICE | NEED_FIELDS | NEED_LADDER);
     HIPCHK(c, hipMemsetAsync(c->accepted, 0, (size_t)c->Tl * c->W * 4, c->stream));
     HIPCHK(c, hipMemsetAsync(c->swaps_total, 0, (size_t)c->T * 8, c->stream));
     HIPCHK(c, hipMemsetAsync(c->swaps_last, 0, (size_t)c->T * 8, c->stream));
@@ -3375,23 +3418,20 @@ int hens_reset_counters(hens_ctx* ctx) {
 
 int hens_set_adapt_time(hens_ctx* ctx, int64_t t) {
     hens_ctx_impl* c = enter(ctx);
-    if (!c) return fail(c, HENS_ERR_INVALID, "null context");
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    state_to_fields(c);                       // (hens_step leaves the state in record mode)
-    flush_adapt(c);
+    if (!c) return no_context();
+    SETTLE(c, NEED_DEVICE | NEED_FIELDS | NEED_LADDER);
     c->adapt_time = t;
     return HENS_OK;
 }
 
 int hens_set_iteration(hens_ctx* ctx, int64_t iter) {
     hens_ctx_impl* c = enter(ctx);
-    if (!c) return fail(c, HENS_ERR_INVALID, "null context");
+    if (!c) return no_context();
     if (iter < 0) return fail(c, HENS_ERR_INVALID, "iteration counter < 0");
     if (pipe_active(c) && c->pipe.sweep > 0)
         return fail(c, HENS_ERR_STATE, "the iteration counter of a pipeline rank that has stepped cannot be moved");
     if (c->expect_split != 0 || c->propose_pending) return fail(c, HENS_ERR_STATE, "a half-step is pending");
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    state_to_fields(c);                       // (column-ordered records are in the OLD counter's order)
+    SETTLE(c, NEED_DEVICE | NEED_FIELDS);     // (column-ordered records are in the OLD counter's order)
     c->win_count = 0;
     c->iter = (uint64_t)iter;                 // (the round-key window re-plans itself when the chain has left it)
     return HENS_OK;
@@ -3399,7 +3439,7 @@ int hens_set_iteration(hens_ctx* ctx, int64_t iter) {
 
 int hens_set_profiling(hens_ctx* ctx, int32_t per_kernel_events) {
     hens_ctx_impl* c = CTX(ctx);
-    if (!c) return fail(c, HENS_ERR_INVALID, "null context");
+    if (!c) return no_context();
     if (per_kernel_events < 0 || per_kernel_events > 2) return fail(c, HENS_ERR_INVALID, "hens_set_profiling: mode 0, 1 or 2");
     c->per_kernel_events = per_kernel_events;
     return HENS_OK;
@@ -3429,8 +3469,8 @@ int hens_debug_launch_times(hens_ctx* ctx, double* out_us, int64_t capacity, int
 
 int hens_debug_trace(hens_ctx* ctx, int32_t enable, uint64_t* out, int64_t capacity, int64_t* n_out) {
     hens_ctx_impl* c = enter(ctx);
-    if (!c) return fail(c, HENS_ERR_INVALID, "null context");
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    if (!c) return no_context();
+    SETTLE(c, NEED_DEVICE);
     const int64_t words = std::max<int64_t>((int64_t)c->Tl * ((c->W + TILE - 1) / TILE), pt_blocks(c)) * 8;
     if (enable) {
         if (!c->d_trace) {
@@ -3458,7 +3498,7 @@ int hens_debug_trace(hens_ctx* ctx, int32_t enable, uint64_t* out, int64_t capac
 int hens_debug_permutation(hens_ctx* ctx, int32_t which, int32_t rung, int64_t iter, int32_t* out) {
     hens_ctx_impl* c = enter(ctx);
     if (!c || !out) return fail(c, HENS_ERR_INVALID, "null argument");
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    SETTLE(c, NEED_DEVICE);
     int32_t* d = reinterpret_cast<int32_t*>(c->xtmp);          // scratch: at least W * 4 bytes
     hipLaunchKernelGGL(k_debug_prp, dim3(grid_for(c->W)), dim3(256), 0, c->stream, d, c->W, c->idx_bits, c->cfg.seed,
                        (uint64_t)iter, which == 0 ? PURPOSE_PTPERM : PURPOSE_SPLIT, (uint32_t)rung);
@@ -3478,18 +3518,9 @@ int hens_debug_draws(hens_ctx* ctx, int64_t iter, int32_t* own, int32_t* cw, dou
                      int32_t* pt_slot, double* u_swap, int32_t* is_mh, double* mh_step, double* mh_u) {
     hens_ctx_impl* c = enter(ctx);
     if (!c || iter < 0) return fail(c, HENS_ERR_INVALID, "null context / negative iteration");
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    SETTLE(c, NEED_DEVICE);
     const size_t TW = (size_t)c->Tl * c->W;
-    struct Scratch {                      // debug path: plain allocations, freed on every exit
-        std::vector<void*> p;
-        ~Scratch() { for (void* q : p) (void)hipFree(q); }
-    } sc;
-    auto grab = [&](size_t bytes) -> void* {
-        void* q = nullptr;
-        if (hipMalloc(&q, std::max<size_t>(bytes, 8)) != hipSuccess) return nullptr;
-        sc.p.push_back(q);
-        return q;
-    };
+    DeviceScratch sc;
     const bool mh = [&] {
         if (c->mh_kind < 0 || c->mh_weight <= 0.0) return false;
         return c->mh_weight >= 1.0 || move_uniform(c->cfg.seed, (uint64_t)iter) < c->mh_weight;
@@ -3497,9 +3528,9 @@ int hens_debug_draws(hens_ctx* ctx, int64_t iter, int32_t* own, int32_t* cw, dou
     if (is_mh) *is_mh = mh ? 1 : 0;
     if (own || cw || u_zz || u_acc) {     // the stretch plan of that iteration, exactly as hens_step's plan kernel makes it
         PlanArgs pa{};
-        pa.dr.own = (int32_t*)grab(TW * 4); pa.dr.cw = (int32_t*)grab(TW * 4);
-        pa.dr.zz = (double*)grab(TW * 8); pa.dr.fac = (double*)grab(TW * 8); pa.dr.lu = (double*)grab(TW * 8);
-        pa.dbg_uzz = (double*)grab(TW * 8); pa.dbg_uacc = (double*)grab(TW * 8);
+        pa.dr.own = sc.grab<int32_t>(TW); pa.dr.cw = sc.grab<int32_t>(TW);
+        pa.dr.zz = sc.grab<double>(TW); pa.dr.fac = sc.grab<double>(TW); pa.dr.lu = sc.grab<double>(TW);
+        pa.dbg_uzz = sc.grab<double>(TW); pa.dbg_uacc = sc.grab<double>(TW);
         if (!pa.dr.own || !pa.dr.cw || !pa.dr.zz || !pa.dr.fac || !pa.dr.lu || !pa.dbg_uzz || !pa.dbg_uacc)
             return fail(c, HENS_ERR_HIP, "hens_debug_draws: out of device memory");
         pa.iter0 = (uint64_t)iter; pa.seed = c->cfg.seed; pa.a = c->cfg.a;
@@ -3507,11 +3538,11 @@ int hens_debug_draws(hens_ctx* ctx, int64_t iter, int32_t* own, int32_t* cw, dou
         pa.T = c->T; pa.cb = c->label_cb;
         if (c->nsplits > 2) {                // (positions then run through the sets one after the other: k_plan_sets)
             pa.nsets = c->nsplits; pa.cb = 0;
-            pa.order = (int32_t*)grab(TW * 4);
+            pa.order = sc.grab<int32_t>(TW);
             if (!pa.order) return fail(c, HENS_ERR_HIP, "hens_debug_draws: out of device memory");
         }
         if (pa.cb) {
-            pa.keys = (uint32_t*)grab((size_t)c->T * 8 * 4);
+            pa.keys = sc.grab<uint32_t>((size_t)c->T * 8);
             if (!pa.keys) return fail(c, HENS_ERR_HIP, "hens_debug_draws: out of device memory");
         }
         launch_plan_kernels(c, c->stream, pa, 1);
@@ -3524,19 +3555,14 @@ int hens_debug_draws(hens_ctx* ctx, int64_t iter, int32_t* own, int32_t* cw, dou
     }
     if ((pt_slot || u_swap) && c->T > 1) {
         const size_t n = (size_t)c->T * c->W;
-        int32_t* ds = (int32_t*)grab(n * 4);
-        double* du = (double*)grab(n * 8);
+        int32_t* ds = sc.grab<int32_t>(n);
+        double* du = sc.grab<double>(n);
         if (!ds || !du) return fail(c, HENS_ERR_HIP, "hens_debug_draws: out of device memory");
-        hipLaunchKernelGGL(k_debug_pt, dim3(grid_for((int64_t)n)), dim3(256), 0, c->stream, ds, du, c->T, c->W, c->idx_bits,
-                           c->cfg.seed, (uint64_t)iter);
-        HIPCHK(c, hipGetLastError());
-        if (pt_slot) HIPCHK(c, hipMemcpyAsync(pt_slot, ds, n * 4, hipMemcpyDeviceToHost, c->stream));
-        if (u_swap) HIPCHK(c, hipMemcpyAsync(u_swap, du, (size_t)(c->T - 1) * c->W * 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (const int r = export_pt_draws(c, ds, du, (uint64_t)iter, pt_slot, u_swap)) return r;
     }
     if ((mh_step || mh_u) && c->mh_kind >= 0) {
         MhDrawArgs d{};
-        d.step = (double*)grab(TW * c->D * 8); d.lu = (double*)grab(TW * 8); d.dbg_u = (double*)grab(TW * 8);
+        d.step = sc.grab<double>(TW * c->D); d.lu = sc.grab<double>(TW); d.dbg_u = sc.grab<double>(TW);
         if (!d.step || !d.lu || !d.dbg_u) return fail(c, HENS_ERR_HIP, "hens_debug_draws: out of device memory");
         d.scale = c->mh_scale; d.iter = (uint64_t)iter; d.seed = c->cfg.seed;
         d.Tl = c->Tl; d.W = c->W; d.D = c->D; d.rung_begin = c->cfg.rung_begin; d.kind = c->mh_kind;
@@ -3558,11 +3584,10 @@ static int rj_set_template_model(hens_ctx_impl* c, int nkinds, int32_t nbranches
                                  int32_t ndata, const double* t, const double* y, double sigma) {
     if (!c || !kinds || !nleaves_max || !nleaves_min || !lo || !hi || !leaf_logp || !t || !y)
         return fail(c, HENS_ERR_INVALID, "null argument");
-    if (c->cfg.likelihood_kind != HENS_LIKE_TEMPLATE) return fail(c, HENS_ERR_STATE, "hens_rj_set_model needs HENS_LIKE_TEMPLATE");
+    if (!is_rj(c)) return fail(c, HENS_ERR_STATE, "hens_rj_set_model needs HENS_LIKE_TEMPLATE");
     if (nbranches < 1 || nbranches > RJ_MAX_BRANCH) return fail(c, HENS_ERR_INVALID, "1..%d branches", RJ_MAX_BRANCH);
     if (ndata < 1 || !(sigma > 0.0)) return fail(c, HENS_ERR_INVALID, "invalid data");
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    state_to_fields(c);                       // (hens_step leaves the state in record mode)
+    SETTLE(c, NEED_DEVICE | NEED_FIELDS);
     if (const int rd = rjchain_drop(c)) return rd;
     RjModel M{};
     M.nb = nbranches; M.ndata = ndata; M.sigma = sigma;
@@ -3670,10 +3695,9 @@ int hens_rj_set_model_general(hens_ctx* ctx, int32_t nbranches, const int32_t* n
                               const int32_t* nleaves_min, const double* lo, const double* hi, const double* leaf_logp) {
     hens_ctx_impl* c = enter(ctx);
     if (!c || !ndims || !nleaves_max || !nleaves_min || !lo || !hi || !leaf_logp) return fail(c, HENS_ERR_INVALID, "null argument");
-    if (c->cfg.likelihood_kind != HENS_LIKE_TEMPLATE) return fail(c, HENS_ERR_STATE, "hens_rj_set_model_general needs HENS_LIKE_TEMPLATE");
+    if (!is_rj(c)) return fail(c, HENS_ERR_STATE, "hens_rj_set_model_general needs HENS_LIKE_TEMPLATE");
     if (nbranches < 1 || nbranches > RJ_MAX_BRANCH) return fail(c, HENS_ERR_INVALID, "1..%d branches", RJ_MAX_BRANCH);
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    state_to_fields(c);
+    SETTLE(c, NEED_DEVICE | NEED_FIELDS);
     if (const int rd = rjchain_drop(c)) return rd;
     RjModel M{};
     M.nb = nbranches; M.ndata = 0; M.sigma = 1.0; M.t_step64 = 0.0;
@@ -3715,12 +3739,12 @@ int hens_rj_set_model_general(hens_ctx* ctx, int32_t nbranches, const int32_t* n
 int hens_rj_set_mh_scale(hens_ctx* ctx, const double* scale) {
     hens_ctx_impl* c = enter(ctx);
     if (!c || !scale) return fail(c, HENS_ERR_INVALID, "null argument");
-    if (c->cfg.likelihood_kind != HENS_LIKE_TEMPLATE || !c->have_like) return fail(c, HENS_ERR_STATE, "hens_rj_set_model first");
+    if (const int rm = need_rj_model(c)) return rm;
     if (c->rj.general) return fail(c, HENS_ERR_STATE, "the Philox in-model move belongs to hens_rj_step: template models only");
     for (int b = 0; b < c->rj.M.nb; ++b)          // [nbranches][the widest branch's parameters]: 3 on a pulse / sine model
         for (int d = 0; d < c->rj.M.nd[b]; ++d) c->rj.M.mh_scale[b][d] = scale[b * c->rj.M.ndmax + d];
     c->rj.have_scale = true; c->rj.have_chol = false;
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    SETTLE(c, NEED_DEVICE);
     return rj_push_ctab(c);
 }
 
@@ -3730,7 +3754,7 @@ int hens_rj_set_mh_scale(hens_ctx* ctx, const double* scale) {
 int hens_rj_set_mh_chol(hens_ctx* ctx, const double* chol) {
     hens_ctx_impl* c = enter(ctx);
     if (!c || !chol) return fail(c, HENS_ERR_INVALID, "null argument");
-    if (c->cfg.likelihood_kind != HENS_LIKE_TEMPLATE || !c->have_like) return fail(c, HENS_ERR_STATE, "hens_rj_set_model first");
+    if (const int rm = need_rj_model(c)) return rm;
     if (c->rj.general) return fail(c, HENS_ERR_STATE, "the Philox in-model move belongs to hens_rj_step: template models only");
     if (c->rj.wide) return fail(c, HENS_ERR_UNSUPPORTED, "full leaf covariances: models of pulses and sines only (diagonal steps: hens_rj_set_mh_scale)");
     for (int b = 0; b < c->rj.M.nb; ++b)
@@ -3747,7 +3771,7 @@ int hens_rj_set_mh_chol(hens_ctx* ctx, const double* chol) {
             c->rj.M.mh_scale[b][d] = c->rj.chol[b][d][d];
         }
     c->rj.have_scale = c->rj.have_chol = true;
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    SETTLE(c, NEED_DEVICE);
     return rj_push_ctab(c);
 }
 
@@ -3845,9 +3869,7 @@ static int rj_forced_move(hens_ctx_impl* c, int move, const hens_rj_draws& d, ui
     int r = rj_ready(c, move == HENS_RJ_MOVE_STRETCH && d.split == 1, propose);
     if (r) return r;
     if ((r = rj_forced_check(c, move, d))) return r;
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    state_to_fields(c);                       // (hens_step leaves the state in record mode)
-    flush_adapt(c);
+    SETTLE(c, NEED_DEVICE | NEED_FIELDS | NEED_LADDER);
     if ((r = rj_ensure_staging(c))) return r;
     RjLaunch l = rj_forced(c, mode_of[move], propose);
     if ((r = rj_forced_stage(c, move, d, l))) return r;
@@ -3906,7 +3928,8 @@ struct RjStepping {
     hens_ctx_impl* c;
     bool stretch = false, fresh = false, armed = false;
     explicit RjStepping(hens_ctx_impl* c_) : c(c_) {}
-    ~RjStepping() { if (armed) { c->rj.defer_adapt = false; flush_adapt(c); } }     // (every way out leaves no adaptation pending and the switch off)
+    void finish() { if (armed) { c->rj.defer_adapt = false; flush_adapt(c); armed = false; } }   // the switch off, no adaptation pending ...
+    ~RjStepping() { finish(); }                                                                  // ... on every way out
     int begin(int64_t n_iters);
     int iteration(double* swaps_aside);
 };
@@ -3918,8 +3941,7 @@ int RjStepping::begin(int64_t n_iters) {
     if (stretch && !c->cfg.live_dangerously && c->W < 2 * c->rj.M.ind_off)           // red_blue.py:103-114 (every slot of every branch counts)
         return fail(c, HENS_ERR_TOO_FEW_WALKERS, "It is unadvisable to use a red-blue move with fewer walkers than twice the number of dimensions. "
                                                  "If you would like to do this, please set live_dangerously to True.");
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    state_to_fields(c);                       // (hens_step leaves the state in record mode)
+    SETTLE(c, NEED_DEVICE | NEED_FIELDS);
     HIPCHK(c, hipEventRecord(c->ev0, c->stream));
     c->step_events = true;
     c->timing = hens_timing{};
@@ -3992,8 +4014,7 @@ int hens_rj_step(hens_ctx* ctx, int64_t n_iters) {
     if ((r = st.begin(n_iters))) return r;
     for (int64_t i = 0; i < n_iters; ++i)
         if ((r = st.iteration(nullptr))) return r;
-    c->rj.defer_adapt = false;
-    flush_adapt(c);
+    st.finish();
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(c->ev1, c->stream));
     c->timing.n_iters = n_iters;
@@ -4005,9 +4026,9 @@ int hens_rj_step(hens_ctx* ctx, int64_t n_iters) {
 // ---- chain store of a leaf-packing context (include/hipensemble.h: hens_rj_chain_*, hens_rj_step_chain; csrc/hens_rj_chain.h) ----
 // The host protocol is `chain store: what both families share` above; here what a leaf-packing chain has of its own.
 static int rjchain_supported(hens_ctx_impl* c) {
-    if (c->cfg.likelihood_kind != HENS_LIKE_TEMPLATE)
+    if (!is_rj(c))
         return fail(c, HENS_ERR_UNSUPPORTED, "hens_rj_chain_*: the chain store of a leaf-packing context (HENS_LIKE_TEMPLATE); others: hens_chain_create / hens_step_chain");
-    if (c->rj.M.nb <= 0 || !c->rj.acc_bd) return fail(c, HENS_ERR_STATE, "hens_rj_chain_*: no model (hens_rj_set_model first)");
+    if (!rj_has_model(c)) return fail(c, HENS_ERR_STATE, "hens_rj_chain_*: no model (hens_rj_set_model first)");
     if (c->rj.general)
         return fail(c, HENS_ERR_UNSUPPORTED, "chain store: needs a device likelihood (a model of hens_rj_set_model_general steps through the caller)");
     if (c->Tl != c->T) return fail(c, HENS_ERR_UNSUPPORTED, "chain store: not on a ladder shard (the whole ladder on one GPU)");
@@ -4030,7 +4051,7 @@ static int rjchain_drop(hens_ctx_impl* c) {
 
 int hens_rj_chain_create(hens_ctx* ctx, int64_t capacity, int32_t ntemps_store) {
     hens_ctx_impl* c = enter(ctx);
-    if (!c) return fail(c, HENS_ERR_INVALID, "null context");
+    if (!c) return no_context();
     int r, Ts = 0;
     if ((r = rjchain_supported(c)) || (r = chain_create_args(c, "hens_rj_chain_create", capacity, ntemps_store, &Ts))) return r;
     hens_chain::RjSizes sz{};
@@ -4046,14 +4067,14 @@ int hens_rj_chain_create(hens_ctx* ctx, int64_t capacity, int32_t ntemps_store) 
 
 int hens_rj_chain_reset(hens_ctx* ctx) {
     hens_ctx_impl* c = enter(ctx);
-    if (!c) return fail(c, HENS_ERR_INVALID, "null context");
+    if (!c) return no_context();
     if (const int r = chain_open(c, true)) return r;
     return chain_reset(c);
 }
 
 int hens_rj_chain_destroy(hens_ctx* ctx) {
     hens_ctx_impl* c = enter(ctx);
-    if (!c) return fail(c, HENS_ERR_INVALID, "null context");
+    if (!c) return no_context();
     return chain_destroy(c, true);
 }
 
@@ -4097,7 +4118,7 @@ static int launch_rj_chain_store(hens_ctx_impl* c, ChainTimer& tm) {
 
 int hens_rj_step_chain(hens_ctx* ctx, int64_t n_store, int64_t iters_per_store) {
     hens_ctx_impl* c = enter(ctx);
-    if (!c) return fail(c, HENS_ERR_INVALID, "null context");
+    if (!c) return no_context();
     int r;
     if ((r = rjchain_supported(c)) || (r = chain_open(c, true)) || (r = rj_ready(c))) return r;
     ChainStore& ch = c->chain;
@@ -4124,15 +4145,14 @@ int hens_rj_step_chain(hens_ctx* ctx, int64_t n_store, int64_t iters_per_store) 
         }
         ch.mark_valid = false;
         if ((r = st.iteration(ch.swaps_step))) return r;
-        flush_adapt(c);                           // (the ladder AFTER the step's adaptation - what hens_download_state returns)
+        SETTLE(c, NEED_LADDER);                   // (the ladder AFTER the step's adaptation - what hens_download_state returns)
         // what hens_download_state runs in front of its copy: the stored log_like is the value the device goes on with
         if (c->rj.tm && c->rj.tm_valid && c->rj.tm_drift && (r = rj_evaluate(c))) return r;
         if ((r = launch_rj_chain_store(c, tm))) return r;
         ch.mark_valid = true;                     // (k_rj_chain_store moved the mark up to now)
         ch.mark_books = c->rj.num_mh + c->rj.num_bd;
     }
-    c->rj.defer_adapt = false;
-    flush_adapt(c);
+    st.finish();
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(c->ev1, c->stream));
     c->timing.n_iters = iters;
@@ -4144,7 +4164,7 @@ int hens_rj_step_chain(hens_ctx* ctx, int64_t n_store, int64_t iters_per_store) 
 int hens_rj_chain_download(hens_ctx* ctx, int64_t first, int64_t count, int32_t branch, double* x, uint8_t* inds, double* logl,
                            double* logp, double* betas, int64_t* iteration, int64_t* adapt_time) {
     hens_ctx_impl* c = enter(ctx);
-    if (!c) return fail(c, HENS_ERR_INVALID, "null context");
+    if (!c) return no_context();
     if (const int r = chain_range(c, true, "hens_rj_chain_download", first, count)) return r;
     if (!hens_chain::rj_branch_ok(c->rj.M.nb, branch) || (branch < 0 && (x || inds)))
         return fail(c, HENS_ERR_INVALID, "hens_rj_chain_download: branch %d of %d (-1: the shared fields, x = inds = NULL)", branch, c->rj.M.nb);
@@ -4156,7 +4176,7 @@ int hens_rj_chain_download(hens_ctx* ctx, int64_t first, int64_t count, int32_t 
 
 int hens_rj_chain_totals(hens_ctx* ctx, double* accepted, double* rj_accepted, double* swaps_accepted) {
     hens_ctx_impl* c = enter(ctx);
-    if (!c) return fail(c, HENS_ERR_INVALID, "null context");
+    if (!c) return no_context();
     if (const int r = chain_open(c, true)) return r;
     return chain_totals(c, {{accepted, c->chain.acc_tot}, {rj_accepted, c->chain.bd_tot}}, swaps_accepted);
 }
@@ -4189,7 +4209,7 @@ static RjStatArgs rj_stat_args(const ChainStore& ch, int32_t branch, const hens_
 int hens_rj_chain_leaves(hens_ctx* ctx, int32_t branch, int64_t first, int64_t count, int64_t thin, int32_t ntemps, uint8_t* nleaves,
                          uint32_t* hist) {
     hens_ctx_impl* c = enter(ctx);
-    if (!c) return fail(c, HENS_ERR_INVALID, "null context");
+    if (!c) return no_context();
     int r;
     hens_chain::RjStatPlan pl{};
     if ((r = rj_stats_enter(c)) || (r = rj_stats_plan(c, "hens_rj_chain_leaves", branch, first, count, thin, ntemps, &pl))) return r;
@@ -4199,7 +4219,7 @@ int hens_rj_chain_leaves(hens_ctx* ctx, int32_t branch, int64_t first, int64_t c
     if (blocks > INT32_MAX || !hens_chain::mul(count, pl.nplaces, &nbytes))
         return fail(c, HENS_ERR_UNSUPPORTED, "hens_rj_chain_leaves: %lld places over %lld kept steps are more than one launch covers", (long long)pl.nplaces, (long long)count);
     if (!nleaves && !hist) return HENS_OK;
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    SETTLE(c, NEED_DEVICE);
     const size_t hbytes = (size_t)pl.nplaces * (size_t)(pl.nl + 1) * 4;
     char* dev = nullptr;
     HIPCHK(c, hipMalloc((void**)&dev, hbytes + (nleaves ? (size_t)nbytes : 0)));
@@ -4214,7 +4234,7 @@ int hens_rj_chain_leaves(hens_ctx* ctx, int32_t branch, int64_t first, int64_t c
 int hens_rj_chain_leaf_moments(hens_ctx* ctx, int32_t branch, int64_t first, int64_t count, int64_t thin, int32_t ntemps, int64_t lo,
                                int64_t hi, double* sum, double* m2, int64_t* n) {
     hens_ctx_impl* c = enter(ctx);
-    if (!c) return fail(c, HENS_ERR_INVALID, "null context");
+    if (!c) return no_context();
     int r;
     hens_chain::RjStatPlan pl{};
     if ((r = rj_stats_enter(c)) || (r = rj_stats_plan(c, "hens_rj_chain_leaf_moments", branch, first, count, thin, ntemps, &pl))) return r;
@@ -4224,7 +4244,7 @@ int hens_rj_chain_leaf_moments(hens_ctx* ctx, int32_t branch, int64_t first, int
     const int64_t blocks = hens_chain::stat_blocks(pl.nseries, RJ_STAT_LANES);
     if (blocks > INT32_MAX) return fail(c, HENS_ERR_UNSUPPORTED, "hens_rj_chain_leaf_moments: %lld series are more than one launch covers", (long long)pl.nseries);
     if (!sum && !m2 && !n) return HENS_OK;
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    SETTLE(c, NEED_DEVICE);
     const size_t sbytes = (size_t)pl.nseries * 8, pbytes = (size_t)pl.nplaces * 8;
     char* dev = nullptr;
     HIPCHK(c, hipMalloc((void**)&dev, 2 * sbytes + pbytes));
@@ -4243,7 +4263,7 @@ int hens_rj_chain_leaf_moments(hens_ctx* ctx, int32_t branch, int64_t first, int
 int hens_rj_chain_moments(hens_ctx* ctx, int32_t field, int32_t branch, int64_t first, int64_t count, int64_t thin, int32_t ntemps,
                           double* sum, double* m2, int64_t* n_finite) {
     hens_ctx_impl* c = enter(ctx);
-    if (!c) return fail(c, HENS_ERR_INVALID, "null context");
+    if (!c) return no_context();
     if (const int r = rj_stats_enter(c)) return r;
     ChainStore& ch = c->chain;
     hens_chain::StatPlan pl{};
@@ -4259,7 +4279,7 @@ int hens_rj_chain_moments(hens_ctx* ctx, int32_t field, int32_t branch, int64_t 
 // ran later (-1: none yet)
 int hens_rj_chain_stats_ms(hens_ctx* ctx, double* leaves_ms, double* moments_ms) {
     hens_ctx_impl* c = CTX(ctx);
-    if (!c) return fail(c, HENS_ERR_INVALID, "null context");
+    if (!c) return no_context();
     if (const int r = rjchain_supported(c)) return r;
     if (leaves_ms) *leaves_ms = c->chain.leaves_ms;
     if (moments_ms) *moments_ms = c->chain.leaf_moments_ms;
@@ -4275,9 +4295,9 @@ int hens_rj_chain_stats_ms(hens_ctx* ctx, double* leaves_ms, double* moments_ms)
 int hens_rj_propose(hens_ctx* ctx, int32_t move, const hens_rj_draws* d, double* q_out, double* logp_out, uint8_t* moved_out) {
     hens_ctx_impl* c = enter(ctx);
     if (!c || !d || !q_out || !logp_out || !moved_out) return fail(c, HENS_ERR_INVALID, "null argument");
-    if (c->cfg.likelihood_kind != HENS_LIKE_TEMPLATE) return fail(c, HENS_ERR_STATE, "hens_rj_* needs a context created with HENS_LIKE_TEMPLATE");
+    if (const int rk = need_rj_context(c)) return rk;
     if (c->rj.accept_pending) return fail(c, HENS_ERR_STATE, "hens_rj_accept must follow hens_rj_propose");
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    SETTLE(c, NEED_DEVICE);
     const size_t TW = (size_t)c->Tl * c->W, RW = (size_t)c->rj.M.RW;
     int r;
     if (!c->rj.hq) {
@@ -4304,7 +4324,7 @@ int hens_rj_accept(hens_ctx* ctx, const double* logl, uint8_t* keep_out) {
     hens_ctx_impl* c = enter(ctx);
     if (!c || !logl) return fail(c, HENS_ERR_INVALID, "null argument");
     if (!c->rj.accept_pending) return fail(c, HENS_ERR_STATE, "hens_rj_accept must follow hens_rj_propose");
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    SETTLE(c, NEED_DEVICE);
     const size_t TW = (size_t)c->Tl * c->W;
     for (size_t i = 0; i < TW; ++i)
         if (logl[i] != logl[i]) return fail(c, HENS_ERR_NONFINITE, "The likelihood function is returning Nan.");       // ensemble.py:1542
@@ -4325,8 +4345,8 @@ int hens_rj_accept(hens_ctx* ctx, const double* logl, uint8_t* keep_out) {
 
 int hens_rj_set_schedule(hens_ctx* ctx, int32_t schedule) {
     hens_ctx_impl* c = enter(ctx);
-    if (!c) return fail(c, HENS_ERR_INVALID, "null context");
-    if (c->cfg.likelihood_kind != HENS_LIKE_TEMPLATE) return fail(c, HENS_ERR_STATE, "hens_rj_* needs a context created with HENS_LIKE_TEMPLATE");
+    if (!c) return no_context();
+    if (const int rk = need_rj_context(c)) return rk;
     if (schedule < 0 || schedule > 3) return fail(c, HENS_ERR_UNSUPPORTED, "rj schedule must be 0 (separate_branches), 1 (iterate_branches), 2 (together) or 3 (none)");
     c->rj.schedule = schedule;
     return HENS_OK;
@@ -4334,8 +4354,8 @@ int hens_rj_set_schedule(hens_ctx* ctx, int32_t schedule) {
 
 int hens_rj_set_in_model(hens_ctx* ctx, int32_t kind) {
     hens_ctx_impl* c = enter(ctx);
-    if (!c) return fail(c, HENS_ERR_INVALID, "null context");
-    if (c->cfg.likelihood_kind != HENS_LIKE_TEMPLATE) return fail(c, HENS_ERR_STATE, "hens_rj_* needs a context created with HENS_LIKE_TEMPLATE");
+    if (!c) return no_context();
+    if (const int rk = need_rj_context(c)) return rk;
     if (c->rj.general) return fail(c, HENS_ERR_STATE, "the Philox in-model move belongs to hens_rj_step: template models only");
     if (kind != HENS_RJ_INMODEL_GAUSSIAN && kind != HENS_RJ_INMODEL_STRETCH)
         return fail(c, HENS_ERR_INVALID, "in-model move must be HENS_RJ_INMODEL_GAUSSIAN or HENS_RJ_INMODEL_STRETCH");
@@ -4348,23 +4368,14 @@ int hens_rj_set_in_model(hens_ctx* ctx, int32_t kind) {
 int hens_rj_debug_draws_stretch(hens_ctx* ctx, int64_t iter, uint8_t* labels, int64_t* rint, double* u_zz, double* u_acc) {
     hens_ctx_impl* c = enter(ctx);
     if (!c || iter < 0) return fail(c, HENS_ERR_INVALID, "null context / negative iteration");
-    if (c->cfg.likelihood_kind != HENS_LIKE_TEMPLATE || c->rj.M.nb <= 0) return fail(c, HENS_ERR_STATE, "hens_rj_set_model first");
+    if (const int rm = need_rj_model(c)) return rm;
     if (!labels || !rint || !u_zz || !u_acc) return fail(c, HENS_ERR_INVALID, "null output");
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    SETTLE(c, NEED_DEVICE);
     const int Tl = c->Tl, W = c->W, nb = c->rj.M.nb, n0 = (W + 1) / 2;
     const size_t TW = (size_t)Tl * W;
-    struct Scratch {
-        std::vector<void*> p;
-        ~Scratch() { for (void* q : p) (void)hipFree(q); }
-    } sc;
-    auto grab = [&](size_t bytes) -> void* {
-        void* q = nullptr;
-        if (hipMalloc(&q, std::max<size_t>(bytes, 8)) != hipSuccess) return nullptr;
-        sc.p.push_back(q);
-        return q;
-    };
+    DeviceScratch sc;
     RjDebugStretchArgs a{};
-    a.own = (int32_t*)grab(TW * 4); a.cw = (int32_t*)grab(TW * nb * 4); a.uzz = (double*)grab(TW * 8); a.uacc = (double*)grab(TW * 8);
+    a.own = sc.grab<int32_t>(TW); a.cw = sc.grab<int32_t>(TW * nb); a.uzz = sc.grab<double>(TW); a.uacc = sc.grab<double>(TW);
     if (!a.own || !a.cw || !a.uzz || !a.uacc) return fail(c, HENS_ERR_HIP, "hens_rj_debug_draws_stretch: out of device memory");
     a.iter = (uint64_t)iter; a.seed = c->cfg.seed;
     a.Tl = Tl; a.W = W; a.rung_begin = c->cfg.rung_begin; a.nb = nb; a.bits = c->idx_bits;
@@ -4405,26 +4416,17 @@ int hens_rj_debug_draws(hens_ctx* ctx, int64_t iter, double* step, double* u_mh,
                         double* birth, double* u_bd, int32_t* slot_mh, double* uswap_mh, int32_t* slot_bd, double* uswap_bd) {
     hens_ctx_impl* c = enter(ctx);
     if (!c || iter < 0) return fail(c, HENS_ERR_INVALID, "null context / negative iteration");
-    if (c->cfg.likelihood_kind != HENS_LIKE_TEMPLATE || c->rj.M.nb <= 0) return fail(c, HENS_ERR_STATE, "hens_rj_set_model first");
+    if (const int rm = need_rj_model(c)) return rm;
     const bool stretch = c->rj.in_model == HENS_RJ_INMODEL_STRETCH;       // (its draws: hens_rj_debug_draws_stretch; step / u_mh are zeros here)
     if (!stretch && !c->rj.have_scale) return fail(c, HENS_ERR_STATE, "in-model step scale not set (hens_rj_set_mh_scale)");
     if (!step || !u_mh || !branch || !coin || !sel || !birth || !u_bd) return fail(c, HENS_ERR_INVALID, "null output");
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    SETTLE(c, NEED_DEVICE);
     const size_t TW = (size_t)c->Tl * c->W, IO = (size_t)c->rj.M.ind_off;
-    struct Scratch {
-        std::vector<void*> p;
-        ~Scratch() { for (void* q : p) (void)hipFree(q); }
-    } sc;
-    auto grab = [&](size_t bytes) -> void* {
-        void* q = nullptr;
-        if (hipMalloc(&q, std::max<size_t>(bytes, 8)) != hipSuccess) return nullptr;
-        sc.p.push_back(q);
-        return q;
-    };
+    DeviceScratch sc;
     RjDebugArgs a{};
     a.M = c->rj.M;
-    a.step = (double*)grab(TW * IO * 8); a.u_mh = (double*)grab(TW * 8); a.coin = (int8_t*)grab(TW);
-    a.sel = (uint32_t*)grab(TW * 4); a.birth = (double*)grab(TW * (size_t)c->rj.M.ndmax * 8); a.u_bd = (double*)grab(TW * 8);
+    a.step = sc.grab<double>(TW * IO); a.u_mh = sc.grab<double>(TW); a.coin = sc.grab<int8_t>(TW);
+    a.sel = sc.grab<uint32_t>(TW); a.birth = sc.grab<double>(TW * (size_t)c->rj.M.ndmax); a.u_bd = sc.grab<double>(TW);
     if (!a.step || !a.u_mh || !a.coin || !a.sel || !a.birth || !a.u_bd) return fail(c, HENS_ERR_HIP, "hens_rj_debug_draws: out of device memory");
     a.iter = (uint64_t)iter; a.seed = c->cfg.seed;
     a.Tl = c->Tl; a.W = c->W; a.rung_begin = c->cfg.rung_begin; a.stretch = stretch ? 1 : 0;
@@ -4452,34 +4454,22 @@ int hens_rj_debug_draws(hens_ctx* ctx, int64_t iter, double* step, double* u_mh,
     }
     if (has_pt(c) && slot_mh && uswap_mh && slot_bd && uswap_bd) {       // the two cascades of the iteration (rj_cascade's keys)
         const size_t n = (size_t)c->T * c->W;
-        int32_t* ds = (int32_t*)grab(n * 4);
-        double* du = (double*)grab(n * 8);
+        int32_t* ds = sc.grab<int32_t>(n);
+        double* du = sc.grab<double>(n);
         if (!ds || !du) return fail(c, HENS_ERR_HIP, "hens_rj_debug_draws: out of device memory");
-        for (int k = 0; k < 2; ++k) {
-            hipLaunchKernelGGL(k_debug_pt, dim3(grid_for((int64_t)n)), dim3(256), 0, c->stream, ds, du, c->T, c->W, c->idx_bits,
-                               c->cfg.seed, 2 * (uint64_t)iter + (uint64_t)k);
-            HIPCHK(c, hipGetLastError());
-            HIPCHK(c, hipMemcpyAsync(k ? slot_bd : slot_mh, ds, n * 4, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipMemcpyAsync(k ? uswap_bd : uswap_mh, du, (size_t)(c->T - 1) * c->W * 8, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-        }
+        for (int k = 0; k < 2; ++k)
+            if (const int r = export_pt_draws(c, ds, du, 2 * (uint64_t)iter + (uint64_t)k, k ? slot_bd : slot_mh, k ? uswap_bd : uswap_mh)) return r;
     }
     return HENS_OK;
 }
 
 int hens_rj_get_counters(hens_ctx* ctx, double* accepted_bd, int64_t* num_mh, int64_t* num_bd) {
     hens_ctx_impl* c = enter(ctx);
-    if (!c) return fail(c, HENS_ERR_INVALID, "null context");
-    if (c->cfg.likelihood_kind != HENS_LIKE_TEMPLATE || !c->rj.acc_bd) return fail(c, HENS_ERR_STATE, "hens_rj_set_model first");
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    state_to_fields(c);                       // (hens_step leaves the state in record mode)
-    const size_t TW = (size_t)c->Tl * c->W;
-    if (accepted_bd) {
-        std::vector<uint32_t> acc(TW);
-        HIPCHK(c, hipMemcpyAsync(acc.data(), c->rj.acc_bd, TW * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        for (size_t i = 0; i < TW; ++i) accepted_bd[i] = (double)acc[i];
-    }
+    if (!c) return no_context();
+    if (const int rm = need_rj_model(c)) return rm;
+    SETTLE(c, NEED_DEVICE | NEED_FIELDS);
+    if (accepted_bd)
+        if (const int r = read_counters(c, (size_t)c->Tl * c->W, {{accepted_bd, c->rj.acc_bd}})) return r;
     if (num_mh) *num_mh = c->rj.num_mh;
     if (num_bd) *num_bd = c->rj.num_bd;
     return HENS_OK;
@@ -4487,12 +4477,10 @@ int hens_rj_get_counters(hens_ctx* ctx, double* accepted_bd, int64_t* num_mh, in
 
 int hens_rj_debug_resident(hens_ctx* ctx, double* rec, double* logl) {
     hens_ctx_impl* c = enter(ctx);
-    if (!c) return fail(c, HENS_ERR_INVALID, "null context");
-    if (c->cfg.likelihood_kind != HENS_LIKE_TEMPLATE || c->rj.M.nb <= 0) return fail(c, HENS_ERR_STATE, "hens_rj_set_model first");
+    if (!c) return no_context();
+    if (const int rm = need_rj_model(c)) return rm;
     if (!c->have_state) return fail(c, HENS_ERR_STATE, "no state uploaded");
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    state_to_fields(c);                       // (hens_step leaves the state in record mode)
-    flush_adapt(c);
+    SETTLE(c, NEED_DEVICE | NEED_FIELDS | NEED_LADDER);
     const size_t TW = (size_t)c->Tl * c->W;
     // (hens_download_state without the evaluation in front of its copy: the log-likelihoods as hens_rj_step's +- leaf updates left them)
     if (rec) {
@@ -4509,8 +4497,7 @@ int hens_rj_debug_resident(hens_ctx* ctx, double* rec, double* logl) {
 int hens_get_device_buffers(hens_ctx* ctx, hens_device_buffers* out) {
     hens_ctx_impl* c = enter(ctx);
     if (!c || !out) return fail(c, HENS_ERR_INVALID, "null argument");
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    state_to_fields(c);                       // (hens_step leaves the state in record mode)
+    SETTLE(c, NEED_DEVICE | NEED_FIELDS);
     int r = ensure_shard_buffers(c);
     if (r) return r;
     out->logl = c->L[c->cur];
@@ -4531,9 +4518,7 @@ int hens_stretch_iter(hens_ctx* ctx) {
     if ((r = counter_room(c, 1))) return r;
     if (c->cfg.likelihood_kind == HENS_LIKE_HOST) return fail(c, HENS_ERR_UNSUPPORTED, "hens_stretch_iter needs a device likelihood");
     if (c->pt_pending) return fail(c, HENS_ERR_STATE, "sharded PT exchange in flight");
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    state_to_fields(c);                       // (hens_step leaves the state in record mode)
-    flush_adapt(c);
+    SETTLE(c, NEED_DEVICE | NEED_FIELDS | NEED_LADDER);
     c->N0 = (c->W + 1) / 2;
     if (!(c->iter >= c->win_from && c->iter < c->win_from + (uint64_t)c->win_count)) {
         // plan a whole batch (splits of the resident rungs + every PT column map) once per NB iterations
@@ -4569,9 +4554,7 @@ int hens_pt_plan_sharded(hens_ctx* ctx, const int64_t* iperm, const int64_t* i1p
         const bool mine = t >= c->cfg.rung_begin && t < c->cfg.rung_end;
         if (mine != (rank_of_rung[t] == my_rank)) return fail(c, HENS_ERR_INVALID, "rank_of_rung disagrees with this context's shard");
     }
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    state_to_fields(c);                       // (hens_step leaves the state in record mode)
-    flush_adapt(c);
+    SETTLE(c, NEED_DEVICE | NEED_FIELDS | NEED_LADDER);
     if ((r = ensure_shard_buffers(c))) return r;
     if ((r = ensure_pt_buffers(c))) return r;
     const size_t PW = (size_t)(T - 1) * W;
@@ -4598,7 +4581,7 @@ int hens_pt_plan_sharded(hens_ctx* ctx, const int64_t* iperm, const int64_t* i1p
     }
     c->adapt_pending = true;
     c->adapt_pending_adaptive = adapt && c->cfg.adaptive;
-    flush_adapt(c);
+    SETTLE(c, NEED_LADDER);                   // (this sweep's own counts)
     // who sends what to whom
     unsigned* counts = c->d_counts;
     HIPCHK(c, hipMemsetAsync(counts, 0, 2 * MAX_RANKS * sizeof(unsigned), c->stream));
@@ -4636,11 +4619,10 @@ int hens_pt_plan_sharded(hens_ctx* ctx, const int64_t* iperm, const int64_t* i1p
 
 int hens_pt_finish_sharded(hens_ctx* ctx, int64_t n_recv) {
     hens_ctx_impl* c = enter(ctx);
-    if (!c) return fail(c, HENS_ERR_INVALID, "null context");
+    if (!c) return no_context();
     if (!c->pt_pending) return fail(c, HENS_ERR_STATE, "no sharded PT exchange in flight");
     if (n_recv != c->n_recv) return fail(c, HENS_ERR_INVALID, "expected %lld received rows, got %lld", (long long)c->n_recv, (long long)n_recv);
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    state_to_fields(c);                       // (hens_step leaves the state in record mode)
+    SETTLE(c, NEED_DEVICE | NEED_FIELDS);
     if (n_recv > 0)
         hipLaunchKernelGGL(k_unpack_rows, dim3(grid_for(n_recv * (c->D + 2))), dim3(256), 0, c->stream, c->pool,
                            c->loc[c->cur ^ 1], c->P[c->cur ^ 1], c->recv_rows, n_recv, c->D, c->W,
@@ -4662,10 +4644,9 @@ int hens_mh_step(hens_ctx* ctx, const double* step, const double* u_acc, uint8_t
     if (c->expect_split != 0) return fail(c, HENS_ERR_STATE, "hens_mh_step between split 0 and split 1");
     if (c->pt_pending) return fail(c, HENS_ERR_STATE, "sharded PT exchange in flight");
     if ((r = counter_room(c, 1))) return r;
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    state_to_fields(c);                       // (hens_step leaves the state in record mode)
+    SETTLE(c, NEED_DEVICE | NEED_FIELDS);
     if ((r = ensure_mh_buffers(c))) return r;
-    flush_adapt(c);
+    SETTLE(c, NEED_LADDER);
     const size_t TW = (size_t)c->Tl * c->W;
     HIPCHK(c, hipMemcpyAsync(c->mh_step, step, TW * c->D * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->mh_u, u_acc, TW * 8, hipMemcpyHostToDevice, c->stream));
@@ -4680,7 +4661,7 @@ int hens_mh_step(hens_ctx* ctx, const double* step, const double* u_acc, uint8_t
 
 int hens_set_mh_proposal(hens_ctx* ctx, int32_t kind, const double* scale, double weight) {
     hens_ctx_impl* c = enter(ctx);
-    if (!c) return fail(c, HENS_ERR_INVALID, "null context");
+    if (!c) return no_context();
     if (kind < 0) {                                   // back to the stretch move only
         c->mh_kind = -1;
         c->mh_weight = 0.0;
@@ -4688,8 +4669,7 @@ int hens_set_mh_proposal(hens_ctx* ctx, int32_t kind, const double* scale, doubl
     }
     if (kind > MH_FULL || !scale) return fail(c, HENS_ERR_INVALID, "kind must be 0 (isotropic), 1 (diagonal) or 2 (full) with its scale");
     if (!(weight >= 0.0 && weight <= 1.0)) return fail(c, HENS_ERR_INVALID, "weight must be a probability");
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    state_to_fields(c);                       // (hens_step leaves the state in record mode)
+    SETTLE(c, NEED_DEVICE | NEED_FIELDS);
     int r = ensure_mh_buffers(c);
     if (r) return r;
     const size_t n = kind == MH_ISO ? 1 : (kind == MH_DIAG ? (size_t)c->D : (size_t)c->D * c->D);
@@ -4704,20 +4684,12 @@ int hens_set_mh_proposal(hens_ctx* ctx, int32_t kind, const double* scale, doubl
 
 int hens_get_mh_counters(hens_ctx* ctx, double* accepted, int64_t* num_proposals) {
     hens_ctx_impl* c = enter(ctx);
-    if (!c) return fail(c, HENS_ERR_INVALID, "null context");
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    state_to_fields(c);                       // (hens_step leaves the state in record mode)
+    if (!c) return no_context();
+    SETTLE(c, NEED_DEVICE | NEED_FIELDS);
     const size_t TW = (size_t)c->Tl * c->W;
-    if (accepted) {
-        if (!c->accepted_mh) {
-            for (size_t i = 0; i < TW; ++i) accepted[i] = 0.0;
-        } else {
-            std::vector<uint32_t> h(TW);
-            HIPCHK(c, hipMemcpyAsync(h.data(), c->accepted_mh, TW * 4, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            for (size_t i = 0; i < TW; ++i) accepted[i] = (double)h[i];
-        }
-    }
+    if (accepted && !c->accepted_mh) std::fill_n(accepted, TW, 0.0);
+    else if (accepted)
+        if (const int r = read_counters(c, TW, {{accepted, c->accepted_mh}})) return r;
     if (num_proposals) *num_proposals = c->num_proposals_mh;
     return HENS_OK;
 }
@@ -4725,15 +4697,14 @@ int hens_get_mh_counters(hens_ctx* ctx, double* accepted, int64_t* num_proposals
 // ---- ladder pipeline set-up -------------------------------------------------------------------------
 int hens_pipe_init(hens_ctx* ctx, int32_t nranks, int32_t my_rank, void* blob_out, int64_t* box_bytes_out) {
     hens_ctx_impl* c = enter(ctx);
-    if (!c) return fail(c, HENS_ERR_INVALID, "null context");
+    if (!c) return no_context();
     if (c->pipe.on) return fail(c, HENS_ERR_STATE, "pipeline already initialised");
     if (!c->cfg.tempered || c->T < 2) return fail(c, HENS_ERR_STATE, "the ladder pipeline needs a tempered ladder");
     if (nranks < 1 || nranks > PIPE_MAX_RANKS || my_rank < 0 || my_rank >= nranks)
         return fail(c, HENS_ERR_INVALID, "nranks must be in [1, %d] and my_rank inside it", PIPE_MAX_RANKS);
     if ((my_rank == 0) != (c->cfg.rung_begin == 0) || (my_rank == nranks - 1) != (c->cfg.rung_end == c->T))
         return fail(c, HENS_ERR_INVALID, "ranks must hold contiguous rung ranges in rank order (rank 0 = coldest rungs)");
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    state_to_fields(c);                       // (hens_step leaves the state in record mode)
+    SETTLE(c, NEED_DEVICE | NEED_FIELDS);
     const size_t bytes = pipe_box_bytes(c->T, c->W, c->D);
     void* box = nullptr;
     HIPCHK(c, hipExtMallocWithFlags(&box, bytes, hipDeviceMallocUncached));
@@ -4798,8 +4769,7 @@ int hens_pipe_connect(hens_ctx* ctx, const void* blobs) {
     if (!c || !blobs) return fail(c, HENS_ERR_INVALID, "null argument");
     if (!c->pipe.on) return fail(c, HENS_ERR_STATE, "hens_pipe_init first");
     if (c->pipe.connected) return fail(c, HENS_ERR_STATE, "pipeline already connected");
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    state_to_fields(c);                       // (hens_step leaves the state in record mode)
+    SETTLE(c, NEED_DEVICE | NEED_FIELDS);
     const char* hb = static_cast<const char*>(blobs);
     for (int q = 0; q < c->pipe.nranks; ++q) {
         if (q == c->pipe.rank) continue;
@@ -4825,12 +4795,11 @@ int hens_pipe_connect(hens_ctx* ctx, const void* blobs) {
 // the message regions between the stages.  RCCL cannot pull, so the LDN message carries the boundary rung's rows.
 int hens_pipe_connect_staged(hens_ctx* ctx) {
     hens_ctx_impl* c = enter(ctx);
-    if (!c) return fail(c, HENS_ERR_INVALID, "null context");
+    if (!c) return no_context();
     if (!c->pipe.on) return fail(c, HENS_ERR_STATE, "hens_pipe_init first");
     if (c->pipe.connected) return fail(c, HENS_ERR_STATE, "pipeline already connected");
     if (c->cfg.adaptation_delay != 0) return fail(c, HENS_ERR_UNSUPPORTED, "the staged transport runs the reference's adaptation schedule");
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    state_to_fields(c);                       // (hens_step leaves the state in record mode)
+    SETTLE(c, NEED_DEVICE | NEED_FIELDS);
     const size_t bytes = c->pipe.box_bytes;
     int r;
     if ((r = dalloc(c, &c->pipe.out_hot, bytes))) return r;
@@ -4894,8 +4863,7 @@ static int pipe_stage_impl(hens_ctx_impl* c, int32_t stage) {
     if (r) return r;
     if (!c->pipe.staged) return fail(c, HENS_ERR_STATE, "hens_pipe_connect_staged first");
     if ((r = counter_room(c, 1))) return r;
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    state_to_fields(c);                       // (hens_step leaves the state in record mode)
+    SETTLE(c, NEED_DEVICE | NEED_FIELDS);
     switch (stage) {
         case 0: {           // the iteration's move (stretch halves or the MH proposal); publishes (L, P) of the boundary rung
             c->N0 = (c->W + 1) / 2;
@@ -4952,7 +4920,7 @@ int hens_comm_init(hens_ctx* ctx, int32_t nranks, int32_t rank, const void* uniq
     if (!c->pipe.on && (r = hens_pipe_init(ctx, nranks, rank, nullptr, &nbytes))) return r;
     if (!c->pipe.connected && (r = hens_pipe_connect_staged(ctx))) return r;
     if (!c->pipe.staged) return fail(c, HENS_ERR_STATE, "the context is connected to the one-sided pipeline already");
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    SETTLE(c, NEED_DEVICE);
     ncclUniqueId id;
     memcpy(&id, unique_id, sizeof id);
     ncclComm_t comm = nullptr;
@@ -4963,7 +4931,7 @@ int hens_comm_init(hens_ctx* ctx, int32_t nranks, int32_t rank, const void* uniq
 }
 int hens_comm_destroy(hens_ctx* ctx) {
     hens_ctx_impl* c = enter(ctx);
-    if (!c) return fail(c, HENS_ERR_INVALID, "null context");
+    if (!c) return no_context();
     if (!c->comm_on) return HENS_OK;
     (void)hipStreamSynchronize(c->stream);
     RcclApi& R = rccl_api();
@@ -4979,7 +4947,7 @@ int hens_comm_selfsend(hens_ctx* ctx, int64_t n, const double* src_host, double*
     if (!c || !src_host || !dst_host || n <= 0) return fail(c, HENS_ERR_INVALID, "bad argument");
     if (!c->comm_on) return fail(c, HENS_ERR_STATE, "hens_comm_init first");
     RcclApi& R = rccl_api();
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    SETTLE(c, NEED_DEVICE);
     double *a = nullptr, *b = nullptr;
     HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&a), (size_t)n * 8));
     HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&b), (size_t)n * 8));
@@ -5090,7 +5058,7 @@ int hens_pipe_debug_stats(hens_ctx* ctx, uint64_t* out16, int32_t reset) {
     hens_ctx_impl* c = enter(ctx);
     if (!c || !out16) return fail(c, HENS_ERR_INVALID, "null argument");
     if (!c->pipe.stats) return fail(c, HENS_ERR_STATE, "set HENS_PIPE_STATS=1 before hens_pipe_init");
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    SETTLE(c, NEED_DEVICE);
     HIPCHK(c, hipMemcpyAsync(out16, c->pipe.stats, 128, hipMemcpyDeviceToHost, c->stream));
     if (reset) HIPCHK(c, hipMemsetAsync(c->pipe.stats, 0, 128, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
