@@ -17,6 +17,7 @@ from ._build import LIB_PATH
 HENS_OK = 0
 ERR_INVALID, ERR_HIP, ERR_STATE, ERR_TOO_FEW_WALKERS, ERR_NONFINITE, ERR_UNSUPPORTED = -1, -2, -3, -4, -5, -6
 LIKE_GAUSS_DENSE, LIKE_GAUSS_DIAG, LIKE_ROSENBROCK, LIKE_HOST, LIKE_TEMPLATE = 0, 1, 2, 3, 4
+PRIOR_UNIFORM, PRIOR_LOG_UNIFORM, PRIOR_NORMAL = 0, 1, 2       # hens_prior_kind (hens_set_prior_terms)
 
 
 class HensConfig(C.Structure):
@@ -76,6 +77,7 @@ SIGNATURES = {
     "hens_last_error": (C.c_char_p, [_P]),
     "hens_synchronize": (C.c_int, [_P]),
     "hens_set_prior_box": (C.c_int, [_P, _P, _P, C.c_double]),
+    "hens_set_prior_terms": (C.c_int, [_P, _P, _P, _P, _P, _P, _P]),
     "hens_set_periodic": (C.c_int, [_P, _P]),
     "hens_set_gaussian": (C.c_int, [_P, _P, _P]),
     "hens_set_rosenbrock": (C.c_int, [_P, C.c_double, C.c_double]),

@@ -7,6 +7,7 @@
 #include "hens_tile2.h"
 #include "hens_aql.h"
 #include "hens_ktable.h"
+#include "hens_prior.h"
 #include "hens_chain.h"
 #include "hens_chain_stats.h"
 #include "hens_rj_chain.h"
@@ -100,6 +101,9 @@ struct hens_ctx_impl {
     double* lo = nullptr; double* hi = nullptr; double* mu = nullptr; double* prec = nullptr; double* prec_sym = nullptr;
     double* period = nullptr;        // [D] periods of the periodic parameters (hens_set_periodic), nullptr: none
     double* period_buf = nullptr;
+    PriorTerm* prior = nullptr;      // [D] per-parameter prior terms (hens_set_prior_terms), nullptr: the box and its constant logp_in
+    PriorTerm* prior_buf = nullptr;
+    double* prior_block = nullptr;   // lo[D] hi[D] terms[D] in one allocation: what k_stretch reads with terms on (StretchArgs::prior_on)
     double logp_in = 0.0, rosen_a = 1.0, rosen_b = 100.0;
     bool have_prior = false, have_like = false, have_state = false, have_logs = false;
 
@@ -314,6 +318,7 @@ constexpr bool DEV_BUILD = false;
 struct Env {
     bool no_aql, aql_release, step_events;                       // queue: HIP stream only / keep the release fence / event pair per call
     bool no_fused, pipe_no_fused, no_iter, no_col, no_fold, pt_no_acc, rj_no_templates;   // A/B knobs of the path decision
+    bool prior_log;                                              // HENS_PRIOR_LOG: which kernel a launch under prior terms went to (tests)
     bool no_xcd, no_tile2, no_tile2_pipe, tile2_pipe_waits, tile2_log, pipe_force_late, debug_noflip;
     int tile2_force, aql_flush, aql_nobar;                       // aql_flush: -1 unset; aql_nobar, debug_noflip: dev-build probes
     long iter_max, pipe_inject_cycles;
@@ -328,7 +333,7 @@ const Env& env() {
         v.no_aql = on("HENS_NO_AQL"); v.aql_release = on("HENS_AQL_RELEASE"); v.step_events = on("HENS_STEP_EVENTS");
         v.no_fused = on("HENS_NO_FUSED"); v.pipe_no_fused = on("HENS_PIPE_NO_FUSED"); v.no_iter = on("HENS_NO_ITER");
         v.no_col = on("HENS_NO_COL"); v.no_fold = on("HENS_NO_FOLD"); v.pt_no_acc = on("HENS_PT_NO_ACC");
-        v.rj_no_templates = on("HENS_RJ_NO_TEMPLATES");
+        v.rj_no_templates = on("HENS_RJ_NO_TEMPLATES"); v.prior_log = on("HENS_PRIOR_LOG");
         v.no_xcd = on("HENS_NO_XCD"); v.no_tile2 = on("HENS_NO_TILE2"); v.no_tile2_pipe = on("HENS_NO_TILE2_PIPE");
         v.tile2_pipe_waits = on("HENS_TILE2_PIPE_WAITS"); v.tile2_log = on("HENS_TILE2_LOG");
         v.pipe_force_late = on("HENS_PIPE_FORCE_LATE"); v.debug_noflip = on("HENS_DEBUG_NOFLIP");
@@ -424,11 +429,12 @@ struct LikeKernels {
     int kind, like;
     const void* (*stretch_fast)(int mode, int D, bool pipe, bool per);
     const void* (*stretch)(int mode);
+    const void* (*stretch_prior)(int mode, int D);
     const void* (*stretch2)(int D, bool pipe);
     const void* (*split1_pt)(int D, bool per, bool shrt, bool pipe, bool col);
     const void* (*iter)(int D, bool per);
 };
-#define HENS_LIKE_KERNELS(KIND_, LIKE_, U) {KIND_, LIKE_, ktab_stretch_fast_##U, ktab_stretch_##U, ktab_stretch2_##U, ktab_split1_pt_##U, ktab_iter_##U}
+#define HENS_LIKE_KERNELS(KIND_, LIKE_, U) {KIND_, LIKE_, ktab_stretch_fast_##U, ktab_stretch_##U, ktab_stretch_prior_##U, ktab_stretch2_##U, ktab_split1_pt_##U, ktab_iter_##U}
 const LikeKernels* like_kernels(int likelihood_kind) {
     static const LikeKernels tab[] = {
         HENS_LIKE_KERNELS(HENS_LIKE_GAUSS_DENSE, LIKE_DENSE, dense),
@@ -483,8 +489,11 @@ size_t plan_lds_bytes(const hens_ctx_impl* c) { return (size_t)6 * c->W + 16; }
 constexpr int FAST_NW_32 = 8;
 int fast_nw(int D) { return (D == 32 || D == 64 || D == 128) ? 8 : 4; }
 // row widths with a compile-time-width kernel (k_stretch_fast)
+// (not with per-parameter prior terms: such a context is a generic-width one to every launch decision - the copying launches of
+//  k_stretch, the cascade and the adaptation as kernels of their own, MH steps through the step buffer)
 bool fast_path(const hens_ctx_impl* c) {
     const int D = c->D;
+    if (c->prior) return false;
     return D == 8 || D == 16 || D == 32 || D == 64 || (D == 128 && c->cfg.likelihood_kind != HENS_LIKE_HOST);
 }
 
@@ -561,12 +570,26 @@ int launch_stretch_like(hens_ctx_impl* c, const LikeKernels& lk, int mode, Stret
         return launch_by_ptr(c, lk.stretch_fast(mode, c->D, pipe, per), "k_stretch_fast", grid, NW * 64, fast_lds_bytes(c->D, NW, like), false,
                              c->aql_now ? nullptr : c->ext_start, c->ext_stop, a);
     }
+    const bool was_aql = c->aql_now;           // (neither kernel below goes to the AQL queue: the HIP stream, as the generic one always did)
+    // Per-parameter prior terms at a compile-time row width: k_stretch_prior (hens_prior.h) - the copying half-step with the terms
+    // formed in phase B and added by the accept wave.  Periodic parameters, the other widths and Rosenbrock rows that cannot be
+    // padded: the generic kernel below, which adds the same sum behind its run-time test.  HENS_PRIOR_LOG=1 (tests): which one.
+    const void* kp = (c->prior && !c->period && !c->pipe.on) ? lk.stretch_prior(mode, c->D) : nullptr;
+    if (env().prior_log && c->prior)
+        fprintf(stderr, "hens: prior terms, D = %d, mode %d: %s\n", c->D, mode, kp ? "k_stretch_prior" : "k_stretch");
+    if (kp) {
+        const int NW = fast_nw(c->D);
+        a.ad_on = 0;
+        c->aql_now = false;
+        const int r = launch_by_ptr(c, kp, "k_stretch_prior", grid, NW * 64, prior_lds_bytes(c->D, NW, like), false, c->ext_start, c->ext_stop, a);
+        c->aql_now = was_aql;
+        return r;
+    }
     int RS;
     const size_t lds = generic_lds_bytes(c->D, &RS);
     if (lds > 160 * 1024) return fail(c, HENS_ERR_UNSUPPORTED, "ndim %d exceeds the LDS row tile", c->D);
     a.RS = RS;
     a.ad_on = 0;
-    const bool was_aql = c->aql_now;           // (the generic-width kernel always goes through the HIP stream, as it did)
     c->aql_now = false;
     const int r = launch_by_ptr(c, lk.stretch(mode), "k_stretch", grid, 256, lds, false, c->ext_start, c->ext_stop, a);
     c->aql_now = was_aql;
@@ -629,6 +652,7 @@ StretchArgs base_args(hens_ctx_impl* c) {
     a.accepted = c->accepted;
     a.lo = c->lo; a.hi = c->hi; a.mu = c->mu; a.prec = c->prec; a.prec_sym = c->prec_sym;
     a.period = c->period;
+    if (c->prior) { a.lo = c->prior_block; a.hi = c->prior_block + c->D; a.prior_on = 1; }
     a.flags = c->flags;
     a.trace = (c->tracing && !c->trace_pt && !c->trace_fused) ? c->d_trace : nullptr;
     a.logp_in = c->logp_in;
@@ -2271,11 +2295,82 @@ int hens_set_prior_box(hens_ctx* ctx, const double* lo, const double* hi, double
     if (!c || !lo || !hi) return fail(c, HENS_ERR_INVALID, "null argument");
     for (int d = 0; d < c->D; ++d)
         if (!(lo[d] < hi[d])) return fail(c, HENS_ERR_INVALID, "prior box needs lo < hi in every dimension (dim %d)", d);
-    SETTLE(c, NEED_DEVICE | NEED_FIELDS);
+    SETTLE(c, NEED_DEVICE | NEED_FIELDS | (c->prior ? NEED_LADDER : 0u));     // (leaving prior terms: the launch path changes)
     HIPCHK(c, hipMemcpyAsync(c->lo, lo, c->D * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->hi, hi, c->D * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->logp_in = logp_inside;
+    c->prior = nullptr;               // (back to the box after hens_set_prior_terms)
+    c->have_prior = true;
+    return HENS_OK;
+}
+
+// prior.py:337-392 with one distribution per parameter (include/hipensemble.h); uniform kinds only: hens_set_prior_box itself
+int hens_set_prior_terms(hens_ctx* ctx, const int32_t* kind, const double* lo, const double* hi, const double* c0, const double* c1,
+                         const double* c2) {
+    hens_ctx_impl* c = enter(ctx);
+    if (!c || !kind || !lo || !hi || !c0 || !c1 || !c2) return fail(c, HENS_ERR_INVALID, "null argument");
+    if (is_rj(c))
+        return fail(c, HENS_ERR_UNSUPPORTED, "prior terms are not built for leaf-packing records (leaves carry box priors: hens_rj_set_model)");
+    const int D = c->D;
+    std::vector<PriorTerm> terms((size_t)D);
+    bool box = true;
+    double logp_box = 0.0;
+    for (int d = 0; d < D; ++d) {
+        PriorTerm& t = terms[(size_t)d];
+        t = PriorTerm{};
+        if (kind[d] != HENS_PRIOR_UNIFORM && kind[d] != HENS_PRIOR_LOG_UNIFORM && kind[d] != HENS_PRIOR_NORMAL)
+            return fail(c, HENS_ERR_INVALID, "unknown prior kind %d (dim %d)", kind[d], d);
+        if (!(lo[d] < hi[d])) return fail(c, HENS_ERR_INVALID, "prior terms need lo < hi in every dimension (dim %d)", d);
+        if (kind[d] == HENS_PRIOR_UNIFORM) {
+            const bool pad = lo[d] == -INFINITY && hi[d] == INFINITY;      // (hens_config::ndim_active: no term)
+            if (!pad && !(std::fabs(c0[d]) < INFINITY)) return fail(c, HENS_ERR_INVALID, "uniform prior term: c0 must be finite (dim %d)", d);
+            t.kind = pad ? PRIOR_NONE : PRIOR_UNIFORM;
+            t.c0 = pad ? 0.0 : c0[d];
+            if (!pad) logp_box += c0[d];                                   // (prior.py:364-383: ascending, from 0.0)
+            continue;
+        }
+        box = false;
+        if (kind[d] == HENS_PRIOR_LOG_UNIFORM) {
+            if (!(lo[d] > 0.0) || !(hi[d] < INFINITY)) return fail(c, HENS_ERR_INVALID, "log-uniform prior term needs 0 < lo < hi < inf (dim %d)", d);
+            if (!(std::fabs(c0[d]) < INFINITY)) return fail(c, HENS_ERR_INVALID, "log-uniform prior term: c0 must be finite (dim %d)", d);
+            t.kind = PRIOR_LOG_UNIFORM;
+            t.c0 = c0[d];
+        } else {
+            if (!(c1[d] > 0.0) || !(c1[d] < INFINITY)) return fail(c, HENS_ERR_INVALID, "normal prior term needs a finite scale > 0 (dim %d)", d);
+            if (!(std::fabs(c0[d]) < INFINITY) || !(std::fabs(c2[d]) < INFINITY))
+                return fail(c, HENS_ERR_INVALID, "normal prior term: loc and log(scale) must be finite (dim %d)", d);
+            t.kind = PRIOR_NORMAL;
+            t.c0 = c0[d]; t.c1 = c1[d];
+            t.c2 = c2[d];
+        }
+    }
+    if (box) return hens_set_prior_box(ctx, lo, hi, logp_box);
+    if (c->pipe.on) return fail(c, HENS_ERR_STATE, "prior terms are not built for a rank of the ladder pipeline");
+    if (c->expect_split != 0 || c->propose_pending) return fail(c, HENS_ERR_STATE, "a half-step is pending");
+    SETTLE(c, NEED_DEVICE | NEED_FIELDS | NEED_LADDER);
+    static_assert(sizeof(PriorTerm) == 32, "PriorTerm: four doubles' worth");
+    if (!c->prior_buf) {
+        PriorTerm* buf = nullptr;
+        const int r = dalloc(c, &buf, (size_t)D);
+        if (r) return r;
+        c->prior_buf = buf;
+    }
+    if (!c->prior_block) {                   // (each pointer on its own: a failed second allocation is not skipped the next time)
+        double* blk = nullptr;
+        const int r = dalloc(c, &blk, (size_t)6 * D);
+        if (r) return r;
+        c->prior_block = blk;
+    }
+    HIPCHK(c, hipMemcpyAsync(c->prior_block, lo, D * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->prior_block + D, hi, D * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->prior_block + 2 * (size_t)D, terms.data(), (size_t)D * sizeof(PriorTerm), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->lo, lo, D * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->hi, hi, D * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->prior_buf, terms.data(), (size_t)D * sizeof(PriorTerm), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->logp_in = 0.0;
+    c->prior = c->prior_buf;
     c->have_prior = true;
     return HENS_OK;
 }
@@ -2601,6 +2696,7 @@ static HostLikeArgs hostlike_args(hens_ctx_impl* c, int32_t split) {
     h.u_acc = c->d_uacc;
     h.accepted = c->accepted; h.flags = c->flags;
     h.logp_in = c->logp_in;
+    h.prior = c->prior;
     h.Tl = c->Tl; h.W = c->W; h.D = c->D; h.split = kernel_split(c, split); h.N0 = c->N0;
     if ((int)c->seg_off.size() == c->nsplits + 1) { h.ns_x = c->seg_off[split + 1] - c->seg_off[split]; h.soff_x = c->seg_off[split]; }
     h.rung_begin = c->cfg.rung_begin; h.home_off = c->parity * c->Tl * c->W; h.tempered = c->cfg.tempered;
@@ -4699,6 +4795,7 @@ int hens_pipe_init(hens_ctx* ctx, int32_t nranks, int32_t my_rank, void* blob_ou
     hens_ctx_impl* c = enter(ctx);
     if (!c) return no_context();
     if (c->pipe.on) return fail(c, HENS_ERR_STATE, "pipeline already initialised");
+    if (c->prior) return fail(c, HENS_ERR_UNSUPPORTED, "prior terms are not built for a rank of the ladder pipeline (hens_set_prior_box returns to the box)");
     if (!c->cfg.tempered || c->T < 2) return fail(c, HENS_ERR_STATE, "the ladder pipeline needs a tempered ladder");
     if (nranks < 1 || nranks > PIPE_MAX_RANKS || my_rank < 0 || my_rank >= nranks)
         return fail(c, HENS_ERR_INVALID, "nranks must be in [1, %d] and my_rank inside it", PIPE_MAX_RANKS);

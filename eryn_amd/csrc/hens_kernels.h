@@ -458,6 +458,38 @@ __device__ __forceinline__ double periodic_wrap(double q, double period) {
     return m;
 }
 
+// Per-parameter prior terms (hens_set_prior_terms; prior.py:337-392 over prior.py:12-136 and scipy.stats.norm): one record per
+// row coordinate.  The support test is the box test on StretchArgs::lo / hi as ever; a point inside every support has
+//   P = ((0.0 + t_0) + t_1) + ... + t_{D-1}     (prior.py:364-383: prior_vals += temp, ascending)
+// with the terms below, in SciPy's operation order (rv_continuous.logpdf: y = (x - loc) / scale, _logpdf(y) - log(scale)).
+// No contraction (the library is built with -ffp-contract=off); one device log per log-uniform coordinate, nothing
+// transcendental otherwise.
+constexpr int PRIOR_UNIFORM = 0, PRIOR_LOG_UNIFORM = 1, PRIOR_NORMAL = 2, PRIOR_NONE = 3;   // NONE: the pad of a padded row
+constexpr double NORM_PDF_LOGC = 0x1.d67f1c864beb4p-1;        // np.log(np.sqrt(2 * np.pi)), SciPy's _norm_pdf_logC
+struct PriorTerm {
+    double c0;       // UNIFORM: log(1/(hi - lo));  LOG_UNIFORM: log(log(b) - log(a));  NORMAL: loc
+    double c1;       // NORMAL: scale
+    double c2;       // NORMAL: log(scale)
+    int32_t kind, pad_;
+};
+__device__ __forceinline__ double prior_term(const PriorTerm& t, double q) {
+    if (t.kind == PRIOR_LOG_UNIFORM) return (-log(q)) - t.c0;
+    if (t.kind == PRIOR_NORMAL) {
+        const double y = (q - t.c0) / t.c1;
+        return (-(y * y) / 2.0 - NORM_PDF_LOGC) - t.c2;
+    }
+    return t.c0;
+}
+// the sum over one row held at `qrow` (stride 1), by ONE lane, in the specified order
+__device__ __forceinline__ double prior_sum(const PriorTerm* __restrict__ terms, const double* qrow, int D) {
+    double acc = 0.0;
+    for (int d = 0; d < D; ++d) {
+        const PriorTerm t = terms[d];
+        if (t.kind != PRIOR_NONE) acc += prior_term(t, qrow[d]);
+    }
+    return acc;
+}
+
 // The state-independent part of one proposal (stretch.py:129-132,223; red_blue.py:294).
 struct Draws {
     int32_t* own;    // [Tl][W] moving walker at each split position (positions < N0: split 0)
@@ -562,6 +594,9 @@ struct StretchArgs {
     int32_t inplace;           // k_stretch_fast: rows are updated IN PLACE and `loc` is read-only - an accepted proposal
                                // overwrites the walker's current row (nobody reads it during the launch: complements come
                                // from the other set), a rejected one writes nothing.  0: the two-home copying scheme
+    int32_t prior_on;          // k_stretch: per-parameter prior terms (hens_set_prior_terms) - `lo`, `hi` and the [D] PriorTerm records
+                               // are ONE block, lo[D] hi[D] terms[D] (prior_terms_of); 0: the box's constant logp_in.  (Fills the
+                               // hole in front of `betas`: no member moves and the struct keeps its size)
     const double* betas;       // [T] or nullptr when not tempered
     Draws dr;
     uint32_t* accepted;        // [Tl][W] cumulative accept counts
@@ -644,6 +679,13 @@ struct StretchArgs {
     int32_t tiles_per_wg;      // k_stretch2 (hens_tile2.h): tiles a persistent workgroup walks (grid.x = tiles per rung / tiles_per_wg)
     AdaptArgs ad;
 };
+// (The implicit kernel arguments follow the struct in the kernarg segment; one more pointer behind `ad` moved them into the next
+//  64-byte line and cost bench.py's headline 0.5 % (LABNOTES 12.4) - the prior terms' flag sits in a hole instead.)
+static_assert(sizeof(StretchArgs) == 696, "StretchArgs grew: the timed launches' kernarg layout is part of what was measured");
+// per-parameter prior terms of a launch (k_stretch only: a context with terms launches no other stepping kernel), or nullptr
+__device__ __forceinline__ const PriorTerm* prior_terms_of(const StretchArgs& A) {
+    return A.prior_on ? reinterpret_cast<const PriorTerm*>(A.hi + A.D) : nullptr;
+}
 
 // One workgroup = TILE (64) walkers of one rung, NW wavefronts.  Generic row width (runtime D).
 //   phase A  lane-per-walker : indices, draws                              (wave 0)
@@ -843,7 +885,14 @@ __global__ __launch_bounds__(256) void k_stretch(const StretchArgs A) {
             logl = -1e300;
             atomicOr(A.flags, FLAG_NAN_LOGL);
         }
-        const double logp = inbox ? A.logp_in : -INFINITY;     // prior.py:80-88
+        double logp = inbox ? A.logp_in : -INFINITY;           // prior.py:80-88
+        if (A.prior_on && inbox) {                             // prior.py:364-383 (the tile holds q itself)
+            logp = prior_sum(prior_terms_of(A), qtile + lane * RS, D);
+            if (!(fabs(logp) < INFINITY)) {                    // a normal coordinate whose y y overflows: outside the support - the
+                logp = -INFINITY;                              // likelihood counts as skipped and filled (ensemble.py:1486-1513)
+                logl = A.fill;
+            }
+        }
         const size_t gi = (size_t)tl * W + own;
         if (EVAL) {
             A.L[gi] = logl;
@@ -3858,6 +3907,7 @@ struct HostLikeArgs {
     double logp_in;
     int32_t Tl, W, D, split, N0, rung_begin, home_off, tempered;
     int32_t ns_x, soff_x;    // see StretchArgs::ns_x
+    const PriorTerm* prior;  // see StretchArgs::prior: k_accept_decide sums the terms of the proposal in qbuf
 };
 
 inline __global__ void k_propose(const HostLikeArgs A) {
@@ -3894,7 +3944,8 @@ inline __global__ void k_accept_decide(const HostLikeArgs A) {
             logl = -1e300;
             atomicOr(A.flags, FLAG_NAN_LOGL);
         }
-        const double logp = inbox ? A.logp_in : -INFINITY;
+        double logp = inbox ? A.logp_in : -INFINITY;
+        if (A.prior && inbox) logp = prior_sum(A.prior, A.qbuf + (size_t)wk * A.D, A.D);   // prior.py:364-383
         const double Lold = A.L[gi], Pold = A.P[gi];
         double logP, prevP;
         if (A.tempered) {                                              // tempering.py:304-306,343-349

@@ -1,6 +1,7 @@
 // hens_ktable.inc - body of a per-likelihood kernel translation unit: define HENS_KT_LIKE (LIKE_DENSE ...) and HENS_KT_NAME
 // (dense ...) and include.  See hens_ktable.h.  HENS_KT_PART (from the build) halves a unit once more: 0 = the half-step kernels
-// (k_stretch_fast, k_stretch), 1 = the fused ones (k_split1_pt, k_iter); undefined = both.
+// (k_stretch_fast, k_stretch), 1 = the fused ones (k_split1_pt, k_iter), 2 = k_stretch_prior (hens_prior.h: a unit of its own, so that
+// the units of the kernels that were there before compile to the code they compiled to); undefined = all.
 #include "hens_kernels.h"
 #include "hens_iter.h"
 #include "hens_tile2.h"
@@ -50,6 +51,33 @@ const void* KT(ktab_stretch2_)(int D, bool pipe) {   // the persistent, software
     return pipe ? KPTR(k_stretch2<64, HENS_KT_LIKE, true>) : KPTR(k_stretch2<64, HENS_KT_LIKE, false>);
 #endif
 }
+#endif
+#if !defined(HENS_KT_PART) || HENS_KT_PART == 2
+}  // namespace hens
+#include "hens_prior.h"
+namespace hens {
+template <int MODE>
+static const void* kt_prior_mode(int D) {
+    constexpr int L = HENS_KT_LIKE;
+#ifdef HENS_DEV_BUILD
+    return nullptr;            // (the generic k_stretch serves prior terms in a dev build)
+#else
+#define KT_PRIOR(DT, NW) if (D == DT) return KPTR(k_stretch_prior<DT, L, MODE, NW>);
+    KT_PRIOR(32, 8) KT_PRIOR(64, 8) KT_PRIOR(16, 4) KT_PRIOR(8, 4) KT_PRIOR(128, 8)
+#undef KT_PRIOR
+    return nullptr;
+#endif
+}
+const void* KT(ktab_stretch_prior_)(int mode, int D) {
+    switch (mode) {
+        case MODE_STRETCH: return kt_prior_mode<MODE_STRETCH>(D);
+        case MODE_EVAL: return kt_prior_mode<MODE_EVAL>(D);
+        case MODE_MH: return kt_prior_mode<MODE_MH>(D);
+    }
+    return nullptr;
+}
+#endif
+#if !defined(HENS_KT_PART) || HENS_KT_PART == 0
 const void* KT(ktab_stretch_)(int mode) {
     constexpr int L = HENS_KT_LIKE;
     switch (mode) {

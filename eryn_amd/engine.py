@@ -70,7 +70,7 @@ class HipEnsemble(ChainStoreCalls):
     def __init__(self, ntemps, nwalkers, ndim, likelihood, lo, hi, a=2.0, tempered=None,
                  adaptive=True, adaptation_lag=10000, adaptation_time=100, stop_adaptation=-1,
                  live_dangerously=False, fill_value=-1e300, seed=0, rung_range=None, device_id=0,
-                 adaptation_delay=0, pad_rows=True):
+                 adaptation_delay=0, pad_rows=True, prior_terms=None):
         self.lib = _lib.load()
         self.T, self.W, self.D = int(ntemps), int(nwalkers), int(ndim)
         if tempered is None:
@@ -99,11 +99,15 @@ class HipEnsemble(ChainStoreCalls):
         if code != _lib.HENS_OK:
             self.ctx = None
             check(code, None)
-        self.lo = f64(np.broadcast_to(lo, (self.D,)))
-        self.hi = f64(np.broadcast_to(hi, (self.D,)))
-        self.logp_inside = box_logp_inside(self.lo, self.hi)
-        lo_w, hi_w = self._pad(self.lo, -np.inf), self._pad(self.hi, np.inf)
-        check(self.lib.hens_set_prior_box(self.ctx, ptr(lo_w), ptr(hi_w), self.logp_inside), self.ctx)
+        self.prior_terms = None
+        if prior_terms is not None:              # (lo / hi are the terms' supports then; the arguments are not read)
+            self.set_prior_terms(prior_terms)
+        else:
+            self.lo = f64(np.broadcast_to(lo, (self.D,)))
+            self.hi = f64(np.broadcast_to(hi, (self.D,)))
+            self.logp_inside = box_logp_inside(self.lo, self.hi)
+            lo_w, hi_w = self._pad(self.lo, -np.inf), self._pad(self.hi, np.inf)
+            check(self.lib.hens_set_prior_box(self.ctx, ptr(lo_w), ptr(hi_w), self.logp_inside), self.ctx)
         if self.RW != self.D:
             likelihood._install(self.lib, self.ctx, row_width=self.RW)
         else:
@@ -118,6 +122,36 @@ class HipEnsemble(ChainStoreCalls):
         out = np.full(a.shape[:-1] + (self.RW,), fill, dtype=np.float64)
         out[..., :self.D] = a
         return out
+
+    def set_prior_terms(self, terms):
+        """One independent prior distribution per parameter: ``terms`` is an ``eryn_amd.prior.ProbDistContainer`` or its
+        ``prior_terms()`` dict (``kind`` int32, ``lo``, ``hi``, ``c0``, ``c1``, ``c2``, each ``[ndim]``); include/hipensemble.h,
+        hens_set_prior_terms.  Uniform kinds only: the box, on the box's launch path."""
+        if hasattr(terms, "prior_terms"):
+            terms = terms.prior_terms()
+        kind = np.ascontiguousarray(terms["kind"], dtype=np.int32)
+        if kind.shape != (self.D,):
+            raise ValueError(f"prior terms must have shape {(self.D,)}")
+        lo, hi, c0, c1, c2 = (f64(terms[k], (self.D,)) for k in ("lo", "hi", "c0", "c1", "c2"))
+        kind_w = kind
+        if self.RW != self.D:                    # pads: uniform on (-inf, +inf), no term
+            kind_w = np.zeros(self.RW, dtype=np.int32)
+            kind_w[:self.D] = kind
+        check(self.lib.hens_set_prior_terms(self.ctx, ptr(kind_w), ptr(self._pad(lo, -np.inf)), ptr(self._pad(hi, np.inf)),
+                                            ptr(self._pad(c0)), ptr(self._pad(c1)), ptr(self._pad(c2))), self.ctx)
+        self.lo, self.hi = lo, hi
+        box = bool(np.all(kind == _lib.PRIOR_UNIFORM))
+        self.prior_terms = None if box else dict(kind=kind, lo=lo, hi=hi, c0=c0, c1=c1, c2=c2)
+        # (the box's constant, summed as the library sums it: ascending from 0.0)
+        self.logp_inside = float(np.add.accumulate(np.concatenate(([0.0], c0)))[-1]) if box else None
+
+    def set_prior_box(self, lo, hi):
+        """Back to (or another) uniform box: include/hipensemble.h, hens_set_prior_box."""
+        self.lo = f64(np.broadcast_to(lo, (self.D,)))
+        self.hi = f64(np.broadcast_to(hi, (self.D,)))
+        self.logp_inside = box_logp_inside(self.lo, self.hi)
+        check(self.lib.hens_set_prior_box(self.ctx, ptr(self._pad(self.lo, -np.inf)), ptr(self._pad(self.hi, np.inf)), self.logp_inside), self.ctx)
+        self.prior_terms = None
 
     def set_stretch_scale(self, a):
         """``StretchMove.a`` for every later proposal (the reference's tuning hook mutates it, utils/updates.py:130-175)."""

@@ -72,9 +72,11 @@ class EnsembleSampler:
         if isinstance(priors, dict):
             priors = ProbDistContainer(priors)
         if not hasattr(priors, "box_bounds"):
-            raise NotImplementedError("priors must be uniform box priors (eryn_amd.prior.ProbDistContainer)")
+            raise NotImplementedError("priors must be per-parameter uniform / log-uniform / normal priors (eryn_amd.prior.ProbDistContainer)")
         self.priors = {self.branch_names[0]: priors}
-        lo, hi = priors.box_bounds()
+        # a box, or one term per parameter (include/hipensemble.h: hens_set_prior_terms) - evaluated on the device either way
+        terms = None if getattr(priors, "is_box", True) else priors.prior_terms()
+        lo, hi = (terms["lo"], terms["hi"]) if terms else priors.box_bounds()
 
         # -- tempering (ensemble.py:321-332): enabled iff tempering_kwargs != {}
         if tempering_kwargs == {}:
@@ -123,7 +125,7 @@ class EnsembleSampler:
         self.seed = int(seed)
         self.engine = HipEnsemble(self.ntemps, self.nwalkers, self.ndim, log_like_fn, lo, hi, a=a_vals.pop(),
                                   tempered=tc is not None, live_dangerously=live,
-                                  fill_value=fill_zero_leaves_val, seed=seed, device_id=device_id, **kw)
+                                  fill_value=fill_zero_leaves_val, seed=seed, device_id=device_id, prior_terms=terms, **kw)
         self._resident = [None]              # the State the device context mirrors, shared by the moves
         for m in self.moves:
             if m.temperature_control is None:

@@ -83,7 +83,9 @@ class DeviceMove(Move):
             return e
         if self.likelihood is None:
             raise ValueError(f"{type(self).__name__} needs likelihood=<eryn_amd.likelihood object>")
-        lo, hi = self._box()
+        pb = self.prior_box                      # a container with other than uniform entries: its terms (hens_set_prior_terms)
+        terms = pb.prior_terms() if hasattr(pb, "prior_terms") and not pb.is_box else None
+        lo, hi = (terms["lo"], terms["hi"]) if terms else self._box()
         tc = self.temperature_control
         kw = {}
         if tc is not None:
@@ -94,7 +96,7 @@ class DeviceMove(Move):
             seed = int(np.random.randint(0, 2**31 - 1)) if self.rng == "philox" else 0
         self.engine = HipEnsemble(T, W, D, self.likelihood, lo, hi, a=self._engine_a, tempered=tc is not None,
                                   live_dangerously=self._engine_live or not self.needs_walker_guard, fill_value=self.fill_value,
-                                  device_id=self.device_id, seed=seed, **kw)
+                                  device_id=self.device_id, seed=seed, prior_terms=terms, **kw)
         return self.engine
 
     def _apply_periodic(self, eng, name, D):

@@ -1,11 +1,27 @@
-"""Box priors with the reference's names (eryn/prior.py:12-136, 219-497), reduced to what the
-device hot path supports: independent uniform distributions per parameter.  The engine
-evaluates the prior inside the fused kernel; these objects only describe the box and draw
-starting points."""
+"""Priors with the reference's names (eryn/prior.py:12-136, 219-497), reduced to what the device hot path supports:
+one independent distribution per parameter - uniform, log-uniform or normal.  The engine evaluates the prior inside its
+kernels (include/hipensemble.h: hens_set_prior_box, hens_set_prior_terms); these objects describe the terms, evaluate
+them on the host in the same arithmetic (``logpdf``) and draw starting points (``rvs``).
+
+The arithmetic of one term is SciPy's (``rv_continuous.logpdf``: ``y = (x - loc) / scale``, the support test,
+``_logpdf(y) - log(scale)``), the sum is the reference container's (prior.py:364-383: ``prior_vals += temp`` from 0.0),
+taken in ascending parameter order."""
 import numpy as np
+
+from ._lib import PRIOR_LOG_UNIFORM, PRIOR_NORMAL, PRIOR_UNIFORM
+
+NORM_PDF_LOGC = float(np.log(np.sqrt(2 * np.pi)))         # SciPy's _norm_pdf_logC
+
+
+def _size(size):
+    if not isinstance(size, (int, tuple)):
+        raise ValueError("size must be an integer or tuple of ints.")
+    return (size,) if isinstance(size, int) else size
 
 
 class UniformDistribution:
+    kind = PRIOR_UNIFORM
+
     def __init__(self, min_val, max_val):
         if min_val > max_val:
             min_val, max_val = max_val, min_val
@@ -17,41 +33,188 @@ class UniformDistribution:
         self.logpdf_val = np.log(self.pdf_val)
 
     def rvs(self, size=1):
-        if not isinstance(size, (int, tuple)):
-            raise ValueError("size must be an integer or tuple of ints.")
-        if isinstance(size, int):
-            size = (size,)
-        return np.random.rand(*size) * self.diff + self.min_val
+        return np.random.rand(*_size(size)) * self.diff + self.min_val
+
+    def logpdf(self, x):
+        """prior.py:80-88: the constant inside [min, max] (inclusive), -inf outside."""
+        x = np.asarray(x, dtype=np.float64)
+        out = np.zeros_like(x)
+        out[(x >= self.min_val) & (x <= self.max_val)] = self.logpdf_val
+        out[~((x >= self.min_val) & (x <= self.max_val))] = -np.inf
+        return out
+
+    def term(self):
+        """(kind, lo, hi, c0, c1, c2) of hens_set_prior_terms."""
+        return self.kind, float(self.min_val), float(self.max_val), float(self.logpdf_val), 0.0, 0.0
 
 
 def uniform_dist(min, max):
     return UniformDistribution(min, max)
 
 
+class LogUniformDistribution:
+    """``scipy.stats.loguniform(a, b)``: density 1 / (x log(b / a)) on [a, b] (inclusive), 0 < a < b.
+
+    ``logpdf`` is SciPy's ``-log(x) - log(log(b) - log(a))``; the second logarithm is formed once, here."""
+    kind = PRIOR_LOG_UNIFORM
+
+    def __init__(self, a, b):
+        a, b = float(a), float(b)
+        if not (0.0 < a < b < np.inf):
+            raise ValueError("log-uniform distribution needs 0 < a < b < inf")
+        self.a, self.b = a, b
+        self.log_norm = float(np.log(np.log(b) - np.log(a)))
+        if not np.isfinite(self.log_norm):
+            raise ValueError("log-uniform distribution: log(b) - log(a) underflows")
+
+    def rvs(self, size=1):
+        return np.exp(np.random.rand(*_size(size)) * (np.log(self.b) - np.log(self.a)) + np.log(self.a))
+
+    def logpdf(self, x):
+        x = np.asarray(x, dtype=np.float64)
+        inside = (x >= self.a) & (x <= self.b)
+        out = np.full(x.shape, -np.inf)
+        out[inside] = (-np.log(x[inside])) - self.log_norm
+        return out
+
+    def term(self):
+        return self.kind, self.a, self.b, self.log_norm, 0.0, 0.0
+
+
+def log_uniform(min, max):
+    """The reference's ``log_uniform(min, max)`` (prior.py:115-136) builds ``scipy.stats.loguniform(min, max - min)``: the
+    distribution's upper bound is ``max - min``, NOT ``max``.  This function reproduces that construction, so the same call
+    gives the same prior and the same chain; for a log-uniform distribution on ``[a, b]`` use
+    ``LogUniformDistribution(a, b)``."""
+    if min > max:
+        min, max = max, min
+    return LogUniformDistribution(min, max - min)
+
+
+class NormalDistribution:
+    """``scipy.stats.norm(loc, scale)``: ``y = (x - loc) / scale``, ``(-(y y) / 2 - log(sqrt(2 pi))) - log(scale)`` on every
+    finite x (the engine refuses non-finite coordinates before any prior is asked: ensemble.py:1258-1262)."""
+    kind = PRIOR_NORMAL
+
+    def __init__(self, loc=0.0, scale=1.0):
+        loc, scale = float(loc), float(scale)
+        if not np.isfinite(loc) or not (0.0 < scale < np.inf):
+            raise ValueError("normal distribution needs a finite loc and a finite scale > 0")
+        self.loc, self.scale = loc, scale
+        self.log_scale = float(np.log(scale))
+
+    def rvs(self, size=1):
+        return np.random.randn(*_size(size)) * self.scale + self.loc
+
+    def logpdf(self, x):
+        x = np.asarray(x, dtype=np.float64)
+        with np.errstate(invalid="ignore", over="ignore"):
+            y = (x - self.loc) / self.scale
+            out = (-(y * y) / 2.0 - NORM_PDF_LOGC) - self.log_scale
+        out = np.asarray(out)
+        out[~np.isfinite(x)] = -np.inf
+        return out
+
+    def term(self):
+        return self.kind, -np.inf, np.inf, self.loc, self.scale, self.log_scale
+
+
+def _from_scipy(dist):
+    """A frozen SciPy ``uniform`` / ``loguniform`` (``reciprocal``) / ``norm`` as one of the classes above, by duck typing
+    (``.dist.name``, ``.args``, ``.kwds``): SciPy is not imported."""
+    name = getattr(getattr(dist, "dist", None), "name", None)
+    if name is None or not hasattr(dist, "args") or not hasattr(dist, "kwds"):
+        return None
+    args, kwds = tuple(dist.args), dict(dist.kwds)
+
+    def shape_loc_scale(nshape):
+        shapes, rest = args[:nshape], args[nshape:]
+        if len(shapes) < nshape or len(rest) > 2 or set(kwds) - {"loc", "scale"} or (len(rest) >= 1 and "loc" in kwds) or (
+                len(rest) == 2 and "scale" in kwds):
+            raise NotImplementedError(f"scipy.stats.{name}: arguments the device path cannot read ({args}, {kwds})")
+        loc = rest[0] if len(rest) >= 1 else kwds.get("loc", 0.0)
+        scale = rest[1] if len(rest) == 2 else kwds.get("scale", 1.0)
+        return shapes, float(loc), float(scale)
+
+    if name == "uniform":
+        _, loc, scale = shape_loc_scale(0)
+        if not scale > 0.0:
+            raise ValueError("scipy.stats.uniform needs scale > 0")
+        return UniformDistribution(loc, loc + scale)
+    if name == "norm":
+        _, loc, scale = shape_loc_scale(0)
+        return NormalDistribution(loc, scale)
+    if name in ("loguniform", "reciprocal"):
+        (a, b), loc, scale = shape_loc_scale(2)
+        if loc != 0.0 or scale != 1.0:
+            raise NotImplementedError("scipy.stats.loguniform with a loc / scale shift is outside the device path")
+        return LogUniformDistribution(a, b)
+    return None
+
+
 class ProbDistContainer:
-    """``{index: distribution}`` container (prior.py:219-335).  Only single-index uniform entries
-    are accepted: anything else cannot run inside the kernel."""
+    """``{index: distribution}`` container (prior.py:219-392).  Single integer keys 0..ndim-1, each with a
+    ``UniformDistribution`` (``uniform_dist``), a ``LogUniformDistribution`` (``log_uniform``), a ``NormalDistribution`` or
+    the frozen SciPy ``uniform`` / ``loguniform`` / ``norm`` equivalent; anything else cannot run inside the kernels.
+
+    The terms are summed in ascending parameter order, whatever the order of the dictionary (the reference adds them in
+    the dictionary's order: write the dictionary in ascending order and both agree to the last bit)."""
 
     def __init__(self, priors_in):
         self.priors_in = dict(priors_in)
+        for k in self.priors_in:
+            if isinstance(k, (tuple, str)) or not isinstance(k, (int, np.integer)):
+                raise NotImplementedError("the device path takes one distribution per single integer parameter key")
         keys = sorted(self.priors_in)
         if keys != list(range(len(keys))):
             raise ValueError("prior keys must be the integers 0..ndim-1")
-        for k, dist in self.priors_in.items():
-            if not isinstance(dist, UniformDistribution):
-                raise NotImplementedError("the device path supports uniform (box) priors only")
+        self.dists = []
+        for k in keys:
+            dist = self.priors_in[k]
+            if not isinstance(dist, (UniformDistribution, LogUniformDistribution, NormalDistribution)):
+                dist = _from_scipy(dist)
+            if dist is None:
+                raise NotImplementedError("the device path supports uniform, log-uniform and normal priors only")
+            self.dists.append(dist)
         self.ndim = len(keys)
-        self.priors = [([k], self.priors_in[k]) for k in keys]
+        self.priors = [([k], self.dists[k]) for k in keys]
+
+    @property
+    def is_box(self):
+        return all(isinstance(d, UniformDistribution) for d in self.dists)
 
     def box_bounds(self):
-        lo = np.array([self.priors_in[k].min_val for k in range(self.ndim)], dtype=np.float64)
-        hi = np.array([self.priors_in[k].max_val for k in range(self.ndim)], dtype=np.float64)
+        if not self.is_box:
+            raise NotImplementedError("box_bounds: the container holds other than uniform distributions (prior_terms)")
+        lo = np.array([d.min_val for d in self.dists], dtype=np.float64)
+        hi = np.array([d.max_val for d in self.dists], dtype=np.float64)
         return lo, hi
+
+    def prior_terms(self):
+        """``dict(kind=int32[ndim], lo, hi, c0, c1, c2)``: the arguments of hens_set_prior_terms (include/hipensemble.h)."""
+        rows = [d.term() for d in self.dists]
+        out = dict(kind=np.array([r[0] for r in rows], dtype=np.int32))
+        for j, name in enumerate(("lo", "hi", "c0", "c1", "c2"), start=1):
+            out[name] = np.array([r[j] for r in rows], dtype=np.float64)
+        return out
+
+    def logpdf(self, x):
+        """prior.py:337-392 for ``x[..., ndim]`` (one point: a scalar comes back)."""
+        x = np.asarray(x, dtype=np.float64)
+        squeeze = x.ndim == 1
+        if squeeze:
+            x = x[None, :]
+        elif x.ndim != 2:
+            raise ValueError("x needs to 1 or 2 dimensional array.")
+        vals = np.zeros(x.shape[0])
+        for k, dist in enumerate(self.dists):
+            vals += dist.logpdf(x[:, k])
+        return vals[0].item() if squeeze else vals
 
     def rvs(self, size=1):
         if isinstance(size, int):
             size = (size,)
         out = np.zeros(tuple(size) + (self.ndim,))
         for k in range(self.ndim):
-            out[..., k] = self.priors_in[k].rvs(size=tuple(size))
+            out[..., k] = self.dists[k].rvs(size=tuple(size))
         return out

@@ -99,6 +99,32 @@ int hens_synchronize(hens_ctx* ctx);
  *   (tests/test_eryn.py:33-35,100-104).  prec has D*D entries (dense) or D (diag).
  * hens_set_rosenbrock: constants of the config-5 stress likelihood. */
 int hens_set_prior_box(hens_ctx* ctx, const double* lo, const double* hi, double logp_inside);
+/* hens_set_prior_terms: ProbDistContainer({i: dist_i}) with one independent distribution per parameter (prior.py:337-392:
+ *   the terms are added in ascending parameter order from 0.0; a parameter outside its support gives -inf).  Per
+ *   parameter d: kind[d] (hens_prior_kind), the inclusive support [lo[d], hi[d]] and three constants formed by the caller
+ *   (so that every value that meets a proposal is the caller's own double):
+ *     HENS_PRIOR_UNIFORM      term c0[d] = log(1/(hi - lo)) (prior.py:28-41,80-88); c1, c2 are not read.  lo = -inf with
+ *                             hi = +inf is the inert interval of a padded row (hens_config::ndim_active): no term at all
+ *     HENS_PRIOR_LOG_UNIFORM  term (-log(q)) - c0[d], c0 = log(log(hi) - log(lo)) (scipy.stats.loguniform(lo, hi),
+ *                             prior.py:115-136); needs 0 < lo; c1, c2 are not read
+ *     HENS_PRIOR_NORMAL       term (-(y y)/2 - log(sqrt(2 pi))) - c2[d] with y = (q - c0[d]) / c1[d]: scipy.stats.norm(
+ *                             loc = c0, scale = c1 > 0), c2 = log(c1); its support is every finite q: pass lo = -inf,
+ *                             hi = +inf
+ *   Uniform kinds only: the call IS hens_set_prior_box(lo, hi, sum of the c0 in ascending order) - same launches, same
+ *   chain.  With another kind among them every entry point evaluates the sum per proposal - k_stretch_prior at the row
+ *   widths 8 / 16 / 32 / 64 / 128, the generic-width k_stretch otherwise and with periodic parameters (hens_step: the copying
+ *   launches, then the cascade and the adaptation as kernels of their own), hens_accept_split's decision kernel; the record /
+ *   one-launch / persistent kernels are not used.  A normal term that is not finite (|q - loc| beyond about 1e154 scales: y y
+ *   overflows) counts as outside the support: log-prior -inf, the likelihood skipped and filled.  Refused on a
+ *   leaf-packing context (HENS_ERR_UNSUPPORTED) and on a rank of the ladder pipeline (HENS_ERR_STATE; hens_pipe_init
+ *   after it: HENS_ERR_UNSUPPORTED).  hens_set_prior_box afterwards returns the context to the box. */
+typedef enum hens_prior_kind {
+    HENS_PRIOR_UNIFORM = 0,
+    HENS_PRIOR_LOG_UNIFORM = 1,
+    HENS_PRIOR_NORMAL = 2
+} hens_prior_kind;
+int hens_set_prior_terms(hens_ctx* ctx, const int32_t* kind, const double* lo, const double* hi, const double* c0,
+                         const double* c1, const double* c2);
 /* hens_set_periodic: the `periodic` argument of EnsembleSampler / Move (ensemble.py:165-168,338-347,528-536; a
  *   PeriodicContainer, utils/periodic.py:11-151) for the single branch: period[d] > 0 makes parameter d periodic - the
  *   stretch move measures c - s the short way round (stretch.py:136-141 -> periodic.py:49-116) and every proposal is
