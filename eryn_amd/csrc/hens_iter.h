@@ -277,8 +277,6 @@ __global__ __launch_bounds__(NW * 64) void k_iter(const IterArgs A) {
     const double2 lov = *reinterpret_cast<const double2*>(A.lo + jl * 2);
     const double2 hiv = *reinterpret_cast<const double2*>(A.hi + jl * 2);
     if (A.ad_on && wv == 5) fold.part2(A.ad, lane, sbeta, lead);        // the row gathers are in flight
-    const int gshift = lane & ~(LPR - 1);
-    const unsigned long long gmask = (LPR == 64) ? ~0ull : (((1ull << (LPR & 63)) - 1ull) << gshift);
     // q = c - (c - s) zz (stretch.py:143,145), box test by ballot over the row's lanes (prior.py:80-88)
     auto propose = [&](const double2 s, const double2 c, const double zz, double* tile, int32_t* flag, const int r, const bool on) {
         bool ok = true, finite = true;
@@ -296,12 +294,7 @@ __global__ __launch_bounds__(NW * 64) void k_iter(const IterArgs A) {
             finite = (fabs(qv.x) < INFINITY) && (fabs(qv.y) < INFINITY);
             *reinterpret_cast<double2*>(tile + r * RS + jl * 2) = qv;
         }
-        const unsigned long long bad = __ballot(!ok);
-        const unsigned long long nonfin = __ballot(!finite);
-        if (jl == 0 && on) {
-            if ((bad & gmask) == 0ull) atomicOr(&flag[r], 1);
-            if ((nonfin & gmask) != 0ull) atomicOr(A.flags, FLAG_NONFINITE_X);
-        }
+        row_verdict(ok, finite, LPR, lane, jl == 0 && on, &flag[r], A.flags);
     };
 #pragma unroll
     for (int p = 0; p < NPASS; ++p) {
@@ -336,23 +329,10 @@ __global__ __launch_bounds__(NW * 64) void k_iter(const IterArgs A) {
         double acc = 0.0;
 #pragma unroll
         for (int w2 = 0; w2 < like_nparts<DT, LIKE, LNW>(); ++w2) acc += part[w2 * TILE + lane];
-        double logl = inbox ? -0.5 * acc : A.fill;                      // ensemble.py:1486-1513
-        if (logl != logl) {                                             // red_blue.py:279-281
-            logl = -1e300;
-            atomicOr(A.flags, FLAG_NAN_LOGL);
-        }
+        logl_out = nan_logl_rule(inbox ? -0.5 * acc : A.fill, A.flags);   // ensemble.py:1486-1513
         const double logp = inbox ? A.logp_in : -INFINITY;              // prior.py:80-88
-        const double beta = sbeta[tm];
-        double lt = logl * beta;                                        // tempering.py:304-306,343-349
-        if (lt != lt) lt = -INFINITY;
-        const double logP = lt + logp;
-        double lo_ = Lold * beta;
-        if (lo_ != lo_) lo_ = -INFINITY;
-        const double prevP = lo_ + Pold;
-        const double lnpdiff = fac + logP - prevP;                      // red_blue.py:292
-        logl_out = logl;
-        newP_out = (fabs(logp) == INFINITY) ? 0.0 : logp;               // move.py:513-532
-        return lnpdiff > lu;                                            // red_blue.py:294
+        newP_out = stored_logp(logp);
+        return accept_test(true, [&] { return sbeta[tm]; }, logl_out, logp, Lold, Pold, fac, lu);
     };
     auto alt_row = [&](const int32_t r) -> int32_t { return r < H ? r + H : r - H; };
     if (wv == 0 && lane < NM) {                                          // the block's own first-half walkers: results count

@@ -490,6 +490,57 @@ __device__ __forceinline__ double prior_sum(const PriorTerm* __restrict__ terms,
     return acc;
 }
 
+// ---------------------------------------------------------------------------------------------
+// The accept rule of every stepping kernel, once.  A site keeps what is its own: where the partial sums, (Lold, Pold), factors,
+// lu and beta come from, its prior-term sums, and every store, counter and flag bit behind the verdict.
+// ---------------------------------------------------------------------------------------------
+// red_blue.py:279-281: a NaN log-likelihood counts as -1e300 and is reported
+__device__ __forceinline__ double nan_logl_rule(double logl, unsigned* flags) {
+    if (logl != logl) {
+        logl = -1e300;
+        atomicOr(flags, FLAG_NAN_LOGL);
+    }
+    return logl;
+}
+// tempering.py:304-306,343-349: the tempered posterior of one side (the proposal, or the old point)
+__device__ __forceinline__ double tempered_post(double L, double beta, double P) {
+    double lt = L * beta;
+    if (lt != lt) lt = -INFINITY;
+    return lt + P;
+}
+// red_blue.py:292,294 (mh.py:155-157, rj.py:330-332) over tempered or untempered (move.py:443-457) sums of both sides.  `beta_of()` is
+// called only under `tempered`: a kernel that has to wait for its beta waits there and nowhere else.
+template <class BetaOf>
+__device__ __forceinline__ bool accept_test(bool tempered, BetaOf&& beta_of, double logl, double logp, double Lold, double Pold,
+                                            double factors, double lu) {
+    double logP, prevP;
+    if (tempered) {
+        const double beta = beta_of();
+        logP = tempered_post(logl, beta, logp);
+        prevP = tempered_post(Lold, beta, Pold);
+    } else {
+        logP = logl + logp;
+        prevP = Lold + Pold;
+    }
+    const double lnpdiff = factors + logP - prevP;
+    return lnpdiff > lu;
+}
+// move.py:513-532: the log-prior an accepted point is stored with
+__device__ __forceinline__ double stored_logp(double logp) { return (fabs(logp) == INFINITY) ? 0.0 : logp; }
+// prior.py:80-88, the row-wide AND: a row's LPR lanes (a power of two <= 64, aligned) each hold `ok` / `finite` of their coordinates;
+// the lane that speaks for a valid row sets bit 0 of the row's flag word when all are inside and reports a non-finite coordinate.
+// Every lane of the wavefront calls it (ballot).
+__device__ __forceinline__ void row_verdict(bool ok, bool finite, int LPR, int lane, bool speaks, int32_t* row_flag, unsigned* flags) {
+    const unsigned long long bad = __ballot(!ok);
+    const unsigned long long nonfin = __ballot(!finite);
+    const int gshift = lane & ~(LPR - 1);
+    const unsigned long long gmask = (LPR == 64) ? ~0ull : (((1ull << (LPR & 63)) - 1ull) << gshift);
+    if (speaks) {
+        if ((bad & gmask) == 0ull) atomicOr(row_flag, 1);
+        if ((nonfin & gmask) != 0ull) atomicOr(flags, FLAG_NONFINITE_X);
+    }
+}
+
 // The state-independent part of one proposal (stretch.py:129-132,223; red_blue.py:294).
 struct Draws {
     int32_t* own;    // [Tl][W] moving walker at each split position (positions < N0: split 0)
@@ -524,16 +575,15 @@ struct __attribute__((aligned(32))) WalkerRec {
 };
 __device__ __forceinline__ WalkerRec make_wrec(double L, double P, int32_t loc, uint32_t acc, int32_t slot = 0) { return WalkerRec{L, P, loc, acc, slot, 0}; }
 
-__device__ __forceinline__ DrawRec draw_values(int own, int cw, double uz, double ua, double a, int D) {
-    double zz = (a - 1.0) * uz + 1.0;              // stretch.py:129-132 (mul, add, square, divide)
-    zz = zz * zz / a;
-    return DrawRec{zz, ((double)D - 1.0) * log(zz) /* stretch.py:223 */, log(ua) /* red_blue.py:294 */, cw, own};
-}
 // the stretch factor alone - what the proposal needs; (D - 1) log zz and log u are the accept test's (two FP64 logarithms: ~2000
-// cycles of dependent ALU that need not sit in front of the first barrier).  Same expressions as draw_values.
+// cycles of dependent ALU that need not sit in front of the first barrier)
 __device__ __forceinline__ double draw_zz(double uz, double a) {
     double zz = (a - 1.0) * uz + 1.0;              // stretch.py:129-132 (mul, add, square, divide)
     return zz * zz / a;
+}
+__device__ __forceinline__ DrawRec draw_values(int own, int cw, double uz, double ua, double a, int D) {
+    const double zz = draw_zz(uz, a);
+    return DrawRec{zz, ((double)D - 1.0) * log(zz) /* stretch.py:223 */, log(ua) /* red_blue.py:294 */, cw, own};
 }
 __device__ __forceinline__ void store_draw(const Draws& d, size_t idx, const DrawRec& r) {
     d.own[idx] = r.own;
@@ -821,15 +871,7 @@ __global__ __launch_bounds__(256) void k_stretch(const StretchArgs A) {
                 }
             }
         }
-        // row-wide AND over the LPR lanes of a row via wavefront ballot (prior.py:80-88)
-        const unsigned long long bad = __ballot(!ok);
-        const unsigned long long nonfin = __ballot(!finite);
-        const int gshift = lane & ~(LPR - 1);
-        const unsigned long long gmask = (LPR == 64) ? ~0ull : (((1ull << LPR) - 1ull) << gshift);
-        if (jl == 0 && rvalid) {
-            if ((bad & gmask) == 0ull) atomicOr(&s_flag[r], 1);
-            if ((nonfin & gmask) != 0ull) atomicOr(A.flags, FLAG_NONFINITE_X);
-        }
+        row_verdict(ok, finite, LPR, lane, jl == 0 && rvalid, &s_flag[r], A.flags);
     }
     __syncthreads();
 
@@ -880,11 +922,7 @@ __global__ __launch_bounds__(256) void k_stretch(const StretchArgs A) {
         double acc = 0.0;
 #pragma unroll
         for (int w2 = 0; w2 < NW; ++w2) acc += s_part[w2 * TILE + lane];
-        double logl = inbox ? -0.5 * acc : A.fill;             // ensemble.py:1486-1513
-        if (logl != logl) {                                    // red_blue.py:279-281
-            logl = -1e300;
-            atomicOr(A.flags, FLAG_NAN_LOGL);
-        }
+        double logl = nan_logl_rule(inbox ? -0.5 * acc : A.fill, A.flags);   // ensemble.py:1486-1513
         double logp = inbox ? A.logp_in : -INFINITY;           // prior.py:80-88
         if (A.prior_on && inbox) {                             // prior.py:364-383 (the tile holds q itself)
             logp = prior_sum(prior_terms_of(A), qtile + lane * RS, D);
@@ -898,24 +936,10 @@ __global__ __launch_bounds__(256) void k_stretch(const StretchArgs A) {
             A.L[gi] = logl;
             A.P[gi] = logp;
         } else {
-            double logP, prevP;
-            if (A.tempered) {                                  // tempering.py:304-306,343-349
-                const double beta = A.betas[A.rung_begin + tl];
-                double lt = logl * beta;
-                if (lt != lt) lt = -INFINITY;
-                logP = lt + logp;
-                double lo_ = Lold * beta;
-                if (lo_ != lo_) lo_ = -INFINITY;
-                prevP = lo_ + Pold;
-            } else {                                           // move.py:443-457
-                logP = logl + logp;
-                prevP = Lold + Pold;
-            }
-            const double lnpdiff = factors + logP - prevP;     // red_blue.py:292
-            const bool keep = lnpdiff > lu;                    // red_blue.py:294
-            if (keep) {                                        // move.py:513-532
+            const bool keep = accept_test(A.tempered, [&] { return A.betas[A.rung_begin + tl]; }, logl, logp, Lold, Pold, factors, lu);
+            if (keep) {
                 A.L[gi] = logl;
-                A.P[gi] = (fabs(logp) == INFINITY) ? 0.0 : logp;
+                A.P[gi] = stored_logp(logp);
                 atomicAdd(&A.accepted[gi], 1u);
                 atomicOr(&s_flag[lane], 2);
             }
@@ -2191,7 +2215,7 @@ __global__ __launch_bounds__(NW * 64) void k_stretch_fast(const StretchArgs A) {
         if (jl == 0 && rv[p]) {                                                                                 \
             if ((bad & gmask) == 0ull) atomicOr(&s_flag[r], 1);                                                 \
             if ((nonfin & gmask) != 0ull) atomicOr(A.flags, FLAG_NONFINITE_X);                                  \
-        }                                                                                                      
+        }
 #pragma unroll
     for (int p = 0; p < HP; ++p) {
         HENS_PROPOSE_PASS(p)
@@ -2277,20 +2301,14 @@ __global__ __launch_bounds__(NW * 64) void k_stretch_fast(const StretchArgs A) {
         double acc = 0.0;
 #pragma unroll
         for (int w2 = 0; w2 < like_nparts<DT, LIKE, NW>(); ++w2) acc += s_part[w2 * TILE + lane];
-        double logl = inbox ? -0.5 * acc : A.fill;             // ensemble.py:1486-1513
-        if (logl != logl) {                                    // red_blue.py:279-281
-            logl = -1e300;
-            atomicOr(A.flags, FLAG_NAN_LOGL);
-        }
+        const double logl = nan_logl_rule(inbox ? -0.5 * acc : A.fill, A.flags);   // ensemble.py:1486-1513
         const double logp = inbox ? A.logp_in : -INFINITY;     // prior.py:80-88
         const size_t gi = (size_t)tl * W + own;
         if (EVAL) {
             A.L[gi] = logl;
             A.P[gi] = logp;
         } else {
-            double logP, prevP;
-            if (A.tempered) {                                  // tempering.py:304-306,343-349
-                double beta = beta_pre;
+            auto beta_of = [&]() -> double {
                 if (ring_me) {                                 // workgroup (0,0) may still be adapting: wait for the value
                     if (beta_ring < 0.0) {                     // (the budget runs on the shader clock: see spin_expired)
                         const unsigned long long t0 = __builtin_amdgcn_s_memtime();
@@ -2300,24 +2318,13 @@ __global__ __launch_bounds__(NW * 64) void k_stretch_fast(const StretchArgs A) {
                             if (spin_expired(t0, 200000000LL)) { atomicOr(A.flags, FLAG_PIPE_TIMEOUT); break; }
                         }
                     }
-                    beta = beta_ring;
-                } else if (ad_on) {
-                    beta = s_beta[A.rung_begin + tl];
+                    return beta_ring;
                 }
-                double lt = logl * beta;
-                if (lt != lt) lt = -INFINITY;
-                logP = lt + logp;
-                double lo_ = Lold * beta;
-                if (lo_ != lo_) lo_ = -INFINITY;
-                prevP = lo_ + Pold;
-            } else {                                           // move.py:443-457
-                logP = logl + logp;
-                prevP = Lold + Pold;
-            }
-            const double lnpdiff = factors + logP - prevP;     // red_blue.py:292
-            const bool keep = lnpdiff > lu;                    // red_blue.py:294
-            const double newP = (fabs(logp) == INFINITY) ? 0.0 : logp;
-            if (keep) {                                        // move.py:513-532
+                return ad_on ? s_beta[A.rung_begin + tl] : beta_pre;
+            };
+            const bool keep = accept_test(A.tempered, beta_of, logl, logp, Lold, Pold, factors, lu);
+            const double newP = stored_logp(logp);
+            if (keep) {
                 if (A.wrec) {
                     if (PIPE || late_kernarg<int32_t>(offsetof(StretchArgs, norel))) {       // (written through: wt_store; a rank: see k_split1_pt's phase G)
                         store_row16(&A.wrec[gi].L, double2{logl, newP});
@@ -3397,7 +3404,7 @@ __global__ __launch_bounds__(NW * 64) void k_split1_pt(const FusedArgs A) {
             if (CEN) qkeep[p] = qv;
             *reinterpret_cast<double2*>(qtile + r * RS + jl * 2) = double2{qv.x - muv.x, qv.y - muv.y};
         }
-        const unsigned long long bad = __ballot(!ok);                    // prior.py:80-88, row-wide AND
+        const unsigned long long bad = __ballot(!ok);                    // prior.py:80-88, row-wide AND (row_verdict, as text: it moved registers here)
         const unsigned long long nonfin = __ballot(!finite);
         const int gshift = lane & ~(LPR - 1);
         const unsigned long long gmask = (LPR == 64) ? ~0ull : (((1ull << (LPR & 63)) - 1ull) << gshift);
@@ -3434,23 +3441,11 @@ __global__ __launch_bounds__(NW * 64) void k_split1_pt(const FusedArgs A) {
         double acc = 0.0;
 #pragma unroll
         for (int w2 = 0; w2 < like_nparts<DT, LIKE, NW>(); ++w2) acc += s_part[w2 * TILE + m];
-        double logl = inbox ? -0.5 * acc : A.fill;                      // ensemble.py:1486-1513
-        if (logl != logl) {                                             // red_blue.py:279-281
-            logl = -1e300;
-            atomicOr(A.flags, FLAG_NAN_LOGL);
-        }
+        const double logl = nan_logl_rule(inbox ? -0.5 * acc : A.fill, A.flags);   // ensemble.py:1486-1513
         const double logp = inbox ? A.logp_in : -INFINITY;              // prior.py:80-88
-        const double beta = sbeta[t];
         const double Lold = wr_n.L, Pold = wr_n.P;
-        double lt = logl * beta;                                        // tempering.py:304-306,343-349
-        if (lt != lt) lt = -INFINITY;
-        const double logP = lt + logp;
-        double lo_ = Lold * beta;
-        if (lo_ != lo_) lo_ = -INFINITY;
-        const double prevP = lo_ + Pold;
-        const double lnpdiff = s_fac[m] + logP - prevP;                 // red_blue.py:292
-        const bool keep = lnpdiff > s_lu[m];                            // red_blue.py:294
-        const double newP = (fabs(logp) == INFINITY) ? 0.0 : logp;      // move.py:513-532
+        const bool keep = accept_test(true, [&] { return sbeta[t]; }, logl, logp, Lold, Pold, s_fac[m], s_lu[m]);
+        const double newP = stored_logp(logp);
         Lc[e] = keep ? logl : Lold;
         Pc[e] = keep ? newP : Pold;
         if (PIPE) {
@@ -3939,32 +3934,15 @@ inline __global__ void k_accept_decide(const HostLikeArgs A) {
         const int own = A.dr.own[di];
         const size_t gi = (size_t)tl * A.W + own;
         const bool inbox = A.inbox[wk] != 0;
-        double logl = A.logl[wk];
-        if (logl != logl) {                                            // red_blue.py:279-281
-            logl = -1e300;
-            atomicOr(A.flags, FLAG_NAN_LOGL);
-        }
+        const double logl = nan_logl_rule(A.logl[wk], A.flags);
         double logp = inbox ? A.logp_in : -INFINITY;
         if (A.prior && inbox) logp = prior_sum(A.prior, A.qbuf + (size_t)wk * A.D, A.D);   // prior.py:364-383
         const double Lold = A.L[gi], Pold = A.P[gi];
-        double logP, prevP;
-        if (A.tempered) {                                              // tempering.py:304-306,343-349
-            const double beta = A.betas[A.rung_begin + tl];
-            double lt = logl * beta;
-            if (lt != lt) lt = -INFINITY;
-            logP = lt + logp;
-            double lo_ = Lold * beta;
-            if (lo_ != lo_) lo_ = -INFINITY;
-            prevP = lo_ + Pold;
-        } else {
-            logP = logl + logp;
-            prevP = Lold + Pold;
-        }
-        const double lnpdiff = A.dr.fac[di] + logP - prevP;           // red_blue.py:292
-        const bool keep = lnpdiff > log(A.u_acc[wk]);                  // red_blue.py:294
-        if (keep) {                                                    // move.py:513-532
+        const bool keep = accept_test(A.tempered, [&] { return A.betas[A.rung_begin + tl]; }, logl, logp, Lold, Pold, A.dr.fac[di],
+                                      log(A.u_acc[wk]));
+        if (keep) {
             A.L[gi] = logl;
-            A.P[gi] = (fabs(logp) == INFINITY) ? 0.0 : logp;
+            A.P[gi] = stored_logp(logp);
             atomicAdd(&A.accepted[gi], 1u);
         }
         A.rs_old[wk] = A.loc[gi];

@@ -148,15 +148,7 @@ __global__ __launch_bounds__(NW * 64) void k_stretch_prior(const StretchArgs A) 
             ttile[r * TS + e] = tx;
             ttile[r * TS + e + 1] = ty;
         }
-        // row-wide AND over the LPR lanes of a row via wavefront ballot (prior.py:80-88, 364-383)
-        const unsigned long long bad = __ballot(!ok);
-        const unsigned long long nonfin = __ballot(!finite);
-        const int gshift = lane & ~(LPR - 1);
-        const unsigned long long gmask = (LPR == 64) ? ~0ull : (((1ull << LPR) - 1ull) << gshift);
-        if (jl == 0 && rvalid) {
-            if ((bad & gmask) == 0ull) atomicOr(&s_flag[r], 1);
-            if ((nonfin & gmask) != 0ull) atomicOr(A.flags, FLAG_NONFINITE_X);
-        }
+        row_verdict(ok, finite, LPR, lane, jl == 0 && rvalid, &s_flag[r], A.flags);   // (`ok`: inside every support, prior.py:364-383)
     }
     if constexpr (DT != 32) mfr = like_prefetch<DT, LIKE, NW>(lane, wv, A.prec_sym);   // (the matrix operand of phase C: in flight across the barrier)
     __syncthreads();
@@ -175,11 +167,7 @@ __global__ __launch_bounds__(NW * 64) void k_stretch_prior(const StretchArgs A) 
         double acc = 0.0;
 #pragma unroll
         for (int w2 = 0; w2 < like_nparts<DT, LIKE, NW>(); ++w2) acc += s_part[w2 * TILE + lane];
-        double logl = inbox ? -0.5 * acc : A.fill;             // ensemble.py:1486-1513
-        if (logl != logl) {                                    // red_blue.py:279-281
-            logl = -1e300;
-            atomicOr(A.flags, FLAG_NAN_LOGL);
-        }
+        const double logl = nan_logl_rule(inbox ? -0.5 * acc : A.fill, A.flags);   // ensemble.py:1486-1513
         double logp = -INFINITY;
         if (inbox) {                                           // prior.py:364-383: prior_vals += temp, ascending, from 0.0
             logp = 0.0;
@@ -192,24 +180,10 @@ __global__ __launch_bounds__(NW * 64) void k_stretch_prior(const StretchArgs A) 
             A.L[gi] = logl;
             A.P[gi] = logp;
         } else {
-            double logP, prevP;
-            if (A.tempered) {                                  // tempering.py:304-306,343-349
-                const double beta = A.betas[A.rung_begin + tl];
-                double lt = logl * beta;
-                if (lt != lt) lt = -INFINITY;
-                logP = lt + logp;
-                double lo_ = Lold * beta;
-                if (lo_ != lo_) lo_ = -INFINITY;
-                prevP = lo_ + Pold;
-            } else {                                           // move.py:443-457
-                logP = logl + logp;
-                prevP = Lold + Pold;
-            }
-            const double lnpdiff = factors + logP - prevP;     // red_blue.py:292
-            const bool keep = lnpdiff > lu;                    // red_blue.py:294
-            if (keep) {                                        // move.py:513-532
+            const bool keep = accept_test(A.tempered, [&] { return A.betas[A.rung_begin + tl]; }, logl, logp, Lold, Pold, factors, lu);
+            if (keep) {
                 A.L[gi] = logl;
-                A.P[gi] = (fabs(logp) == INFINITY) ? 0.0 : logp;
+                A.P[gi] = stored_logp(logp);
                 atomicAdd(&A.accepted[gi], 1u);
                 atomicOr(&s_flag[lane], 2);
             }

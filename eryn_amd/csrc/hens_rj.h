@@ -798,11 +798,7 @@ __global__ __launch_bounds__(RJ_WAVES * 64) __attribute__((amdgpu_waves_per_eu(R
         }
 #pragma unroll
         for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off);
-        logl = -0.5 * acc;
-        if (logl != logl) {
-            logl = -1e300;
-            atomicOr(A.flags, FLAG_NAN_LOGL);
-        }
+        logl = nan_logl_rule(-0.5 * acc, A.flags);
         if (!evaluated) logl = A.fill;
     } else if (evaluated && by_diff) {
         // the strided forms (no uniform grid; parity API): template' = template + (born leaf) - (dead leaf) per branch under proposal: one leaf's values instead of every leaf's
@@ -857,11 +853,7 @@ __global__ __launch_bounds__(RJ_WAVES * 64) __attribute__((amdgpu_waves_per_eu(R
         }
 #pragma unroll
         for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off);
-        logl = -0.5 * acc;
-        if (logl != logl) {
-            logl = -1e300;
-            atomicOr(A.flags, FLAG_NAN_LOGL);
-        }
+        logl = nan_logl_rule(-0.5 * acc, A.flags);
     } else if (evaluated || (HAVE_TM && MODE == RJ_MODE_EVAL && total_leaves > 0)) {     // (an evaluation always leaves a true template behind)
         double acc = 0.0;
         // Leaves outside, NPT data points per lane inside: a leaf's three parameters are read (LDS) and its 1 / (2 c^2)
@@ -934,11 +926,7 @@ __global__ __launch_bounds__(RJ_WAVES * 64) __attribute__((amdgpu_waves_per_eu(R
         }
 #pragma unroll
         for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off);
-        logl = -0.5 * acc;
-        if (logl != logl) {
-            logl = -1e300;
-            atomicOr(A.flags, FLAG_NAN_LOGL);
-        }
+        logl = nan_logl_rule(-0.5 * acc, A.flags);
         if (!evaluated) logl = A.fill;
     } else {
         logl = A.fill;                           // (no leaves: the template that goes with it is all zeros)
@@ -964,33 +952,17 @@ __global__ __launch_bounds__(RJ_WAVES * 64) __attribute__((amdgpu_waves_per_eu(R
         }
         return;
     }
-    double logP, prevP;
-    if (A.tempered) {                                                  // tempering.py:304-306,343-349
-        double beta;
+    auto beta_of = [&]() -> double {
         if (FOLD && A.ad_fold) {                 // the ladder of this launch: published by wave 0 (long ago, as a rule)
             // (relaxed agent-scope loads - they read past the caches that are not coherent across XCDs; an ACQUIRE here invalidates
             //  the XCD's L2 once per wave: measured, the launch took twice as long)
-            if (have_beta) {
-                beta = beta_e;
-            } else {
-                while (__hip_atomic_load(A.ad_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != A.ad_serial) __builtin_amdgcn_s_sleep(4);
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                beta = __hip_atomic_load(A.betas + (A.rung_begin + tl), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        } else {
-            beta = A.betas[A.rung_begin + tl];
+            if (have_beta) return beta_e;
+            while (__hip_atomic_load(A.ad_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != A.ad_serial) __builtin_amdgcn_s_sleep(4);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            return __hip_atomic_load(A.betas + (A.rung_begin + tl), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
-        double lt = logl * beta;
-        if (lt != lt) lt = -INFINITY;
-        logP = lt + logp;
-        double lo_ = Lold * beta;
-        if (lo_ != lo_) lo_ = -INFINITY;
-        prevP = lo_ + Pold;
-    } else {
-        logP = logl + logp;
-        prevP = Lold + Pold;
-    }
-    const double lnpdiff = factors + logP - prevP;                     // mh.py:155, rj.py:330
+        return A.betas[A.rung_begin + tl];
+    };
     double lu;
     if (A.u_acc) {
         lu = log(A.u_acc[MODE == RJ_MODE_STRETCH ? slot : gw]);
@@ -998,13 +970,13 @@ __global__ __launch_bounds__(RJ_WAVES * 64) __attribute__((amdgpu_waves_per_eu(R
         // (in-model, birth / death: drawn along with the proposal - same key, same value)
         lu = log(u_have ? u_drawn : rj_accept_uniform(A.seed, A.iter, wid, MODE, MODE == RJ_MODE_BD ? (A.branch >= 0 ? A.branch : M.nb) : 0));
     }
-    const bool keep = lnpdiff > lu;                                    // mh.py:157, rj.py:332
+    const bool keep = accept_test(A.tempered, beta_of, logl, logp, Lold, Pold, factors, lu);
     if (keep) {                                                        // Move.update (move.py:472-703)
         store_template();
         for (int i = lane; i < RW; i += 64) row[i] = q[i];
         if (lane == 0) {
             A.L[gw] = logl;
-            A.P[gw] = (fabs(logp) == INFINITY) ? 0.0 : logp;
+            A.P[gw] = stored_logp(logp);
             if (A.accepted) A.accepted[gw] += 1u;     // ("iterate_branches": the move's mask is its LAST branch's, rj.py:385-386)
         }
     }
@@ -1029,27 +1001,13 @@ __global__ __launch_bounds__(256) void k_rj_accept(const RjAcceptArgs A) {
     if (!A.hmoved[gw]) { if (lane == 0 && A.keep_out) A.keep_out[gw] = 0; return; }
     const int tl = (int)(gw / A.W);
     const double logl = A.logl[gw], logp = A.hlogp[gw], Lold = A.L[gw], Pold = A.P[gw];
-    double logP, prevP;
-    if (A.tempered) {                                                  // tempering.py:304-306,343-349
-        const double beta = A.betas[A.rung_begin + tl];
-        double lt = logl * beta;
-        if (lt != lt) lt = -INFINITY;
-        logP = lt + logp;
-        double lo_ = Lold * beta;
-        if (lo_ != lo_) lo_ = -INFINITY;
-        prevP = lo_ + Pold;
-    } else {
-        logP = logl + logp;
-        prevP = Lold + Pold;
-    }
-    const double lnpdiff = A.hfac[gw] + logP - prevP;
-    const bool keep = lnpdiff > A.hlu[gw];
+    const bool keep = accept_test(A.tempered, [&] { return A.betas[A.rung_begin + tl]; }, logl, logp, Lold, Pold, A.hfac[gw], A.hlu[gw]);
     if (keep) {
         double* row = A.pool + (size_t)A.loc[gw] * A.RW;
         for (int i = lane; i < A.RW; i += 64) row[i] = A.hq[(size_t)gw * A.RW + i];
         if (lane == 0) {
             A.L[gw] = logl;
-            A.P[gw] = (fabs(logp) == INFINITY) ? 0.0 : logp;
+            A.P[gw] = stored_logp(logp);
             if (A.accepted) A.accepted[gw] += 1u;
         }
     }

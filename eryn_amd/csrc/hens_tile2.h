@@ -624,13 +624,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void k
             double acc = 0.0;
 #pragma unroll
             for (int w2 = 0; w2 < like_nparts<DT, LIKE, NW>(); ++w2) acc += s_part[w2 * TILE + lane];
-            double logl = inbox ? -0.5 * acc : A.fill;             // ensemble.py:1486-1513
-            if (logl != logl) {                                    // red_blue.py:279-281
-                logl = -1e300;
-                atomicOr(A.flags, FLAG_NAN_LOGL);
-            }
+            const double logl = nan_logl_rule(inbox ? -0.5 * acc : A.fill, A.flags);   // ensemble.py:1486-1513
             const double logp = inbox ? A.logp_in : -INFINITY;     // prior.py:80-88
             const size_t gi = (size_t)tl * W + own;
+            // (accept_test as text: through the function this kernel's forced-tile shape at D = 64 measured 0.7 % slower, LABNOTES 12.5)
             double logP, prevP;
             if (A.tempered) {                                      // tempering.py:304-306,343-349
                 double beta = beta_pre;
@@ -659,8 +656,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void k
             }
             const double lnpdiff = factors + logP - prevP;         // red_blue.py:292
             const bool keep = lnpdiff > lu;                        // red_blue.py:294
-            const double newP = (fabs(logp) == INFINITY) ? 0.0 : logp;
-            if (keep) {                                            // move.py:513-532
+            const double newP = stored_logp(logp);
+            if (keep) {
                 if (PIPE || late_kernarg<int32_t>(offsetof(StretchArgs, norel))) {
                     store_row16(&A.wrec[gi].L, double2{logl, newP});
                     wt_store(&A.wrec[gi].acc, acc_old + 1u);
