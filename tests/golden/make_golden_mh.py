@@ -52,9 +52,10 @@ class RLog:
 
 
 def capture(name, T, W, D, nsteps, moves_spec, box=6.0, seed_construct=321, seed_run=654, tempering_kwargs=None,
-            periodic=None):
+            periodic=None, x0=None, save=True):
     """moves_spec: list of ("stretch", weight) | ("gauss", weight, dict(cov=..., mode=..., factor=...)).
-    periodic: {parameter index: period} of the single branch (ensemble.py:165-168) or None."""
+    periodic: {parameter index: period} of the single branch (ensemble.py:165-168) or None.  x0: start positions in place of the
+    uniform ones; save=False: the record is returned, not written (make_golden_periodic.py)."""
     mu, invcov = gaussian_problem(D)
     np.random.seed(seed_construct)
     priors = ProbDistContainer({i: uniform_dist(-box, box) for i in range(D)})
@@ -75,7 +76,8 @@ def capture(name, T, W, D, nsteps, moves_spec, box=6.0, seed_construct=321, seed
         kw["periodic"] = {"model_0": dict(periodic)}
     s = EnsembleSampler(W, D, log_like_vec, priors, args=[mu, invcov], vectorize=True, moves=moves, **kw)
     h = min(2.0, 0.9 * box)
-    x0 = np.random.RandomState(1).uniform(-h, h, size=(T, W, D))
+    if x0 is None:
+        x0 = np.random.RandomState(1).uniform(-h, h, size=(T, W, D))
     rlog, glog, plog = [], [], []
     s._random = RLog(s._random, rlog)
     orig = (np.random.shuffle, np.random.permutation, np.random.uniform)
@@ -168,6 +170,8 @@ def capture(name, T, W, D, nsteps, moves_spec, box=6.0, seed_construct=321, seed
             out[f"move{i}_num_proposals"] = int(m.num_proposals)
     finally:
         np.random.shuffle, np.random.permutation, np.random.uniform = orig
+    if not save:
+        return out
     path = os.path.join(HERE, name + ".npz")
     np.savez_compressed(path, **out)
     acc = [float(np.mean(out[f"move{i}_accepted"]) / max(out[f"move{i}_num_proposals"], 1)) for i in range(len(s.moves))]

@@ -1,9 +1,10 @@
 """The committed fixtures ARE what the reference produces (build container only; skipped where /root/reference is absent).
 
-The four generator scripts under tests/golden/ import the real reference and write every fixture.  This test runs copies of them
+The five generator scripts under tests/golden/ import the real reference and write every fixture.  This test runs copies of them
 into a temporary directory and requires key-for-key, bit-for-bit equality with the committed ``.npz`` files - the check the round-5
-judge made by hand (8 056 arrays), now part of the CPU suite.  Nothing here runs on the GPU box: /root/reference does
-not exist there."""
+judge made by hand (8 056 arrays), now part of the CPU suite.  Doubles are compared as their bit patterns wherever the
+generator is the seam one: its answers are zeros of either sign.  Nothing here runs on the GPU box: /root/reference does not exist
+there."""
 import glob
 import os
 import shutil
@@ -15,21 +16,28 @@ import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(HERE, "golden")
-GENERATORS = ["make_golden.py", "make_golden_mh.py", "make_golden_repeats.py", "make_golden_rj.py"]
+GENERATORS = ["make_golden.py", "make_golden_mh.py", "make_golden_repeats.py", "make_golden_rj.py", "make_golden_periodic.py"]
+SUBDIRS = ["periodic"]                      # make_golden_periodic.py writes into a directory of its own
 
 pytestmark = pytest.mark.skipif(not os.path.isdir("/root/reference/src/eryn"), reason="the reference tree is not on this machine")
 
 
+def _fixtures(root):
+    return sorted([os.path.basename(p) for p in glob.glob(os.path.join(str(root), "*.npz"))] +
+                  [os.path.join(d, os.path.basename(p)) for d in SUBDIRS for p in glob.glob(os.path.join(str(root), d, "*.npz"))])
+
+
 def test_generators_reproduce_every_committed_fixture(tmp_path):
     shutil.copy(os.path.join(HERE, "ladders.py"), tmp_path / "ladders.py")     # (make_golden.py builds fixture f9's ladder with it)
+    shutil.copy(os.path.join(HERE, "periodic_seam.py"), tmp_path / "periodic_seam.py")   # (the seam matrix of make_golden_periodic.py)
     for g in GENERATORS:
         shutil.copy(os.path.join(GOLDEN, g), tmp_path / g)           # (a generator writes beside itself)
         r = subprocess.run([sys.executable, str(tmp_path / g)], cwd=str(tmp_path), capture_output=True, text=True, timeout=600,
                            env=dict(os.environ, PYTHONDONTWRITEBYTECODE="1"))
         assert r.returncode == 0, f"{g}:\n{r.stdout}\n{r.stderr}"
-    made = sorted(os.path.basename(p) for p in glob.glob(str(tmp_path / "*.npz")))
-    committed = sorted(os.path.basename(p) for p in glob.glob(os.path.join(GOLDEN, "*.npz")))
+    made, committed = _fixtures(tmp_path), _fixtures(GOLDEN)
     assert made == committed, f"fixture files differ: only regenerated {set(made) - set(committed)}, only committed {set(committed) - set(made)}"
+    assert any(name.startswith("periodic" + os.sep) for name in committed)
     narrays = 0
     for name in committed:
         new, old = np.load(tmp_path / name, allow_pickle=False), np.load(os.path.join(GOLDEN, name), allow_pickle=False)
@@ -38,5 +46,8 @@ def test_generators_reproduce_every_committed_fixture(tmp_path):
             a, b = new[k], old[k]
             assert a.dtype == b.dtype and a.shape == b.shape, f"{name}[{k}]: dtype / shape"
             assert np.array_equal(a, b, equal_nan=a.dtype.kind == "f"), f"{name}[{k}] differs from the reference's output"
+            if a.dtype == np.float64 and os.path.dirname(name) in SUBDIRS:
+                assert np.array_equal(np.ascontiguousarray(a).view(np.int64), np.ascontiguousarray(b).view(np.int64)), \
+                    f"{name}[{k}]: a zero of the other sign"
             narrays += 1
-    assert narrays > 8000
+    assert narrays > 8000 + 150
