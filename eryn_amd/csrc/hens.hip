@@ -201,6 +201,7 @@ struct hens_ctx_impl {
         RjModel M{};                         // the model as the kernels see it (RjArgs::M)
         bool general = false;                // hens_rj_set_model_general: leaf widths other than 3 / no template likelihood - hens_rj_propose / _accept only
         bool wide = false;                   // hens_rj_set_model_kinds with a leaf kind beyond pulse / sine: the WIDE instantiations of k_rj
+        PriorTerm terms[RJ_MAX_BRANCH][RJ_MAX_ND] = {};        // hens_rj_set_prior_terms (M.prior_on): a branch's term per leaf parameter, supports in M.lo / hi
         double* t = nullptr; double* y = nullptr;              // [ndata] data of the template likelihood
         double* ctab = nullptr; int32_t* cbn = nullptr;        // RjArgs::ctab / cbn: what a lane needs about its record coordinate (rj_push_ctab)
         double* step = nullptr; double* u = nullptr; double* birth = nullptr;         // the caller's draws of a teacher-forced move (rj_ensure_staging)
@@ -1739,6 +1740,11 @@ int rj_push_ctab(hens_ctx_impl* c) {
                 if (c->rj.have_chol && d < RJ_ND)
                     for (int j = 0; j < RJ_ND; ++j) tab[RJ_CTAB_CHOL + j * RJ_MAX_RW + i] = c->rj.chol[b][d][j];
                 bn[i] = b | (n << 4) | (d << 10) | (M.kind[b] << 12) | ((M.slot0[b] + n) << 16);
+                if (M.prior_on) {                         // the coordinate's prior term record (hens_rj_set_prior_terms)
+                    const PriorTerm& t = c->rj.terms[b][d];
+                    tab[RJ_CTAB_C0 + i] = t.c0; tab[RJ_CTAB_C1 + i] = t.c1; tab[RJ_CTAB_C2 + i] = t.c2;
+                    bn[i] |= t.kind << 24;
+                }
             }
     int r;
     if (!c->rj.ctab) {
@@ -1842,7 +1848,9 @@ int rj_launch(hens_ctx_impl* c, const RjLaunch& l) {
         a.hq = c->rj.hq; a.hlogp = c->rj.hlogp; a.hfac = c->rj.hfac; a.hlu = c->rj.hlu; a.hmoved = c->rj.hmoved;
     }
     const bool chol = mode == RJ_MODE_MH && l.draws == RjLaunch::PHILOX && c->rj.have_chol && tmm != -2;
-    const bool wide = c->rj.wide && tmm != -2;        // (the proposal half of a host-callable move has the widths at run time already)
+    // (the proposal half of a host-callable move has the widths at run time already; a model under prior terms - pulses and sines
+    //  too - takes the WIDE instantiations, whose per-point leaf values serve every kind: the box instantiations carry no terms)
+    const bool wide = (c->rj.wide || c->rj.M.prior_on) && tmm != -2;
     const RjInst* inst = nullptr;
     for (const RjInst& i : RJ_INSTS)
         if (i.mode == mode && i.tmm == tmm && i.chol == chol && i.wide == wide) inst = &i;
@@ -2311,7 +2319,7 @@ int hens_set_prior_terms(hens_ctx* ctx, const int32_t* kind, const double* lo, c
     hens_ctx_impl* c = enter(ctx);
     if (!c || !kind || !lo || !hi || !c0 || !c1 || !c2) return fail(c, HENS_ERR_INVALID, "null argument");
     if (is_rj(c))
-        return fail(c, HENS_ERR_UNSUPPORTED, "prior terms are not built for leaf-packing records (leaves carry box priors: hens_rj_set_model)");
+        return fail(c, HENS_ERR_UNSUPPORTED, "hens_set_prior_terms describes one row of parameters: the leaves of a leaf-packing record take theirs through hens_rj_set_prior_terms");
     const int D = c->D;
     std::vector<PriorTerm> terms((size_t)D);
     bool box = true;
@@ -3853,6 +3861,7 @@ int hens_rj_set_mh_chol(hens_ctx* ctx, const double* chol) {
     if (const int rm = need_rj_model(c)) return rm;
     if (c->rj.general) return fail(c, HENS_ERR_STATE, "the Philox in-model move belongs to hens_rj_step: template models only");
     if (c->rj.wide) return fail(c, HENS_ERR_UNSUPPORTED, "full leaf covariances: models of pulses and sines only (diagonal steps: hens_rj_set_mh_scale)");
+    if (c->rj.M.prior_on) return fail(c, HENS_ERR_UNSUPPORTED, "full leaf covariances: not together with prior terms (hens_rj_set_prior_terms; diagonal steps: hens_rj_set_mh_scale)");
     for (int b = 0; b < c->rj.M.nb; ++b)
         for (int d = 0; d < RJ_ND; ++d)
             for (int j = 0; j < RJ_ND; ++j) {
@@ -3869,6 +3878,78 @@ int hens_rj_set_mh_chol(hens_ctx* ctx, const double* chol) {
     c->rj.have_scale = c->rj.have_chol = true;
     SETTLE(c, NEED_DEVICE);
     return rj_push_ctab(c);
+}
+
+// Per-parameter prior terms on the leaves of the model in place (any of the three hens_rj_set_model* calls): kind / lo / hi / c0 / c1 /
+// c2 run over the branches' leaf parameters one after the other (sum_b ndims[b] entries, as hens_rj_set_model_general takes lo / hi),
+// a term's meaning and constants are hens_set_prior_terms's.  The terms replace the model's box: the log-prior of a slot, the Hastings
+// factor -+ log q(leaf) of a birth / death and the distribution a leaf is born from (distgenrj.py:188-214) are all this prior.  An
+// all-uniform specification IS a box: it goes into M.lo / hi / leaf_logp and the context keeps the box's kernels.
+int hens_rj_set_prior_terms(hens_ctx* ctx, const int32_t* kind, const double* lo, const double* hi, const double* c0, const double* c1,
+                            const double* c2) {
+    hens_ctx_impl* c = enter(ctx);
+    if (!c || !kind || !lo || !hi || !c0 || !c1 || !c2) return fail(c, HENS_ERR_INVALID, "null argument");
+    if (const int rk = need_rj_context(c)) return rk;
+    if (const int rm = need_rj_model(c)) return rm;
+    if (c->rj.accept_pending) return fail(c, HENS_ERR_STATE, "hens_rj_accept must follow hens_rj_propose");
+    RjModel M = c->rj.M;
+    PriorTerm terms[RJ_MAX_BRANCH][RJ_MAX_ND] = {};
+    bool box = true;
+    int k = 0, slots = 0;
+    for (int b = 0; b < M.nb; ++b) {
+        double logp_box = 0.0;
+        slots += M.nl[b];
+        for (int d = 0; d < M.nd[b]; ++d, ++k) {
+            PriorTerm& t = terms[b][d];
+            if (kind[k] != HENS_PRIOR_UNIFORM && kind[k] != HENS_PRIOR_LOG_UNIFORM && kind[k] != HENS_PRIOR_NORMAL)
+                return fail(c, HENS_ERR_INVALID, "unknown prior kind %d (branch %d, parameter %d)", kind[k], b, d);
+            if (!(lo[k] < hi[k])) return fail(c, HENS_ERR_INVALID, "prior terms need lo < hi for every parameter (branch %d, parameter %d)", b, d);
+            if (!(std::fabs(c0[k]) < INFINITY)) return fail(c, HENS_ERR_INVALID, "prior term: c0 must be finite (branch %d, parameter %d)", b, d);
+            M.lo[b][d] = lo[k]; M.hi[b][d] = hi[k];
+            t.c0 = c0[k];
+            if (kind[k] == HENS_PRIOR_UNIFORM) {
+                if (!(std::fabs(lo[k]) < INFINITY) || !(std::fabs(hi[k]) < INFINITY))
+                    return fail(c, HENS_ERR_INVALID, "uniform prior term needs finite bounds (branch %d, parameter %d)", b, d);
+                t.kind = PRIOR_UNIFORM;
+                logp_box += c0[k];                                         // (prior.py:364-383: ascending, from 0.0)
+                continue;
+            }
+            box = false;
+            if (kind[k] == HENS_PRIOR_LOG_UNIFORM) {
+                if (!(lo[k] > 0.0) || !(hi[k] < INFINITY)) return fail(c, HENS_ERR_INVALID, "log-uniform prior term needs 0 < lo < hi < inf (branch %d, parameter %d)", b, d);
+                t.kind = PRIOR_LOG_UNIFORM;
+            } else {
+                if (!(c1[k] > 0.0) || !(c1[k] < INFINITY)) return fail(c, HENS_ERR_INVALID, "normal prior term needs a finite scale > 0 (branch %d, parameter %d)", b, d);
+                if (!(std::fabs(c2[k]) < INFINITY)) return fail(c, HENS_ERR_INVALID, "normal prior term: log(scale) must be finite (branch %d, parameter %d)", b, d);
+                t.kind = PRIOR_NORMAL;
+                t.c1 = c1[k]; t.c2 = c2[k];
+            }
+        }
+        M.leaf_logp[b] = logp_box;
+    }
+    if (!box) {
+        if (c->rj.have_chol) return fail(c, HENS_ERR_UNSUPPORTED, "prior terms: not together with full leaf covariances (hens_rj_set_mh_chol; diagonal steps: hens_rj_set_mh_scale)");
+        // (the instantiations that carry the terms index a record's slots and coordinates at run time: their limits)
+        if (slots > 64) return fail(c, HENS_ERR_UNSUPPORTED, "prior terms: %d leaf slots, at most 64 over all branches", slots);
+        if (c->D > RJ_MAX_RW) return fail(c, HENS_ERR_UNSUPPORTED, "prior terms: record width ndim = %d, at most %d doubles", c->D, RJ_MAX_RW);
+    }
+    SETTLE(c, NEED_DEVICE | NEED_FIELDS);
+    if (const int rd = rjchain_drop(c)) return rd;
+    M.prior_on = box ? 0 : 1;
+    if (M.prior_on) M.t_step64 = 0.0;          // (no uniform-grid form under terms: per-point leaf values)
+    // (a box of its own: the uniform-grid recurrences were admitted for the model's narrowest pulse, rj_set_template_model - a box
+    //  that lets |c| go below it takes the per-point form, which is right on every grid)
+    for (int b = 0; b < M.nb && M.t_step64 != 0.0; ++b)
+        if (M.kind[b] == RJ_KIND_PULSE) {
+            auto cmin = [](double l, double h) { return (l <= 0.0 && h >= 0.0) ? 0.0 : std::min(std::fabs(l), std::fabs(h)); };
+            if (cmin(M.lo[b][2], M.hi[b][2]) < cmin(c->rj.M.lo[b][2], c->rj.M.hi[b][2])) M.t_step64 = 0.0;
+        }
+    const RjModel before = c->rj.M;
+    c->rj.M = M;
+    memcpy(c->rj.terms, terms, sizeof(terms));
+    if (const int r = rj_push_ctab(c)) { c->rj.M = before; return r; }
+    c->rj.tm_valid = false;
+    return HENS_OK;
 }
 
 // ---- teacher-forced moves on leaf-packing records: the caller's draws (hens_rj_draws), the device's arithmetic ------------------
@@ -4528,6 +4609,7 @@ int hens_rj_debug_draws(hens_ctx* ctx, int64_t iter, double* step, double* u_mh,
     a.Tl = c->Tl; a.W = c->W; a.rung_begin = c->cfg.rung_begin; a.stretch = stretch ? 1 : 0;
     a.use_chol = c->rj.have_chol ? 1 : 0;
     memcpy(a.chol, c->rj.chol, sizeof(a.chol));
+    a.ctab = c->rj.ctab; a.cbn = c->rj.cbn;
     // "separate_branches" (and no birth / death move at all: what one WOULD draw): the chosen branch's draws; "iterate_branches",
     // "together": every branch's, in order (outputs [nbranches][...])
     const bool every = c->rj.schedule == 1 || c->rj.schedule == 2;

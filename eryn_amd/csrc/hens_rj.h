@@ -36,7 +36,13 @@ constexpr int RJ_MAX_ND = 4;
 #define RJ_CBN_KIND(v) (((v) >> 12) & 15)
 #define RJ_CBN_SLOT(v) ((v) >> 16)
 constexpr int RJ_CTAB_LO = 0, RJ_CTAB_HI = RJ_MAX_RW, RJ_CTAB_SCALE = 2 * RJ_MAX_RW, RJ_CTAB_LOGP = 3 * RJ_MAX_RW;     // RjArgs::ctab
-constexpr int RJ_CTAB_CHOL = 4 * RJ_MAX_RW, RJ_CTAB_ROWS = 7;          // rows 4 - 6: L[d][0 .. 2] of the coordinate's dimension d (hens_rj_set_mh_chol)
+constexpr int RJ_CTAB_CHOL = 4 * RJ_MAX_RW;                            // rows 4 - 6: L[d][0 .. 2] of the coordinate's dimension d (hens_rj_set_mh_chol)
+// rows 7 - 9: the coordinate's prior term record (hens_rj_set_prior_terms: PriorTerm::c0 / c1 / c2 of hens_kernels.h; its kind: RJ_CBN_PK,
+// its support: rows lo / hi) - read by the instantiations that serve prior-term models (RjModel::prior_on) only
+constexpr int RJ_CTAB_C0 = 7 * RJ_MAX_RW, RJ_CTAB_C1 = 8 * RJ_MAX_RW, RJ_CTAB_C2 = 9 * RJ_MAX_RW, RJ_CTAB_ROWS = 10;
+// (cbn under prior terms: the term's kind in bits 24 - 25, zero on a box model, so RJ_CBN_SLOT stays a plain shift for the box instantiations)
+#define RJ_CBN_PK(v) (((v) >> 24) & 3)
+#define RJ_CBN_SLOT8(v) (((v) >> 16) & 255)
 // leaf kinds (hens_rj_set_model_kinds; include/hipensemble.h HENS_RJ_KIND_*): value at data point t and parameters per leaf
 //   pulse (a, b, c) a exp(-(t - b)^2 / (2 c^2))   sine (a, b, c) a sin(2 pi b t + c)   offset (a) a   ramp (a, b) a + b t
 //   lorentz (a, b, c) a / (1 + ((t - b) / c)^2)   chirp (a, b, c) a sin(2 pi b t + c t^2)
@@ -58,7 +64,8 @@ struct RjModel {
     double t_step64;                                // the data points lie on a uniform grid: 64 grid steps (else 0), see k_rj
     // leaf parameters per branch, first leaf-slot number per branch, the widest branch (= the stride of the birth arrays): 3,
     // off / 3, 3 for the pulse / sine models; read by the host-likelihood (k_rj<MODE, -2>) and the WIDE instantiations only
-    int32_t nd[RJ_MAX_BRANCH], slot0[RJ_MAX_BRANCH], ndmax, pad_;
+    // prior_on: the leaf parameters carry prior terms (hens_rj_set_prior_terms) - the records in RjArgs::ctab rows 7 - 9, leaf_logp unused
+    int32_t nd[RJ_MAX_BRANCH], slot0[RJ_MAX_BRANCH], ndmax, prior_on;
 };
 
 struct RjArgs {
@@ -264,6 +271,25 @@ __device__ __forceinline__ double rj_birth_coord(uint64_t seed, uint64_t it, uin
     const u4 e = rj_philox(seed, it, wid, rj_birth_key(branch, d));
     return u01(e.x, e.y) * (hi - lo) + lo;
 }
+// ... from its prior term (hens_rj_set_prior_terms; the prior is the birth proposal, distgenrj.py:199-214) out of the same call's words:
+//   uniform      u (hi - lo) + lo, u = u01(x, y)                                                        (prior.py:60-66)
+//   log-uniform  exp(u (log b - log a) + log a), the same u                                             (scipy.stats.loguniform.rvs)
+//   normal       loc + scale z, z = sqrt(-2 log(r)) cos(2 pi v): Box-Muller in full double precision, r = 1 - u01(x, y) in (0, 1],
+//                v = u01(z, w); library log / sqrt / sincospi.  (Not the 32-bit-radius normals of the in-model step: this draw's density
+//                is the move's Hastings factor, and a 32-bit radius ends the tails at 6.7 sigma.)
+__device__ __forceinline__ double rj_birth_value(const u4 e, const int pk, const double lo, const double hi, const double c0, const double c1) {
+    const double u = u01(e.x, e.y);
+    if (pk == PRIOR_LOG_UNIFORM) {
+        const double la = log(lo);
+        return exp(u * (log(hi) - la) + la);
+    }
+    if (pk == PRIOR_NORMAL) {
+        double sn, cs;
+        sincospi(2.0 * u01(e.z, e.w), &sn, &cs);
+        return c0 + c1 * (sqrt(-2.0 * log(1.0 - u)) * cs);
+    }
+    return u * (hi - lo) + lo;
+}
 // accept uniform of the in-model (mode 1) / birth-death (mode 2) move: mh.py:157, rj.py:332
 __device__ __forceinline__ double rj_accept_uniform(uint64_t seed, uint64_t it, uint32_t wid, int mode, int branch) {
     const u4 d = rj_philox(seed, it, wid, rj_acc_key(mode, branch));
@@ -365,6 +391,29 @@ __global__ __launch_bounds__(RJ_WAVES * 64) __attribute__((amdgpu_waves_per_eu(R
     auto ndb = [&](const int b) { return GEN ? M.nd[b] : RJ_ND; };
     auto slot0 = [&](const int b) { return GEN ? M.slot0[b] : M.off[b] / RJ_ND; };
     const int bstride = GEN ? M.ndmax : RJ_ND;
+    // prior terms (hens_rj_set_prior_terms): a wave-uniform branch of the GEN instantiations, which serve every such model (pulse / sine
+    // models too: hens.hip rj_launch) - the box instantiations of the pulse / sine models carry none of it
+    const bool pri = GEN && M.prior_on != 0;
+    // log q(leaf) of branch B's leaf whose coordinate d is lane l0 + d's `v`: lane l0 + d forms prior_term(term_d, v) from the record of
+    // the branch's first leaf (a branch's terms are the same for every leaf), the sum is the log-prior phase's - ascending from 0.0,
+    // -inf if a coordinate is outside its support or a term non-finite - and comes back wave-uniform
+    auto leaf_logq = [&](const int B, const int l0, const double v) -> double {
+        const int d = lane - l0;
+        const bool mine = d >= 0 && d < ndb(B);
+        const int i = M.off[B] + (mine ? d : 0);
+        const PriorTerm tr{A.ctab[RJ_CTAB_C0 + i], A.ctab[RJ_CTAB_C1 + i], A.ctab[RJ_CTAB_C2 + i], RJ_CBN_PK(A.cbn[i]), 0};
+        const double lo = A.ctab[RJ_CTAB_LO + i], hi = A.ctab[RJ_CTAB_HI + i];
+        double t = 0.0;
+        bool bad = false;
+        if (mine) {
+            bad = !((v >= lo) && (v <= hi));
+            if (!bad) { t = prior_term(tr, v); bad = !(fabs(t) < INFINITY); }
+        }
+        if (__ballot(bad) != 0ull) return -INFINITY;
+        double s = 0.0;
+        for (int k = 0; k < ndb(B); ++k) s = s + __shfl(t, l0 + k);
+        return s;
+    };
     // stretch half-step: the walker at this position - the caller's list, or (production) the split permutation's: its round keys are
     // two Philox calls, lanes 0 and 1 one each, kept in scalar registers for the complements
     int st_walker = 0;
@@ -534,16 +583,35 @@ __global__ __launch_bounds__(RJ_WAVES * 64) __attribute__((amdgpu_waves_per_eu(R
         ch_sign[B] = c; ch_leaf[B] = lf;
         if (c < 0) {                                                  // death: factor +log q(leaf) (:188-197)
             mask_set(B, mask_of(B) & ~(1u << lf));
-            bool in = true;
-            for (int d = 0; d < ndb(B); ++d) {
-                const double v = cur[M.off[B] + lf * ndb(B) + d];
-                in = in && (v >= M.lo[B][d]) && (v <= M.hi[B][d]);
+            if (pri) {                                                // (the dying leaf's coordinates, from the record: lane d)
+                factors = factors + leaf_logq(B, 0, cur[M.off[B] + lf * ndb(B) + (lane < ndb(B) ? lane : 0)]);
+            } else {
+                bool in = true;
+                for (int d = 0; d < ndb(B); ++d) {
+                    const double v = cur[M.off[B] + lf * ndb(B) + d];
+                    in = in && (v >= M.lo[B][d]) && (v <= M.hi[B][d]);
+                }
+                factors = factors + (in ? M.leaf_logp[B] : -INFINITY);
             }
-            factors = factors + (in ? M.leaf_logp[B] : -INFINITY);
         } else if (c > 0) {                                           // birth from the prior: factor -log q(leaf) (:199-214)
             mask_set(B, mask_of(B) | (1u << lf));
             bool in = true;
-            if (A.birth) {
+            if (pri) {
+                // the born leaf from the caller (lane d) or from the branch's prior terms (lane 1 + d: the call above), its log-density
+                const int l0 = A.birth ? 0 : 1;
+                const int d = lane >= l0 && lane < l0 + ndb(B) ? lane - l0 : 0;
+                const bool mine = lane >= l0 && lane < l0 + ndb(B);
+                double v;
+                if (A.birth) {
+                    v = A.birth[(bo + (size_t)gw) * bstride + d];
+                } else {
+                    const int i = M.off[B] + d;
+                    v = rj_birth_value(dr_bd, RJ_CBN_PK(A.cbn[i]), A.ctab[RJ_CTAB_LO + i], A.ctab[RJ_CTAB_HI + i], A.ctab[RJ_CTAB_C0 + i],
+                                       A.ctab[RJ_CTAB_C1 + i]);
+                }
+                if (mine) q[M.off[B] + lf * ndb(B) + d] = v;
+                factors = factors - leaf_logq(B, l0, v);
+            } else if (A.birth) {
                 for (int d = 0; d < ndb(B); ++d) {
                     const double v = A.birth[(bo + (size_t)gw) * bstride + d];
                     in = in && (v >= M.lo[B][d]) && (v <= M.hi[B][d]);
@@ -560,7 +628,7 @@ __global__ __launch_bounds__(RJ_WAVES * 64) __attribute__((amdgpu_waves_per_eu(R
                 in = __ballot(mine && !((v >= lo) && (v <= hi))) == 0ull;
                 if (mine) q[M.off[B] + lf * ndb(B) + d] = v;
             }
-            factors = factors - (in ? M.leaf_logp[B] : -INFINITY);
+            if (!pri) factors = factors - (in ? M.leaf_logp[B] : -INFINITY);
         }
         if (!(M.nlmin[B] == M.nl[B] || M.nlmin[B] + 1 == M.nl[B])) {  // edge factors (rj.py:236-270)
             const int nnew = __builtin_popcount(mask_of(B));
@@ -580,7 +648,61 @@ __global__ __launch_bounds__(RJ_WAVES * 64) __attribute__((amdgpu_waves_per_eu(R
     // ---- log-prior over the leaf slots (ensemble.py:1189-1210): dead slots count 0.0, NumPy's sum order per branch ------
     double logp = 0.0;
     int total_leaves = 0;
-    {
+    if (pri) {
+        // prior terms: the lane of coordinate i forms prior_term(term_i, q[i]) of an active slot inside its support (the record: one
+        // coalesced load per field out of RjArgs::ctab) and leaves it in LDS; a non-finite term - a normal coordinate whose y y
+        // overflows - counts as outside, as in k_stretch_prior.  The lane of a slot's first coordinate adds the slot's terms in
+        // ascending order from 0.0 (prior.py:364-383); a dead slot counts 0.0 and none of its coordinates is evaluated.
+        if constexpr (GEN) {
+            __shared__ double s_term[RJ_WAVES][RJ_MAX_RW];
+            double* tv = s_term[wv];
+            uint64_t outb[2];
+            int bn2[2];
+#pragma unroll
+            for (int p = 0; p < 2; ++p) {
+                const int i = p * 64 + lane;
+                bool outside = false;
+                bn2[p] = 0;
+                if (i < M.ind_off) {
+                    const int bn = p == 0 ? c_bn : A.cbn[i];
+                    const double lo = p == 0 ? c_lo : A.ctab[RJ_CTAB_LO + i], hi = p == 0 ? c_hi : A.ctab[RJ_CTAB_HI + i];
+                    const PriorTerm tr{A.ctab[RJ_CTAB_C0 + i], A.ctab[RJ_CTAB_C1 + i], A.ctab[RJ_CTAB_C2 + i], RJ_CBN_PK(bn), 0};
+                    bn2[p] = bn;
+                    double t = 0.0;
+                    if ((mask_of(RJ_CBN_B(bn)) >> RJ_CBN_N(bn)) & 1u) {
+                        const double x = q[i];
+                        outside = !((x >= lo) && (x <= hi));
+                        if (!(fabs(x) < INFINITY)) atomicOr(A.flags, FLAG_NONFINITE_X);
+                        if (!outside) { t = prior_term(tr, x); outside = !(fabs(t) < INFINITY); }
+                    }
+                    tv[i] = t;
+                }
+                outb[p] = __ballot(outside);
+            }
+            RJ_LDS_SYNC();
+#pragma unroll
+            for (int p = 0; p < 2; ++p) {
+                const int i = p * 64 + lane;
+                if (i < M.ind_off && RJ_CBN_D(bn2[p]) == 0) {
+                    const int b = RJ_CBN_B(bn2[p]), nd = M.nd[b];
+                    const uint64_t w0 = p == 0 ? outb[0] : outb[1], w1 = p == 0 ? outb[1] : 0ull;
+                    const uint32_t o3 = (uint32_t)((w0 >> lane) | (lane > 60 ? w1 << (64 - lane) : 0ull)) & ((1u << nd) - 1u);
+                    const bool active = (mask_of(b) >> RJ_CBN_N(bn2[p])) & 1u;
+                    double sv = 0.0;
+                    if (active) {
+                        if (o3) sv = -INFINITY;
+                        else for (int d = 0; d < nd; ++d) sv = sv + tv[i + d];
+                    }
+                    leafv[RJ_CBN_SLOT8(bn2[p])] = sv;
+                }
+            }
+            RJ_LDS_SYNC();
+            for (int b = 0; b < M.nb; ++b) {
+                logp = logp + numpy_sum(leafv + slot0(b), M.nl[b]);
+                total_leaves += __builtin_popcount(mask_of(b));
+            }
+        }
+    } else {
         // a lane per COORDINATE tests its box (bounds out of RjArgs::ctab), a ballot collects the "outside" bits; a lane per leaf
         // SLOT turns its three bits into the slot's term - 0.0 dead, the branch's constant log-density, -inf outside - and the
         // terms are summed branch by branch out of LDS in NumPy's order
@@ -1029,6 +1151,7 @@ struct RjDebugArgs {
     int32_t stretch;     // the in-model move is the stretch move: step / u_mh are zeros (its draws: k_rj_debug_stretch)
     int32_t use_chol;    // hens_rj_set_mh_chol: step_d = sum_{j <= d} chol[b][d][j] z_j, ascending j
     double chol[RJ_MAX_BRANCH][RJ_ND][RJ_ND];
+    const double* ctab; const int32_t* cbn;      // RjArgs::ctab / cbn: the prior term records of a model under hens_rj_set_prior_terms
 };
 __global__ void k_rj_debug_draws(const RjDebugArgs A) {
     const int64_t gw = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1057,8 +1180,17 @@ __global__ void k_rj_debug_draws(const RjDebugArgs A) {
     const u4 d = rj_bd_raw(A.seed, A.iter, wid, A.branch);
     A.coin[gw] = (d.x & 1u) ? +1 : -1;
     A.sel[gw] = d.y;
-    for (int k = 0; k < M.ndmax; ++k)
-        A.birth[(size_t)gw * M.ndmax + k] = k < M.nd[A.branch] ? rj_birth_coord(A.seed, A.iter, wid, A.branch, k, M.lo[A.branch][k], M.hi[A.branch][k]) : 0.0;
+    for (int k = 0; k < M.ndmax; ++k) {
+        double v = 0.0;
+        if (k < M.nd[A.branch] && M.prior_on) {             // (k_rj's own function on the same words and record)
+            const int i = M.off[A.branch] + k;
+            v = rj_birth_value(rj_philox(A.seed, A.iter, wid, rj_birth_key(A.branch, k)), RJ_CBN_PK(A.cbn[i]), A.ctab[RJ_CTAB_LO + i],
+                               A.ctab[RJ_CTAB_HI + i], A.ctab[RJ_CTAB_C0 + i], A.ctab[RJ_CTAB_C1 + i]);
+        } else if (k < M.nd[A.branch]) {
+            v = rj_birth_coord(A.seed, A.iter, wid, A.branch, k, M.lo[A.branch][k], M.hi[A.branch][k]);
+        }
+        A.birth[(size_t)gw * M.ndmax + k] = v;
+    }
     A.u_bd[gw] = rj_accept_uniform(A.seed, A.iter, wid, RJ_MODE_BD, A.acc_branch);
 }
 

@@ -25,42 +25,60 @@ _KINDS = {**{k: v[0] for k, v in LEAF_KINDS.items()}, "gauss": KIND_PULSE, **{v[
 _WIDTH = {v[0]: v[1] for v in LEAF_KINDS.values()}
 
 
+def _leaf_prior(branch, box):
+    """The prior of one leaf, from ``box`` - a list of (lo, hi) per leaf parameter - or, in its place, an
+    ``eryn_amd.prior.ProbDistContainer`` or anything it accepts (a dict of distributions, frozen SciPy ``uniform`` / ``loguniform`` /
+    ``norm`` among them).  Sets ``lo`` / ``hi`` (the inclusive supports), ``terms`` (the arguments of hens_rj_set_prior_terms for this
+    branch), ``prior`` (the container, None for a box), ``is_box`` and - all-uniform branches - ``leaf_logp``, the constant leaf
+    log-density (None otherwise: the density is no constant)."""
+    from .prior import ProbDistContainer
+    if isinstance(box, dict):
+        box = ProbDistContainer(box)
+    if isinstance(box, ProbDistContainer):
+        branch.prior, branch.terms = box, box.prior_terms()
+        branch.lo, branch.hi = f64(branch.terms["lo"]), f64(branch.terms["hi"])
+    else:
+        branch.prior = None
+        branch.lo = f64([b[0] for b in box])
+        branch.hi = f64([b[1] for b in box])
+        n = branch.lo.shape[0]
+        branch.terms = dict(kind=np.zeros(n, dtype=np.int32), lo=branch.lo, hi=branch.hi, c0=f64(np.log(1 / (branch.hi - branch.lo))),
+                            c1=np.zeros(n), c2=np.zeros(n))
+    branch.is_box = bool(np.all(branch.terms["kind"] == _lib.PRIOR_UNIFORM))
+    branch.leaf_logp = None
+    if branch.is_box:
+        acc = np.zeros(1)                      # prior.py:364-383: sequential ``prior_vals += temp`` from 0.0
+        for d in range(branch.lo.shape[0]):
+            acc += np.log(1 / (branch.hi[d] - branch.lo[d]))
+        branch.leaf_logp = float(acc[0])
+
+
 class TemplateBranch:
     """One model type: leaf kind (a name of LEAF_KINDS; "gauss" is "pulse"), a uniform box per leaf parameter - as many as the kind
-    has -, leaf budget."""
+    has - or a prior container in its place (``_leaf_prior``: uniform, log-uniform and normal parameters), leaf budget."""
 
     def __init__(self, name, kind, box, nleaves_max, nleaves_min=0):
         self.name, self.kind = str(name), _KINDS[kind]
-        self.lo = f64([b[0] for b in box])
-        self.hi = f64([b[1] for b in box])
+        _leaf_prior(self, box)
         self.ndim = _WIDTH[self.kind]
         if self.lo.shape != (self.ndim,):
             raise ValueError(f"a leaf of this kind has {self.ndim} parameter{'s' if self.ndim != 1 else ''}: a box of {self.lo.shape[0]}")
         self.nleaves_max, self.nleaves_min = int(nleaves_max), int(nleaves_min)
-        acc = np.zeros(1)                      # prior.py:364-383: sequential ``prior_vals += temp`` from 0.0
-        for d in range(self.ndim):
-            acc += np.log(1 / (self.hi[d] - self.lo[d]))
-        self.leaf_logp = float(acc[0])
 
 
 class LeafBranch:
     """One model type WITHOUT a device likelihood (round 6): a uniform box per leaf parameter - 1 to 4 of them, the reference's
-    ``ndims[name]`` (ensemble.py:325-329) - and a leaf budget.  For chains whose likelihood is the caller's Python function
-    (CallableLikelihood, hens_rj_set_model_general)."""
+    ``ndims[name]`` (ensemble.py:325-329) - or a prior container in its place (``_leaf_prior``), and a leaf budget.  For chains whose
+    likelihood is the caller's Python function (CallableLikelihood, hens_rj_set_model_general)."""
     kind = 0
 
     def __init__(self, name, box, nleaves_max, nleaves_min=0):
         self.name = str(name)
-        self.lo = f64([b[0] for b in box])
-        self.hi = f64([b[1] for b in box])
+        _leaf_prior(self, box)
         self.ndim = int(self.lo.shape[0])
         if not 1 <= self.ndim <= 4:
             raise NotImplementedError("a leaf has 1 to 4 parameters")
         self.nleaves_max, self.nleaves_min = int(nleaves_max), int(nleaves_min)
-        acc = np.zeros(1)                      # prior.py:364-383: sequential ``prior_vals += temp`` from 0.0
-        for d in range(self.ndim):
-            acc += np.log(1 / (self.hi[d] - self.lo[d]))
-        self.leaf_logp = float(acc[0])
 
 
 class _TemplateLikelihood:
@@ -182,14 +200,18 @@ class RJEngine(ChainStoreCalls):
         kinds = np.array([b.kind for b in self.branches], dtype=np.int32)
         nlmax = np.array([b.nleaves_max for b in self.branches], dtype=np.int32)
         nlmin = np.array([b.nleaves_min for b in self.branches], dtype=np.int32)
-        lp = f64([b.leaf_logp for b in self.branches])
+        # a branch with a prior term other than uniform: the model is set with a stand-in box (the terms' supports where they are
+        # finite) and hens_rj_set_prior_terms replaces it; all-uniform branches ARE boxes and never reach that call
+        self.prior_terms = any(not b.is_box for b in self.branches)
+        lp = f64([0.0 if b.leaf_logp is None else b.leaf_logp for b in self.branches])
         self.wide = False
         if self.general:
             nds = np.array([b.ndim for b in self.branches], dtype=np.int32)
-            lo, hi = f64(np.concatenate([b.lo for b in self.branches])), f64(np.concatenate([b.hi for b in self.branches]))
+            lo, hi = self._stand_in_box()
             check(self.lib.hens_rj_set_model_general(self.ctx, nb, ptr(nds), ptr(nlmax), ptr(nlmin), ptr(lo), ptr(hi), ptr(lp)), self.ctx)
+            self._set_prior_terms()
             return
-        lo, hi = f64(np.concatenate([b.lo for b in self.branches])), f64(np.concatenate([b.hi for b in self.branches]))
+        lo, hi = self._stand_in_box()
         t, y = f64(t), f64(y)
         if t.shape != y.shape or t.ndim != 1:
             raise ValueError("t and y must be 1-D arrays of the same length")
@@ -197,6 +219,19 @@ class RJEngine(ChainStoreCalls):
         set_model = self.lib.hens_rj_set_model_kinds if (self.wide if kinds_entry is None else kinds_entry) else self.lib.hens_rj_set_model
         check(set_model(self.ctx, nb, ptr(kinds), ptr(nlmax), ptr(nlmin), ptr(lo), ptr(hi), ptr(lp),
                         int(t.shape[0]), ptr(t), ptr(y), float(sigma)), self.ctx)
+        self._set_prior_terms()
+
+    def _stand_in_box(self):
+        lo, hi = np.concatenate([b.lo for b in self.branches]), np.concatenate([b.hi for b in self.branches])
+        return f64(np.where(np.isfinite(lo), lo, -1.0)), f64(np.where(np.isfinite(hi), hi, 1.0))      # (a normal parameter's support is the line)
+
+    def _set_prior_terms(self):
+        if not self.prior_terms:
+            return
+        tm = {k: np.ascontiguousarray(np.concatenate([b.terms[k] for b in self.branches]), dtype=(np.int32 if k == "kind" else np.float64))
+              for k in ("kind", "lo", "hi", "c0", "c1", "c2")}
+        check(self.lib.hens_rj_set_prior_terms(self.ctx, ptr(tm["kind"]), ptr(tm["lo"]), ptr(tm["hi"]), ptr(tm["c0"]), ptr(tm["c1"]),
+                                               ptr(tm["c2"])), self.ctx)
 
     def close(self):
         self.eng.close()
@@ -362,6 +397,8 @@ class RJEngine(ChainStoreCalls):
         with a leaf kind beyond pulse / sine -> NotImplementedError."""
         if self.wide:
             raise NotImplementedError("full leaf covariances: models of pulses and sines only (diagonal steps: set_mh_scale)")
+        if self.prior_terms:
+            raise NotImplementedError("full leaf covariances: not with log-uniform / normal leaf priors (diagonal steps: set_mh_scale)")
         L = f64(chol, (len(self.branches), 3, 3))
         check(self.lib.hens_rj_set_mh_chol(self.ctx, ptr(L)), self.ctx)
 
@@ -599,7 +636,13 @@ class RJEnsembleSampler:
                   runs in front of the copy, so a stored ``State.log_like`` is exactly what the device continues with and a chain
                   resumed from it is the uninterrupted chain bit for bit).  Consequence: WHERE the re-evaluations fall depends
                   on ``store`` / ``thin_by``, so two runs that differ only in those agree to rounding (log-likelihoods to ~1e-13
-                  relative), not bit for bit - as two reference runs with a different likelihood summation order would."""
+                  relative), not bit for bit - as two reference runs with a different likelihood summation order would.
+
+    priors: per branch a ``ProbDistContainer`` or the dict it is made of - ``uniform_dist``, ``log_uniform``, ``NormalDistribution`` or
+    the frozen SciPy ``uniform`` / ``loguniform`` / ``norm`` per leaf parameter (prior.py:219-392).  The prior is also the birth
+    proposal (distgenrj.py:188-214): log-prior, the factor -+ log q(leaf) and the born leaf's draw all follow it in both ``rng`` modes
+    (include/hipensemble.h: hens_rj_set_prior_terms); with a log-uniform or normal parameter the Philox Gaussian move takes diagonal
+    covariances only."""
 
     def __init__(self, nwalkers, ndims, log_like_fn, priors, tempering_kwargs=None, nbranches=None, branch_names=None,
                  nleaves_max=None, nleaves_min=None, moves=None, rj_moves="separate_branches", rng="numpy", seed=None,
@@ -607,6 +650,7 @@ class RJEnsembleSampler:
                  backend=None, **unused):
         from .backend import RJDeviceBackend
         from .moves.tempering import TemperatureControl
+        from .prior import ProbDistContainer
         # backend: None - the stored steps are a list of States (``self.chain``) - or an eryn_amd.backend.RJDeviceBackend: they stay
         # in device memory until somebody reads them (one device call per chain segment, hens_rj_step_chain)
         if backend is not None and not isinstance(backend, RJDeviceBackend):
@@ -653,15 +697,23 @@ class RJEnsembleSampler:
             if isinstance(moves, GaussianLeafMove) and moves.cov[k].shape != (nd, nd):
                 raise ValueError(f"branch {k}: the proposal covariance must be {nd} x {nd}")
             pr = priors[k]
-            box = pr.box_bounds() if hasattr(pr, "box_bounds") else \
-                ([pr[i].min_val for i in range(nd)], [pr[i].max_val for i in range(nd)])
-            if len(box[0]) != nd:
-                raise ValueError(f"branch {k}: {len(box[0])} prior boxes for ndims = {nd}")
-            if self.host_like is not None:     # (no device likelihood: 1 .. 4 parameters per leaf, hens_rj_set_model_general)
-                self.branches.append(LeafBranch(k, list(zip(box[0], box[1])), self.nleaves_max[k], self.nleaves_min[k]))
+            # a container (or the dict it is made of) with a log-uniform or normal parameter goes to the branch as it is; boxes as ever
+            if isinstance(pr, dict) and not all(hasattr(pr.get(i), "min_val") for i in range(nd)):
+                pr = ProbDistContainer(pr)
+            if isinstance(pr, ProbDistContainer) and not pr.is_box:
+                if pr.ndim != nd:
+                    raise ValueError(f"branch {k}: {pr.ndim} prior distributions for ndims = {nd}")
+                leaf_prior = pr
             else:
-                self.branches.append(TemplateBranch(k, log_like_fn.kinds[k], list(zip(box[0], box[1])), self.nleaves_max[k],
-                                                    self.nleaves_min[k]))
+                box = pr.box_bounds() if hasattr(pr, "box_bounds") else \
+                    ([pr[i].min_val for i in range(nd)], [pr[i].max_val for i in range(nd)])
+                if len(box[0]) != nd:
+                    raise ValueError(f"branch {k}: {len(box[0])} prior boxes for ndims = {nd}")
+                leaf_prior = list(zip(box[0], box[1]))
+            if self.host_like is not None:     # (no device likelihood: 1 .. 4 parameters per leaf, hens_rj_set_model_general)
+                self.branches.append(LeafBranch(k, leaf_prior, self.nleaves_max[k], self.nleaves_min[k]))
+            else:
+                self.branches.append(TemplateBranch(k, log_like_fn.kinds[k], leaf_prior, self.nleaves_max[k], self.nleaves_min[k]))
         total_ndim = sum(self.nleaves_max[k] * self.ndims[k] for k in self.branch_names)     # ensemble.py:325-329
         tk = dict(tempering_kwargs or {})
         if not tk:
@@ -687,6 +739,8 @@ class RJEnsembleSampler:
                 self.engine.set_mh_scale([np.sqrt(np.diag(moves.cov[k])) for k in self.branch_names])
             elif self.engine.wide:
                 raise NotImplementedError("rng='philox' with a leaf kind beyond pulse / sine: diagonal proposal covariances only")
+            elif self.engine.prior_terms:
+                raise NotImplementedError("rng='philox' with log-uniform / normal leaf priors: diagonal proposal covariances only")
             else:
                 self.engine.set_mh_chol(np.stack([np.linalg.cholesky(moves.cov[k]) for k in self.branch_names]))
         moves.accepted = np.zeros((self.ntemps, self.nwalkers))
@@ -819,7 +873,10 @@ class RJEnsembleSampler:
     def _draw_births(b, nbirth):
         draws = np.zeros((nbirth, b.ndim))
         for d in range(b.ndim):                                                 # ProbDistContainer.rvs: GLOBAL stream, per parameter
-            draws[:, d] = np.random.rand(nbirth) * (b.hi[d] - b.lo[d]) + b.lo[d]          # prior.py:60-66, 432-497
+            if b.prior is not None:            # the parameter's own distribution (SciPy's rvs bit for bit: eryn_amd.prior)
+                draws[:, d] = b.prior.dists[d].rvs(nbirth)
+            else:
+                draws[:, d] = np.random.rand(nbirth) * (b.hi[d] - b.lo[d]) + b.lo[d]      # prior.py:60-66, 432-497
         return draws
 
     def _bd_numpy(self, bi):

@@ -116,7 +116,7 @@ int hens_set_prior_box(hens_ctx* ctx, const double* lo, const double* hi, double
  *   launches, then the cascade and the adaptation as kernels of their own), hens_accept_split's decision kernel; the record /
  *   one-launch / persistent kernels are not used.  A normal term that is not finite (|q - loc| beyond about 1e154 scales: y y
  *   overflows) counts as outside the support: log-prior -inf, the likelihood skipped and filled.  Refused on a
- *   leaf-packing context (HENS_ERR_UNSUPPORTED) and on a rank of the ladder pipeline (HENS_ERR_STATE; hens_pipe_init
+ *   leaf-packing context (HENS_ERR_UNSUPPORTED: its leaves take their terms through hens_rj_set_prior_terms) and on a rank of the ladder pipeline (HENS_ERR_STATE; hens_pipe_init
  *   after it: HENS_ERR_UNSUPPORTED).  hens_set_prior_box afterwards returns the context to the box. */
 typedef enum hens_prior_kind {
     HENS_PRIOR_UNIFORM = 0,
@@ -619,6 +619,29 @@ int hens_rj_set_mh_scale(hens_ctx* ctx, const double* scale);
  * hens_rj_debug_draws exports the correlated step.  Entries above the diagonal must be zero; a non-finite entry or a diagonal
  * entry <= 0 (the covariance was not positive definite) -> HENS_ERR_INVALID.  The last of the two setters called holds. */
 int hens_rj_set_mh_chol(hens_ctx* ctx, const double* chol);
+/* Per-parameter prior terms on the leaves: ProbDistContainer({i: dist_i}) per branch with uniform, log-uniform and normal
+ * distributions (prior.py:337-392) in place of the box of the hens_rj_set_model* call that came before.  kind / lo / hi / c0 / c1 /
+ * c2 run over the branches' leaf parameters one after the other (sum_b ndims[b] entries, as hens_rj_set_model_general takes lo /
+ * hi); a term's meaning and constants are hens_set_prior_terms's.  On a leaf-packing chain the prior enters three times, and all
+ * three follow the terms:
+ *   log-prior      per active slot ((0.0 + t_0) + t_1) + ... in ascending parameter order, -inf if a parameter is outside its
+ *                  support or a term is not finite; dead slots count 0.0 and are not evaluated; slots and branches summed as ever
+ *   Hastings       a death adds, a birth subtracts log q(leaf): the same sum on the dying / born leaf (distgenrj.py:188-214)
+ *   births         hens_rj_step draws parameter d of a born leaf from the Philox call keyed (branch, d), words (x, y, z, w):
+ *                  uniform u (hi - lo) + lo; log-uniform exp(u (log hi - log lo) + log lo), u = the 53-bit uniform of (x, y);
+ *                  normal c0 + c1 sqrt(-2 log(1 - u)) cos(2 pi v), v the 53-bit uniform of (z, w): Box-Muller in double precision.
+ *                  hens_rj_debug_draws exports them.  Teacher-forced moves take the caller's `birth` as before.
+ * Every entry point that computes a log-prior on records follows: hens_eval_state, hens_rj_step / hens_rj_step_chain (every
+ * schedule, both in-model moves), the parity moves, hens_rj_propose / hens_rj_accept.  A model with a term other than uniform
+ * runs on the kernels that read leaf widths at run time (a pulse / sine model too: per-point leaf values, as under
+ * hens_rj_set_model_kinds - no uniform-grid recurrence), so its limits are theirs: 64 leaf slots, 128 record doubles
+ * (HENS_ERR_UNSUPPORTED beyond).  Uniform kinds only: the call IS the box lo / hi with leaf_logp[b] = the branch's c0 summed
+ * in ascending order - same kernels, same chain as that box model.  HENS_ERR_STATE on another context or before a model;
+ * HENS_ERR_INVALID for an unknown kind, lo >= hi, a non-finite constant, scale <= 0, a log-uniform term without 0 < lo < hi <
+ * inf; HENS_ERR_UNSUPPORTED together with full leaf covariances (hens_rj_set_mh_chol, in either order).  A refused call changes
+ * nothing.  A later hens_rj_set_model* call returns to that model's box. */
+int hens_rj_set_prior_terms(hens_ctx* ctx, const int32_t* kind, const double* lo, const double* hi, const double* c0,
+                            const double* c1, const double* c2);
 int hens_rj_mh_step(hens_ctx* ctx, const double* step, const double* u_acc, uint8_t* keep_out);
 int hens_rj_bd_step(hens_ctx* ctx, int32_t branch, const int8_t* change, const int32_t* leaf, const double* birth,
                     const double* u_acc, uint8_t* keep_out);
