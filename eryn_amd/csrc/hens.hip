@@ -2313,7 +2313,10 @@ int hens_set_prior_box(hens_ctx* ctx, const double* lo, const double* hi, double
     return HENS_OK;
 }
 
-// prior.py:337-392 with one distribution per parameter (include/hipensemble.h); uniform kinds only: hens_set_prior_box itself
+// prior.py:337-392 with one distribution per parameter (include/hipensemble.h); uniform kinds only: hens_set_prior_box itself.
+// Every term is read by hens_prior_host.h's parse_term, here and in hens_rj_set_prior_terms; a refusal is its reason and this place.
+static_assert(HENS_PRIOR_UNIFORM == PRIOR_UNIFORM && HENS_PRIOR_LOG_UNIFORM == PRIOR_LOG_UNIFORM && HENS_PRIOR_NORMAL == PRIOR_NORMAL,
+              "parse_term takes the caller's kinds as they are");
 int hens_set_prior_terms(hens_ctx* ctx, const int32_t* kind, const double* lo, const double* hi, const double* c0, const double* c1,
                          const double* c2) {
     hens_ctx_impl* c = enter(ctx);
@@ -2322,42 +2325,16 @@ int hens_set_prior_terms(hens_ctx* ctx, const int32_t* kind, const double* lo, c
         return fail(c, HENS_ERR_UNSUPPORTED, "hens_set_prior_terms describes one row of parameters: the leaves of a leaf-packing record take theirs through hens_rj_set_prior_terms");
     const int D = c->D;
     std::vector<PriorTerm> terms((size_t)D);
-    bool box = true;
-    double logp_box = 0.0;
-    for (int d = 0; d < D; ++d) {
-        PriorTerm& t = terms[(size_t)d];
-        t = PriorTerm{};
-        if (kind[d] != HENS_PRIOR_UNIFORM && kind[d] != HENS_PRIOR_LOG_UNIFORM && kind[d] != HENS_PRIOR_NORMAL)
-            return fail(c, HENS_ERR_INVALID, "unknown prior kind %d (dim %d)", kind[d], d);
-        if (!(lo[d] < hi[d])) return fail(c, HENS_ERR_INVALID, "prior terms need lo < hi in every dimension (dim %d)", d);
-        if (kind[d] == HENS_PRIOR_UNIFORM) {
-            const bool pad = lo[d] == -INFINITY && hi[d] == INFINITY;      // (hens_config::ndim_active: no term)
-            if (!pad && !(std::fabs(c0[d]) < INFINITY)) return fail(c, HENS_ERR_INVALID, "uniform prior term: c0 must be finite (dim %d)", d);
-            t.kind = pad ? PRIOR_NONE : PRIOR_UNIFORM;
-            t.c0 = pad ? 0.0 : c0[d];
-            if (!pad) logp_box += c0[d];                                   // (prior.py:364-383: ascending, from 0.0)
-            continue;
-        }
-        box = false;
-        if (kind[d] == HENS_PRIOR_LOG_UNIFORM) {
-            if (!(lo[d] > 0.0) || !(hi[d] < INFINITY)) return fail(c, HENS_ERR_INVALID, "log-uniform prior term needs 0 < lo < hi < inf (dim %d)", d);
-            if (!(std::fabs(c0[d]) < INFINITY)) return fail(c, HENS_ERR_INVALID, "log-uniform prior term: c0 must be finite (dim %d)", d);
-            t.kind = PRIOR_LOG_UNIFORM;
-            t.c0 = c0[d];
-        } else {
-            if (!(c1[d] > 0.0) || !(c1[d] < INFINITY)) return fail(c, HENS_ERR_INVALID, "normal prior term needs a finite scale > 0 (dim %d)", d);
-            if (!(std::fabs(c0[d]) < INFINITY) || !(std::fabs(c2[d]) < INFINITY))
-                return fail(c, HENS_ERR_INVALID, "normal prior term: loc and log(scale) must be finite (dim %d)", d);
-            t.kind = PRIOR_NORMAL;
-            t.c0 = c0[d]; t.c1 = c1[d];
-            t.c2 = c2[d];
-        }
+    for (int d = 0; d < D; ++d) {                  // (a (-inf, +inf) uniform term: the pad of hens_config::ndim_active)
+        const ParsedTerm p = parse_term(kind[d], lo[d], hi[d], c0[d], c1[d], c2[d], /*admit_pad=*/true);
+        if (p.why[0]) return fail(c, HENS_ERR_INVALID, "%s (dim %d)", p.why, d);
+        terms[(size_t)d] = p.term;
     }
-    if (box) return hens_set_prior_box(ctx, lo, hi, logp_box);
+    const PriorBox box = fold_box(terms.data(), D);
+    if (box.box) return hens_set_prior_box(ctx, lo, hi, box.logp);
     if (c->pipe.on) return fail(c, HENS_ERR_STATE, "prior terms are not built for a rank of the ladder pipeline");
     if (c->expect_split != 0 || c->propose_pending) return fail(c, HENS_ERR_STATE, "a half-step is pending");
     SETTLE(c, NEED_DEVICE | NEED_FIELDS | NEED_LADDER);
-    static_assert(sizeof(PriorTerm) == 32, "PriorTerm: four doubles' worth");
     if (!c->prior_buf) {
         PriorTerm* buf = nullptr;
         const int r = dalloc(c, &buf, (size_t)D);
@@ -3897,35 +3874,16 @@ int hens_rj_set_prior_terms(hens_ctx* ctx, const int32_t* kind, const double* lo
     bool box = true;
     int k = 0, slots = 0;
     for (int b = 0; b < M.nb; ++b) {
-        double logp_box = 0.0;
         slots += M.nl[b];
-        for (int d = 0; d < M.nd[b]; ++d, ++k) {
-            PriorTerm& t = terms[b][d];
-            if (kind[k] != HENS_PRIOR_UNIFORM && kind[k] != HENS_PRIOR_LOG_UNIFORM && kind[k] != HENS_PRIOR_NORMAL)
-                return fail(c, HENS_ERR_INVALID, "unknown prior kind %d (branch %d, parameter %d)", kind[k], b, d);
-            if (!(lo[k] < hi[k])) return fail(c, HENS_ERR_INVALID, "prior terms need lo < hi for every parameter (branch %d, parameter %d)", b, d);
-            if (!(std::fabs(c0[k]) < INFINITY)) return fail(c, HENS_ERR_INVALID, "prior term: c0 must be finite (branch %d, parameter %d)", b, d);
+        for (int d = 0; d < M.nd[b]; ++d, ++k) {       // (no pads in a record: a uniform term has finite bounds)
+            const ParsedTerm p = parse_term(kind[k], lo[k], hi[k], c0[k], c1[k], c2[k], /*admit_pad=*/false);
+            if (p.why[0]) return fail(c, HENS_ERR_INVALID, "%s (branch %d, parameter %d)", p.why, b, d);
+            terms[b][d] = p.term;
             M.lo[b][d] = lo[k]; M.hi[b][d] = hi[k];
-            t.c0 = c0[k];
-            if (kind[k] == HENS_PRIOR_UNIFORM) {
-                if (!(std::fabs(lo[k]) < INFINITY) || !(std::fabs(hi[k]) < INFINITY))
-                    return fail(c, HENS_ERR_INVALID, "uniform prior term needs finite bounds (branch %d, parameter %d)", b, d);
-                t.kind = PRIOR_UNIFORM;
-                logp_box += c0[k];                                         // (prior.py:364-383: ascending, from 0.0)
-                continue;
-            }
-            box = false;
-            if (kind[k] == HENS_PRIOR_LOG_UNIFORM) {
-                if (!(lo[k] > 0.0) || !(hi[k] < INFINITY)) return fail(c, HENS_ERR_INVALID, "log-uniform prior term needs 0 < lo < hi < inf (branch %d, parameter %d)", b, d);
-                t.kind = PRIOR_LOG_UNIFORM;
-            } else {
-                if (!(c1[k] > 0.0) || !(c1[k] < INFINITY)) return fail(c, HENS_ERR_INVALID, "normal prior term needs a finite scale > 0 (branch %d, parameter %d)", b, d);
-                if (!(std::fabs(c2[k]) < INFINITY)) return fail(c, HENS_ERR_INVALID, "normal prior term: log(scale) must be finite (branch %d, parameter %d)", b, d);
-                t.kind = PRIOR_NORMAL;
-                t.c1 = c1[k]; t.c2 = c2[k];
-            }
         }
-        M.leaf_logp[b] = logp_box;
+        const PriorBox pb = fold_box(terms[b], M.nd[b]);
+        M.leaf_logp[b] = pb.logp;
+        box = box && pb.box;
     }
     if (!box) {
         if (c->rj.have_chol) return fail(c, HENS_ERR_UNSUPPORTED, "prior terms: not together with full leaf covariances (hens_rj_set_mh_chol; diagonal steps: hens_rj_set_mh_scale)");

@@ -22,6 +22,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <type_traits>
+#include "hens_prior_host.h"
 
 namespace hens {
 
@@ -464,14 +465,8 @@ __device__ __forceinline__ double periodic_wrap(double q, double period) {
 // with the terms below, in SciPy's operation order (rv_continuous.logpdf: y = (x - loc) / scale, _logpdf(y) - log(scale)).
 // No contraction (the library is built with -ffp-contract=off); one device log per log-uniform coordinate, nothing
 // transcendental otherwise.
-constexpr int PRIOR_UNIFORM = 0, PRIOR_LOG_UNIFORM = 1, PRIOR_NORMAL = 2, PRIOR_NONE = 3;   // NONE: the pad of a padded row
+// The record (PriorTerm), its kinds (PRIOR_*) and the host's parser of a caller's term: hens_prior_host.h.
 constexpr double NORM_PDF_LOGC = 0x1.d67f1c864beb4p-1;        // np.log(np.sqrt(2 * np.pi)), SciPy's _norm_pdf_logC
-struct PriorTerm {
-    double c0;       // UNIFORM: log(1/(hi - lo));  LOG_UNIFORM: log(log(b) - log(a));  NORMAL: loc
-    double c1;       // NORMAL: scale
-    double c2;       // NORMAL: log(scale)
-    int32_t kind, pad_;
-};
 __device__ __forceinline__ double prior_term(const PriorTerm& t, double q) {
     if (t.kind == PRIOR_LOG_UNIFORM) return (-log(q)) - t.c0;
     if (t.kind == PRIOR_NORMAL) {

@@ -1,5 +1,5 @@
 // hens_prior.h - k_stretch_prior<DT, LIKE, MODE, NW>: the copying half-step at a compile-time row width under per-parameter prior
-// terms (hens_set_prior_terms; PriorTerm / prior_term: hens_kernels.h).
+// terms (hens_set_prior_terms; PriorTerm: hens_prior_host.h; prior_term: hens_kernels.h).
 //
 // One workgroup = TILE (64) walkers of one rung, NW wavefronts, the five phases of k_stretch_fast's copying launch without what a
 // single, non-pipeline context on the copying path does not need: no PIPE, no folded adaptation (k_adapt stands alone), no rows in

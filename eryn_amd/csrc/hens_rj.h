@@ -37,7 +37,7 @@ constexpr int RJ_MAX_ND = 4;
 #define RJ_CBN_SLOT(v) ((v) >> 16)
 constexpr int RJ_CTAB_LO = 0, RJ_CTAB_HI = RJ_MAX_RW, RJ_CTAB_SCALE = 2 * RJ_MAX_RW, RJ_CTAB_LOGP = 3 * RJ_MAX_RW;     // RjArgs::ctab
 constexpr int RJ_CTAB_CHOL = 4 * RJ_MAX_RW;                            // rows 4 - 6: L[d][0 .. 2] of the coordinate's dimension d (hens_rj_set_mh_chol)
-// rows 7 - 9: the coordinate's prior term record (hens_rj_set_prior_terms: PriorTerm::c0 / c1 / c2 of hens_kernels.h; its kind: RJ_CBN_PK,
+// rows 7 - 9: the coordinate's prior term record (hens_rj_set_prior_terms: PriorTerm::c0 / c1 / c2 of hens_prior_host.h; its kind: RJ_CBN_PK,
 // its support: rows lo / hi) - read by the instantiations that serve prior-term models (RjModel::prior_on) only
 constexpr int RJ_CTAB_C0 = 7 * RJ_MAX_RW, RJ_CTAB_C1 = 8 * RJ_MAX_RW, RJ_CTAB_C2 = 9 * RJ_MAX_RW, RJ_CTAB_ROWS = 10;
 // (cbn under prior terms: the term's kind in bits 24 - 25, zero on a box model, so RJ_CBN_SLOT stays a plain shift for the box instantiations)

@@ -6,15 +6,12 @@ import numpy as np
 
 from . import _lib
 from ._lib import HensConfig, HensDeviceBuffers, HensTiming, check, f64, ptr
+from .prior import prior_spec, term_arrays
 
 
 def box_logp_inside(lo, hi):
-    """sum_d log(1/(hi_d - lo_d)) accumulated in the reference's order
-    (prior.py:28-41 ``logpdf_val``; prior.py:364-383 sequential ``prior_vals += temp``)."""
-    acc = np.zeros(1)
-    for d in range(len(lo)):
-        acc += np.log(1 / (hi[d] - lo[d]))
-    return float(acc[0])
+    """sum_d log(1/(hi_d - lo_d)) (prior.py:28-41 ``logpdf_val``) accumulated in the reference's order: ``prior.box_constant``."""
+    return prior_spec((lo, hi), len(lo), bounds=True).logp_inside
 
 
 FAST_WIDTHS = (8, 16, 32, 64, 128)       # row widths with compile-time-width kernels (csrc/hens.hip: fast_path)
@@ -99,15 +96,10 @@ class HipEnsemble(ChainStoreCalls):
         if code != _lib.HENS_OK:
             self.ctx = None
             check(code, None)
-        self.prior_terms = None
         if prior_terms is not None:              # (lo / hi are the terms' supports then; the arguments are not read)
             self.set_prior_terms(prior_terms)
         else:
-            self.lo = f64(np.broadcast_to(lo, (self.D,)))
-            self.hi = f64(np.broadcast_to(hi, (self.D,)))
-            self.logp_inside = box_logp_inside(self.lo, self.hi)
-            lo_w, hi_w = self._pad(self.lo, -np.inf), self._pad(self.hi, np.inf)
-            check(self.lib.hens_set_prior_box(self.ctx, ptr(lo_w), ptr(hi_w), self.logp_inside), self.ctx)
+            self.set_prior_box(lo, hi)
         if self.RW != self.D:
             likelihood._install(self.lib, self.ctx, row_width=self.RW)
         else:
@@ -127,31 +119,19 @@ class HipEnsemble(ChainStoreCalls):
         """One independent prior distribution per parameter: ``terms`` is an ``eryn_amd.prior.ProbDistContainer`` or its
         ``prior_terms()`` dict (``kind`` int32, ``lo``, ``hi``, ``c0``, ``c1``, ``c2``, each ``[ndim]``); include/hipensemble.h,
         hens_set_prior_terms.  Uniform kinds only: the box, on the box's launch path."""
-        if hasattr(terms, "prior_terms"):
-            terms = terms.prior_terms()
-        kind = np.ascontiguousarray(terms["kind"], dtype=np.int32)
-        if kind.shape != (self.D,):
-            raise ValueError(f"prior terms must have shape {(self.D,)}")
-        lo, hi, c0, c1, c2 = (f64(terms[k], (self.D,)) for k in ("lo", "hi", "c0", "c1", "c2"))
-        kind_w = kind
-        if self.RW != self.D:                    # pads: uniform on (-inf, +inf), no term
-            kind_w = np.zeros(self.RW, dtype=np.int32)
-            kind_w[:self.D] = kind
-        check(self.lib.hens_set_prior_terms(self.ctx, ptr(kind_w), ptr(self._pad(lo, -np.inf)), ptr(self._pad(hi, np.inf)),
-                                            ptr(self._pad(c0)), ptr(self._pad(c1)), ptr(self._pad(c2))), self.ctx)
-        self.lo, self.hi = lo, hi
-        box = bool(np.all(kind == _lib.PRIOR_UNIFORM))
-        self.prior_terms = None if box else dict(kind=kind, lo=lo, hi=hi, c0=c0, c1=c1, c2=c2)
-        # (the box's constant, summed as the library sums it: ascending from 0.0)
-        self.logp_inside = float(np.add.accumulate(np.concatenate(([0.0], c0)))[-1]) if box else None
+        spec = prior_spec(terms, self.D)
+        check(self.lib.hens_set_prior_terms(self.ctx, *map(ptr, term_arrays(spec.terms, self.RW))), self.ctx)
+        self._keep_prior(spec)
 
     def set_prior_box(self, lo, hi):
         """Back to (or another) uniform box: include/hipensemble.h, hens_set_prior_box."""
-        self.lo = f64(np.broadcast_to(lo, (self.D,)))
-        self.hi = f64(np.broadcast_to(hi, (self.D,)))
-        self.logp_inside = box_logp_inside(self.lo, self.hi)
-        check(self.lib.hens_set_prior_box(self.ctx, ptr(self._pad(self.lo, -np.inf)), ptr(self._pad(self.hi, np.inf)), self.logp_inside), self.ctx)
-        self.prior_terms = None
+        spec = prior_spec((lo, hi), self.D, bounds=True)
+        check(self.lib.hens_set_prior_box(self.ctx, ptr(self._pad(spec.lo, -np.inf)), ptr(self._pad(spec.hi, np.inf)), spec.logp_inside), self.ctx)
+        self._keep_prior(spec)
+
+    def _keep_prior(self, spec):
+        """``lo`` / ``hi``: the supports; ``prior_terms``: the terms, None under a box; ``logp_inside``: the box's constant, None under terms."""
+        self.lo, self.hi, self.prior_terms, self.logp_inside = spec.lo, spec.hi, spec.terms_beyond_box, spec.logp_inside
 
     def set_stretch_scale(self, a):
         """``StretchMove.a`` for every later proposal (the reference's tuning hook mutates it, utils/updates.py:130-175)."""

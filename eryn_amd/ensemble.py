@@ -16,7 +16,7 @@ from .engine import HipEnsemble
 from .model import Model
 from .moves import DeviceMove, GaussianMove, MHMove, StretchMove, TemperatureControl
 from .periodic import PeriodicContainer, period_vector
-from .prior import ProbDistContainer
+from .prior import prior_spec
 from .state import DeviceState, State
 
 
@@ -69,14 +69,11 @@ class EnsembleSampler:
         # -- priors (ensemble.py:334-348): dict of dists, a container, or {branch: container}
         if isinstance(priors, dict) and self.branch_names[0] in priors:
             priors = priors[self.branch_names[0]]
-        if isinstance(priors, dict):
-            priors = ProbDistContainer(priors)
-        if not hasattr(priors, "box_bounds"):
-            raise NotImplementedError("priors must be per-parameter uniform / log-uniform / normal priors (eryn_amd.prior.ProbDistContainer)")
-        self.priors = {self.branch_names[0]: priors}
         # a box, or one term per parameter (include/hipensemble.h: hens_set_prior_terms) - evaluated on the device either way
-        terms = None if getattr(priors, "is_box", True) else priors.prior_terms()
-        lo, hi = (terms["lo"], terms["hi"]) if terms else priors.box_bounds()
+        prior = prior_spec(priors, self.ndim)
+        if prior.container is None:              # (bounds or bare terms: this sampler keeps the reference's ``priors`` of distributions)
+            raise NotImplementedError("priors must be per-parameter uniform / log-uniform / normal priors (eryn_amd.prior.ProbDistContainer)")
+        self.priors = {self.branch_names[0]: prior.container}
 
         # -- tempering (ensemble.py:321-332): enabled iff tempering_kwargs != {}
         if tempering_kwargs == {}:
@@ -123,9 +120,9 @@ class EnsembleSampler:
         if seed is None:
             seed = int(np.random.randint(0, 2**31 - 1)) if rng == "philox" else 0
         self.seed = int(seed)
-        self.engine = HipEnsemble(self.ntemps, self.nwalkers, self.ndim, log_like_fn, lo, hi, a=a_vals.pop(),
+        self.engine = HipEnsemble(self.ntemps, self.nwalkers, self.ndim, log_like_fn, prior.lo, prior.hi, a=a_vals.pop(),
                                   tempered=tc is not None, live_dangerously=live,
-                                  fill_value=fill_zero_leaves_val, seed=seed, device_id=device_id, prior_terms=terms, **kw)
+                                  fill_value=fill_zero_leaves_val, seed=seed, device_id=device_id, prior_terms=prior.terms_beyond_box, **kw)
         self._resident = [None]              # the State the device context mirrors, shared by the moves
         for m in self.moves:
             if m.temperature_control is None:

@@ -4,6 +4,7 @@ import numpy as np
 
 from ..engine import HipEnsemble
 from ..periodic import period_vector
+from ..prior import prior_spec
 from ..state import DeviceState, State
 from .move import Move
 
@@ -62,14 +63,6 @@ class DeviceMove(Move):
         Move.accepted.fset(self, accepted)
 
     # -- engine -----------------------------------------------------------------------------------
-    def _box(self):
-        pb = self.prior_box
-        if pb is None:
-            raise ValueError(f"{type(self).__name__} needs prior_box=(lo, hi) or a ProbDistContainer")
-        if hasattr(pb, "box_bounds"):
-            return pb.box_bounds()
-        return pb
-
     def attach_engine(self, engine, shared=None):
         """Share one device context between the sampler, its moves and the temperature control.
         ``shared``: a one-element list holding the State the context currently mirrors (so that the
@@ -83,9 +76,9 @@ class DeviceMove(Move):
             return e
         if self.likelihood is None:
             raise ValueError(f"{type(self).__name__} needs likelihood=<eryn_amd.likelihood object>")
-        pb = self.prior_box                      # a container with other than uniform entries: its terms (hens_set_prior_terms)
-        terms = pb.prior_terms() if hasattr(pb, "prior_terms") and not pb.is_box else None
-        lo, hi = (terms["lo"], terms["hi"]) if terms else self._box()
+        if self.prior_box is None:
+            raise ValueError(f"{type(self).__name__} needs prior_box=(lo, hi) or a ProbDistContainer")
+        prior = prior_spec(self.prior_box, D, bounds=True)       # (a container with other than uniform entries: hens_set_prior_terms)
         tc = self.temperature_control
         kw = {}
         if tc is not None:
@@ -94,9 +87,9 @@ class DeviceMove(Move):
         seed = self.seed
         if seed is None:
             seed = int(np.random.randint(0, 2**31 - 1)) if self.rng == "philox" else 0
-        self.engine = HipEnsemble(T, W, D, self.likelihood, lo, hi, a=self._engine_a, tempered=tc is not None,
+        self.engine = HipEnsemble(T, W, D, self.likelihood, prior.lo, prior.hi, a=self._engine_a, tempered=tc is not None,
                                   live_dangerously=self._engine_live or not self.needs_walker_guard, fill_value=self.fill_value,
-                                  device_id=self.device_id, seed=seed, prior_terms=terms, **kw)
+                                  device_id=self.device_id, seed=seed, prior_terms=prior.terms_beyond_box, **kw)
         return self.engine
 
     def _apply_periodic(self, eng, name, D):

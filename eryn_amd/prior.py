@@ -6,9 +6,11 @@ them on the host in the same arithmetic (``logpdf``) and draw starting points (`
 The arithmetic of one term is SciPy's (``rv_continuous.logpdf``: ``y = (x - loc) / scale``, the support test,
 ``_logpdf(y) - log(scale)``), the sum is the reference container's (prior.py:364-383: ``prior_vals += temp`` from 0.0),
 taken in ascending parameter order."""
+from typing import NamedTuple, Optional
+
 import numpy as np
 
-from ._lib import PRIOR_LOG_UNIFORM, PRIOR_NORMAL, PRIOR_UNIFORM
+from ._lib import PRIOR_LOG_UNIFORM, PRIOR_NORMAL, PRIOR_UNIFORM, f64
 
 NORM_PDF_LOGC = float(np.log(np.sqrt(2 * np.pi)))         # SciPy's _norm_pdf_logC
 
@@ -121,7 +123,10 @@ class NormalDistribution:
 
 def _from_scipy(dist):
     """A frozen SciPy ``uniform`` / ``loguniform`` (``reciprocal``) / ``norm`` as one of the classes above, by duck typing
-    (``.dist.name``, ``.args``, ``.kwds``): SciPy is not imported."""
+    (``.dist.name``, ``.args``, ``.kwds``): SciPy is not imported.  And what carries ``min_val`` / ``max_val``, as the reference's own
+    ``UniformDistribution`` does (prior.py:12-88; the leaf-packing sampler has always read those two), as a ``UniformDistribution``."""
+    if hasattr(dist, "min_val") and hasattr(dist, "max_val"):
+        return UniformDistribution(dist.min_val, dist.max_val)
     name = getattr(getattr(dist, "dist", None), "name", None)
     if name is None or not hasattr(dist, "args") or not hasattr(dist, "kwds"):
         return None
@@ -218,3 +223,85 @@ class ProbDistContainer:
         for k in range(self.ndim):
             out[..., k] = self.dists[k].rvs(size=tuple(size))
         return out
+
+
+# ---- one specification of "the caller's prior" for every consumer: both samplers, the moves, both engines -------------------------------
+TERM_KEYS = ("kind", "lo", "hi", "c0", "c1", "c2")          # the arguments of hens_set_prior_terms / hens_rj_set_prior_terms, in order
+_PAD = dict(kind=PRIOR_UNIFORM, lo=-np.inf, hi=np.inf, c0=0.0, c1=0.0, c2=0.0)      # a padded row's pad: uniform on the line, no term
+
+
+def box_constant(c0):
+    """The constant log-density inside a box from its uniform terms' constants ``log(1/(hi_d - lo_d))``: ``((0.0 + c0_0) + c0_1) +
+    ...``, the reference's sequential ``prior_vals += temp`` (prior.py:364-383) in ascending parameter order - the sum the library
+    forms (csrc/hens_prior_host.h: fold_box)."""
+    acc = np.zeros(1)
+    for v in c0:
+        acc += v
+    return float(acc[0])
+
+
+class PriorSpec(NamedTuple):
+    """What ``prior_spec`` makes of a caller's prior."""
+    container: Optional[ProbDistContainer]      # None: the caller gave bounds or terms, no distributions
+    terms: dict                                 # kind int32, lo / hi / c0 / c1 / c2 float64, each C-contiguous [ndim]
+    lo: np.ndarray                              # terms["lo"], terms["hi"]: the inclusive supports
+    hi: np.ndarray
+    is_box: bool                                # every term uniform
+    logp_inside: Optional[float]                # a box's constant log-density (box_constant), None otherwise
+
+    @property
+    def terms_beyond_box(self):
+        """The terms where they say more than ``lo`` / ``hi`` do (``HipEnsemble(prior_terms=...)``): None for a box."""
+        return None if self.is_box else self.terms
+
+
+def prior_spec(priors, ndim=None, bounds=False):
+    """One reading of a prior, however the caller wrote it: a ``ProbDistContainer``; the ``{index: distribution}`` dict it is made
+    of; a ``prior_terms()`` dict; a list of ``(lo, hi)`` per parameter (a box); with ``bounds=True`` the box as ``(lo, hi)``, two
+    arrays or scalars that broadcast to ``ndim``; or a ``PriorSpec``.  ``ndim`` given: the number of parameters it must describe."""
+    if isinstance(priors, PriorSpec):
+        spec = priors
+    else:
+        container = None
+        if isinstance(priors, dict) and "kind" not in priors:
+            priors = ProbDistContainer(priors)
+        if isinstance(priors, ProbDistContainer):
+            container, terms = priors, priors.prior_terms()
+        elif isinstance(priors, dict):
+            terms = priors
+        elif priors is not None and bounds:
+            lo, hi = (f64(np.broadcast_to(b, (ndim,))) for b in priors)
+            terms = _box_terms(lo, hi)
+        elif isinstance(priors, (list, tuple)):
+            terms = _box_terms(f64([b[0] for b in priors]), f64([b[1] for b in priors]))
+        else:
+            raise NotImplementedError("priors must be per-parameter uniform / log-uniform / normal priors (eryn_amd.prior.ProbDistContainer)")
+        kind = np.ascontiguousarray(terms["kind"], dtype=np.int32)
+        n = kind.shape[0] if ndim is None and kind.ndim == 1 else ndim
+        if kind.shape != (n,):
+            raise ValueError(f"prior terms must have shape {(n,)}")
+        terms = dict(kind=kind, **{k: f64(terms[k], (n,)) for k in TERM_KEYS[1:]})
+        is_box = bool(np.all(kind == PRIOR_UNIFORM))
+        spec = PriorSpec(container, terms, terms["lo"], terms["hi"], is_box, box_constant(terms["c0"]) if is_box else None)
+    if ndim is not None and spec.lo.shape != (ndim,):
+        raise ValueError(f"prior terms must have shape {(ndim,)}")
+    return spec
+
+
+def _box_terms(lo, hi):
+    n = lo.shape[0]
+    return dict(kind=np.zeros(n, dtype=np.int32), lo=lo, hi=hi, c0=[np.log(1 / (hi[d] - lo[d])) for d in range(n)], c1=np.zeros(n), c2=np.zeros(n))
+
+
+def term_arrays(terms, width=None):
+    """The six array arguments of hens_set_prior_terms / hens_rj_set_prior_terms (``TERM_KEYS``) from one terms dict or from a list
+    of them, one after the other (a model's branches); ``width``: padded to that many entries with the pad of a padded row."""
+    if isinstance(terms, dict):
+        terms = [terms]
+    out = []
+    for k in TERM_KEYS:
+        a = np.concatenate([t[k] for t in terms])
+        if width is not None and width > a.shape[0]:
+            a = np.concatenate([a, np.full(width - a.shape[0], _PAD[k])])
+        out.append(np.ascontiguousarray(a, dtype=np.int32 if k == "kind" else np.float64))
+    return out

@@ -14,6 +14,7 @@ import numpy as np
 from . import _lib
 from ._lib import check, f64, ptr
 from .engine import ChainStoreCalls, HipEnsemble
+from .prior import prior_spec, term_arrays
 
 KIND_PULSE, KIND_SINE = 0, 1
 # the leaf kinds the device evaluates, name -> (id, parameters per leaf) (include/hipensemble.h: HENS_RJ_KIND_*): value at data point t
@@ -28,29 +29,11 @@ _WIDTH = {v[0]: v[1] for v in LEAF_KINDS.values()}
 def _leaf_prior(branch, box):
     """The prior of one leaf, from ``box`` - a list of (lo, hi) per leaf parameter - or, in its place, an
     ``eryn_amd.prior.ProbDistContainer`` or anything it accepts (a dict of distributions, frozen SciPy ``uniform`` / ``loguniform`` /
-    ``norm`` among them).  Sets ``lo`` / ``hi`` (the inclusive supports), ``terms`` (the arguments of hens_rj_set_prior_terms for this
-    branch), ``prior`` (the container, None for a box), ``is_box`` and - all-uniform branches - ``leaf_logp``, the constant leaf
-    log-density (None otherwise: the density is no constant)."""
-    from .prior import ProbDistContainer
-    if isinstance(box, dict):
-        box = ProbDistContainer(box)
-    if isinstance(box, ProbDistContainer):
-        branch.prior, branch.terms = box, box.prior_terms()
-        branch.lo, branch.hi = f64(branch.terms["lo"]), f64(branch.terms["hi"])
-    else:
-        branch.prior = None
-        branch.lo = f64([b[0] for b in box])
-        branch.hi = f64([b[1] for b in box])
-        n = branch.lo.shape[0]
-        branch.terms = dict(kind=np.zeros(n, dtype=np.int32), lo=branch.lo, hi=branch.hi, c0=f64(np.log(1 / (branch.hi - branch.lo))),
-                            c1=np.zeros(n), c2=np.zeros(n))
-    branch.is_box = bool(np.all(branch.terms["kind"] == _lib.PRIOR_UNIFORM))
-    branch.leaf_logp = None
-    if branch.is_box:
-        acc = np.zeros(1)                      # prior.py:364-383: sequential ``prior_vals += temp`` from 0.0
-        for d in range(branch.lo.shape[0]):
-            acc += np.log(1 / (branch.hi[d] - branch.lo[d]))
-        branch.leaf_logp = float(acc[0])
+    ``norm`` among them): ``eryn_amd.prior.prior_spec``.  Sets ``lo`` / ``hi`` (the inclusive supports), ``terms`` (the arguments of
+    hens_rj_set_prior_terms for this branch), ``prior`` (the container, None for bounds), ``is_box`` and - all-uniform branches -
+    ``leaf_logp``, the constant leaf log-density (None otherwise: the density is no constant)."""
+    spec = prior_spec(box)
+    branch.prior, branch.terms, branch.lo, branch.hi, branch.is_box, branch.leaf_logp = spec
 
 
 class TemplateBranch:
@@ -228,10 +211,7 @@ class RJEngine(ChainStoreCalls):
     def _set_prior_terms(self):
         if not self.prior_terms:
             return
-        tm = {k: np.ascontiguousarray(np.concatenate([b.terms[k] for b in self.branches]), dtype=(np.int32 if k == "kind" else np.float64))
-              for k in ("kind", "lo", "hi", "c0", "c1", "c2")}
-        check(self.lib.hens_rj_set_prior_terms(self.ctx, ptr(tm["kind"]), ptr(tm["lo"]), ptr(tm["hi"]), ptr(tm["c0"]), ptr(tm["c1"]),
-                                               ptr(tm["c2"])), self.ctx)
+        check(self.lib.hens_rj_set_prior_terms(self.ctx, *map(ptr, term_arrays([b.terms for b in self.branches]))), self.ctx)
 
     def close(self):
         self.eng.close()
@@ -650,7 +630,6 @@ class RJEnsembleSampler:
                  backend=None, **unused):
         from .backend import RJDeviceBackend
         from .moves.tempering import TemperatureControl
-        from .prior import ProbDistContainer
         # backend: None - the stored steps are a list of States (``self.chain``) - or an eryn_amd.backend.RJDeviceBackend: they stay
         # in device memory until somebody reads them (one device call per chain segment, hens_rj_step_chain)
         if backend is not None and not isinstance(backend, RJDeviceBackend):
@@ -696,20 +675,9 @@ class RJEnsembleSampler:
                 raise NotImplementedError(f"branch {k}: a leaf of its kind has {_WIDTH[log_like_fn.kinds[k]]} parameters, ndims says {nd}")
             if isinstance(moves, GaussianLeafMove) and moves.cov[k].shape != (nd, nd):
                 raise ValueError(f"branch {k}: the proposal covariance must be {nd} x {nd}")
-            pr = priors[k]
-            # a container (or the dict it is made of) with a log-uniform or normal parameter goes to the branch as it is; boxes as ever
-            if isinstance(pr, dict) and not all(hasattr(pr.get(i), "min_val") for i in range(nd)):
-                pr = ProbDistContainer(pr)
-            if isinstance(pr, ProbDistContainer) and not pr.is_box:
-                if pr.ndim != nd:
-                    raise ValueError(f"branch {k}: {pr.ndim} prior distributions for ndims = {nd}")
-                leaf_prior = pr
-            else:
-                box = pr.box_bounds() if hasattr(pr, "box_bounds") else \
-                    ([pr[i].min_val for i in range(nd)], [pr[i].max_val for i in range(nd)])
-                if len(box[0]) != nd:
-                    raise ValueError(f"branch {k}: {len(box[0])} prior boxes for ndims = {nd}")
-                leaf_prior = list(zip(box[0], box[1]))
+            leaf_prior = prior_spec(priors[k])       # (a container, the dict it is made of, or (lo, hi) per leaf parameter)
+            if leaf_prior.lo.shape != (nd,):
+                raise ValueError(f"branch {k}: {leaf_prior.lo.shape[0]} prior {'boxes' if leaf_prior.is_box else 'distributions'} for ndims = {nd}")
             if self.host_like is not None:     # (no device likelihood: 1 .. 4 parameters per leaf, hens_rj_set_model_general)
                 self.branches.append(LeafBranch(k, leaf_prior, self.nleaves_max[k], self.nleaves_min[k]))
             else:

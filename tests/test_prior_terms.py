@@ -193,6 +193,49 @@ def test_python_surface():
     for args in ((0.0, 0.0), (0.0, -1.0), (np.inf, 1.0), (0.0, np.inf)):
         with pytest.raises(ValueError):
             NormalDistribution(*args)
+    # one reading of a prior, however it is written (prior_spec), and one gather of the C arguments (term_arrays)
+    from eryn_amd.prior import box_constant, prior_spec, term_arrays
+    forms = [prior_spec(box), prior_spec(box.priors_in), prior_spec(t), prior_spec(list(zip(lo, hi))), prior_spec((lo, hi), 2, bounds=True)]
+    for s in forms:
+        assert s.is_box and s.terms_beyond_box is None and s.logp_inside == box_logp_inside(lo, hi) == box_constant(t["c0"])
+        assert all(np.array_equal(s.terms[k], t[k]) and s.terms[k].dtype == t[k].dtype and s.terms[k].flags.c_contiguous for k in t)
+        assert s.lo is s.terms["lo"] and s.hi is s.terms["hi"] and prior_spec(s) is s
+    assert forms[0].container is box and forms[1].container.is_box and all(s.container is None for s in forms[2:])
+    assert box_constant([1e16, 1.0, 1.0]) == 1e16 != box_constant([1.0, 1.0, 1e16]), "ascending, from 0.0"
+    b1 = prior_spec((-1.0, 2.0), 3, bounds=True)
+    assert np.array_equal(b1.lo, [-1.0] * 3) and b1.logp_inside == (np.log(1 / 3.0) + np.log(1 / 3.0)) + np.log(1 / 3.0)
+    m = prior_spec(mixed, 3)
+    assert not m.is_box and m.logp_inside is None and m.terms_beyond_box is m.terms and m.container is mixed
+    with pytest.raises(ValueError, match="prior terms must have shape"):
+        prior_spec(mixed, 4)
+    with pytest.raises(NotImplementedError, match="priors must be per-parameter"):
+        prior_spec(None)
+    wide = term_arrays(m.terms, 5)
+    assert [a.dtype for a in wide] == [np.int32] + [np.float64] * 5 and all(a.shape == (5,) and a.flags.c_contiguous for a in wide)
+    assert wide[0].tolist() == [2, 1, 0, 0, 0] and np.isneginf(wide[1][3:]).all() and np.isposinf(wide[2][3:]).all(), "the pad: uniform on the line"
+    assert all(np.array_equal(a[:3], m.terms[k]) and (k in ("kind", "lo", "hi") or not a[3:].any()) for k, a in zip(t, wide))
+    both = term_arrays([m.terms, t])
+    assert all(np.array_equal(a, np.concatenate([m.terms[k], t[k]])) for k, a in zip(t, both)) and both[0].dtype == np.int32
+
+
+def test_term_parser_and_box_fold_under_a_sanitizer_build(tmp_path):
+    """tools/prior_host_check.cpp: a stand-alone program over csrc/hens_prior_host.h - the one parser of a caller's prior term (every
+    refusal tests/test_hip_priors.py and tests/test_hip_rj_priors.py list, in both entry points' modes, and an accepted term of each
+    kind byte for byte) and the fold of a parsed run into a box - built with -fsanitize=address,undefined where the compiler has the
+    runtimes (plainly otherwise) and run on the CPU."""
+    cxx = shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
+    assert cxx, "no host C++ compiler"
+    src, exe = os.path.join(os.path.dirname(HERE), "tools", "prior_host_check.cpp"), str(tmp_path / "prior_host_check")
+    base = [cxx, "-std=c++17", "-O1", "-g", src, "-o", exe]
+    r = subprocess.run(base + ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"], capture_output=True, text=True)
+    build = "sanitizer build (address, undefined)"
+    if r.returncode != 0:
+        build = "plain build - the sanitizer build failed: " + (r.stderr.strip().splitlines() or ["no message"])[-1]
+        r = subprocess.run(base, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    print("prior_host_check:", build)                # (pytest -rA shows which build ran)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stdout + r.stderr
 
 
 def test_scipy_objects_are_recognised_by_duck_typing():
