@@ -8,6 +8,7 @@
 #include "hens_aql.h"
 #include "hens_ktable.h"
 #include "hens_prior.h"
+#include "hens_dist.h"
 #include "hens_chain.h"
 #include "hens_chain_stats.h"
 #include "hens_rj_chain.h"
@@ -189,7 +190,9 @@ struct hens_ctx_impl {
     uint32_t* accepted_mh = nullptr;       // [Tl][W] accept counts of the MH move
     uint32_t* accepted_mark = nullptr;     // [2][Tl][W] hens_step_marked: stretch / MH accept counts in front of the call's last iterations
     bool mark_valid = false, mark_mh = false;
-    int mh_kind = -1;                      // -1: hens_step runs the stretch move only
+    int mh_kind = -1;                      // -1: hens_step runs the stretch move only; MH_DIST: the slot holds hens_set_dist_proposal's generator
+    double* dist_block = nullptr;          // the generator of MH_DIST: lo[D] hi[D] terms[D] in one allocation (DistArgs::glo / ghi / gterms)
+    double* dist_factors = nullptr;        // [Tl][W] hens_dist_step's factors_out staging
     double mh_weight = 0.0;                // probability that an iteration of hens_step is an MH proposal
     int64_t num_proposals_mh = 0;
     uint8_t* mask_buf = nullptr;     // hens_step_report: [Tl][W] accept counts of the call's last iterations
@@ -431,11 +434,12 @@ struct LikeKernels {
     const void* (*stretch_fast)(int mode, int D, bool pipe, bool per);
     const void* (*stretch)(int mode);
     const void* (*stretch_prior)(int mode, int D);
+    const void* (*dist)(int D);
     const void* (*stretch2)(int D, bool pipe);
     const void* (*split1_pt)(int D, bool per, bool shrt, bool pipe, bool col);
     const void* (*iter)(int D, bool per);
 };
-#define HENS_LIKE_KERNELS(KIND_, LIKE_, U) {KIND_, LIKE_, ktab_stretch_fast_##U, ktab_stretch_##U, ktab_stretch_prior_##U, ktab_stretch2_##U, ktab_split1_pt_##U, ktab_iter_##U}
+#define HENS_LIKE_KERNELS(KIND_, LIKE_, U) {KIND_, LIKE_, ktab_stretch_fast_##U, ktab_stretch_##U, ktab_stretch_prior_##U, ktab_dist_##U, ktab_stretch2_##U, ktab_split1_pt_##U, ktab_iter_##U}
 const LikeKernels* like_kernels(int likelihood_kind) {
     static const LikeKernels tab[] = {
         HENS_LIKE_KERNELS(HENS_LIKE_GAUSS_DENSE, LIKE_DENSE, dense),
@@ -1686,10 +1690,56 @@ int mh_launch(hens_ctx_impl* c, bool want_keep, LaunchTimer* tm, bool inline_dra
     return HENS_OK;
 }
 
+// DistributionGenerate (hens_dist.h): one full-ensemble proposal from the generator in the MH slot.  forced: the caller's points
+// and log-uniforms are in mh_step / mh_lu (hens_dist_step); else the launch draws both (hens_step).  Always in place, the pool's
+// parity stays; on the HIP stream with its release.  A pending ladder adaptation runs as a kernel of its own in front of it.
+int dist_launch(hens_ctx_impl* c, bool forced, bool want_keep, bool want_factors, LaunchTimer* tm) {
+    const LikeKernels* lk = like_kernels(c->cfg.likelihood_kind);
+    const void* fn = lk ? lk->dist(c->D) : nullptr;
+    if (!fn) return fail(c, HENS_ERR_UNSUPPORTED, "k_dist: no such instantiation in this build (ndim %d, likelihood kind %d)", c->D, c->cfg.likelihood_kind);
+    flush_adapt(c);
+    DistArgs a{};
+    a.pool = c->pool;
+    a.loc = c->loc[c->cur];
+    a.L = c->L[c->cur];
+    a.P = c->P[c->cur];
+    a.wrec = c->packed ? c->wrec[c->cur] : nullptr;        // hens_step's record mode (slot order: no column order with an MH move set)
+    a.betas = c->cfg.tempered ? c->betas[c->bcur] : nullptr;
+    a.lo = c->prior ? c->prior_block : c->lo;
+    a.hi = c->prior ? c->prior_block + c->D : c->hi;
+    a.pterms = c->prior;
+    a.glo = c->dist_block;
+    a.ghi = c->dist_block + c->D;
+    a.gterms = reinterpret_cast<const PriorTerm*>(c->dist_block + 2 * (size_t)c->D);
+    a.q = forced ? c->mh_step : nullptr;
+    a.lu = forced ? c->mh_lu : nullptr;
+    a.accepted = c->accepted_mh;
+    a.keep_out = want_keep ? c->mh_keep : nullptr;
+    a.factors_out = want_factors ? c->dist_factors : nullptr;
+    a.mu = c->mu; a.prec = c->prec; a.prec_sym = c->prec_sym;
+    a.flags = c->flags;
+    a.logp_in = c->logp_in;
+    a.fill = c->cfg.fill_value;
+    a.rosen_a = c->rosen_a; a.rosen_b = c->rosen_b;
+    a.seed = c->cfg.seed; a.iter = c->iter;
+    a.Tl = c->Tl; a.W = c->W; a.rung_begin = c->cfg.rung_begin; a.tempered = c->cfg.tempered;
+    const int NW = fast_nw(c->D);
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    time_launch(c, tm, 0, e0, e1);
+    const bool was_aql = c->aql_now;                     // (never on the AQL queue: aql_able requires mh_kind < 0)
+    c->aql_now = false;
+    const int r = launch_by_ptr(c, fn, "k_dist", dim3((c->W + TILE - 1) / TILE, c->Tl), NW * 64, prior_lds_bytes(c->D, NW, lk->like), false, e0, e1, a);
+    c->aql_now = was_aql;
+    if (r) return r;
+    c->num_proposals_mh += 1;
+    return HENS_OK;
+}
+
 // Philox mode: draw the iteration's steps and accept uniforms on the device, then propose.  Isotropic and
 // axis-aligned proposals on the fast row widths are drawn inside the MH launch itself (one Box-Muller pair per
 // lane); a full covariance (Cholesky product) and the generic row widths go through k_mh_draw + the step buffer.
 int mh_iteration(hens_ctx_impl* c, LaunchTimer* tm, bool inplace) {
+    if (c->mh_kind == MH_DIST) return dist_launch(c, false, false, false, tm);      // (in place in either state form)
     const bool inline_draws = c->mh_kind != MH_FULL && fast_path(c);
     if (!inline_draws) {
         MhDrawArgs d{};
@@ -3595,6 +3645,22 @@ int hens_get_iteration(hens_ctx* ctx, int64_t* iter_out) {
     return HENS_OK;
 }
 
+// hens_debug_draws under the distribution proposal: what k_dist draws in iteration `iter` - q[tl][w][d] from the same function
+// (dist_draw; a pad coordinate, which has no draw, reads 0) and the accept uniform of every walker (mh_uniform).  Export only.
+__global__ void k_dist_draw(double* q, double* u, const double* glo, const double* ghi, const PriorTerm* gterms, uint64_t seed, uint64_t iter,
+                            int Tl, int W, int D, int rung_begin) {
+    const int64_t n = (int64_t)Tl * W * D;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const int d = (int)(i % D);
+        const int64_t tw = i / D;
+        const int tl = (int)(tw / W), w = (int)(tw % W);
+        const uint32_t wid = (uint32_t)(rung_begin + tl) * (uint32_t)W + (uint32_t)w;
+        const PriorTerm t = gterms[d];
+        q[i] = t.kind == PRIOR_NONE ? 0.0 : dist_draw(seed, iter, wid, d, t, glo[d], ghi[d]);
+        if (d == 0) u[tw] = mh_uniform(seed, iter, wid);
+    }
+}
+
 int hens_debug_draws(hens_ctx* ctx, int64_t iter, int32_t* own, int32_t* cw, double* u_zz, double* u_acc,
                      int32_t* pt_slot, double* u_swap, int32_t* is_mh, double* mh_step, double* mh_u) {
     hens_ctx_impl* c = enter(ctx);
@@ -3641,7 +3707,18 @@ int hens_debug_draws(hens_ctx* ctx, int64_t iter, int32_t* own, int32_t* cw, dou
         if (!ds || !du) return fail(c, HENS_ERR_HIP, "hens_debug_draws: out of device memory");
         if (const int r = export_pt_draws(c, ds, du, (uint64_t)iter, pt_slot, u_swap)) return r;
     }
-    if ((mh_step || mh_u) && c->mh_kind >= 0) {
+    if ((mh_step || mh_u) && c->mh_kind == MH_DIST) {      // the drawn points q and the accept uniforms of that iteration
+        double* dq = sc.grab<double>(TW * c->D);
+        double* du = sc.grab<double>(TW);
+        if (!dq || !du) return fail(c, HENS_ERR_HIP, "hens_debug_draws: out of device memory");
+        hipLaunchKernelGGL(k_dist_draw, dim3(grid_for((int64_t)TW * c->D)), dim3(256), 0, c->stream, dq, du, c->dist_block, c->dist_block + c->D,
+                           reinterpret_cast<const PriorTerm*>(c->dist_block + 2 * (size_t)c->D), c->cfg.seed, (uint64_t)iter, c->Tl, c->W, c->D,
+                           (int)c->cfg.rung_begin);
+        HIPCHK(c, hipGetLastError());
+        if (mh_step) HIPCHK(c, hipMemcpyAsync(mh_step, dq, TW * c->D * 8, hipMemcpyDeviceToHost, c->stream));
+        if (mh_u) HIPCHK(c, hipMemcpyAsync(mh_u, du, TW * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    } else if ((mh_step || mh_u) && c->mh_kind >= 0) {
         MhDrawArgs d{};
         d.step = sc.grab<double>(TW * c->D); d.lu = sc.grab<double>(TW); d.dbg_u = sc.grab<double>(TW);
         if (!d.step || !d.lu || !d.dbg_u) return fail(c, HENS_ERR_HIP, "hens_debug_draws: out of device memory");
@@ -4818,6 +4895,76 @@ int hens_set_mh_proposal(hens_ctx* ctx, int32_t kind, const double* scale, doubl
     return HENS_OK;
 }
 
+// ---- DistributionGenerate (distgen.py:10-104): the independence proposal in the context's one MH slot -------------------------------
+int hens_set_dist_proposal(hens_ctx* ctx, const int32_t* kind, const double* lo, const double* hi, const double* c0, const double* c1,
+                           const double* c2, double weight) {
+    hens_ctx_impl* c = enter(ctx);
+    if (!c) return no_context();
+    if (!kind || !lo || !hi || !c0 || !c1 || !c2) return fail(c, HENS_ERR_INVALID, "null argument");
+    if (!(weight >= 0.0 && weight <= 1.0)) return fail(c, HENS_ERR_INVALID, "weight must be a probability");
+    if (is_rj(c)) return fail(c, HENS_ERR_UNSUPPORTED, "the distribution proposal is not built for leaf-packing records");
+    if (c->pipe.on) return fail(c, HENS_ERR_STATE, "the distribution proposal is not built for a rank of the ladder pipeline");
+    if (c->cfg.likelihood_kind == HENS_LIKE_HOST) return fail(c, HENS_ERR_UNSUPPORTED, "the distribution proposal needs a device likelihood");
+    const LikeKernels* lk = like_kernels(c->cfg.likelihood_kind);
+    if (!lk || !lk->dist(c->D))
+        return fail(c, HENS_ERR_UNSUPPORTED, "the distribution proposal is built for row widths 8, 16, 32, 64 and 128 (this context's rows are %d wide)", c->D);
+    // a distribution one draws from: finite uniform supports, as for the leaves' priors; a padded row's pads have no draw and no term
+    const int D = c->D, Da = dim_active(c);
+    std::vector<PriorTerm> terms((size_t)D);
+    for (int d = 0; d < D; ++d) {
+        const ParsedTerm p = parse_term(kind[d], lo[d], hi[d], c0[d], c1[d], c2[d], /*admit_pad=*/d >= Da);
+        if (p.why[0]) return fail(c, HENS_ERR_INVALID, "%s (dim %d)", p.why, d);
+        if (d >= Da && p.term.kind != PRIOR_NONE) return fail(c, HENS_ERR_INVALID, "a pad of the row takes the uniform term on (-inf, +inf) (dim %d)", d);
+        terms[(size_t)d] = p.term;
+    }
+    SETTLE(c, NEED_DEVICE | NEED_FIELDS | NEED_LADDER);
+    int r = ensure_mh_buffers(c);
+    if (r) return r;
+    if (!c->dist_block) {
+        double* blk = nullptr;
+        if ((r = dalloc(c, &blk, (size_t)6 * D))) return r;
+        c->dist_block = blk;
+    }
+    if (!c->dist_factors) {
+        double* f = nullptr;
+        if ((r = dalloc(c, &f, (size_t)c->Tl * c->W))) return r;
+        c->dist_factors = f;
+    }
+    HIPCHK(c, hipMemcpyAsync(c->dist_block, lo, D * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->dist_block + D, hi, D * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->dist_block + 2 * (size_t)D, terms.data(), (size_t)D * sizeof(PriorTerm), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->mh_kind = MH_DIST;
+    c->mh_weight = weight;
+    return HENS_OK;
+}
+
+// the teacher-forced twin of hens_mh_step: the caller's points and accept uniforms
+int hens_dist_step(hens_ctx* ctx, const double* q, const double* u_acc, uint8_t* keep_out, double* factors_out) {
+    hens_ctx_impl* c = enter(ctx);
+    int r = ready(c, true);
+    if (r) return r;
+    if (!q || !u_acc) return fail(c, HENS_ERR_INVALID, "null argument");
+    if (c->mh_kind != MH_DIST) return fail(c, HENS_ERR_STATE, "no generator set (hens_set_dist_proposal)");
+    if (c->expect_split != 0) return fail(c, HENS_ERR_STATE, "hens_dist_step between split 0 and split 1");
+    if (c->pt_pending) return fail(c, HENS_ERR_STATE, "sharded PT exchange in flight");
+    if ((r = counter_room(c, 1))) return r;
+    SETTLE(c, NEED_DEVICE | NEED_FIELDS);
+    if ((r = ensure_mh_buffers(c))) return r;
+    SETTLE(c, NEED_LADDER);
+    const size_t TW = (size_t)c->Tl * c->W;
+    HIPCHK(c, hipMemcpyAsync(c->mh_step, q, TW * c->D * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->mh_u, u_acc, TW * 8, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_mh_prep, dim3(grid_for((int64_t)TW)), dim3(256), 0, c->stream, c->mh_u, c->mh_lu, (int64_t)TW);
+    c->win_count = 0;
+    if ((r = dist_launch(c, true, true, factors_out != nullptr, nullptr))) return r;
+    if (keep_out) HIPCHK(c, hipMemcpyAsync(keep_out, c->mh_keep, TW, hipMemcpyDeviceToHost, c->stream));
+    if (factors_out) HIPCHK(c, hipMemcpyAsync(factors_out, c->dist_factors, TW * 8, hipMemcpyDeviceToHost, c->stream));
+    if ((r = check_flags(c, true))) return r;
+    if (!has_pt(c)) c->iter += 1;
+    return HENS_OK;
+}
+
 int hens_get_mh_counters(hens_ctx* ctx, double* accepted, int64_t* num_proposals) {
     hens_ctx_impl* c = enter(ctx);
     if (!c) return no_context();
@@ -4836,6 +4983,7 @@ int hens_pipe_init(hens_ctx* ctx, int32_t nranks, int32_t my_rank, void* blob_ou
     if (!c) return no_context();
     if (c->pipe.on) return fail(c, HENS_ERR_STATE, "pipeline already initialised");
     if (c->prior) return fail(c, HENS_ERR_UNSUPPORTED, "prior terms are not built for a rank of the ladder pipeline (hens_set_prior_box returns to the box)");
+    if (c->mh_kind == MH_DIST) return fail(c, HENS_ERR_UNSUPPORTED, "the distribution proposal is not built for a rank of the ladder pipeline (hens_set_mh_proposal(-1, ...) returns to the stretch move)");
     if (!c->cfg.tempered || c->T < 2) return fail(c, HENS_ERR_STATE, "the ladder pipeline needs a tempered ladder");
     if (nranks < 1 || nranks > PIPE_MAX_RANKS || my_rank < 0 || my_rank >= nranks)
         return fail(c, HENS_ERR_INVALID, "nranks must be in [1, %d] and my_rank inside it", PIPE_MAX_RANKS);

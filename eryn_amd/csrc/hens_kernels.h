@@ -116,8 +116,9 @@ __device__ __forceinline__ uint32_t prp_inv(uint32_t y, const uint32_t* k, int b
 
 // (the PT helpers that use these follow the enum)
 enum : uint32_t { PURPOSE_STRETCH = 0, PURPOSE_STRETCH_ACC = 2, PURPOSE_SPLIT = 8, PURPOSE_PTPERM = 9,
-                  PURPOSE_PTU = 10, PURPOSE_MH_ACC = 11, PURPOSE_MH_NORMAL = 12, PURPOSE_MOVE = 13 };
-enum { MH_ISO = 0, MH_DIAG = 1, MH_FULL = 2 };
+                  PURPOSE_PTU = 10, PURPOSE_MH_ACC = 11, PURPOSE_MH_NORMAL = 12, PURPOSE_MOVE = 13,
+                  PURPOSE_DIST = 14 };          // DistributionGenerate's proposal, one call per coordinate: PURPOSE_DIST | d << 8 (hens_dist.h)
+enum { MH_ISO = 0, MH_DIAG = 1, MH_FULL = 2, MH_DIST = 3 };   // (MH_DIST: hens_set_dist_proposal occupies the context's one MH slot)
 
 // Philox-mode PT draws: column c of the cascade meets slot pt_slot(t, c) of global rung t - every rung its own keyed
 // permutation, i.e. pair (i, i-1) is matched through two permutations like the reference's (tempering.py:526-532) - and
@@ -474,6 +475,26 @@ __device__ __forceinline__ double prior_term(const PriorTerm& t, double q) {
         return (-(y * y) / 2.0 - NORM_PDF_LOGC) - t.c2;
     }
     return t.c0;
+}
+// A draw FROM one term out of the four words of one Philox call - the birth of a leaf coordinate from its prior (hens_rj.h; the prior
+// is the birth proposal, distgenrj.py:199-214) and a coordinate of DistributionGenerate's proposal (hens_dist.h; distgen.py:97):
+//   uniform      u (hi - lo) + lo, u = u01(x, y)                                                        (prior.py:60-66)
+//   log-uniform  exp(u (log b - log a) + log a), the same u                                             (scipy.stats.loguniform.rvs)
+//   normal       loc + scale z, z = sqrt(-2 log(r)) cos(2 pi v): Box-Muller in full double precision, r = 1 - u01(x, y) in (0, 1],
+//                v = u01(z, w); library log / sqrt / sincospi.  (Not the 32-bit-radius normals of the in-model step: this draw's density
+//                is the move's Hastings factor, and a 32-bit radius ends the tails at 6.7 sigma.)
+__device__ __forceinline__ double rj_birth_value(const u4 e, const int pk, const double lo, const double hi, const double c0, const double c1) {
+    const double u = u01(e.x, e.y);
+    if (pk == PRIOR_LOG_UNIFORM) {
+        const double la = log(lo);
+        return exp(u * (log(hi) - la) + la);
+    }
+    if (pk == PRIOR_NORMAL) {
+        double sn, cs;
+        sincospi(2.0 * u01(e.z, e.w), &sn, &cs);
+        return c0 + c1 * (sqrt(-2.0 * log(1.0 - u)) * cs);
+    }
+    return u * (hi - lo) + lo;
 }
 // the sum over one row held at `qrow` (stride 1), by ONE lane, in the specified order
 __device__ __forceinline__ double prior_sum(const PriorTerm* __restrict__ terms, const double* qrow, int D) {

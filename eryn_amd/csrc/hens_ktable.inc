@@ -1,7 +1,7 @@
 // hens_ktable.inc - body of a per-likelihood kernel translation unit: define HENS_KT_LIKE (LIKE_DENSE ...) and HENS_KT_NAME
 // (dense ...) and include.  See hens_ktable.h.  HENS_KT_PART (from the build) halves a unit once more: 0 = the half-step kernels
 // (k_stretch_fast, k_stretch), 1 = the fused ones (k_split1_pt, k_iter), 2 = k_stretch_prior (hens_prior.h: a unit of its own, so that
-// the units of the kernels that were there before compile to the code they compiled to); undefined = all.
+// the units of the kernels that were there before compile to the code they compiled to), 3 = k_dist (hens_dist.h: likewise); undefined = all.
 #include "hens_kernels.h"
 #include "hens_iter.h"
 #include "hens_tile2.h"
@@ -75,6 +75,23 @@ const void* KT(ktab_stretch_prior_)(int mode, int D) {
         case MODE_MH: return kt_prior_mode<MODE_MH>(D);
     }
     return nullptr;
+}
+#endif
+#if !defined(HENS_KT_PART) || HENS_KT_PART == 3
+}  // namespace hens
+#include "hens_dist.h"
+namespace hens {
+const void* KT(ktab_dist_)(int D) {
+    constexpr int L = HENS_KT_LIKE;
+#ifdef HENS_DEV_BUILD
+    (void)D;
+    return nullptr;            // (a dev build carries no DistributionGenerate launch)
+#else
+#define KT_DIST(DT, NW) if (D == DT) return KPTR(k_dist<DT, L, NW>);
+    KT_DIST(32, 8) KT_DIST(64, 8) KT_DIST(16, 4) KT_DIST(8, 4) KT_DIST(128, 8)
+#undef KT_DIST
+    return nullptr;
+#endif
 }
 #endif
 #if !defined(HENS_KT_PART) || HENS_KT_PART == 0

@@ -272,24 +272,7 @@ __device__ __forceinline__ double rj_birth_coord(uint64_t seed, uint64_t it, uin
     return u01(e.x, e.y) * (hi - lo) + lo;
 }
 // ... from its prior term (hens_rj_set_prior_terms; the prior is the birth proposal, distgenrj.py:199-214) out of the same call's words:
-//   uniform      u (hi - lo) + lo, u = u01(x, y)                                                        (prior.py:60-66)
-//   log-uniform  exp(u (log b - log a) + log a), the same u                                             (scipy.stats.loguniform.rvs)
-//   normal       loc + scale z, z = sqrt(-2 log(r)) cos(2 pi v): Box-Muller in full double precision, r = 1 - u01(x, y) in (0, 1],
-//                v = u01(z, w); library log / sqrt / sincospi.  (Not the 32-bit-radius normals of the in-model step: this draw's density
-//                is the move's Hastings factor, and a 32-bit radius ends the tails at 6.7 sigma.)
-__device__ __forceinline__ double rj_birth_value(const u4 e, const int pk, const double lo, const double hi, const double c0, const double c1) {
-    const double u = u01(e.x, e.y);
-    if (pk == PRIOR_LOG_UNIFORM) {
-        const double la = log(lo);
-        return exp(u * (log(hi) - la) + la);
-    }
-    if (pk == PRIOR_NORMAL) {
-        double sn, cs;
-        sincospi(2.0 * u01(e.z, e.w), &sn, &cs);
-        return c0 + c1 * (sqrt(-2.0 * log(1.0 - u)) * cs);
-    }
-    return u * (hi - lo) + lo;
-}
+// rj_birth_value (hens_kernels.h, beside prior_term: k_dist of hens_dist.h draws its proposals with the same function).
 // accept uniform of the in-model (mode 1) / birth-death (mode 2) move: mh.py:157, rj.py:332
 __device__ __forceinline__ double rj_accept_uniform(uint64_t seed, uint64_t it, uint32_t wid, int mode, int branch) {
     const u4 d = rj_philox(seed, it, wid, rj_acc_key(mode, branch));

@@ -482,6 +482,27 @@ class HipEnsemble(ChainStoreCalls):
             scale = full
         check(self.lib.hens_set_mh_proposal(self.ctx, k, ptr(scale), float(weight)), self.ctx)
 
+    # -- DistributionGenerate (include/hipensemble.h: hens_set_dist_proposal, hens_dist_step) ------------
+    def set_dist_proposal(self, terms, weight):
+        """The generator of the independence proposal into the context's one MH slot: ``terms`` is anything ``prior_spec`` reads
+        (a ``ProbDistContainer``, its dict, a ``prior_terms()`` dict), ``weight`` the probability that an iteration of ``step()``
+        runs this move.  ``set_mh_proposal`` replaces it and it replaces ``set_mh_proposal``; ``set_mh_proposal(None, ...)``
+        switches either off."""
+        self._move_cfg = None
+        spec = prior_spec(terms, self.D)
+        check(self.lib.hens_set_dist_proposal(self.ctx, *map(ptr, term_arrays(spec.terms, self.RW)), float(weight)), self.ctx)
+
+    def dist_step(self, q, u_acc, want_factors=False):
+        """One full-ensemble independence proposal with the caller's points ``q[Tl, W, D]`` and accept uniforms; returns the accept
+        mask ``[Tl, W]``, with ``want_factors`` also the Hastings factors ``logq(old) - logq(new)``."""
+        self.state_epoch += 1
+        q = self._pad(np.ascontiguousarray(q, dtype=np.float64).reshape(self.Tl, self.W, self.D))
+        u_acc = np.ascontiguousarray(u_acc, dtype=np.float64).reshape(self.Tl, self.W)
+        keep = np.empty((self.Tl, self.W), dtype=np.uint8)
+        fac = np.empty((self.Tl, self.W)) if want_factors else None
+        check(self.lib.hens_dist_step(self.ctx, ptr(q), ptr(u_acc), ptr(keep), ptr(fac)), self.ctx)
+        return (keep.astype(bool), fac) if want_factors else keep.astype(bool)
+
     def mh_counters(self):
         acc = np.zeros((self.Tl, self.W))
         n = C.c_int64(0)

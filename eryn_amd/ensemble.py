@@ -14,7 +14,8 @@ import numpy as np
 from .backend import Backend, DeviceBackend
 from .engine import HipEnsemble
 from .model import Model
-from .moves import DeviceMove, GaussianMove, MHMove, StretchMove, TemperatureControl
+from .moves import DeviceMove, DistributionGenerate, GaussianMove, MHMove, StretchMove, TemperatureControl
+from .moves.device import mh_slot_key, push_mh_slot
 from .periodic import PeriodicContainer, period_vector
 from .prior import prior_spec
 from .state import DeviceState, State
@@ -110,7 +111,7 @@ class EnsembleSampler:
                       stop_adaptation=tc.stop_adaptation)
         for m in self.moves:
             if not isinstance(m, DeviceMove):
-                raise NotImplementedError("only eryn_amd.moves.StretchMove / GaussianMove run on the device path")
+                raise NotImplementedError("only eryn_amd.moves.StretchMove / GaussianMove / DistributionGenerate run on the device path")
         stretch_moves = [m for m in self.moves if isinstance(m, StretchMove)]
         # the W >= 2 ndim guard belongs to the red-blue move (red_blue.py:108-114): without one it does not apply
         live = any(m.live_dangerously for m in stretch_moves) or not stretch_moves
@@ -132,13 +133,14 @@ class EnsembleSampler:
             m.attach_engine(self.engine, self._resident)
             m.trust_resident = True
             m.accepted = np.zeros((self.ntemps, self.nwalkers))
-        # device-side draws (rng="philox"): at most one stretch move and one Gaussian MH move, mixed by weight
+        # device-side draws (rng="philox"): at most one stretch move and one MH move (Gaussian or DistributionGenerate), mixed by weight
         self._philox_moves = None
         if rng == "philox":
             mh = [(m, w) for m, w in zip(self.moves, self.weights) if isinstance(m, MHMove)]
             st = [(m, w) for m, w in zip(self.moves, self.weights) if isinstance(m, StretchMove)]
-            if len(mh) > 1 or len(st) > 1 or any(not isinstance(m, GaussianMove) for m, _ in mh):
-                raise NotImplementedError("rng='philox' mixes at most one StretchMove with one GaussianMove")
+            if len(mh) > 1 or len(st) > 1 or any(not isinstance(m, (GaussianMove, DistributionGenerate)) for m, _ in mh):
+                raise NotImplementedError("rng='philox' mixes at most one StretchMove with one GaussianMove or one DistributionGenerate "
+                                          "(the device context has one MH slot)")
             self._mh_weight = float(mh[0][1]) if mh else 0.0
             self._mh_pushed = None
             if mh:
@@ -279,12 +281,13 @@ class EnsembleSampler:
         return state, thin_by
 
     def _push_mh_proposal(self, mh_move):
-        """Hand the Gaussian move's proposal to the device if it differs from what the device holds (construction; a ``tune`` hook
-        that rescales the move, ensemble.py:983-984 - the reference's hook mutates the move object the next proposal reads)."""
-        kind, scale = mh_move.device_proposal()
-        key = (kind, np.asarray(scale, dtype=np.float64).tobytes())
+        """Hand the MH move's proposal - a Gaussian move's scale, a DistributionGenerate's terms - to the device if it differs from
+        what the device holds (construction; a ``tune`` hook that rescales the move, ensemble.py:983-984 - the reference's hook
+        mutates the move object the next proposal reads)."""
+        proposal = mh_move.device_proposal()
+        key = mh_slot_key(proposal)
         if key != self._mh_pushed:
-            self.engine.set_mh_proposal(kind, scale, self._mh_weight)
+            push_mh_slot(self.engine, proposal, self._mh_weight)
             self._mh_pushed = key
 
     def philox_checkpoint(self):

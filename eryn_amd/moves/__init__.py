@@ -2,6 +2,7 @@ from .move import Move
 from .device import DeviceMove
 from .stretch import StretchMove
 from .gaussian import GaussianMove, MHMove
+from .distgen import DistributionGenerate
 from .tempering import TemperatureControl, make_ladder
 
 __all__ = ["Move", "DeviceMove", "StretchMove", "GaussianMove", "MHMove", "TemperatureControl", "make_ladder"]

@@ -195,12 +195,9 @@ class DeviceMove(Move):
         tc = self.temperature_control
         self._apply_periodic(eng, name, D)
         self._upload_if_needed(eng, state, br)
-        want = ("mh",) + tuple(np.asarray(v).tobytes() if i else v for i, v in enumerate(mh_proposal)) if mh_proposal else ("stretch",)
+        want = ("mh",) + mh_slot_key(mh_proposal) if mh_proposal else ("stretch",)
         if getattr(eng, "_move_cfg", None) != want:          # which move the context's next iteration runs (weight 1: no mix inside)
-            if mh_proposal:
-                eng.set_mh_proposal(mh_proposal[0], mh_proposal[1], 1.0)
-            else:
-                eng.set_mh_proposal(None, None, 0.0)
+            push_mh_slot(eng, mh_proposal, 1.0)
             eng._move_cfg = want
         self._bump(eng)
         acc, swaps, betas = eng.step_report(1, 1)
@@ -231,6 +228,24 @@ class DeviceMove(Move):
                         betas=None if tc is None else tc.betas, random_state=state.random_state)
         self._set_resident(out)
         return out, accepted
+
+
+# The context's one MH slot as a move describes it (``device_proposal()``): ("iso" | "diag" | "full", scale) of a GaussianMove,
+# ("dist", prior_terms dict) of a DistributionGenerate, None for the stretch move alone.
+def mh_slot_key(proposal):
+    kind, what = proposal
+    if kind == "dist":
+        return (kind,) + tuple(np.asarray(what[k]).tobytes() for k in sorted(what))
+    return kind, np.asarray(what, dtype=np.float64).tobytes()
+
+
+def push_mh_slot(eng, proposal, weight):
+    if proposal is None:
+        eng.set_mh_proposal(None, None, 0.0)
+    elif proposal[0] == "dist":
+        eng.set_dist_proposal(proposal[1], weight)
+    else:
+        eng.set_mh_proposal(proposal[0], proposal[1], weight)
 
 
 def _swap_draws(tc, T, W):

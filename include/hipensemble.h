@@ -452,6 +452,39 @@ int hens_set_mh_proposal(hens_ctx* ctx, int32_t kind, const double* scale, doubl
 /* accept counts [Tl][W] and number of MH proposals so far (Move.accepted / num_proposals of the MH move). */
 int hens_get_mh_counters(hens_ctx* ctx, double* accepted, int64_t* num_proposals);
 
+/* ---- Draw-from-distribution proposals: DistributionGenerate (distgen.py:10-104) -----------------------
+ * The independence proposal: every walker of every resident rung is proposed a fresh point from a generator of one
+ * distribution per parameter (distgen.py:97) and carries the Hastings factor
+ *   factors = (0.0 + logq(old)) + (-logq(new))                                     (distgen.py:84,94,100)
+ * into MHMove.propose's accept test (mh.py:155-157); logq is the generator's log-density, its terms added in ascending
+ * parameter order from 0.0 (prior.py:364-383), -inf outside a support - an old point outside the generator is never moved.
+ * One launch (csrc/hens_dist.h), rows updated in place in either state form.
+ *
+ * hens_set_dist_proposal: the generator as terms with hens_set_prior_terms' meaning (kind / lo / hi / c0 / c1 / c2, each [D];
+ * the pads of a padded row as there).  A distribution one draws from needs a finite uniform support (the rule and the texts of
+ * hens_rj_set_prior_terms).  The generator occupies the context's ONE MH slot: it replaces what hens_set_mh_proposal set, and
+ * hens_set_mh_proposal replaces it; hens_set_mh_proposal(-1, ...) stays the one "stretch only" call.  With probability `weight`
+ * an iteration of hens_step is this move (the weighted move choice, the MH counters and their marks, hens_step_report and the
+ * chain store count it as they count the Gaussian move).  Device draws: coordinate d of walker wid = global rung * W + walker in
+ * iteration `iter` comes from ONE Philox4x32-10 call, counter (iter lo, iter hi, wid, 14 | d << 8), key = the seed, through the
+ * function that draws a leaf's birth (uniform u (hi - lo) + lo; log-uniform exp(u (log hi - log lo) + log lo); normal
+ * loc + scale sqrt(-2 log(1 - u)) cos(2 pi v) in double precision); a uniform or log-uniform draw is clamped into [lo, hi]
+ * (rounding can put exp(log lo) an ulp below lo, where logq(new) would be -inf).  The accept uniform is the MH move's.
+ * Periodic parameters do not enter the move (the reference neither measures a distance nor wraps here).
+ * Refused: a leaf-packing context, a host-callable likelihood, row widths other than 8 / 16 / 32 / 64 / 128 after padding
+ * (HENS_ERR_UNSUPPORTED); a rank of the ladder pipeline (HENS_ERR_STATE; hens_pipe_init after the move is set:
+ * HENS_ERR_UNSUPPORTED); a weight outside [0, 1] or a null array (HENS_ERR_INVALID).
+ *
+ * hens_dist_step: the teacher-forced twin of hens_mh_step - one proposal with the caller's points.
+ *   q     f64 [Tl][W][D]  the proposed points (distgen.py:97: the container's rvs), taken as they are
+ *   u_acc f64 [Tl][W]     accept uniforms (mh.py:157)
+ *   keep_out u8 [Tl][W]   accept mask, or NULL
+ *   factors_out f64 [Tl][W]  the Hastings factors, or NULL
+ * HENS_ERR_STATE if no generator is set.  The PT sweep that ends the reference's propose() is hens_pt_sweep. */
+int hens_set_dist_proposal(hens_ctx* ctx, const int32_t* kind, const double* lo, const double* hi, const double* c0,
+                           const double* c1, const double* c2, double weight);
+int hens_dist_step(hens_ctx* ctx, const double* q, const double* u_acc, uint8_t* keep_out, double* factors_out);
+
 /* ---- Ladder pipeline: sharded stepping by neighbour exchange (one process per GPU) ------------------
  * No reference counterpart (the reference has no distributed path; it walks the whole ladder in one
  * process, tempering.py:598-649).  Each rank keeps a contiguous rung range (rank 0 = coldest rungs)
@@ -761,7 +794,9 @@ int hens_set_iteration(hens_ctx* ctx, int64_t iter);
  *   u_swap [T-1][W]       row j = the uniforms of pair (T-1-j, T-2-j) in column order (tempering.py:535)
  *   is_mh                 1 if the weighted move choice of that iteration (ensemble.py:971) picks the MH move
  *   mh_step [Tl][W][D], mh_u [Tl][W]   the GaussianMove step rows (gaussian.py:166-167,265-268) and accept
- *                         uniforms (mh.py:157), if hens_set_mh_proposal was called
+ *                         uniforms (mh.py:157), if hens_set_mh_proposal was called.  With hens_set_dist_proposal's
+ *                         generator in the MH slot mh_step carries the drawn POINTS q of that iteration (distgen.py:97;
+ *                         a pad coordinate reads 0) and mh_u the accept uniforms
  * Any output pointer may be NULL.  Does not touch the sampler state. */
 int hens_debug_draws(hens_ctx* ctx, int64_t iter, int32_t* own, int32_t* cw, double* u_zz, double* u_acc,
                      int32_t* pt_slot, double* u_swap, int32_t* is_mh, double* mh_step, double* mh_u);

@@ -1,0 +1,72 @@
+"""``eryn_amd.moves.DistributionGenerate`` + ``StretchMove`` under the REAL reference sampler (build container only; CPU): the
+unmodified ``eryn.ensemble.EnsembleSampler`` drives both moves through ``run_mcmc`` and must land on the chain captured from the
+reference's own moves (tests/golden/distgen/dg1_mix.npz).  As in tests/test_dropin_reference.py the device context is a stand-in with
+the same method surface whose compute is the specification (tests/dist_move.py, the pinned oracle): what is under test is the
+plugin protocol - the kernels are pinned by the -m gpu tests.
+
+Skipped where the reference tree does not exist (the GPU box)."""
+import os
+import sys
+
+import numpy as np
+
+from oracle import eryn_oracle as orc
+from tests import dist_move as dm
+from tests import prior_terms as pt
+from tests.test_dropin_reference import OracleEngine, _loglike, eryn  # noqa: F401  (eryn: the module fixture that imports the reference)
+from tests.test_prior_terms import needs_reference
+
+pytestmark = needs_reference
+
+
+class SpecEngine(OracleEngine):
+    """OracleEngine under prior terms, with the two calls the new move makes."""
+
+    def __init__(self, T, W, D, loglike, prior, **kw):
+        OracleEngine.__init__(self, T, W, D, loglike, prior["lo"], prior["hi"], **kw)
+        self.prior, self.gen = prior, None
+
+    def set_dist_proposal(self, terms, weight):
+        from eryn_amd.prior import prior_spec
+        self.gen = prior_spec(terms, self.D).terms
+        self.calls.append(("dist_proposal", weight))
+
+    def dist_step(self, q, u_acc, want_factors=False):
+        _, _, _, keep, fac = dm.dist_step(self.x, self.L, self.P, self.betas, np.asarray(q), np.asarray(u_acc), self.prior, self.gen, self.loglike)
+        return (keep, fac) if want_factors else keep
+
+
+def test_hip_distribution_generate_under_the_real_sampler(eryn, monkeypatch):  # noqa: F811
+    from eryn.ensemble import EnsembleSampler
+    from eryn_amd.likelihood import GaussianLikelihood
+    from eryn_amd.moves import DistributionGenerate, StretchMove
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
+    import make_golden_dist as mgd             # (the reference's constructors with the fixture's arguments)
+    fx = dm.load_fixture("dg1_mix")
+    prior, gen = dm.fixture_specs(fx)
+    _, gen_c = dm.fixture_containers(fx)
+    T, W, D, n = int(fx["T"]), int(fx["W"]), int(fx["D"]), int(fx["nsteps"])
+    mu, invcov = fx["mu"], fx["invcov"]
+    monkeypatch.setattr(orc, "box_log_prior", pt.box_prior_substitute(prior))
+    like = GaussianLikelihood(mu, invcov)
+    stretch = StretchMove(a=float(fx["a"]), likelihood=like, prior_box=dm.fixture_containers(fx)[0])
+    move = DistributionGenerate({"model_0": gen_c}, likelihood=like, prior_box=dm.fixture_containers(fx)[0])
+    eng = SpecEngine(T, W, D, lambda x: _loglike(x, mu, invcov), prior, a=float(fx["a"]))
+    stretch.attach_engine(eng)
+    move.attach_engine(eng)
+    np.random.seed(int(fx["seed_construct"]))
+    s = EnsembleSampler(W, D, _loglike, mgd.container(fx["prior_kind"], fx["prior_p0"], fx["prior_p1"]), args=[mu, invcov], vectorize=True,
+                        moves=[(stretch, 0.5), (move, 0.5)], tempering_kwargs=dict(ntemps=T))
+    assert move.temperature_control is s.temperature_control and move.accepted.shape == (T, W)
+    np.random.seed(int(fx["seed_run"]))
+    state = s.run_mcmc(fx["x0"], n, store=True)
+    assert np.array_equal(state.branches["model_0"].coords[:, :, 0, :], fx["all_x"][n - 1])
+    assert np.array_equal(state.log_like, fx["all_L"][n - 1]) and np.array_equal(state.log_prior, fx["all_P"][n - 1])
+    assert np.array_equal(state.betas, fx["all_betas"][n - 1])
+    assert np.array_equal(s.temperature_control.swaps_accepted, fx["all_swaps_accepted"][n - 1])
+    assert np.array_equal(move.accepted, fx["accepted_dist"]) and move.num_proposals == int(fx["num_proposals_dist"])
+    assert np.array_equal(stretch.accepted, fx["accepted_stretch"])
+    chain = s.get_chain()["model_0"]
+    for it in range(n):
+        assert np.array_equal(chain[it][:, :, 0, :], fx["all_x"][it]), f"stored step {it}"
+    assert ("dist_proposal", 1.0) in eng.calls and "upload" in eng.calls
