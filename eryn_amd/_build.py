@@ -13,8 +13,12 @@ OBJ_DIR = os.environ.get("HENS_OBJ_DIR") or os.path.join(os.path.dirname(HERE), 
 UNITS = [("hens", "hens.hip", [])] + [(f"hens_k_{k}_{part}", f"hens_k_{k}.hip", [f"-DHENS_KT_PART={part}"])
                                       for k in ("dense", "diag", "rosen") for part in (0, 1, 2, 3)]
 SOURCES = sorted({os.path.join(SRC_DIR, u[1]) for u in UNITS})
-DEPS = SOURCES + [os.path.join(SRC_DIR, h) for h in ("hens_kernels.h", "hens_rj.h", "hens_iter.h", "hens_tile2.h", "hens_aql.h", "hens_ktable.h", "hens_ktable.inc", "hens_prior.h", "hens_dist.h", "hens_chain.h", "hens_chain_stats.h", "hens_rj_chain.h", "hens_rj_chain_stats.h", "hens_chain_host.h", "hens_prior_host.h")] + [
-    os.path.join(os.path.dirname(HERE), "include", "hipensemble.h")]
+# what a unit includes, by kind of unit: every unit, hens.hip alone, the kernel units alone (they see neither hens.hip nor the RJ / AQL headers)
+HDRS_ALL = ("hens_kernels.h", "hens_iter.h", "hens_tile2.h", "hens_ktable.h", "hens_prior.h", "hens_dist.h", "hens_prior_host.h")
+HDRS_HOST = ("hens_rj.h", "hens_aql.h", "hens_chain.h", "hens_chain_stats.h", "hens_rj_chain.h", "hens_rj_chain_stats.h", "hens_chain_host.h")
+HDRS_KERNEL = ("hens_ktable.inc",)
+API_HEADER = os.path.join(os.path.dirname(HERE), "include", "hipensemble.h")
+DEPS = SOURCES + [os.path.join(SRC_DIR, h) for h in HDRS_ALL + HDRS_HOST + HDRS_KERNEL] + [API_HEADER]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-Wno-cuda-compat"] + os.environ.get("HENS_BUILD_DEFS", "").split()   # (inline __global__: see hens_kernels.h)
 
 
@@ -51,11 +55,9 @@ def build(force=False, verbose=False):
     for name, src, defs in UNITS:
         obj = os.path.join(OBJ_DIR, name + ".o")
         cmd = [hipcc] + FLAGS + defs + include + ["-c", os.path.join(SRC_DIR, src), "-o", obj]
-        # an object is kept if it is newer than everything its unit includes (the kernel units see neither hens.hip nor the RJ / AQL
-        # headers) and was made by the same command
-        deps = [os.path.join(SRC_DIR, src), os.path.join(os.path.dirname(HERE), "include", "hipensemble.h"), os.path.abspath(__file__)] + [
-            os.path.join(SRC_DIR, h) for h in (("hens_kernels.h", "hens_iter.h", "hens_tile2.h", "hens_ktable.h", "hens_prior.h", "hens_dist.h", "hens_prior_host.h") +
-                                               (("hens_rj.h", "hens_aql.h", "hens_chain.h", "hens_chain_stats.h", "hens_rj_chain.h", "hens_rj_chain_stats.h", "hens_chain_host.h") if name == "hens" else ("hens_ktable.inc",)))]
+        # an object is kept if it is newer than everything its unit includes and was made by the same command
+        deps = [os.path.join(SRC_DIR, src), API_HEADER, os.path.abspath(__file__)] + [
+            os.path.join(SRC_DIR, h) for h in HDRS_ALL + (HDRS_HOST if name == "hens" else HDRS_KERNEL)]
         stamp = obj + ".cmd"
         fresh = (os.path.exists(obj) and os.path.exists(stamp) and open(stamp).read() == " ".join(cmd) and
                  all(os.path.getmtime(d) <= os.path.getmtime(obj) for d in deps))
@@ -66,7 +68,7 @@ def build(force=False, verbose=False):
             print(" ".join(cmd), flush=True)
         jobs.append((obj, cmd, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True), stamp))
     failed = []
-    for obj, cmd, proc, stamp in jobs:     # (10 compilers side by side: about 1.5 GB each at their peak)
+    for obj, cmd, proc, stamp in jobs:     # (13 compilers side by side: about 1.5 GB each at their peak)
         if proc is None:
             continue
         out, _ = proc.communicate()

@@ -56,6 +56,17 @@ struct DrawBuf {                     // one batch of planned iterations
 };
 constexpr int KEY_WINDOW = 1024;     // iterations of round keys planned at once for the two-launch iteration (hens_ctx_impl::ikeys)
 
+// D per-coordinate terms and their supports on the device, lo[D] hi[D] terms[D] in one allocation (the form k_stretch reads with
+// StretchArgs::prior_on): the context's prior terms, and the generator of MH_DIST
+struct TermBlock {
+    double* p = nullptr;      // [6 D] doubles, D the context's row width
+    int D = 0;
+    const double* lo() const { return p; }
+    const double* hi() const { return p + D; }
+    const PriorTerm* terms() const { return reinterpret_cast<const PriorTerm*>(p + 2 * (size_t)D); }
+    int upload(struct hens_ctx_impl* c, const double* lo, const double* hi, const PriorTerm* terms);      // allocates on first use; asynchronous
+};
+
 struct hens_ctx_impl {
     hens_config cfg{};
     int T = 0, W = 0, D = 0, Tl = 0, N0 = 0;
@@ -104,7 +115,7 @@ struct hens_ctx_impl {
     double* period_buf = nullptr;
     PriorTerm* prior = nullptr;      // [D] per-parameter prior terms (hens_set_prior_terms), nullptr: the box and its constant logp_in
     PriorTerm* prior_buf = nullptr;
-    double* prior_block = nullptr;   // lo[D] hi[D] terms[D] in one allocation: what k_stretch reads with terms on (StretchArgs::prior_on)
+    TermBlock prior_block;           // what the kernels read with terms on
     double logp_in = 0.0, rosen_a = 1.0, rosen_b = 100.0;
     bool have_prior = false, have_like = false, have_state = false, have_logs = false;
 
@@ -191,7 +202,7 @@ struct hens_ctx_impl {
     uint32_t* accepted_mark = nullptr;     // [2][Tl][W] hens_step_marked: stretch / MH accept counts in front of the call's last iterations
     bool mark_valid = false, mark_mh = false;
     int mh_kind = -1;                      // -1: hens_step runs the stretch move only; MH_DIST: the slot holds hens_set_dist_proposal's generator
-    double* dist_block = nullptr;          // the generator of MH_DIST: lo[D] hi[D] terms[D] in one allocation (DistArgs::glo / ghi / gterms)
+    TermBlock dist_block;                  // the generator of MH_DIST (DistArgs::glo / ghi / gterms)
     double* dist_factors = nullptr;        // [Tl][W] hens_dist_step's factors_out staging
     double mh_weight = 0.0;                // probability that an iteration of hens_step is an MH proposal
     int64_t num_proposals_mh = 0;
@@ -308,6 +319,16 @@ template <typename Tp>
 int dalloc(hens_ctx_impl* c, Tp** p, size_t n) {
     HIPCHK(c, hipMalloc(reinterpret_cast<void**>(p), std::max<size_t>(n, 1) * sizeof(Tp)));
     c->allocs.push_back(*p);
+    return HENS_OK;
+}
+
+int TermBlock::upload(hens_ctx_impl* c, const double* lo, const double* hi, const PriorTerm* terms) {
+    D = c->D;
+    if (!p)
+        if (const int r = dalloc(c, &p, (size_t)6 * D)) return r;
+    HIPCHK(c, hipMemcpyAsync(p, lo, D * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(p + D, hi, D * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(p + 2 * (size_t)D, terms, (size_t)D * sizeof(PriorTerm), hipMemcpyHostToDevice, c->stream));
     return HENS_OK;
 }
 
@@ -525,6 +546,16 @@ int xcd_shift(const hens_ctx_impl* c, int gx) {
     return sh + 1;
 }
 
+// a launch for the HIP stream whatever the iteration's path (k_stretch_prior, k_dist, the generic k_stretch): the AQL queue set aside
+template <class Launch>
+int on_hip_stream(hens_ctx_impl* c, Launch&& launch) {
+    const bool was_aql = c->aql_now;
+    c->aql_now = false;
+    const int r = launch();
+    c->aql_now = was_aql;
+    return r;
+}
+
 int launch_stretch_like(hens_ctx_impl* c, const LikeKernels& lk, int mode, StretchArgs a, int ntiles) {
     const dim3 grid(ntiles, c->Tl);
     const int like = lk.like;
@@ -575,7 +606,6 @@ int launch_stretch_like(hens_ctx_impl* c, const LikeKernels& lk, int mode, Stret
         return launch_by_ptr(c, lk.stretch_fast(mode, c->D, pipe, per), "k_stretch_fast", grid, NW * 64, fast_lds_bytes(c->D, NW, like), false,
                              c->aql_now ? nullptr : c->ext_start, c->ext_stop, a);
     }
-    const bool was_aql = c->aql_now;           // (neither kernel below goes to the AQL queue: the HIP stream, as the generic one always did)
     // Per-parameter prior terms at a compile-time row width: k_stretch_prior (hens_prior.h) - the copying half-step with the terms
     // formed in phase B and added by the accept wave.  Periodic parameters, the other widths and Rosenbrock rows that cannot be
     // padded: the generic kernel below, which adds the same sum behind its run-time test.  HENS_PRIOR_LOG=1 (tests): which one.
@@ -585,20 +615,14 @@ int launch_stretch_like(hens_ctx_impl* c, const LikeKernels& lk, int mode, Stret
     if (kp) {
         const int NW = fast_nw(c->D);
         a.ad_on = 0;
-        c->aql_now = false;
-        const int r = launch_by_ptr(c, kp, "k_stretch_prior", grid, NW * 64, prior_lds_bytes(c->D, NW, like), false, c->ext_start, c->ext_stop, a);
-        c->aql_now = was_aql;
-        return r;
+        return on_hip_stream(c, [&] { return launch_by_ptr(c, kp, "k_stretch_prior", grid, NW * 64, prior_lds_bytes(c->D, NW, like), false, c->ext_start, c->ext_stop, a); });
     }
     int RS;
     const size_t lds = generic_lds_bytes(c->D, &RS);
     if (lds > 160 * 1024) return fail(c, HENS_ERR_UNSUPPORTED, "ndim %d exceeds the LDS row tile", c->D);
     a.RS = RS;
     a.ad_on = 0;
-    c->aql_now = false;
-    const int r = launch_by_ptr(c, lk.stretch(mode), "k_stretch", grid, 256, lds, false, c->ext_start, c->ext_stop, a);
-    c->aql_now = was_aql;
-    return r;
+    return on_hip_stream(c, [&] { return launch_by_ptr(c, lk.stretch(mode), "k_stretch", grid, 256, lds, false, c->ext_start, c->ext_stop, a); });
 }
 
 int launch_hostlike_eval(hens_ctx_impl* c, StretchArgs a, int ntiles) {
@@ -657,7 +681,7 @@ StretchArgs base_args(hens_ctx_impl* c) {
     a.accepted = c->accepted;
     a.lo = c->lo; a.hi = c->hi; a.mu = c->mu; a.prec = c->prec; a.prec_sym = c->prec_sym;
     a.period = c->period;
-    if (c->prior) { a.lo = c->prior_block; a.hi = c->prior_block + c->D; a.prior_on = 1; }
+    if (c->prior) { a.lo = c->prior_block.lo(); a.hi = c->prior_block.hi(); a.prior_on = 1; }
     a.flags = c->flags;
     a.trace = (c->tracing && !c->trace_pt && !c->trace_fused) ? c->d_trace : nullptr;
     a.logp_in = c->logp_in;
@@ -1705,12 +1729,12 @@ int dist_launch(hens_ctx_impl* c, bool forced, bool want_keep, bool want_factors
     a.P = c->P[c->cur];
     a.wrec = c->packed ? c->wrec[c->cur] : nullptr;        // hens_step's record mode (slot order: no column order with an MH move set)
     a.betas = c->cfg.tempered ? c->betas[c->bcur] : nullptr;
-    a.lo = c->prior ? c->prior_block : c->lo;
-    a.hi = c->prior ? c->prior_block + c->D : c->hi;
+    a.lo = c->prior ? c->prior_block.lo() : c->lo;
+    a.hi = c->prior ? c->prior_block.hi() : c->hi;
     a.pterms = c->prior;
-    a.glo = c->dist_block;
-    a.ghi = c->dist_block + c->D;
-    a.gterms = reinterpret_cast<const PriorTerm*>(c->dist_block + 2 * (size_t)c->D);
+    a.glo = c->dist_block.lo();
+    a.ghi = c->dist_block.hi();
+    a.gterms = c->dist_block.terms();
     a.q = forced ? c->mh_step : nullptr;
     a.lu = forced ? c->mh_lu : nullptr;
     a.accepted = c->accepted_mh;
@@ -1726,11 +1750,8 @@ int dist_launch(hens_ctx_impl* c, bool forced, bool want_keep, bool want_factors
     const int NW = fast_nw(c->D);
     hipEvent_t e0 = nullptr, e1 = nullptr;
     time_launch(c, tm, 0, e0, e1);
-    const bool was_aql = c->aql_now;                     // (never on the AQL queue: aql_able requires mh_kind < 0)
-    c->aql_now = false;
-    const int r = launch_by_ptr(c, fn, "k_dist", dim3((c->W + TILE - 1) / TILE, c->Tl), NW * 64, prior_lds_bytes(c->D, NW, lk->like), false, e0, e1, a);
-    c->aql_now = was_aql;
-    if (r) return r;
+    const dim3 grid((c->W + TILE - 1) / TILE, c->Tl);      // (never on the AQL queue: aql_able requires mh_kind < 0)
+    if (const int r = on_hip_stream(c, [&] { return launch_by_ptr(c, fn, "k_dist", grid, NW * 64, prior_lds_bytes(c->D, NW, lk->like), false, e0, e1, a); })) return r;
     c->num_proposals_mh += 1;
     return HENS_OK;
 }
@@ -1769,10 +1790,11 @@ double move_uniform(uint64_t seed, uint64_t it) {
     const uint64_t v = ((uint64_t)c0 << 32) | c1;
     return (double)(v >> 11) * (1.0 / 9007199254740992.0);
 }
-bool iteration_is_mh(const hens_ctx_impl* c) {
+bool iteration_is_mh(const hens_ctx_impl* c, uint64_t iter) {
     if (c->mh_kind < 0 || c->mh_weight <= 0.0) return false;
-    return c->mh_weight >= 1.0 || move_uniform(c->cfg.seed, c->iter) < c->mh_weight;
+    return c->mh_weight >= 1.0 || move_uniform(c->cfg.seed, iter) < c->mh_weight;
 }
+bool iteration_is_mh(const hens_ctx_impl* c) { return iteration_is_mh(c, c->iter); }
 
 // ---- reversible-jump leaf packing ---------------------------------------------------------------------------------------
 // RjArgs::ctab / cbn from the model (hens_rj_set_model, hens_rj_set_mh_scale): per record coordinate its box, step scale, the
@@ -2391,15 +2413,7 @@ int hens_set_prior_terms(hens_ctx* ctx, const int32_t* kind, const double* lo, c
         if (r) return r;
         c->prior_buf = buf;
     }
-    if (!c->prior_block) {                   // (each pointer on its own: a failed second allocation is not skipped the next time)
-        double* blk = nullptr;
-        const int r = dalloc(c, &blk, (size_t)6 * D);
-        if (r) return r;
-        c->prior_block = blk;
-    }
-    HIPCHK(c, hipMemcpyAsync(c->prior_block, lo, D * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->prior_block + D, hi, D * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->prior_block + 2 * (size_t)D, terms.data(), (size_t)D * sizeof(PriorTerm), hipMemcpyHostToDevice, c->stream));
+    if (const int r = c->prior_block.upload(c, lo, hi, terms.data())) return r;
     HIPCHK(c, hipMemcpyAsync(c->lo, lo, D * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->hi, hi, D * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->prior_buf, terms.data(), (size_t)D * sizeof(PriorTerm), hipMemcpyHostToDevice, c->stream));
@@ -3668,10 +3682,7 @@ int hens_debug_draws(hens_ctx* ctx, int64_t iter, int32_t* own, int32_t* cw, dou
     SETTLE(c, NEED_DEVICE);
     const size_t TW = (size_t)c->Tl * c->W;
     DeviceScratch sc;
-    const bool mh = [&] {
-        if (c->mh_kind < 0 || c->mh_weight <= 0.0) return false;
-        return c->mh_weight >= 1.0 || move_uniform(c->cfg.seed, (uint64_t)iter) < c->mh_weight;
-    }();
+    const bool mh = iteration_is_mh(c, (uint64_t)iter);
     if (is_mh) *is_mh = mh ? 1 : 0;
     if (own || cw || u_zz || u_acc) {     // the stretch plan of that iteration, exactly as hens_step's plan kernel makes it
         PlanArgs pa{};
@@ -3711,9 +3722,8 @@ int hens_debug_draws(hens_ctx* ctx, int64_t iter, int32_t* own, int32_t* cw, dou
         double* dq = sc.grab<double>(TW * c->D);
         double* du = sc.grab<double>(TW);
         if (!dq || !du) return fail(c, HENS_ERR_HIP, "hens_debug_draws: out of device memory");
-        hipLaunchKernelGGL(k_dist_draw, dim3(grid_for((int64_t)TW * c->D)), dim3(256), 0, c->stream, dq, du, c->dist_block, c->dist_block + c->D,
-                           reinterpret_cast<const PriorTerm*>(c->dist_block + 2 * (size_t)c->D), c->cfg.seed, (uint64_t)iter, c->Tl, c->W, c->D,
-                           (int)c->cfg.rung_begin);
+        hipLaunchKernelGGL(k_dist_draw, dim3(grid_for((int64_t)TW * c->D)), dim3(256), 0, c->stream, dq, du, c->dist_block.lo(), c->dist_block.hi(),
+                           c->dist_block.terms(), c->cfg.seed, (uint64_t)iter, c->Tl, c->W, c->D, (int)c->cfg.rung_begin);
         HIPCHK(c, hipGetLastError());
         if (mh_step) HIPCHK(c, hipMemcpyAsync(mh_step, dq, TW * c->D * 8, hipMemcpyDeviceToHost, c->stream));
         if (mh_u) HIPCHK(c, hipMemcpyAsync(mh_u, du, TW * 8, hipMemcpyDeviceToHost, c->stream));
@@ -4848,28 +4858,35 @@ int hens_pt_finish_sharded(hens_ctx* ctx, int64_t n_recv) {
 }
 
 // ---- Metropolis-Hastings proposals ----------------------------------------------------------
-int hens_mh_step(hens_ctx* ctx, const double* step, const double* u_acc, uint8_t* keep_out) {
-    hens_ctx_impl* c = enter(ctx);
+// The teacher-forced MH entry points: the caller's payload ([Tl][W][D]: steps for hens_mh_step, points for hens_dist_step, `dist`) and
+// accept uniforms go to mh_step / mh_u, the move's launch proposes from them, keep_out (and hens_dist_step's factors) are copied out.
+static int forced_mh_step(hens_ctx_impl* c, bool dist, const double* payload, const double* u_acc, uint8_t* keep_out, double* factors_out) {
     int r = ready(c, true);
     if (r) return r;
-    if (!step || !u_acc) return fail(c, HENS_ERR_INVALID, "null argument");
-    if (c->cfg.likelihood_kind == HENS_LIKE_HOST) return fail(c, HENS_ERR_UNSUPPORTED, "hens_mh_step needs a device likelihood");
-    if (c->expect_split != 0) return fail(c, HENS_ERR_STATE, "hens_mh_step between split 0 and split 1");
+    if (!payload || !u_acc) return fail(c, HENS_ERR_INVALID, "null argument");
+    if (dist && c->mh_kind != MH_DIST) return fail(c, HENS_ERR_STATE, "no generator set (hens_set_dist_proposal)");
+    if (!dist && c->cfg.likelihood_kind == HENS_LIKE_HOST) return fail(c, HENS_ERR_UNSUPPORTED, "hens_mh_step needs a device likelihood");
+    if (c->expect_split != 0) return fail(c, HENS_ERR_STATE, "%s between split 0 and split 1", dist ? "hens_dist_step" : "hens_mh_step");
     if (c->pt_pending) return fail(c, HENS_ERR_STATE, "sharded PT exchange in flight");
     if ((r = counter_room(c, 1))) return r;
     SETTLE(c, NEED_DEVICE | NEED_FIELDS);
     if ((r = ensure_mh_buffers(c))) return r;
     SETTLE(c, NEED_LADDER);
     const size_t TW = (size_t)c->Tl * c->W;
-    HIPCHK(c, hipMemcpyAsync(c->mh_step, step, TW * c->D * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->mh_step, payload, TW * c->D * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->mh_u, u_acc, TW * 8, hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(k_mh_prep, dim3(grid_for((int64_t)TW)), dim3(256), 0, c->stream, c->mh_u, c->mh_lu, (int64_t)TW);
     c->win_count = 0;
-    if ((r = mh_launch(c, true, nullptr))) return r;
+    if ((r = dist ? dist_launch(c, true, true, factors_out != nullptr, nullptr) : mh_launch(c, true, nullptr))) return r;
     if (keep_out) HIPCHK(c, hipMemcpyAsync(keep_out, c->mh_keep, TW, hipMemcpyDeviceToHost, c->stream));
+    if (factors_out) HIPCHK(c, hipMemcpyAsync(factors_out, c->dist_factors, TW * 8, hipMemcpyDeviceToHost, c->stream));
     if ((r = check_flags(c, true))) return r;
     if (!has_pt(c)) c->iter += 1;
     return HENS_OK;
+}
+
+int hens_mh_step(hens_ctx* ctx, const double* step, const double* u_acc, uint8_t* keep_out) {
+    return forced_mh_step(enter(ctx), false, step, u_acc, keep_out, nullptr);
 }
 
 int hens_set_mh_proposal(hens_ctx* ctx, int32_t kind, const double* scale, double weight) {
@@ -4920,19 +4937,12 @@ int hens_set_dist_proposal(hens_ctx* ctx, const int32_t* kind, const double* lo,
     SETTLE(c, NEED_DEVICE | NEED_FIELDS | NEED_LADDER);
     int r = ensure_mh_buffers(c);
     if (r) return r;
-    if (!c->dist_block) {
-        double* blk = nullptr;
-        if ((r = dalloc(c, &blk, (size_t)6 * D))) return r;
-        c->dist_block = blk;
-    }
     if (!c->dist_factors) {
         double* f = nullptr;
         if ((r = dalloc(c, &f, (size_t)c->Tl * c->W))) return r;
         c->dist_factors = f;
     }
-    HIPCHK(c, hipMemcpyAsync(c->dist_block, lo, D * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->dist_block + D, hi, D * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->dist_block + 2 * (size_t)D, terms.data(), (size_t)D * sizeof(PriorTerm), hipMemcpyHostToDevice, c->stream));
+    if ((r = c->dist_block.upload(c, lo, hi, terms.data()))) return r;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->mh_kind = MH_DIST;
     c->mh_weight = weight;
@@ -4941,28 +4951,7 @@ int hens_set_dist_proposal(hens_ctx* ctx, const int32_t* kind, const double* lo,
 
 // the teacher-forced twin of hens_mh_step: the caller's points and accept uniforms
 int hens_dist_step(hens_ctx* ctx, const double* q, const double* u_acc, uint8_t* keep_out, double* factors_out) {
-    hens_ctx_impl* c = enter(ctx);
-    int r = ready(c, true);
-    if (r) return r;
-    if (!q || !u_acc) return fail(c, HENS_ERR_INVALID, "null argument");
-    if (c->mh_kind != MH_DIST) return fail(c, HENS_ERR_STATE, "no generator set (hens_set_dist_proposal)");
-    if (c->expect_split != 0) return fail(c, HENS_ERR_STATE, "hens_dist_step between split 0 and split 1");
-    if (c->pt_pending) return fail(c, HENS_ERR_STATE, "sharded PT exchange in flight");
-    if ((r = counter_room(c, 1))) return r;
-    SETTLE(c, NEED_DEVICE | NEED_FIELDS);
-    if ((r = ensure_mh_buffers(c))) return r;
-    SETTLE(c, NEED_LADDER);
-    const size_t TW = (size_t)c->Tl * c->W;
-    HIPCHK(c, hipMemcpyAsync(c->mh_step, q, TW * c->D * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->mh_u, u_acc, TW * 8, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_mh_prep, dim3(grid_for((int64_t)TW)), dim3(256), 0, c->stream, c->mh_u, c->mh_lu, (int64_t)TW);
-    c->win_count = 0;
-    if ((r = dist_launch(c, true, true, factors_out != nullptr, nullptr))) return r;
-    if (keep_out) HIPCHK(c, hipMemcpyAsync(keep_out, c->mh_keep, TW, hipMemcpyDeviceToHost, c->stream));
-    if (factors_out) HIPCHK(c, hipMemcpyAsync(factors_out, c->dist_factors, TW * 8, hipMemcpyDeviceToHost, c->stream));
-    if ((r = check_flags(c, true))) return r;
-    if (!has_pt(c)) c->iter += 1;
-    return HENS_OK;
+    return forced_mh_step(enter(ctx), true, q, u_acc, keep_out, factors_out);
 }
 
 int hens_get_mh_counters(hens_ctx* ctx, double* accepted, int64_t* num_proposals) {

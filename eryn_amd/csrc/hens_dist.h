@@ -5,14 +5,13 @@
 //   factors = (0.0 + logq(old)) + (-logq(new))                                             (distgen.py:84,94,100)
 // into the accept rule every stepping kernel shares (accept_test).
 //
-// Modelled on k_stretch_prior (hens_prior.h): one workgroup = TILE (64) walkers of one rung, NW = fast_nw(D) wavefronts, lanes over
-// d at 16 B each, the same like_partials / like_prefetch calls (the FP64 matrix pipe for dense D = 32 / 64 / 128) and the same LDS
-// layout and size (prior_lds_bytes).  It has its own argument struct: StretchArgs' offsets are part of the timed kernels.
+// On k_stretch_prior's term tile (TermTile, hens_prior.h: its LDS, row passes, pair_terms, term_sum, prologue and logl): one workgroup =
+// TILE (64) walkers of one rung, NW = fast_nw(D) wavefronts.  Its own argument struct: StretchArgs' offsets are part of the timed kernels.
 //   phase A  lane-per-walker : own row, {L, P} (walker record by slot in record mode, else by field), log u          (wave 0)
 //   phase B  lanes-over-d    : the lane reads its two coordinates of the walker's own row; q is the caller's point (teacher-forced) or
 //                              the device draw (dist_draw: one Philox call per coordinate, rj_birth_value's transform, clamped into
 //                              a uniform / log-uniform support); a pad coordinate (PRIOR_NONE) keeps its value and has no term.
-//                              Up to three per-coordinate terms, each formed by prior_term from the lane's registers:
+//                              Up to three per-coordinate terms, each formed by pair_terms from the lane's registers:
 //                                B1 the generator's at the OLD coordinate, B2 the generator's at the NEW one, B3 the context's prior
 //                                at the new one (contexts with prior terms; a box keeps its ballot and its constant logp_in)
 //                              with three support tests: old row inside the generator (else logq(old) = -inf: never accepted), new
@@ -74,50 +73,28 @@ __device__ __forceinline__ double dist_draw(uint64_t seed, uint64_t it, uint32_t
 // row-wide AND of a generator support test: the lane that speaks for a valid row sets `bit` of its flag word when all its LPR lanes
 // are inside (row_verdict's ballot without the prior's bit and the non-finite report).  Every lane of the wavefront calls it.
 __device__ __forceinline__ void dist_row_all(bool ok, int LPR, int lane, bool speaks, int32_t* row_flag, int bit) {
-    const unsigned long long bad = __ballot(!ok);
-    const int gshift = lane & ~(LPR - 1);
-    const unsigned long long gmask = (LPR == 64) ? ~0ull : (((1ull << (LPR & 63)) - 1ull) << gshift);
-    if (speaks && (bad & gmask) == 0ull) atomicOr(row_flag, bit);
-}
-
-// one coordinate against one term's support; `t` its term when inside and finite, 0.0 otherwise (never read then)
-__device__ __forceinline__ bool dist_term(const PriorTerm& tm, double lo, double hi, double x, double& t) {
-    t = 0.0;
-    if (tm.kind == PRIOR_NONE) return true;
-    if (!((x >= lo) && (x <= hi))) return false;
-    t = prior_term(tm, x);
-    return fabs(t) < INFINITY;
+    const unsigned long long bad = row_ballot(!ok, LPR, lane);
+    if (speaks && bad == 0ull) atomicOr(row_flag, bit);
 }
 
 template <int DT, int LIKE, int NW>
 __global__ __launch_bounds__(NW * 64) void k_dist(const DistArgs A) {
     static_assert(DT == 8 || DT == 16 || DT == 32 || DT == 64 || DT == 128, "power-of-two row width");
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    constexpr int D = DT, RS = DT + 2, TS = DT + 1, NT = NW * 64;
-    constexpr int LPR = DT / 2;                // lanes per row, 16 B each
-    constexpr int RPP = NT / LPR;              // rows per pass
-    constexpr int NPASS = (TILE + RPP - 1) / RPP;
-    constexpr int F_IN = 1, F_KEEP = 2, F_VALID = 4, F_OLD = 16, F_NEW = 32;
-    // (k_stretch_prior's layout: prior_lds_bytes)
-    double* qtile = reinterpret_cast<double*>(smem_raw);                 // [TILE][RS] proposals
-    double* ttile = qtile + TILE * RS;                                   // [TILE][TS] terms, one kind at a time
-    double* s_part = ttile + TILE * TS + TILE;                           // [NW][TILE] (behind the [TILE] doubles that hold k_stretch_prior's zz)
-    int32_t* s_rs = reinterpret_cast<int32_t*>(s_part + NW * TILE);      // [TILE] own row
-    int32_t* s_flag = s_rs + 3 * TILE;                                   // F_* per walker of the tile
-    double* s_mu = reinterpret_cast<double*>(s_flag + TILE + 4);         // [D] dense D = 32 / 64 / 128: mu for the matrix pipe (16-byte aligned)
+    using Tile = TermTile<DT, NW>;                 // (s_zz, s_rc and s_dst stay unused: one layout, one size)
+    constexpr int D = DT, RS = Tile::RS, LPR = Tile::LPR;
+    constexpr int F_OLD = 16, F_NEW = 32;          // row-flag bits of this kernel: old / new row inside the generator's supports
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const Tile T(smem_raw, tid);
     const int tl = blockIdx.y;
     const int W = A.W;
     const int k0 = blockIdx.x * TILE;
     const bool forced = A.q != nullptr;
 
-    if constexpr (like_mf<DT, LIKE, NW>()) {
-        if (tid < DT / 2) *reinterpret_cast<double2*>(s_mu + 2 * tid) = *reinterpret_cast<const double2*>(A.mu + 2 * tid);
-    }
-    MfRegs mfr = like_prefetch<DT == 32 ? DT : 0, LIKE, NW>(lane, wv, A.prec_sym);
+    MfRegs mfr = T.template prologue<LIKE>(A, tid, lane, wv);
 
     // ---- phase A
     double lu = 0.0, Lold = 0.0, Pold = 0.0;
@@ -140,35 +117,27 @@ __global__ __launch_bounds__(NW * 64) void k_dist(const DistArgs A) {
                 Pold = A.P[gi];
             }
         }
-        s_rs[lane] = rs;
-        s_flag[lane] = valid ? F_VALID : 0;
+        T.s_rs[lane] = rs;
+        T.s_flag[lane] = valid ? F_VALID : 0;
     }
     __syncthreads();
 
-    // the wave that adds: walker `lane`'s terms of the tile, ascending from 0.0, pads skipped (prior.py:364-383)
-    auto add_terms = [&](const PriorTerm* __restrict__ tm) {
-        double acc = 0.0;
-        const double* trow = ttile + lane * TS;
-        for (int d = 0; d < D; ++d)
-            if (tm[d].kind != PRIOR_NONE) acc += trow[d];
-        return acc;
-    };
-
     // ---- phase B1: own row, proposal, the generator's terms at the OLD row
-    const int jl = tid & (LPR - 1);
-    const int rsub = tid / LPR;
-    const int e = 2 * jl;
+    const int e = T.e;
+    const bool speaker = T.jl == 0;
     const double2 glov = *reinterpret_cast<const double2*>(A.glo + e);
     const double2 ghiv = *reinterpret_cast<const double2*>(A.ghi + e);
     const PriorTerm g0 = A.gterms[e], g1 = A.gterms[e + 1];
     double* __restrict__ pool = A.pool;
+    auto q_at = [&](int r) { return *reinterpret_cast<const double2*>(T.qtile + r * RS + e); };
+    // (TermTile::rows' loop written out: as a lambda the unrolled rounds each repeat the draw's row-invariant work)
 #pragma unroll
-    for (int p = 0; p < NPASS; ++p) {
-        const int r = p * RPP + rsub;
-        const bool rvalid = (r < TILE) && (s_flag[r < TILE ? r : 0] & F_VALID) != 0;
-        bool ok = true;
+    for (int p = 0; p < Tile::NPASS; ++p) {
+        const int r = p * Tile::RPP + T.rsub;
+        const bool rvalid = (r < TILE) && (T.s_flag[r < TILE ? r : 0] & F_VALID) != 0;
+        PairTerms pt = NO_PAIR;
         if (rvalid) {
-            const double2 sv = *reinterpret_cast<const double2*>(pool + (size_t)s_rs[r] * D + e);
+            const double2 sv = *reinterpret_cast<const double2*>(pool + (size_t)T.s_rs[r] * D + e);
             double2 qv;
             if (forced) {
                 qv = *reinterpret_cast<const double2*>(A.q + ((size_t)tl * W + k0 + r) * D + e);
@@ -179,97 +148,60 @@ __global__ __launch_bounds__(NW * 64) void k_dist(const DistArgs A) {
             }
             if (g0.kind == PRIOR_NONE) qv.x = sv.x;         // a pad: no draw, no term
             if (g1.kind == PRIOR_NONE) qv.y = sv.y;
-            double tx, ty;
-            const bool okx = dist_term(g0, glov.x, ghiv.x, sv.x, tx);          // + log q(old), distgen.py:94
-            const bool oky = dist_term(g1, glov.y, ghiv.y, sv.y, ty);
-            ok = okx && oky;
-            *reinterpret_cast<double2*>(qtile + r * RS + e) = qv;
-            ttile[r * TS + e] = tx;
-            ttile[r * TS + e + 1] = ty;
+            *reinterpret_cast<double2*>(T.qtile + r * RS + e) = qv;
+            pt = T.put_terms(r, pair_terms<true>(g0, g1, glov, ghiv, sv));          // + log q(old), distgen.py:94
         }
-        dist_row_all(ok, LPR, lane, jl == 0 && rvalid, &s_flag[r], F_OLD);
+        dist_row_all(pt.ok, LPR, lane, speaker && rvalid, &T.s_flag[r], F_OLD);
     }
     __syncthreads();
     double sum_old = 0.0;
-    if (wv == 0 && valid) sum_old = add_terms(A.gterms);
+    if (wv == 0 && valid) sum_old = T.term_sum(lane, A.gterms);
     __syncthreads();
 
     // ---- phase B2: the generator's terms at the NEW row; under a box prior the row's ballot
     const double2 lov = *reinterpret_cast<const double2*>(A.lo + e);
     const double2 hiv = *reinterpret_cast<const double2*>(A.hi + e);
-#pragma unroll
-    for (int p = 0; p < NPASS; ++p) {
-        const int r = p * RPP + rsub;
-        const bool rvalid = (r < TILE) && (s_flag[r < TILE ? r : 0] & F_VALID) != 0;
-        bool ok = true, inbox = true, finite = true;
+    T.rows([&](int r, int fl) {
+        const bool rvalid = (fl & F_VALID) != 0;
+        PairTerms pt = NO_PAIR;
+        bool inbox = true;
         if (rvalid) {
-            const double2 qv = *reinterpret_cast<const double2*>(qtile + r * RS + e);
-            double tx, ty;
-            const bool okx = dist_term(g0, glov.x, ghiv.x, qv.x, tx);          // - log q(new), distgen.py:100
-            const bool oky = dist_term(g1, glov.y, ghiv.y, qv.y, ty);
-            ok = okx && oky;
-            ttile[r * TS + e] = tx;
-            ttile[r * TS + e + 1] = ty;
-            inbox = (qv.x >= lov.x) && (qv.x <= hiv.x) && (qv.y >= lov.y) && (qv.y <= hiv.y);      // prior.py:80-88
-            finite = (fabs(qv.x) < INFINITY) && (fabs(qv.y) < INFINITY);
+            const double2 qv = q_at(r);
+            pt = T.put_terms(r, pair_terms<true>(g0, g1, glov, ghiv, qv));          // - log q(new), distgen.py:100
+            inbox = pair_inside(qv, lov, hiv);                                      // prior.py:80-88
         }
-        dist_row_all(ok, LPR, lane, jl == 0 && rvalid, &s_flag[r], F_NEW);
-        if (!A.pterms) row_verdict(inbox, finite, LPR, lane, jl == 0 && rvalid, &s_flag[r], A.flags);
-    }
+        dist_row_all(pt.ok, LPR, lane, speaker && rvalid, &T.s_flag[r], F_NEW);
+        if (!A.pterms) row_verdict(inbox, pt.finite, LPR, lane, speaker && rvalid, &T.s_flag[r], A.flags);
+    });
     __syncthreads();
     double factors = 0.0;
     if (wv == 0 && valid) {
-        const int fl = s_flag[lane];
+        const int fl = T.s_flag[lane];
         const double lq_old = (fl & F_OLD) ? sum_old : -INFINITY;
-        const double lq_new = (fl & F_NEW) ? add_terms(A.gterms) : -INFINITY;
+        const double lq_new = (fl & F_NEW) ? T.term_sum(lane, A.gterms) : -INFINITY;
         factors = (0.0 + lq_old) + (-lq_new);                                   // distgen.py:84,94,100
     }
 
-    // ---- phase B3 (prior terms): the prior's supports and terms at the new row, as k_stretch_prior forms them
+    // ---- phase B3 (prior terms): the prior's supports and terms at the new row, by k_stretch_prior's rule
     if (A.pterms) {
         __syncthreads();
         const PriorTerm t0 = A.pterms[e], t1 = A.pterms[e + 1];
-#pragma unroll
-        for (int p = 0; p < NPASS; ++p) {
-            const int r = p * RPP + rsub;
-            const bool rvalid = (r < TILE) && (s_flag[r < TILE ? r : 0] & F_VALID) != 0;
-            bool ok = true, finite = true;
-            if (rvalid) {
-                const double2 qv = *reinterpret_cast<const double2*>(qtile + r * RS + e);
-                ok = (qv.x >= lov.x) && (qv.x <= hiv.x) && (qv.y >= lov.y) && (qv.y <= hiv.y);
-                finite = (fabs(qv.x) < INFINITY) && (fabs(qv.y) < INFINITY);
-                double tx = 0.0, ty = 0.0;
-                if (ok) {
-                    if (t0.kind != PRIOR_NONE) tx = prior_term(t0, qv.x);
-                    if (t1.kind != PRIOR_NONE) ty = prior_term(t1, qv.y);
-                    ok = (fabs(tx) < INFINITY) && (fabs(ty) < INFINITY);
-                }
-                ttile[r * TS + e] = tx;
-                ttile[r * TS + e + 1] = ty;
-            }
-            row_verdict(ok, finite, LPR, lane, jl == 0 && rvalid, &s_flag[r], A.flags);
-        }
+        T.rows([&](int r, int fl) {
+            const bool rvalid = (fl & F_VALID) != 0;
+            PairTerms pt = NO_PAIR;
+            if (rvalid) pt = T.put_terms(r, pair_terms<false>(t0, t1, lov, hiv, q_at(r)));
+            row_verdict(pt.ok, pt.finite, LPR, lane, speaker && rvalid, &T.s_flag[r], A.flags);
+        });
     }
     if constexpr (DT != 32) mfr = like_prefetch<DT, LIKE, NW>(lane, wv, A.prec_sym);   // (the matrix operand of phase C: in flight across the barrier)
     __syncthreads();
 
-    // ---- phase C
-    {
-        const bool inbox = (s_flag[lane] & F_IN) != 0;
-        like_partials<DT, LIKE, NW, false>(qtile, s_part, lane, wv, inbox, like_mf<DT, LIKE, NW>() ? s_mu : A.mu, A.prec, A.prec_sym, A.rosen_a,
-                                           A.rosen_b, mfr);
-    }
-    __syncthreads();
-
-    // ---- phase D
+    // ---- phase C, phase D
+    const double logl = T.template logl<LIKE>(A, lane, wv, wv == 0 && valid, mfr);
     if (wv == 0 && valid) {
-        const bool inbox = (s_flag[lane] & F_IN) != 0;
-        double acc = 0.0;
-#pragma unroll
-        for (int w2 = 0; w2 < like_nparts<DT, LIKE, NW>(); ++w2) acc += s_part[w2 * TILE + lane];
-        const double logl = nan_logl_rule(inbox ? -0.5 * acc : A.fill, A.flags);   // ensemble.py:1486-1513
+        const bool inbox = (T.s_flag[lane] & F_IN) != 0;
         double logp = -INFINITY;
-        if (inbox) logp = A.pterms ? add_terms(A.pterms) : A.logp_in;              // prior.py:364-383 / 80-88
+        if (inbox) logp = A.pterms ? T.term_sum(lane, A.pterms) : A.logp_in;       // prior.py:364-383 / 80-88
         const size_t gi = (size_t)tl * W + own;
         const bool keep = accept_test(A.tempered, [&] { return A.betas[A.rung_begin + tl]; }, logl, logp, Lold, Pold, factors, lu);
         if (keep) {
@@ -281,7 +213,7 @@ __global__ __launch_bounds__(NW * 64) void k_dist(const DistArgs A) {
                 A.P[gi] = newP;
             }
             atomicAdd(&A.accepted[gi], 1u);        // (the MH move counts in an array of its own)
-            atomicOr(&s_flag[lane], F_KEEP);
+            atomicOr(&T.s_flag[lane], F_KEEP);
         }
         if (A.keep_out) A.keep_out[gi] = keep ? 1 : 0;
         if (A.factors_out) A.factors_out[gi] = factors;
@@ -289,14 +221,10 @@ __global__ __launch_bounds__(NW * 64) void k_dist(const DistArgs A) {
     __syncthreads();
 
     // ---- phase E: accepted rows only, in place
-#pragma unroll
-    for (int p = 0; p < NPASS; ++p) {
-        const int r = p * RPP + rsub;
-        if (r >= TILE) continue;
-        const int fl = s_flag[r];
-        if ((fl & (F_VALID | F_KEEP)) != (F_VALID | F_KEEP)) continue;
-        *reinterpret_cast<double2*>(pool + (size_t)s_rs[r] * D + e) = *reinterpret_cast<const double2*>(qtile + r * RS + e);
-    }
+    T.rows([&](int r, int fl) {
+        if ((fl & (F_VALID | F_KEEP)) != (F_VALID | F_KEEP)) return;
+        *reinterpret_cast<double2*>(pool + (size_t)T.s_rs[r] * D + e) = q_at(r);
+    });
 }
 
 }  // namespace hens

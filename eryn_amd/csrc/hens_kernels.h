@@ -543,17 +543,23 @@ __device__ __forceinline__ bool accept_test(bool tempered, BetaOf&& beta_of, dou
 }
 // move.py:513-532: the log-prior an accepted point is stored with
 __device__ __forceinline__ double stored_logp(double logp) { return (fabs(logp) == INFINITY) ? 0.0 : logp; }
-// prior.py:80-88, the row-wide AND: a row's LPR lanes (a power of two <= 64, aligned) each hold `ok` / `finite` of their coordinates;
-// the lane that speaks for a valid row sets bit 0 of the row's flag word when all are inside and reports a non-finite coordinate.
-// Every lane of the wavefront calls it (ballot).
-__device__ __forceinline__ void row_verdict(bool ok, bool finite, int LPR, int lane, bool speaks, int32_t* row_flag, unsigned* flags) {
-    const unsigned long long bad = __ballot(!ok);
-    const unsigned long long nonfin = __ballot(!finite);
+// the bits of a row's flag word: inside every support of the prior, proposal kept, the row holds a walker
+constexpr int F_IN = 1, F_KEEP = 2, F_VALID = 4;
+// A row's LPR lanes (a power of two <= 64, aligned): those among them that say `v`.  Every lane of the wavefront calls it (ballot).
+__device__ __forceinline__ unsigned long long row_ballot(bool v, int LPR, int lane) {
+    const unsigned long long said = __ballot(v);
     const int gshift = lane & ~(LPR - 1);
     const unsigned long long gmask = (LPR == 64) ? ~0ull : (((1ull << (LPR & 63)) - 1ull) << gshift);
+    return said & gmask;
+}
+// prior.py:80-88, the row-wide AND: a row's lanes each hold `ok` / `finite` of their coordinates; the lane that speaks for a valid
+// row sets F_IN of the row's flag word when all are inside and reports a non-finite coordinate.  Every lane of the wavefront calls it.
+__device__ __forceinline__ void row_verdict(bool ok, bool finite, int LPR, int lane, bool speaks, int32_t* row_flag, unsigned* flags) {
+    const unsigned long long bad = row_ballot(!ok, LPR, lane);
+    const unsigned long long nonfin = row_ballot(!finite, LPR, lane);
     if (speaks) {
-        if ((bad & gmask) == 0ull) atomicOr(row_flag, 1);
-        if ((nonfin & gmask) != 0ull) atomicOr(flags, FLAG_NONFINITE_X);
+        if (bad == 0ull) atomicOr(row_flag, F_IN);
+        if (nonfin != 0ull) atomicOr(flags, FLAG_NONFINITE_X);
     }
 }
 

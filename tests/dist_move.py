@@ -243,6 +243,7 @@ CASES = {
     "2x136x32_dense_box": case(2, 136, 32, "dense", "box", "normal_lu"),   # matrix pipe, two full tiles + 8
     "2x64x64_dense_terms": case(2, 64, 64, "dense", "terms", "mixed"),      # all three sums through the term tile
     "2x65x128_rosen_box": case(2, 65, 128, "rosen", "box", "uniform_normal"),   # the D = 128 LDS budget, a tile of one walker
+    "2x65x128_dense_terms": case(2, 65, 128, "dense", "terms", "mixed"),    # ... with all three sums through the one tile that fits there
     "1x64x24_dense_box": case(1, 64, 24, "dense", "box", "mixed", weight=1.0),       # untempered, pad to 32, no stretch iteration
     # walker records (hens_step packs them where W is a multiple of the block-balanced labelling's column block, 128 / T for these
     # ladders: none of the shapes above is): {L, P} read and written in the records by slot, the stretch iterations on the
