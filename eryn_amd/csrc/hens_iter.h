@@ -65,7 +65,9 @@ __host__ __device__ inline size_t iter_lds_bytes(int D, int NW) {
 // The ladder adaptation of one wavefront (tempering.py:563-596; the arithmetic of k_stretch_fast's folded form), T <= 128:
 // lane l owns rungs l and l + 64.  part1 (ratios, dS, exp, deltaT) needs the counts only; part2 (cumulative sum,
 // reciprocals, update) runs while the row gathers are in flight.
-struct LadderFold {
+// Not hens_ladder_fold.inc's text: the older chain (two reciprocals per rung, kappa formed on the device), books through IterArgs::ad,
+// no ring.  Joining changes k_iter's instructions, so it waits for an A/B of k_iter's launch; none has been run.
+struct IterLadderFold {
     double c0 = 0.0, c1 = 0.0, dT0 = 0.0, dT1 = 0.0, b0n = 1.0, b1n = 1.0, bb0 = 1.0, bb1 = 1.0;
     __device__ __forceinline__ void part1(const AdaptArgs& ad, int lane, double cnt0, double cnt1, double b, double b1) {
         const int T = ad.T;
@@ -188,7 +190,7 @@ __global__ __launch_bounds__(NW * 64) void k_iter(const IterArgs A) {
     int32_t gi_m = 0;
     uint32_t acc_m = 0;                                                  // the slot's accept counter (WalkerRec::acc)
     const int tm = lane >> (CS - 1);                                     // rung of the m-th walker of a half
-    LadderFold fold;
+    IterLadderFold fold;
     if (wv < 3) s_flag[wv * TILE + lane] = 0;
     if (wv < 3 && lane < NM) {
         const DrawRec* src = wv == 0 ? A.rec1 : (wv == 1 ? A.rec3 : A.rec2);
