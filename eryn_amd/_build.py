@@ -8,14 +8,14 @@ SRC_DIR = os.path.join(HERE, "csrc")
 LIB_DIR = os.path.join(HERE, "lib")
 LIB_PATH = os.environ.get("HENS_LIB") or os.path.join(LIB_DIR, "libhipensemble.so")
 OBJ_DIR = os.environ.get("HENS_OBJ_DIR") or os.path.join(os.path.dirname(HERE), "build", "hens_obj")      # (A/B libraries: objects of their own)
-# hens.hip: the C ABI, the host logic and the small kernels; hens_k_<likelihood>.hip (x 4 parts): the stepping kernels' instantiations
+# hens.hip: the C ABI, the host logic and the small kernels; hens_k_<likelihood>.hip (x 5 parts): the stepping kernels' instantiations
 # (csrc/hens_ktable.h) - one translation unit per (likelihood, part), compiled side by side, then linked.
 UNITS = [("hens", "hens.hip", [])] + [(f"hens_k_{k}_{part}", f"hens_k_{k}.hip", [f"-DHENS_KT_PART={part}"])
-                                      for k in ("dense", "diag", "rosen") for part in (0, 1, 2, 3)]
+                                      for k in ("dense", "diag", "rosen") for part in (0, 1, 2, 3, 4)]
 SOURCES = sorted({os.path.join(SRC_DIR, u[1]) for u in UNITS})
 # what a unit includes, by kind of unit: every unit, hens.hip alone, the kernel units alone (they see neither hens.hip nor the RJ / AQL headers)
 HDRS_ALL = ("hens_kernels.h", "hens_ladder_fold.inc", "hens_iter.h", "hens_tile2.h", "hens_ktable.h", "hens_prior.h", "hens_dist.h", "hens_prior_host.h")
-HDRS_HOST = ("hens_rj.h", "hens_aql.h", "hens_chain.h", "hens_chain_stats.h", "hens_rj_chain.h", "hens_rj_chain_stats.h", "hens_chain_host.h")
+HDRS_HOST = ("hens_gibbs_host.h", "hens_rj.h", "hens_aql.h", "hens_chain.h", "hens_chain_stats.h", "hens_rj_chain.h", "hens_rj_chain_stats.h", "hens_chain_host.h")
 HDRS_KERNEL = ("hens_ktable.inc",)
 API_HEADER = os.path.join(os.path.dirname(HERE), "include", "hipensemble.h")
 DEPS = SOURCES + [os.path.join(SRC_DIR, h) for h in HDRS_ALL + HDRS_HOST + HDRS_KERNEL] + [API_HEADER]
@@ -68,7 +68,7 @@ def build(force=False, verbose=False):
             print(" ".join(cmd), flush=True)
         jobs.append((obj, cmd, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True), stamp))
     failed = []
-    for obj, cmd, proc, stamp in jobs:     # (13 compilers side by side: about 1.5 GB each at their peak)
+    for obj, cmd, proc, stamp in jobs:     # (16 compilers side by side: about 1.5 GB each at their peak)
         if proc is None:
             continue
         out, _ = proc.communicate()

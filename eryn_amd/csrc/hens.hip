@@ -9,6 +9,7 @@
 #include "hens_ktable.h"
 #include "hens_prior.h"
 #include "hens_dist.h"
+#include "hens_gibbs_host.h"
 #include "hens_chain.h"
 #include "hens_chain_stats.h"
 #include "hens_rj_chain.h"
@@ -204,6 +205,21 @@ struct hens_ctx_impl {
     int mh_kind = -1;                      // -1: hens_step runs the stretch move only; MH_DIST: the slot holds hens_set_dist_proposal's generator
     TermBlock dist_block;                  // the generator of MH_DIST (DistArgs::glo / ghi / gterms)
     double* dist_factors = nullptr;        // [Tl][W] hens_dist_step's factors_out staging
+    // Gibbs parameter blocks (hens_set_gibbs; hens_gibbs_host.h): a block table per move - [0] the stretch move, [1] the MH slot.
+    // While either has one (gibbs_on) every proposing launch is a block's: k_stretch_prior<GIBBS> on the block's image, a move
+    // without a table of its own being one all-true block.
+    struct Gibbs {
+        int nblocks = 0;                   // 0: no table
+        std::vector<int32_t> n, mask;      // [nblocks], [nblocks][D] (parse_gibbs)
+        double* img = nullptr;             // [GIBBS_MAX_BLOCKS] device images lo[D] hi[D] terms[D] mask[D], blocks() of them in use
+        bool img_ok = false;               // ... and they are the current prior's and table's (gibbs_rebuild)
+        int sel = 0;                       // hens_gibbs_select: the block of the next teacher-forced move
+        int cur = 0;                       // the block the next launch of the move reads (hens_step: block after block; else sel)
+        int blocks() const { return nblocks > 0 ? nblocks : 1; }
+    } gibbs[2];
+    std::vector<double> h_lo, h_hi;        // the prior's supports and, under terms, its records as the host gave them last
+    std::vector<PriorTerm> h_terms;        //   (hens_set_prior_box / _terms): what a block's image is made of
+    Draws gdr{};                           // [Tl][W] one block's planned draws (k_plan_block; own: the iteration's plan)
     double mh_weight = 0.0;                // probability that an iteration of hens_step is an MH proposal
     int64_t num_proposals_mh = 0;
     uint8_t* mask_buf = nullptr;     // hens_step_report: [Tl][W] accept counts of the call's last iterations
@@ -456,11 +472,12 @@ struct LikeKernels {
     const void* (*stretch)(int mode);
     const void* (*stretch_prior)(int mode, int D);
     const void* (*dist)(int D);
+    const void* (*stretch_gibbs)(int mode, int D);
     const void* (*stretch2)(int D, bool pipe);
     const void* (*split1_pt)(int D, bool per, bool shrt, bool pipe, bool col);
     const void* (*iter)(int D, bool per);
 };
-#define HENS_LIKE_KERNELS(KIND_, LIKE_, U) {KIND_, LIKE_, ktab_stretch_fast_##U, ktab_stretch_##U, ktab_stretch_prior_##U, ktab_dist_##U, ktab_stretch2_##U, ktab_split1_pt_##U, ktab_iter_##U}
+#define HENS_LIKE_KERNELS(KIND_, LIKE_, U) {KIND_, LIKE_, ktab_stretch_fast_##U, ktab_stretch_##U, ktab_stretch_prior_##U, ktab_dist_##U, ktab_stretch_gibbs_##U, ktab_stretch2_##U, ktab_split1_pt_##U, ktab_iter_##U}
 const LikeKernels* like_kernels(int likelihood_kind) {
     static const LikeKernels tab[] = {
         HENS_LIKE_KERNELS(HENS_LIKE_GAUSS_DENSE, LIKE_DENSE, dense),
@@ -517,11 +534,17 @@ int fast_nw(int D) { return (D == 32 || D == 64 || D == 128) ? 8 : 4; }
 // row widths with a compile-time-width kernel (k_stretch_fast)
 // (not with per-parameter prior terms: such a context is a generic-width one to every launch decision - the copying launches of
 //  k_stretch, the cascade and the adaptation as kernels of their own, MH steps through the step buffer)
-bool fast_path(const hens_ctx_impl* c) {
+// (nor with a Gibbs block table on either move, hens_set_gibbs: likewise - but its evaluation launch, which proposes nothing, stays
+//  the one of the context without a table: fast_width)
+bool gibbs_on(const hens_ctx_impl* c) { return c->gibbs[0].nblocks > 0 || c->gibbs[1].nblocks > 0; }
+bool fast_width(const hens_ctx_impl* c) {
     const int D = c->D;
     if (c->prior) return false;
     return D == 8 || D == 16 || D == 32 || D == 64 || (D == 128 && c->cfg.likelihood_kind != HENS_LIKE_HOST);
 }
+bool fast_path(const hens_ctx_impl* c) { return fast_width(c) && !gibbs_on(c); }
+// the real parameters a proposal of move `m` (0 stretch, 1 MH) moves: the current block's count under a table (stretch.py:55-72)
+int gibbs_dim(const hens_ctx_impl* c, int m) { return c->gibbs[m].nblocks > 0 ? c->gibbs[m].n[(size_t)c->gibbs[m].cur] : dim_active(c); }
 
 size_t generic_lds_bytes(int D, int* RS_out) {
     const int RS = (D % 2 == 0) ? D + 2 : D;
@@ -560,7 +583,18 @@ int launch_stretch_like(hens_ctx_impl* c, const LikeKernels& lk, int mode, Stret
     const dim3 grid(ntiles, c->Tl);
     const int like = lk.like;
     a.xcd_shift = xcd_shift(c, ntiles);
-    if (fast_path(c)) {
+    // A Gibbs block's half-step (hens_set_gibbs): k_stretch_prior<GIBBS> on the image of the move's current block - the prior's
+    // supports and records (a box as uniform terms) with the block's mask behind them.  HENS_PRIOR_LOG=1 (tests): says so.
+    if (gibbs_on(c) && mode != MODE_EVAL) {
+        const hens_ctx_impl::Gibbs& G = c->gibbs[mode == MODE_MH ? 1 : 0];
+        const double* img = G.img + (size_t)G.cur * gibbs_image_doubles(c->D);
+        a.lo = img; a.hi = img + c->D; a.prior_on = 2;
+        a.ad_on = 0;
+        if (env().prior_log) fprintf(stderr, "hens: Gibbs block %d of %d, D = %d, mode %d: k_stretch_prior<GIBBS>\n", G.cur, G.blocks(), c->D, mode);
+        const int NW = fast_nw(c->D);
+        return on_hip_stream(c, [&] { return launch_by_ptr(c, lk.stretch_gibbs(mode, c->D), "k_stretch_prior<GIBBS>", grid, NW * 64, prior_lds_bytes(c->D, NW, like), false, c->ext_start, c->ext_stop, a); });
+    }
+    if (mode == MODE_EVAL ? fast_width(c) : fast_path(c)) {
         // (periodic parameters: an instantiation of their own - on a pipeline rank too - but not for the evaluation launch, which
         //  proposes nothing)
         const bool pipe = c->pipe.on, per = mode != MODE_EVAL && c->period;
@@ -1256,7 +1290,7 @@ int stretch_pair(hens_ctx_impl* c, int which, int ib, LaunchTimer* tm, bool inpl
     const int Tl = c->Tl, W = c->W;
     for (int split = 0; split < 2; ++split) {
         StretchArgs a = base_args(c);
-        a.dr = draws_at(c->db[which], (size_t)ib * Tl * W);
+        a.dr = gibbs_on(c) ? c->gdr : draws_at(c->db[which], (size_t)ib * Tl * W);      // (a block's plan: gibbs_iteration)
         a.split = split;
         a.inplace = inplace ? 1 : 0;
         a.home_off = c->parity * Tl * W;
@@ -1767,6 +1801,7 @@ int mh_iteration(hens_ctx_impl* c, LaunchTimer* tm, bool inplace) {
         d.step = c->mh_step; d.lu = c->mh_lu; d.scale = c->mh_scale;
         d.iter = c->iter; d.seed = c->cfg.seed;
         d.Tl = c->Tl; d.W = c->W; d.D = c->D; d.rung_begin = c->cfg.rung_begin; d.kind = c->mh_kind;
+        d.block = gibbs_on(c) ? (uint32_t)c->gibbs[1].cur : 0u;
         size_t lds = (size_t)64 * (c->D + 1) * 8;
         d.chol_lds = (c->mh_kind == MH_FULL && lds + (size_t)c->D * (c->D + 1) * 8 <= 60000) ? 1 : 0;
         if (d.chol_lds) lds += (size_t)c->D * (c->D + 1) * 8;
@@ -1984,6 +2019,37 @@ void step_cascade(hens_ctx_impl* c, LaunchTimer* tm) {
     cascade_ran(c, use_acc ? p.swap_part : nullptr, p.acc_rows, c->cfg.adaptive != 0);
 }
 
+// The move of one iteration under Gibbs block tables (hens_set_gibbs; a single, whole-ladder context on Iteration::COPYING): block
+// after block of the iteration's move - a plan of the block's draws on the iteration's labels and the two copying half-steps
+// (red_blue.py:119-333), or k_mh_draw with the block's words and the MH launch (mh.py:79-193) - every block against the rows the
+// block before it left.  The caller runs the ONE cascade behind the last block.  num_proposals / num_proposals_mh advance per block.
+int ensure_gibbs_draws(hens_ctx_impl* c) {
+    if (c->gdr.cw) return HENS_OK;
+    const size_t TW = (size_t)c->Tl * c->W;
+    int r;
+    if ((r = dalloc(c, &c->gdr.cw, TW)) || (r = dalloc(c, &c->gdr.zz, TW)) || (r = dalloc(c, &c->gdr.fac, TW)) || (r = dalloc(c, &c->gdr.lu, TW))) return r;
+    return HENS_OK;
+}
+int gibbs_iteration(hens_ctx_impl* c, bool mh, int ib, LaunchTimer* tm) {
+    state_to_fields(c);
+    hens_ctx_impl::Gibbs& G = c->gibbs[mh ? 1 : 0];
+    int r = HENS_OK;
+    for (int b = 0; b < G.blocks() && !r; ++b) {
+        G.cur = b;
+        if (mh) { r = mh_iteration(c, tm, false); continue; }
+        PlanBlockArgs pb{};
+        pb.own = c->db[0].d.own + (size_t)ib * c->Tl * c->W;
+        pb.dr = c->gdr;
+        pb.iter = c->iter; pb.seed = c->cfg.seed; pb.a = c->cfg.a;
+        pb.Tl = c->Tl; pb.W = c->W; pb.nb = gibbs_dim(c, 0); pb.rung_begin = c->cfg.rung_begin; pb.block = (uint32_t)b;
+        c->gdr.own = const_cast<int32_t*>(pb.own);
+        hipLaunchKernelGGL(k_plan_block, dim3((c->W + 255) / 256, c->Tl), dim3(256), 0, c->stream, pb);
+        r = stretch_pair(c, 0, ib, tm, false);
+    }
+    G.cur = G.sel;
+    return r;
+}
+
 // one iteration of hens_step on the call's path, from batch slot `ib` of the draw plan; an MH iteration of a mix replaces the
 // stretch move and is followed by a cascade of its own
 int run_iteration(hens_ctx_impl* c, const StepPath& path, int ib, LaunchTimer* tm) {
@@ -1994,6 +2060,11 @@ int run_iteration(hens_ctx_impl* c, const StepPath& path, int ib, LaunchTimer* t
     if (!mh && path.it == Iteration::INPLACE2) return fused_iteration(c, path, tm);
     const bool inplace = !path.piped() && fast_path(c);
     int r;
+    if (gibbs_on(c)) {
+        if ((r = gibbs_iteration(c, mh, ib, tm))) return r;
+        step_cascade(c, tm);
+        return HENS_OK;
+    }
     if (mh) {
         // (the fast kernels and the cascade read the walker records too; other MH launches want the by-field arrays)
         if (path.records()) state_to_records(c, path.col);
@@ -2370,6 +2441,45 @@ int hens_set_stream(hens_ctx* ctx, void* s) {
     return HENS_OK;
 }
 
+// The device images of one move's Gibbs blocks (hens_gibbs_host.h: gibbs_image) from the prior as the host holds it - its terms, or
+// the box as uniform terms that add up to logp_in - and the table's masks; a move without a table: one all-true block.  Room for
+// GIBBS_MAX_BLOCKS images is allocated once per move (at most 0.85 MB, D = 128): a table that is replaced by a longer one takes no
+// new memory.  hens_set_gibbs rebuilds the move it changes (and the other move's single image if that was never built or the prior
+// has changed since); the prior's setters rebuild both while a table is on.
+static int gibbs_rebuild(hens_ctx_impl* c, int move) {
+    hens_ctx_impl::Gibbs& G = c->gibbs[move];
+    G.img_ok = false;
+    if (!gibbs_on(c) || c->h_lo.empty()) return HENS_OK;
+    const int D = c->D, Da = dim_active(c), nb = G.blocks();
+    const size_t stride = gibbs_image_doubles(D);
+    if (!G.img)
+        if (const int r = dalloc(c, &G.img, (size_t)GIBBS_MAX_BLOCKS * stride)) return r;
+    std::vector<PriorTerm> terms(c->h_terms);
+    if (terms.empty()) { terms.resize((size_t)D); box_as_terms(c->logp_in, D, Da, terms.data()); }
+    std::vector<double> host((size_t)nb * stride);
+    std::vector<int32_t> all((size_t)D, 0);
+    for (int d = 0; d < Da; ++d) all[(size_t)d] = 1;
+    for (int b = 0; b < nb; ++b)
+        gibbs_image(c->h_lo.data(), c->h_hi.data(), terms.data(), G.nblocks > 0 ? G.mask.data() + (size_t)b * D : all.data(), D, host.data() + (size_t)b * stride);
+    HIPCHK(c, hipStreamSynchronize(c->stream));      // (a launch in flight may still read the images about to be replaced)
+    HIPCHK(c, hipMemcpy(G.img, host.data(), host.size() * 8, hipMemcpyHostToDevice));      // (synchronous: `host` is a local)
+    G.img_ok = true;
+    return HENS_OK;
+}
+// after hens_set_gibbs changed `move`'s table: its images, and the other move's where they are not the current prior's
+static int gibbs_rebuild_for(hens_ctx_impl* c, int move) {
+    if (const int r = gibbs_rebuild(c, move)) return r;
+    return c->gibbs[move ^ 1].img_ok ? HENS_OK : gibbs_rebuild(c, move ^ 1);
+}
+static int keep_prior_host(hens_ctx_impl* c, const double* lo, const double* hi, const PriorTerm* terms) {
+    c->h_lo.assign(lo, lo + c->D);
+    c->h_hi.assign(hi, hi + c->D);
+    if (terms) c->h_terms.assign(terms, terms + c->D);
+    else c->h_terms.clear();
+    if (const int r = gibbs_rebuild(c, 0)) return r;
+    return gibbs_rebuild(c, 1);
+}
+
 int hens_set_prior_box(hens_ctx* ctx, const double* lo, const double* hi, double logp_inside) {
     hens_ctx_impl* c = enter(ctx);
     if (!c || !lo || !hi) return fail(c, HENS_ERR_INVALID, "null argument");
@@ -2382,7 +2492,7 @@ int hens_set_prior_box(hens_ctx* ctx, const double* lo, const double* hi, double
     c->logp_in = logp_inside;
     c->prior = nullptr;               // (back to the box after hens_set_prior_terms)
     c->have_prior = true;
-    return HENS_OK;
+    return keep_prior_host(c, lo, hi, nullptr);
 }
 
 // prior.py:337-392 with one distribution per parameter (include/hipensemble.h); uniform kinds only: hens_set_prior_box itself.
@@ -2421,6 +2531,64 @@ int hens_set_prior_terms(hens_ctx* ctx, const int32_t* kind, const double* lo, c
     c->logp_in = 0.0;
     c->prior = c->prior_buf;
     c->have_prior = true;
+    return keep_prior_host(c, lo, hi, terms.data());
+}
+
+// ---- Gibbs parameter blocks (move.py:113-221; red_blue.py:119-333, mh.py:79-193 for one branch, nleaves_max == 1) ---------------------
+// The state a block table needs: a single whole-ladder context with a device likelihood at a compile-time row width, a two-set
+// stretch move, no periodic parameters, nothing half done.
+static int gibbs_supported(hens_ctx_impl* c, int32_t move) {
+    if (move != HENS_GIBBS_STRETCH && move != HENS_GIBBS_MH) return fail(c, HENS_ERR_INVALID, "move must be HENS_GIBBS_STRETCH (0) or HENS_GIBBS_MH (1)");
+    if (c->expect_split != 0 || c->propose_pending) return fail(c, HENS_ERR_STATE, "a half-step is pending");
+    if (is_rj(c)) return fail(c, HENS_ERR_UNSUPPORTED, "Gibbs blocks are not built for leaf-packing records");
+    if (c->cfg.likelihood_kind == HENS_LIKE_HOST) return fail(c, HENS_ERR_UNSUPPORTED, "Gibbs blocks need a device likelihood");
+    if (c->pipe.on || c->Tl != c->T) return fail(c, HENS_ERR_UNSUPPORTED, "Gibbs blocks are not built for a rank of the ladder pipeline or a ladder shard");
+    if (c->period) return fail(c, HENS_ERR_UNSUPPORTED, "Gibbs blocks are not built for periodic parameters (hens_set_periodic)");
+    if (c->nsplits != 2) return fail(c, HENS_ERR_UNSUPPORTED, "Gibbs blocks step a two-set stretch move (hens_set_nsplits(2))");
+    const LikeKernels* lk = like_kernels(c->cfg.likelihood_kind);
+    if (!lk || !lk->stretch_gibbs(MODE_STRETCH, c->D))
+        return fail(c, HENS_ERR_UNSUPPORTED, "Gibbs blocks are built for row widths 8, 16, 32, 64 and 128 (this context's rows are %d wide)", c->D);
+    return HENS_OK;
+}
+
+int hens_set_gibbs(hens_ctx* ctx, int32_t move, int32_t nblocks, const uint8_t* mask) {
+    hens_ctx_impl* c = enter(ctx);
+    if (!c) return no_context();
+    if (nblocks == 0 && (move == HENS_GIBBS_STRETCH || move == HENS_GIBBS_MH)) {     // clears the table, whatever the context
+        if (c->expect_split != 0 || c->propose_pending) return fail(c, HENS_ERR_STATE, "a half-step is pending");
+        if (c->gibbs[move].nblocks == 0) return HENS_OK;
+        SETTLE(c, NEED_DEVICE | NEED_FIELDS | NEED_LADDER);
+        hens_ctx_impl::Gibbs& G = c->gibbs[move];
+        G.nblocks = 0; G.n.clear(); G.mask.clear(); G.sel = G.cur = 0;
+        c->win_count = 0;
+        return gibbs_rebuild_for(c, move);
+    }
+    if (const int r = gibbs_supported(c, move)) return r;
+    if (move == HENS_GIBBS_MH && c->mh_kind == MH_DIST)
+        return fail(c, HENS_ERR_UNSUPPORTED, "Gibbs blocks are not built for the distribution proposal in the MH slot (hens_set_dist_proposal)");
+    ParsedGibbs p = parse_gibbs(nblocks, mask, c->D, dim_active(c));
+    if (p.why[0]) return fail(c, HENS_ERR_INVALID, "hens_set_gibbs: %s", p.why);
+    SETTLE(c, NEED_DEVICE | NEED_FIELDS | NEED_LADDER);      // (the launch path changes)
+    if (const int r = ensure_gibbs_draws(c)) return r;
+    hens_ctx_impl::Gibbs& G = c->gibbs[move];
+    G.nblocks = nblocks;
+    G.n = std::move(p.n);
+    G.mask = std::move(p.mask);
+    G.sel = G.cur = 0;
+    c->win_count = 0;
+    return gibbs_rebuild_for(c, move);
+}
+
+// teacher-forced: the block the next hens_stretch_split pair (move 0) or hens_mh_step (move 1) belongs to; between complete moves
+int hens_gibbs_select(hens_ctx* ctx, int32_t move, int32_t block) {
+    hens_ctx_impl* c = enter(ctx);
+    if (!c) return no_context();
+    if (move != HENS_GIBBS_STRETCH && move != HENS_GIBBS_MH) return fail(c, HENS_ERR_INVALID, "move must be HENS_GIBBS_STRETCH (0) or HENS_GIBBS_MH (1)");
+    if (c->expect_split != 0 || c->propose_pending) return fail(c, HENS_ERR_STATE, "hens_gibbs_select between the half-steps of a move");
+    hens_ctx_impl::Gibbs& G = c->gibbs[move];
+    if (G.nblocks == 0) return fail(c, HENS_ERR_STATE, "no Gibbs table on this move (hens_set_gibbs)");
+    if (block < 0 || block >= G.nblocks) return fail(c, HENS_ERR_INVALID, "block must be in [0, %d)", G.nblocks);
+    G.sel = G.cur = block;
     return HENS_OK;
 }
 
@@ -2439,6 +2607,7 @@ int hens_set_periodic(hens_ctx* ctx, const double* period) {
         if (!any && !c->period) return HENS_OK;
         return fail(c, HENS_ERR_STATE, "set the periodic parameters before hens_pipe_init");
     }
+    if (any && gibbs_on(c)) return fail(c, HENS_ERR_UNSUPPORTED, "periodic parameters are not built under Gibbs blocks (hens_set_gibbs(ctx, move, 0, NULL) clears a table)");
     SETTLE(c, NEED_DEVICE | NEED_FIELDS | NEED_LADDER);
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (!any) {                       // back to the compile-time-width kernels
@@ -2690,7 +2859,7 @@ static int prepare_split(hens_ctx_impl* c, int32_t split, const uint8_t* labels,
     if (u_acc) HIPCHK(c, hipMemcpyAsync(c->d_uacc, u_acc, n * 8, hipMemcpyHostToDevice, c->stream));
     c->win_count = 0;
     hipLaunchKernelGGL(k_prep_draws, dim3(grid_for((int64_t)n)), dim3(256), 0, c->stream, c->order, c->d_rint, c->d_uzz,
-                       u_acc ? c->d_uacc : c->d_uzz, c->db[0].d, Tl, W, c->seg_off[split], Ns, c->cfg.a, dim_active(c));
+                       u_acc ? c->d_uacc : c->d_uzz, c->db[0].d, Tl, W, c->seg_off[split], Ns, c->cfg.a, gibbs_dim(c, 0));      // (the selected block's count: hens_gibbs_select)
     *Ns_out = Ns;
     return HENS_OK;
 }
@@ -2770,6 +2939,7 @@ int hens_set_nsplits(hens_ctx* ctx, int32_t nsplits) {
     if (nsplits < 2 || nsplits > 8) return fail(c, HENS_ERR_INVALID, "nsplits must be in [2, 8]");
     if (nsplits > c->W) return fail(c, HENS_ERR_INVALID, "more sets than walkers");
     if (c->expect_split != 0 || c->propose_pending) return fail(c, HENS_ERR_STATE, "a red-blue move is under way");
+    if (nsplits != 2 && gibbs_on(c)) return fail(c, HENS_ERR_UNSUPPORTED, "Gibbs blocks step a two-set stretch move (hens_set_gibbs(ctx, move, 0, NULL) clears a table)");
     c->nsplits = nsplits;
     c->seg_off.clear();
     return HENS_OK;
@@ -3677,8 +3847,20 @@ __global__ void k_dist_draw(double* q, double* u, const double* glo, const doubl
 
 int hens_debug_draws(hens_ctx* ctx, int64_t iter, int32_t* own, int32_t* cw, double* u_zz, double* u_acc,
                      int32_t* pt_slot, double* u_swap, int32_t* is_mh, double* mh_step, double* mh_u) {
+    return hens_debug_draws_block(ctx, iter, 0, own, cw, u_zz, u_acc, pt_slot, u_swap, is_mh, mh_step, mh_u);
+}
+
+// ... of Gibbs block `block` of that iteration's move (hens_set_gibbs): own, the PT draws and the move choice are the iteration's;
+// cw, u_zz, u_acc (k_plan_block) and mh_step, mh_u (k_mh_draw) come from the block's purpose words.  Block 0 is hens_debug_draws.
+int hens_debug_draws_block(hens_ctx* ctx, int64_t iter, int32_t block, int32_t* own, int32_t* cw, double* u_zz, double* u_acc,
+                           int32_t* pt_slot, double* u_swap, int32_t* is_mh, double* mh_step, double* mh_u) {
     hens_ctx_impl* c = enter(ctx);
     if (!c || iter < 0) return fail(c, HENS_ERR_INVALID, "null context / negative iteration");
+    if (block < 0 || block >= c->gibbs[iteration_is_mh(c, (uint64_t)iter) ? 1 : 0].blocks())
+        return fail(c, HENS_ERR_INVALID, "block must be in [0, %d): the blocks of that iteration's move", c->gibbs[iteration_is_mh(c, (uint64_t)iter) ? 1 : 0].blocks());
+    // the OTHER move's arrays are the block's only where its table has such a block: else they are not written
+    if (block >= c->gibbs[0].blocks()) cw = nullptr, u_zz = u_acc = nullptr;
+    if (block >= c->gibbs[1].blocks()) mh_step = mh_u = nullptr;
     SETTLE(c, NEED_DEVICE);
     const size_t TW = (size_t)c->Tl * c->W;
     DeviceScratch sc;
@@ -3704,6 +3886,14 @@ int hens_debug_draws(hens_ctx* ctx, int64_t iter, int32_t* own, int32_t* cw, dou
             if (!pa.keys) return fail(c, HENS_ERR_HIP, "hens_debug_draws: out of device memory");
         }
         launch_plan_kernels(c, c->stream, pa, 1);
+        if (block > 0 && block < c->gibbs[0].nblocks) {      // the block's draws over the iteration's position lists; a block the stretch
+                                                             // table lacks (an MH iteration's): `own` alone is read, the iteration's
+            PlanBlockArgs pb{};
+            pb.own = pa.dr.own; pb.dr = pa.dr; pb.dbg_uzz = pa.dbg_uzz; pb.dbg_uacc = pa.dbg_uacc;
+            pb.iter = (uint64_t)iter; pb.seed = c->cfg.seed; pb.a = c->cfg.a;
+            pb.Tl = c->Tl; pb.W = c->W; pb.nb = c->gibbs[0].n[(size_t)block]; pb.rung_begin = c->cfg.rung_begin; pb.block = (uint32_t)block;
+            hipLaunchKernelGGL(k_plan_block, dim3((c->W + 255) / 256, c->Tl), dim3(256), 0, c->stream, pb);
+        }
         HIPCHK(c, hipGetLastError());
         if (own) HIPCHK(c, hipMemcpyAsync(own, pa.dr.own, TW * 4, hipMemcpyDeviceToHost, c->stream));
         if (cw) HIPCHK(c, hipMemcpyAsync(cw, pa.dr.cw, TW * 4, hipMemcpyDeviceToHost, c->stream));
@@ -3735,6 +3925,7 @@ int hens_debug_draws(hens_ctx* ctx, int64_t iter, int32_t* own, int32_t* cw, dou
         d.scale = c->mh_scale; d.iter = (uint64_t)iter; d.seed = c->cfg.seed;
         d.Tl = c->Tl; d.W = c->W; d.D = c->D; d.rung_begin = c->cfg.rung_begin; d.kind = c->mh_kind;
         d.chol_lds = 0;
+        d.block = (uint32_t)block;
         hipLaunchKernelGGL(k_mh_draw, dim3((c->W + 63) / 64, c->Tl), dim3(256), (size_t)64 * (c->D + 1) * 8, c->stream, d);
         HIPCHK(c, hipGetLastError());
         if (mh_step) HIPCHK(c, hipMemcpyAsync(mh_step, d.step, TW * c->D * 8, hipMemcpyDeviceToHost, c->stream));
@@ -4922,6 +5113,7 @@ int hens_set_dist_proposal(hens_ctx* ctx, const int32_t* kind, const double* lo,
     if (is_rj(c)) return fail(c, HENS_ERR_UNSUPPORTED, "the distribution proposal is not built for leaf-packing records");
     if (c->pipe.on) return fail(c, HENS_ERR_STATE, "the distribution proposal is not built for a rank of the ladder pipeline");
     if (c->cfg.likelihood_kind == HENS_LIKE_HOST) return fail(c, HENS_ERR_UNSUPPORTED, "the distribution proposal needs a device likelihood");
+    if (c->gibbs[1].nblocks > 0) return fail(c, HENS_ERR_UNSUPPORTED, "the distribution proposal is not built under Gibbs blocks on the MH slot (hens_set_gibbs(ctx, HENS_GIBBS_MH, 0, NULL) clears the table)");
     const LikeKernels* lk = like_kernels(c->cfg.likelihood_kind);
     if (!lk || !lk->dist(c->D))
         return fail(c, HENS_ERR_UNSUPPORTED, "the distribution proposal is built for row widths 8, 16, 32, 64 and 128 (this context's rows are %d wide)", c->D);
@@ -4973,6 +5165,7 @@ int hens_pipe_init(hens_ctx* ctx, int32_t nranks, int32_t my_rank, void* blob_ou
     if (c->pipe.on) return fail(c, HENS_ERR_STATE, "pipeline already initialised");
     if (c->prior) return fail(c, HENS_ERR_UNSUPPORTED, "prior terms are not built for a rank of the ladder pipeline (hens_set_prior_box returns to the box)");
     if (c->mh_kind == MH_DIST) return fail(c, HENS_ERR_UNSUPPORTED, "the distribution proposal is not built for a rank of the ladder pipeline (hens_set_mh_proposal(-1, ...) returns to the stretch move)");
+    if (gibbs_on(c)) return fail(c, HENS_ERR_UNSUPPORTED, "Gibbs blocks are not built for a rank of the ladder pipeline (hens_set_gibbs(ctx, move, 0, NULL) clears a table)");
     if (!c->cfg.tempered || c->T < 2) return fail(c, HENS_ERR_STATE, "the ladder pipeline needs a tempered ladder");
     if (nranks < 1 || nranks > PIPE_MAX_RANKS || my_rank < 0 || my_rank >= nranks)
         return fail(c, HENS_ERR_INVALID, "nranks must be in [1, %d] and my_rank inside it", PIPE_MAX_RANKS);

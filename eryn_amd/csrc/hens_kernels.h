@@ -151,10 +151,12 @@ __device__ __forceinline__ double pt_uniform(uint64_t seed, uint64_t it, int j, 
 // 53-bit uniforms behind zz (stretch.py:129-132) and the accept test (red_blue.py:294), and - from the 2 x 11 low bits the
 // uniforms do not use - a 22-bit number that indexes the complement half (stretch.py:93-99; a second call for the accept
 // uniform alone was a quarter of the plan's instructions).
+// `block`: the Gibbs block the proposal belongs to (hens_set_gibbs; hens_gibbs_host.h) - purpose word PURPOSE_STRETCH | block << 8, the
+// convention of PURPOSE_DIST | d << 8; block 0's word is the word of a context without a table.
 struct StretchDraw { double uz, ua; uint32_t r22; };
 constexpr int STRETCH_INDEX_BITS = 22;
-__device__ __forceinline__ StretchDraw stretch_draw(uint64_t seed, uint64_t it, uint32_t wid) {
-    const u4 d = philox4x32_10(u4{(uint32_t)it, (uint32_t)(it >> 32), wid, PURPOSE_STRETCH}, (uint32_t)seed, (uint32_t)(seed >> 32));
+__device__ __forceinline__ StretchDraw stretch_draw(uint64_t seed, uint64_t it, uint32_t wid, uint32_t block = 0) {
+    const u4 d = philox4x32_10(u4{(uint32_t)it, (uint32_t)(it >> 32), wid, PURPOSE_STRETCH | (block << 8)}, (uint32_t)seed, (uint32_t)(seed >> 32));
     return StretchDraw{u01(d.x, d.y), u01(d.z, d.w), ((d.y & 0x7FFu) << 11) | (d.w & 0x7FFu)};
 }
 __device__ __forceinline__ int stretch_index(uint32_t r22, int Nc) {          // uniform on [0, Nc), Nc <= 2^22
@@ -191,28 +193,29 @@ __device__ __forceinline__ double2 mh_normal_from32(const uint32_t a, const uint
     const float r = __builtin_sqrtf(-2.0f * lf);
     return double2{(double)(r * __builtin_amdgcn_cosf(ang)), (double)(r * __builtin_amdgcn_sinf(ang))};
 }
-__device__ __forceinline__ uint32_t mh_normal_key(uint32_t pr) { return PURPOSE_MH_NORMAL | (pr << 8); }
+// (Gibbs block `block`, hens_set_gibbs: the pair already sits at bit 8 - up to 64 pairs - so the block rides at bit 16; block 0: today's word)
+__device__ __forceinline__ uint32_t mh_normal_key(uint32_t pr, uint32_t block = 0) { return PURPOSE_MH_NORMAL | (pr << 8) | (block << 16); }
 // FOUR normals per Philox call: the pairs (2 pr, 2 pr + 1) of TWO walkers of a rung, g rows apart (w with bit g clear: words x, y;
 // bit g set: z, w) - the two rows one lane of the in-place MH launch owns in adjacent passes (g = its rows per pass, mh_pair_rows(D);
 // g = 0: every walker its own call, words x, y).  The launch was bound by the 40 quarter-rate multiplies of a call per pair
 // (config 5 on one GPU: 147 us for 268 MB of rows); k_mh_draw and hens_debug_draws evaluate the same function of (walker, pair).
-__device__ __forceinline__ u4 mh_normal_quad(uint64_t seed, uint64_t it, uint32_t rung, uint32_t W, uint32_t w_low, uint32_t pr) {
-    const u4 ctr{(uint32_t)it, (uint32_t)(it >> 32), rung * W + w_low, mh_normal_key(pr)};
+__device__ __forceinline__ u4 mh_normal_quad(uint64_t seed, uint64_t it, uint32_t rung, uint32_t W, uint32_t w_low, uint32_t pr, uint32_t block = 0) {
+    const u4 ctr{(uint32_t)it, (uint32_t)(it >> 32), rung * W + w_low, mh_normal_key(pr, block)};
     return philox4x32_10(ctr, (uint32_t)seed, (uint32_t)(seed >> 32));
 }
-__device__ __forceinline__ double2 mh_normal_pair(uint64_t seed, uint64_t it, uint32_t rung, uint32_t W, uint32_t w, uint32_t pr, uint32_t g) {
-    const u4 d = mh_normal_quad(seed, it, rung, W, w & ~g, pr);
+__device__ __forceinline__ double2 mh_normal_pair(uint64_t seed, uint64_t it, uint32_t rung, uint32_t W, uint32_t w, uint32_t pr, uint32_t g, uint32_t block = 0) {
+    const u4 d = mh_normal_quad(seed, it, rung, W, w & ~g, pr, block);
     return (w & g) ? mh_normal_from32(d.z, d.w) : mh_normal_from32(d.x, d.y);
 }
 __host__ __device__ constexpr int mh_pair_rows(int D) {        // rows per pass of k_stretch_fast<D> (RPP) where a lane owns two rows or more
     return D == 128 ? 8 : (D == 64 ? 16 : ((D == 32 || D == 16) ? 32 : 0));
 }
-__device__ __forceinline__ double mh_uniform(uint64_t seed, uint64_t it, uint32_t wid) {         // mh.py:157
-    const u4 ctr{(uint32_t)it, (uint32_t)(it >> 32), wid, PURPOSE_MH_ACC};
+__device__ __forceinline__ double mh_uniform(uint64_t seed, uint64_t it, uint32_t wid, uint32_t block = 0) {         // mh.py:157
+    const u4 ctr{(uint32_t)it, (uint32_t)(it >> 32), wid, PURPOSE_MH_ACC | (block << 8)};
     const u4 d = philox4x32_10(ctr, (uint32_t)seed, (uint32_t)(seed >> 32));
     return u01(d.x, d.y);
 }
-__device__ __forceinline__ double mh_log_uniform(uint64_t seed, uint64_t it, uint32_t wid) { return log(mh_uniform(seed, it, wid)); }
+__device__ __forceinline__ double mh_log_uniform(uint64_t seed, uint64_t it, uint32_t wid, uint32_t block = 0) { return log(mh_uniform(seed, it, wid, block)); }
 
 // ---------------------------------------------------------------------------------------------
 // Ladder-pipeline primitives (used by the stretch kernels too; the protocol is described at k_pipe_*).
@@ -757,6 +760,11 @@ static_assert(sizeof(StretchArgs) == 696, "StretchArgs grew: the timed launches'
 // per-parameter prior terms of a launch (k_stretch only: a context with terms launches no other stepping kernel), or nullptr
 __device__ __forceinline__ const PriorTerm* prior_terms_of(const StretchArgs& A) {
     return A.prior_on ? reinterpret_cast<const PriorTerm*>(A.hi + A.D) : nullptr;
+}
+// prior_on == 2 (a Gibbs block's launch, hens_set_gibbs): the block's coordinate mask follows the records - lo[D] hi[D] terms[D]
+// mask[D], one int32 per coordinate, 0 = frozen (gibbs_image: hens_gibbs_host.h)
+__device__ __forceinline__ const int32_t* gibbs_mask_of(const StretchArgs& A) {
+    return reinterpret_cast<const int32_t*>(prior_terms_of(A) + A.D);
 }
 
 // One workgroup = TILE (64) walkers of one rung, NW wavefronts.  Generic row width (runtime D).
@@ -2330,6 +2338,7 @@ struct MhDrawArgs {
     uint64_t iter, seed;
     int32_t Tl, W, D, rung_begin, kind, chol_lds;
     double* dbg_u;           // debug (hens_debug_draws): the raw accept uniforms [Tl][W], or nullptr
+    uint32_t block;          // the Gibbs block the proposal belongs to (hens_set_gibbs), 0 without a table: the draws' purpose words
 };
 // Philox mode: step = scale * z (isotropic / diagonal) or chol * z (full covariance), z ~ N(0, 1) by
 // Box-Muller from Philox counters keyed (iteration, global rung, walker, coordinate pair); the accept
@@ -2347,14 +2356,14 @@ inline __global__ __launch_bounds__(256) void k_mh_draw(const MhDrawArgs A) {
     for (int i = threadIdx.x; i < 64 * npair; i += blockDim.x) {
         const int wl = i / npair, pr = i - wl * npair, w = w0 + wl;
         if (w >= W) continue;
-        const double2 n2 = mh_normal_pair(A.seed, A.iter, rung, (uint32_t)W, (uint32_t)w, (uint32_t)pr, (uint32_t)mh_pair_rows(D));
+        const double2 n2 = mh_normal_pair(A.seed, A.iter, rung, (uint32_t)W, (uint32_t)w, (uint32_t)pr, (uint32_t)mh_pair_rows(D), A.block);
         z[wl * ZS + 2 * pr] = n2.x;
         if (2 * pr + 1 < D) z[wl * ZS + 2 * pr + 1] = n2.y;
     }
     if (threadIdx.x < 64 && w0 + (int)threadIdx.x < W) {
         const int w = w0 + threadIdx.x;
-        A.lu[(size_t)tl * W + w] = mh_log_uniform(A.seed, A.iter, rung * (uint32_t)W + (uint32_t)w);
-        if (A.dbg_u) A.dbg_u[(size_t)tl * W + w] = mh_uniform(A.seed, A.iter, rung * (uint32_t)W + (uint32_t)w);
+        A.lu[(size_t)tl * W + w] = mh_log_uniform(A.seed, A.iter, rung * (uint32_t)W + (uint32_t)w, A.block);
+        if (A.dbg_u) A.dbg_u[(size_t)tl * W + w] = mh_uniform(A.seed, A.iter, rung * (uint32_t)W + (uint32_t)w, A.block);
     }
     __syncthreads();
     const bool in_lds = A.kind == MH_FULL && A.chol_lds;
@@ -2607,6 +2616,45 @@ inline __global__ __launch_bounds__(256) void k_plan_draws(const PlanArgs A) {
     if (A.dbg_uzz) {
         A.dbg_uzz[base + q] = pd.uz;
         A.dbg_uacc[base + q] = pd.ua;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// The plan of ONE Gibbs block (hens_set_gibbs) on top of an iteration's plan: the split labels and both position lists are the
+// iteration's (red_blue.py:119-124: drawn once, before the block loop) - `own` of the planned slot, by either plan above - and
+// position q of block b draws its complement index and its two uniforms from stretch_draw's word PURPOSE_STRETCH | b << 8, the
+// shapes of a proposal without Gibbs (red_blue.py:148-197).  The complement of a first-half position is the walker at place
+// stretch_index(r22, W - N0) of the second half and the reverse: own[N0 + r] / own[r] in both plans' orders (k_plan: halves of
+// ceil(W / 2) and floor(W / 2); block-balanced labels: W even).  The factor is the block's, (n_b - 1) log zz (stretch.py:55-72).
+// Block 0 with n_b = the row's real dimension writes what the iteration's plan holds.
+// ---------------------------------------------------------------------------------------------
+struct PlanBlockArgs {
+    const int32_t* own;   // [Tl][W] the planned iteration's position lists
+    Draws dr;             // [Tl][W] cw, zz, fac, lu of the block (dr.own is not written: the launches read `own`)
+    double* dbg_uzz;      // debug (hens_debug_draws_block): the raw uniforms, or nullptr
+    double* dbg_uacc;
+    uint64_t iter, seed;
+    double a;
+    int32_t Tl, W, nb, rung_begin;
+    uint32_t block;
+};
+inline __global__ __launch_bounds__(256) void k_plan_block(const PlanBlockArgs A) {
+    const int tl = blockIdx.y, W = A.W, N0 = (W + 1) / 2;
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= W) return;
+    const uint32_t rung = (uint32_t)(A.rung_begin + tl);
+    const size_t base = (size_t)tl * W;
+    const bool s0 = q < N0;
+    const StretchDraw sd = stretch_draw(A.seed, A.iter, rung * (uint32_t)W + (uint32_t)q, A.block);
+    const int r = stretch_index(sd.r22, s0 ? W - N0 : N0);
+    const DrawRec rc = draw_values(A.own[base + q], A.own[base + (s0 ? N0 : 0) + r], sd.uz, sd.ua, A.a, A.nb);
+    A.dr.cw[base + q] = rc.cw;
+    A.dr.zz[base + q] = rc.zz;
+    A.dr.fac[base + q] = rc.fac;
+    A.dr.lu[base + q] = rc.lu;
+    if (A.dbg_uzz) {
+        A.dbg_uzz[base + q] = sd.uz;
+        A.dbg_uacc[base + q] = sd.ua;
     }
 }
 

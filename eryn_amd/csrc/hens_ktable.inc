@@ -1,7 +1,8 @@
 // hens_ktable.inc - body of a per-likelihood kernel translation unit: define HENS_KT_LIKE (LIKE_DENSE ...) and HENS_KT_NAME
 // (dense ...) and include.  See hens_ktable.h.  HENS_KT_PART (from the build) halves a unit once more: 0 = the half-step kernels
 // (k_stretch_fast, k_stretch), 1 = the fused ones (k_split1_pt, k_iter), 2 = k_stretch_prior (hens_prior.h: a unit of its own, so that
-// the units of the kernels that were there before compile to the code they compiled to), 3 = k_dist (hens_dist.h: likewise); undefined = all.
+// the units of the kernels that were there before compile to the code they compiled to), 3 = k_dist (hens_dist.h: likewise),
+// 4 = k_stretch_prior<GIBBS> (hens_prior.h: the half-step of a Gibbs block, likewise); undefined = all.
 #include "hens_kernels.h"
 #include "hens_iter.h"
 #include "hens_tile2.h"
@@ -73,6 +74,31 @@ const void* KT(ktab_stretch_prior_)(int mode, int D) {
         case MODE_STRETCH: return kt_prior_mode<MODE_STRETCH>(D);
         case MODE_EVAL: return kt_prior_mode<MODE_EVAL>(D);
         case MODE_MH: return kt_prior_mode<MODE_MH>(D);
+    }
+    return nullptr;
+}
+#endif
+#if !defined(HENS_KT_PART) || HENS_KT_PART == 4
+}  // namespace hens
+#include "hens_prior.h"
+namespace hens {
+template <int MODE>
+static const void* kt_gibbs_mode(int D) {
+    constexpr int L = HENS_KT_LIKE;
+#ifdef HENS_DEV_BUILD
+    (void)D;
+    return nullptr;            // (a dev build carries no Gibbs launch)
+#else
+#define KT_GIBBS(DT, NW) if (D == DT) return KPTR(k_stretch_prior<DT, L, MODE, NW, true>);
+    KT_GIBBS(32, 8) KT_GIBBS(64, 8) KT_GIBBS(16, 4) KT_GIBBS(8, 4) KT_GIBBS(128, 8)
+#undef KT_GIBBS
+    return nullptr;
+#endif
+}
+const void* KT(ktab_stretch_gibbs_)(int mode, int D) {
+    switch (mode) {
+        case MODE_STRETCH: return kt_gibbs_mode<MODE_STRETCH>(D);
+        case MODE_MH: return kt_gibbs_mode<MODE_MH>(D);
     }
     return nullptr;
 }

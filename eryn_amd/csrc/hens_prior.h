@@ -22,6 +22,14 @@
 // tile's stride DT + 2 (chosen for its b128 reads) would put lanes l and l + 16 on one pair at DT = 32, 64, 128.  D = 128, NW = 8:
 // 66.6 kB proposal tile + 66.0 kB term tile + 1 kB mu + 5.6 kB = 139 kB of the CU's 160: it fits, one workgroup per CU.
 // Launched on the HIP stream with a release, like every copying launch; not among the fence-free kernels of the store census.
+//
+// GIBBS (hens_set_gibbs; instantiated in a unit of its own, MODE_STRETCH and MODE_MH): the half-step of ONE Gibbs block
+// (move.py:113-221, red_blue.py:119-333, mh.py:79-193).  The launch's term block carries the block's coordinate mask behind the
+// records (prior_on == 2, gibbs_mask_of); the lane that holds coordinates e, e + 1 reads its two mask words once and phase B forms
+// q_d = m_d ? proposal : s_d - a frozen coordinate is the old row's BITS (a select, never s + 0.0: the sign of a zero survives;
+// move.py:321-324 puts the old values back).  Pads are frozen by the host's mask.  Everything else is the code above, called: the
+// supports and terms of the whole row, the likelihood of the whole row, the accept test, phase E.  The planned Hastings factor is
+// the block's, (n_b - 1) log zz (stretch.py:55-72).
 #pragma once
 #include "hens_kernels.h"
 
@@ -144,10 +152,11 @@ __device__ __forceinline__ PairTerms pair_terms(const PriorTerm& t0, const Prior
     return o;
 }
 
-template <int DT, int LIKE, int MODE, int NW>
+template <int DT, int LIKE, int MODE, int NW, bool GIBBS = false>
 __global__ __launch_bounds__(NW * 64) void k_stretch_prior(const StretchArgs A) {
     constexpr bool EVAL = MODE == MODE_EVAL, MH = MODE == MODE_MH;
     static_assert(DT == 8 || DT == 16 || DT == 32 || DT == 64 || DT == 128, "power-of-two row width");
+    static_assert(!GIBBS || !EVAL, "an evaluation proposes nothing: no mask to apply");
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     using Tile = TermTile<DT, NW>;
     constexpr int D = DT, RS = Tile::RS, LPR = Tile::LPR;
@@ -212,6 +221,8 @@ __global__ __launch_bounds__(NW * 64) void k_stretch_prior(const StretchArgs A) 
     const double2 lov = *reinterpret_cast<const double2*>(A.lo + e);
     const double2 hiv = *reinterpret_cast<const double2*>(A.hi + e);
     const PriorTerm t0 = terms[e], t1 = terms[e + 1];
+    int2 mk{1, 1};
+    if constexpr (GIBBS) mk = *reinterpret_cast<const int2*>(gibbs_mask_of(A) + e);
     const double* __restrict__ pool_r = A.pool;
     T.rows([&](int r, int fl) {
         const bool rvalid = (fl & F_VALID) != 0;
@@ -231,6 +242,10 @@ __global__ __launch_bounds__(NW * 64) void k_stretch_prior(const StretchArgs A) 
                 } else {
                     qv.x = cv.x - (cv.x - sv.x) * zz; // stretch.py:143,145
                     qv.y = cv.y - (cv.y - sv.y) * zz;
+                }
+                if constexpr (GIBBS) {                // move.py:321-324: outside the block the old row, bit for bit
+                    qv.x = mk.x ? qv.x : sv.x;
+                    qv.y = mk.y ? qv.y : sv.y;
                 }
             }
             *reinterpret_cast<double2*>(T.qtile + r * RS + e) = qv;

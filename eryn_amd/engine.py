@@ -88,6 +88,7 @@ class HipEnsemble(ChainStoreCalls):
                          fill_value=float(fill_value), adaptation_lag=float(adaptation_lag),
                          adaptation_time=float(adaptation_time), seed=int(seed) & (2**64 - 1))
         self.tempered = bool(tempered)
+        self.gibbs = dict(stretch=None, mh=None)      # the block tables the context holds (set_gibbs), [nblocks, D] bool or None
         self.state_epoch = 0         # bumped by every call that changes the walkers: a DeviceState (eryn_amd/state.py) is current while it matches
         self.lazy_downloads = 0
         self.a = float(a)
@@ -375,8 +376,9 @@ class HipEnsemble(ChainStoreCalls):
         check(self.lib.hens_get_iteration(self.ctx, C.byref(n)), self.ctx)
         return int(n.value)
 
-    def debug_draws(self, it, mh=False):
-        """The Philox draws ``step`` consumes in iteration ``it`` (include/hipensemble.h: hens_debug_draws)."""
+    def debug_draws(self, it, mh=False, block=0):
+        """The Philox draws ``step`` consumes in iteration ``it`` (include/hipensemble.h: hens_debug_draws); ``block``: those of
+        that Gibbs block of the iteration's move (hens_debug_draws_block)."""
         T, Tl, W, D = self.T, self.Tl, self.W, self.D
         out = dict(own=np.empty((Tl, W), dtype=np.int32), cw=np.empty((Tl, W), dtype=np.int32),
                    u_zz=np.empty((Tl, W)), u_acc=np.empty((Tl, W)))
@@ -386,11 +388,16 @@ class HipEnsemble(ChainStoreCalls):
         if mh:
             out.update(mh_step=np.empty((Tl, W, self.RW)), mh_u=np.empty((Tl, W)))
         is_mh = C.c_int32(0)
-        check(self.lib.hens_debug_draws(self.ctx, int(it), ptr(out["own"]), ptr(out["cw"]), ptr(out["u_zz"]),
-                                        ptr(out["u_acc"]), ptr(out.get("pt_slot")), ptr(out.get("u_swap")),
-                                        C.byref(is_mh), ptr(out.get("mh_step")), ptr(out.get("mh_u"))), self.ctx)
+        fn, head = (self.lib.hens_debug_draws_block, (int(it), int(block))) if block else (self.lib.hens_debug_draws, (int(it),))
+        check(fn(self.ctx, *head, ptr(out["own"]), ptr(out["cw"]), ptr(out["u_zz"]), ptr(out["u_acc"]), ptr(out.get("pt_slot")),
+                 ptr(out.get("u_swap")), C.byref(is_mh), ptr(out.get("mh_step")), ptr(out.get("mh_u"))), self.ctx)
         out["is_mh"] = bool(is_mh.value)
-        if mh and self.RW != D:
+        for move, keys in (("stretch", ("cw", "u_zz", "u_acc")), ("mh", ("mh_step", "mh_u"))) if block else ():
+            table = self.gibbs[move]               # (the other move's table may be shorter: its arrays are not written then)
+            if block >= (1 if table is None else len(table)):
+                for k in keys:
+                    out.pop(k, None)
+        if mh and self.RW != D and "mh_step" in out:
             out["mh_step"] = np.ascontiguousarray(out["mh_step"][..., :D])
         return out
 
@@ -502,6 +509,29 @@ class HipEnsemble(ChainStoreCalls):
         fac = np.empty((self.Tl, self.W)) if want_factors else None
         check(self.lib.hens_dist_step(self.ctx, ptr(q), ptr(u_acc), ptr(keep), ptr(fac)), self.ctx)
         return (keep.astype(bool), fac) if want_factors else keep.astype(bool)
+
+    # -- Gibbs parameter blocks (include/hipensemble.h: hens_set_gibbs, hens_gibbs_select) ---------------
+    GIBBS_MOVES = dict(stretch=0, mh=1)
+
+    def set_gibbs(self, move, masks):
+        """The block table of ``move`` ("stretch" | "mh"): ``masks`` bool ``[nblocks, ndim]``, one row per Gibbs block (true = the
+        coordinate moves with the block), or None / empty to clear it.  ``step()`` then proposes block after block and runs one
+        cascade per iteration; the teacher-forced calls propose the block ``gibbs_select`` names."""
+        m = self.GIBBS_MOVES[move]
+        masks = None if masks is None else np.atleast_2d(np.asarray(masks, dtype=bool))
+        if masks is None or masks.shape[0] == 0:
+            check(self.lib.hens_set_gibbs(self.ctx, m, 0, None), self.ctx)
+            self.gibbs[move] = None
+            return
+        if masks.ndim != 2 or masks.shape[1] != self.D:
+            raise ValueError(f"masks must have shape (nblocks, {self.D})")
+        padded = np.zeros((masks.shape[0], self.RW), dtype=np.uint8)
+        padded[:, :self.D] = masks
+        check(self.lib.hens_set_gibbs(self.ctx, m, masks.shape[0], ptr(padded)), self.ctx)
+        self.gibbs[move] = masks.copy()
+
+    def gibbs_select(self, move, block):
+        check(self.lib.hens_gibbs_select(self.ctx, self.GIBBS_MOVES[move], int(block)), self.ctx)
 
     def mh_counters(self):
         acc = np.zeros((self.Tl, self.W))

@@ -112,6 +112,11 @@ class EnsembleSampler:
         for m in self.moves:
             if not isinstance(m, DeviceMove):
                 raise NotImplementedError("only eryn_amd.moves.StretchMove / GaussianMove / DistributionGenerate run on the device path")
+            if m.gibbs_sampling_setup is not None:
+                if hasattr(log_like_fn, "evaluate"):
+                    raise NotImplementedError("gibbs_sampling_setup steps on the device: it needs a device likelihood "
+                                              "(eryn_amd.likelihood), not a Python function")
+                m.gibbs_masks(self.branch_names[0], self.ndim)       # (the shapes, before anything runs)
         stretch_moves = [m for m in self.moves if isinstance(m, StretchMove)]
         # the W >= 2 ndim guard belongs to the red-blue move (red_blue.py:108-114): without one it does not apply
         live = any(m.live_dangerously for m in stretch_moves) or not stretch_moves
@@ -322,6 +327,13 @@ class EnsembleSampler:
             eng.set_nsplits(st_move.nsplits)
         if st_move is not None and eng.a != float(st_move.a):
             eng.set_stretch_scale(st_move.a)
+        for m in (st_move, mh_move):                         # both moves' Gibbs block tables (hens_set_gibbs)
+            if m is not None:
+                m._sync_gibbs(eng, name, self.ndim)
+        if st_move is None and eng.gibbs["stretch"] is not None:
+            eng.set_gibbs("stretch", None)
+        if mh_move is None and eng.gibbs["mh"] is not None:
+            eng.set_gibbs("mh", None)
 
     def _sample_philox(self, state, iterations, thin_by, store, tune=False):
         eng, tc, name = self.engine, self.temperature_control, self.branch_names[0]

@@ -100,6 +100,21 @@ class DeviceMove(Move):
         if (per is None) != (cur is None) or (per is not None and not np.array_equal(per, cur)):
             eng.set_periodic(per)
 
+    # -- Gibbs parameter blocks: the move's table on the context (csrc/hens.hip: hens_set_gibbs) -------------
+    GIBBS_KEY = None                   # "stretch" | "mh": which of the context's two block tables is this move's
+
+    def _sync_gibbs(self, eng, name, D):
+        """The context's table for this move's slot := this move's blocks (None: cleared); returns them, ``[nblocks, D]`` or None.
+        Moves of one sampler share the context, so every proposal states its own."""
+        masks = self.gibbs_masks(name, D)
+        if masks is not None and hasattr(eng.likelihood, "evaluate"):
+            raise NotImplementedError("gibbs_sampling_setup steps on the device: it needs a device likelihood (eryn_amd.likelihood), "
+                                      "not a Python function")
+        cur = eng.gibbs[self.GIBBS_KEY] if hasattr(eng, "gibbs") else None      # (a duck-typed context holds no table)
+        if (masks is None) != (cur is None) or (masks is not None and not np.array_equal(masks, cur)):
+            eng.set_gibbs(self.GIBBS_KEY, masks)
+        return masks
+
     @staticmethod
     def _single_branch(state):
         names = list(state.branches.keys())
@@ -195,13 +210,15 @@ class DeviceMove(Move):
         tc = self.temperature_control
         self._apply_periodic(eng, name, D)
         self._upload_if_needed(eng, state, br)
+        gibbs = self._sync_gibbs(eng, name, D)
         want = ("mh",) + mh_slot_key(mh_proposal) if mh_proposal else ("stretch",)
         if getattr(eng, "_move_cfg", None) != want:          # which move the context's next iteration runs (weight 1: no mix inside)
             push_mh_slot(eng, mh_proposal, 1.0)
             eng._move_cfg = want
         self._bump(eng)
         acc, swaps, betas = eng.step_report(1, 1)
-        accepted = acc.view(np.bool_)                                  # (one iteration: the counts are 0 / 1)
+        # (one iteration: the counts are 0 / 1 - under Gibbs blocks a walker's accepted block proposals: the mask is "any block")
+        accepted = acc.view(np.bool_) if gibbs is None else acc != 0
         if tc is not None:
             tc.swaps_accepted = swaps if T > 1 else np.empty(0)
             if T > 1 and tc.adaptive:

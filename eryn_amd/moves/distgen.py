@@ -23,6 +23,9 @@ class DistributionGenerate(MHMove):
     reference's does) or the ``{index: distribution}`` dict it is made of; uniform, log-uniform and normal entries."""
 
     def __init__(self, generate_dist, **kwargs):
+        if kwargs.get("gibbs_sampling_setup") is not None:
+            raise NotImplementedError("DistributionGenerate(gibbs_sampling_setup=...) is not built: the device draws whole rows from the "
+                                      "generator (Gibbs blocks: eryn_amd.moves.StretchMove, GaussianMove)")
         if not isinstance(generate_dist, dict):                            # distgen.py:21-24
             raise ValueError(
                 "When entering directly into the DistributionGenerate class, generate_dist must be a dictionary. The keys are branch names and the items are ProbDistContainer objects."

@@ -16,6 +16,8 @@ class MHMove(DeviceMove):
     """Base of the full-ensemble Metropolis-Hastings moves: subclasses return the step ``q - x`` of every
     walker from ``get_step(random, n, ndim)`` (the device adds it, so factors = 0: symmetric proposals)."""
 
+    GIBBS_KEY = "mh"
+
     def get_step(self, random, n, ndim):
         raise NotImplementedError("The proposal must be implemented by subclasses")
 
@@ -28,13 +30,20 @@ class MHMove(DeviceMove):
             return self._propose_philox(model, state, mh_proposal=self.device_proposal())
         self._apply_periodic(eng, name, D)
         self._upload_if_needed(eng, state, br)
+        gibbs = self._sync_gibbs(eng, name, D)
         self._bump(eng)
-        step = self.get_step(model.random, T * W, D)                   # gaussian.py:116 (all leaves active)
-        u_acc = model.random.rand(T, W)                                # mh.py:157
-        accepted = eng.mh_step(step, u_acc)
-        if self._accepted is not None:
-            self.accepted += accepted                                  # mh.py:186
-        self.num_proposals += 1
+        accepted = np.zeros((T, W), dtype=bool)                        # mh.py:77
+        for b, mask in enumerate([None] if gibbs is None else gibbs):  # mh.py:80-187: block after block
+            if mask is not None:
+                if not mask.any():                                     # mh.py:106-107
+                    continue
+                eng.gibbs_select("mh", b)
+            step = self.get_step(model.random, T * W, D)               # gaussian.py:116 (all leaves active; every coordinate is drawn,
+            u_acc = model.random.rand(T, W)                            #   the device puts the old values back outside the block); mh.py:157
+            accepted = eng.mh_step(step, u_acc)                        # (the LAST block's mask goes back: mh.py:171,193)
+            if self._accepted is not None:
+                self.accepted += accepted                              # mh.py:186
+            self.num_proposals += 1
         return self._finish(eng, state, name, br, T, W), accepted
 
 

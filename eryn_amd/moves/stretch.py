@@ -35,6 +35,7 @@ class StretchMove(DeviceMove):
     """
 
     needs_walker_guard = True          # red_blue.py:108-114
+    GIBBS_KEY = "stretch"
 
     def __init__(self, a=2.0, nsplits=2, randomize_split=True, live_dangerously=False, likelihood=None,
                  prior_box=None, device_id=0, fill_value=-1e300, trust_resident=False, return_gpu=False,
@@ -61,30 +62,39 @@ class StretchMove(DeviceMove):
             return self._propose_philox(model, state)
         self._apply_periodic(eng, name, D)
         self._upload_if_needed(eng, state, br)
+        gibbs = self._sync_gibbs(eng, name, D)
         self._bump(eng)
 
+        # The reference's block loop (red_blue.py:131-327), one block without a setup: one labelling for all blocks; per block and
+        # split the usual draws; ``accepted`` is the running OR over the blocks so far and is added to ``self.accepted`` after EVERY
+        # block (red_blue.py:306-308, 326-327: a walker accepted in block 0 counts again in block 1); one cascade behind the last.
         accepted = np.zeros((T, W), dtype=bool)
         labels = np.tile(np.arange(W), (T, 1)) % self.nsplits         # red_blue.py:119-124
         if self.randomize_split:
             [np.random.shuffle(row) for row in labels]
         tt = np.arange(T)[:, None]
-        for split in range(self.nsplits):
-            S = np.stack([np.flatnonzero(labels[t] == split) for t in range(T)])
-            Ns = S.shape[1]
-            Nc = W - Ns
-            rint = model.random.randint(Nc, size=(T, Ns))              # stretch.py:93-99
-            u_zz = model.random.rand(T, Ns)                            # stretch.py:129-132
-            if hasattr(eng.likelihood, "evaluate"):
-                # arbitrary Python likelihood: propose on the device, evaluate here, accept on the device
-                q, inbox = eng.propose_split(split, labels, rint, u_zz)
-                logl = eng.likelihood.evaluate(q, inbox)               # ensemble.py:1219-1545
-                u_acc = model.random.rand(T, Ns)                       # red_blue.py:294 (drawn after the likelihood)
-                keep = eng.accept_split(split, logl, u_acc)
-            else:
-                u_acc = model.random.rand(T, Ns)                       # red_blue.py:294
-                keep = eng.stretch_split(split, labels, rint, u_zz, u_acc)
-            accepted[tt, S] = keep
-        if self._accepted is not None:
-            self.accepted += accepted                                  # red_blue.py:326-327
-        self.num_proposals += 1
+        for b, mask in enumerate([None] if gibbs is None else gibbs):
+            if mask is not None:
+                if not mask.any():                                     # red_blue.py:143-144: nothing to propose, no draw
+                    continue
+                eng.gibbs_select("stretch", b)
+            for split in range(self.nsplits):
+                S = np.stack([np.flatnonzero(labels[t] == split) for t in range(T)])
+                Ns = S.shape[1]
+                Nc = W - Ns
+                rint = model.random.randint(Nc, size=(T, Ns))          # stretch.py:93-99
+                u_zz = model.random.rand(T, Ns)                        # stretch.py:129-132
+                if hasattr(eng.likelihood, "evaluate"):
+                    # arbitrary Python likelihood: propose on the device, evaluate here, accept on the device
+                    q, inbox = eng.propose_split(split, labels, rint, u_zz)
+                    logl = eng.likelihood.evaluate(q, inbox)           # ensemble.py:1219-1545
+                    u_acc = model.random.rand(T, Ns)                   # red_blue.py:294 (drawn after the likelihood)
+                    keep = eng.accept_split(split, logl, u_acc)
+                else:
+                    u_acc = model.random.rand(T, Ns)                   # red_blue.py:294
+                    keep = eng.stretch_split(split, labels, rint, u_zz, u_acc)
+                accepted[tt, S] |= keep
+            if self._accepted is not None:
+                self.accepted += accepted                              # red_blue.py:326-327
+            self.num_proposals += 1
         return self._finish(eng, state, name, br, T, W), accepted

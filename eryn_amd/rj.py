@@ -576,11 +576,18 @@ class TemplateLikelihood:
         self.t, self.y, self.sigma = (None if t is None else f64(t)), (None if y is None else f64(y)), float(sigma)
 
 
+def _no_leaf_gibbs(gibbs_sampling_setup):
+    if gibbs_sampling_setup is not None:
+        raise NotImplementedError("gibbs_sampling_setup over leaves and branches is not built: leaf-packing records step every leaf of "
+                                  "every branch in one move (Gibbs blocks: eryn_amd.EnsembleSampler with moves.StretchMove / GaussianMove)")
+
+
 class GaussianLeafMove:
     """``GaussianMove(cov_all)`` of the reference on leaf-packing records (gaussian.py:9-66): ``cov_all[name]`` is the
     3 x 3 proposal covariance of a leaf of that branch (the reference's ``_proposal``: ``multivariate_normal``)."""
 
-    def __init__(self, cov_all):
+    def __init__(self, cov_all, gibbs_sampling_setup=None):
+        _no_leaf_gibbs(gibbs_sampling_setup)
         self.cov = {k: np.atleast_2d(np.asarray(v, dtype=np.float64)) for k, v in cov_all.items()}
         for k, c in self.cov.items():
             if c.ndim != 2 or c.shape[0] != c.shape[1] or not 1 <= c.shape[0] <= 4:
@@ -593,7 +600,8 @@ class StretchLeafMove:
     red_blue.py:103-330): every branch and every leaf slot of a walker moves - one complement walker per branch, one stretch
     factor per walker.  (The reference advises against it beside reversible jump, ensemble.py:509-514, and runs it.)"""
 
-    def __init__(self, a=2.0, live_dangerously=False):
+    def __init__(self, a=2.0, live_dangerously=False, gibbs_sampling_setup=None):
+        _no_leaf_gibbs(gibbs_sampling_setup)
         self.a = float(a)
         self.live_dangerously = bool(live_dangerously)         # red_blue.py:41-47,108: fewer walkers than 2 x (all leaf slots' coordinates)
         self.accepted, self.num_proposals = None, 0
@@ -630,6 +638,8 @@ class RJEnsembleSampler:
                  backend=None, **unused):
         from .backend import RJDeviceBackend
         from .moves.tempering import TemperatureControl
+        for m in (moves if isinstance(moves, (list, tuple)) else [moves]):
+            _no_leaf_gibbs(getattr(m[0] if isinstance(m, (list, tuple)) else m, "gibbs_sampling_setup", None))
         # backend: None - the stored steps are a list of States (``self.chain``) - or an eryn_amd.backend.RJDeviceBackend: they stay
         # in device memory until somebody reads them (one device call per chain segment, hens_rj_step_chain)
         if backend is not None and not isinstance(backend, RJDeviceBackend):

@@ -485,6 +485,45 @@ int hens_set_dist_proposal(hens_ctx* ctx, const int32_t* kind, const double* lo,
                            const double* c1, const double* c2, double weight);
 int hens_dist_step(hens_ctx* ctx, const double* q, const double* u_acc, uint8_t* keep_out, double* factors_out);
 
+/* ---- Gibbs parameter blocks: gibbs_sampling_setup (move.py:113-221) ------------------------------------
+ * The reference's moves take a list of parameter blocks and propose block after block: for every block the move's usual draws,
+ * the proposal, the old values put back in every coordinate outside the block (move.py:321-324), prior and likelihood of the
+ * whole row, the accept test, the update - and ONE swap cascade behind the last block (red_blue.py:119-333, mh.py:79-193).  Here,
+ * for one branch with nleaves_max == 1: a block table per move.
+ *
+ * hens_set_gibbs(ctx, move, nblocks, mask): move = HENS_GIBBS_STRETCH (the stretch move) or HENS_GIBBS_MH (the Gaussian move in
+ * the MH slot) - each its own table, as each reference move has its own setup; mask u8 [nblocks][D], non-zero = the coordinate
+ * moves with the block (D the context's row width; the pads of a padded row must be 0).  Blocks may overlap and need not cover
+ * every coordinate; nblocks == 0 clears the table.  While either move has a table the context steps on the copying launches (as
+ * one with prior terms does); an iteration of hens_step / _marked / _report / _chain is, per block of the iteration's move, a
+ * plan of the block's draws and the two copying half-steps - or k_mh_draw and the MH launch - then one cascade.  A move without a
+ * table of its own runs as one all-true block.  The stretch move's Hastings factor is (n_b - 1) log zz, n_b the block's true
+ * coordinates (stretch.py:55-72); a frozen coordinate keeps the old row's bits.
+ * Device draws: block b draws from the functions a context without a table uses, with the purpose word of the counter
+ * (word 3) carrying the block: PURPOSE_STRETCH | b << 8 (complement index, u_zz, accept uniform), PURPOSE_MH_ACC | b << 8, and
+ * PURPOSE_MH_NORMAL | pair << 8 | b << 16 (the pair of coordinates already sits at bit 8).  Block 0's words are those of a
+ * context without a table: one all-true block draws what no table draws.  The split labels (one labelling per iteration, as in
+ * the reference), the move choice and the PT draws do not depend on the block.
+ * Counters: `accepted` (hens_get_counters / hens_get_mh_counters) counts a walker once per accepted block proposal - the MH
+ * move's rule in the reference (mh.py:186); its red-blue move adds the running OR over the blocks so far (red_blue.py:306-327),
+ * which eryn_amd's rng="numpy" moves reproduce on the host.  num_proposals advances by the number of blocks per iteration
+ * (the reference's += 1 per block).  The mask of hens_step_report counts a walker's accepted block proposals over the call's
+ * last iterations: non-zero = "any block".
+ * Refused, with the context unchanged: nblocks < 0 or > 128, a block without a true coordinate (the reference skips it
+ * silently), a true pad (HENS_ERR_INVALID); a half-step pending (HENS_ERR_STATE); periodic parameters, a rank of the ladder
+ * pipeline or a ladder shard, hens_set_nsplits other than 2, a leaf-packing context, a host-callable likelihood, a row width
+ * other than 8 / 16 / 32 / 64 / 128 after padding, HENS_GIBBS_MH while hens_set_dist_proposal's generator holds the MH slot
+ * (HENS_ERR_UNSUPPORTED) - and, the other way round, hens_set_periodic with a period, hens_set_nsplits(> 2), hens_pipe_init and
+ * hens_set_dist_proposal while a table stands in their way.
+ *
+ * hens_gibbs_select(ctx, move, block): teacher-forced stepping - the block that the next hens_stretch_split pair (move 0) or
+ * hens_mh_step (move 1) belongs to, until the next call; allowed only between complete moves (HENS_ERR_STATE between the
+ * half-steps; HENS_ERR_STATE without a table; HENS_ERR_INVALID outside [0, nblocks)).  hens_set_gibbs selects block 0.  The
+ * cascade stays the caller's hens_pt_sweep. */
+enum { HENS_GIBBS_STRETCH = 0, HENS_GIBBS_MH = 1 };
+int hens_set_gibbs(hens_ctx* ctx, int32_t move, int32_t nblocks, const uint8_t* mask);
+int hens_gibbs_select(hens_ctx* ctx, int32_t move, int32_t block);
+
 /* ---- Ladder pipeline: sharded stepping by neighbour exchange (one process per GPU) ------------------
  * No reference counterpart (the reference has no distributed path; it walks the whole ladder in one
  * process, tempering.py:598-649).  Each rank keeps a contiguous rung range (rank 0 = coldest rungs)
@@ -800,6 +839,12 @@ int hens_set_iteration(hens_ctx* ctx, int64_t iter);
  * Any output pointer may be NULL.  Does not touch the sampler state. */
 int hens_debug_draws(hens_ctx* ctx, int64_t iter, int32_t* own, int32_t* cw, double* u_zz, double* u_acc,
                      int32_t* pt_slot, double* u_swap, int32_t* is_mh, double* mh_step, double* mh_u);
+/* ... of Gibbs block `block` of that iteration's move (hens_set_gibbs): cw, u_zz, u_acc and mh_step, mh_u are the block's; own,
+ * pt_slot, u_swap and is_mh the iteration's.  Block 0 is hens_debug_draws.  HENS_ERR_INVALID outside the blocks of that iteration's
+ * move.  The arrays of the OTHER move are written only where its table has a block `block` too (the two tables may differ in
+ * length): cw, u_zz, u_acc are left untouched for block >= the stretch table's blocks, mh_step, mh_u for block >= the MH table's. */
+int hens_debug_draws_block(hens_ctx* ctx, int64_t iter, int32_t block, int32_t* own, int32_t* cw, double* u_zz, double* u_acc,
+                           int32_t* pt_slot, double* u_swap, int32_t* is_mh, double* mh_step, double* mh_u);
 
 /* Static description of the build. */
 const char* hens_version(void);
