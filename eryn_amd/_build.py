@@ -8,13 +8,13 @@ SRC_DIR = os.path.join(HERE, "csrc")
 LIB_DIR = os.path.join(HERE, "lib")
 LIB_PATH = os.environ.get("HENS_LIB") or os.path.join(LIB_DIR, "libhipensemble.so")
 OBJ_DIR = os.environ.get("HENS_OBJ_DIR") or os.path.join(os.path.dirname(HERE), "build", "hens_obj")      # (A/B libraries: objects of their own)
-# hens.hip: the C ABI, the host logic and the small kernels; hens_k_<likelihood>.hip (x 5 parts): the stepping kernels' instantiations
+# hens.hip: the C ABI, the host logic and the small kernels; hens_k_<likelihood>.hip (x 6 parts): the stepping kernels' instantiations
 # (csrc/hens_ktable.h) - one translation unit per (likelihood, part), compiled side by side, then linked.
 UNITS = [("hens", "hens.hip", [])] + [(f"hens_k_{k}_{part}", f"hens_k_{k}.hip", [f"-DHENS_KT_PART={part}"])
-                                      for k in ("dense", "diag", "rosen") for part in (0, 1, 2, 3, 4)]
+                                      for k in ("dense", "diag", "rosen") for part in (0, 1, 2, 3, 4, 5)]
 SOURCES = sorted({os.path.join(SRC_DIR, u[1]) for u in UNITS})
 # what a unit includes, by kind of unit: every unit, hens.hip alone, the kernel units alone (they see neither hens.hip nor the RJ / AQL headers)
-HDRS_ALL = ("hens_kernels.h", "hens_ladder_fold.inc", "hens_iter.h", "hens_tile2.h", "hens_ktable.h", "hens_prior.h", "hens_dist.h", "hens_prior_host.h")
+HDRS_ALL = ("hens_kernels.h", "hens_ladder_fold.inc", "hens_iter.h", "hens_tile2.h", "hens_ktable.h", "hens_prior.h", "hens_dist.h", "hens_mt.h", "hens_prior_host.h")
 HDRS_HOST = ("hens_gibbs_host.h", "hens_rj.h", "hens_aql.h", "hens_chain.h", "hens_chain_stats.h", "hens_rj_chain.h", "hens_rj_chain_stats.h", "hens_chain_host.h")
 HDRS_KERNEL = ("hens_ktable.inc",)
 API_HEADER = os.path.join(os.path.dirname(HERE), "include", "hipensemble.h")

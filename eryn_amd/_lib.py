@@ -104,6 +104,9 @@ SIGNATURES = {
     "hens_get_mh_counters": (C.c_int, [_P, _P, _P]),
     "hens_set_dist_proposal": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_double]),
     "hens_dist_step": (C.c_int, [_P, _P, _P, _P, _P]),
+    "hens_set_mt_dist_proposal": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_double]),
+    "hens_mt_dist_step": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P]),
+    "hens_mt_debug_draws": (C.c_int, [_P, C.c_int64, _P, _P, _P]),
     "hens_step_marked": (C.c_int, [_P, C.c_int64, C.c_int64]),
     "hens_get_marked_counters": (C.c_int, [_P, _P, _P]),
     "hens_step_report": (C.c_int, [_P, C.c_int64, C.c_int64, _P, _P, _P]),

@@ -9,6 +9,7 @@
 #include "hens_ktable.h"
 #include "hens_prior.h"
 #include "hens_dist.h"
+#include "hens_mt.h"
 #include "hens_gibbs_host.h"
 #include "hens_chain.h"
 #include "hens_chain_stats.h"
@@ -205,6 +206,13 @@ struct hens_ctx_impl {
     int mh_kind = -1;                      // -1: hens_step runs the stretch move only; MH_DIST: the slot holds hens_set_dist_proposal's generator
     TermBlock dist_block;                  // the generator of MH_DIST (DistArgs::glo / ghi / gterms)
     double* dist_factors = nullptr;        // [Tl][W] hens_dist_step's factors_out staging
+    // MH_MT_DIST (hens_set_mt_dist_proposal; hens_mt.h): the generator is dist_block; the teacher-forced call's staging
+    int mt_K = 0;                          // num_try
+    size_t mt_q_cap = 0;                   // doubles mt_q holds
+    double* mt_q = nullptr;                // [Tl][W][K][D] hens_mt_dist_step's tries
+    double* mt_upick = nullptr;            // [Tl][W] pick uniforms
+    int32_t* mt_pick = nullptr;            // [Tl][W] pick_out staging
+    double* mt_lsw = nullptr;              // [2][Tl][W] lsw_out staging
     // Gibbs parameter blocks (hens_set_gibbs; hens_gibbs_host.h): a block table per move - [0] the stretch move, [1] the MH slot.
     // While either has one (gibbs_on) every proposing launch is a block's: k_stretch_prior<GIBBS> on the block's image, a move
     // without a table of its own being one all-true block.
@@ -472,12 +480,13 @@ struct LikeKernels {
     const void* (*stretch)(int mode);
     const void* (*stretch_prior)(int mode, int D);
     const void* (*dist)(int D);
+    const void* (*mt_dist)(int D);
     const void* (*stretch_gibbs)(int mode, int D);
     const void* (*stretch2)(int D, bool pipe);
     const void* (*split1_pt)(int D, bool per, bool shrt, bool pipe, bool col);
     const void* (*iter)(int D, bool per);
 };
-#define HENS_LIKE_KERNELS(KIND_, LIKE_, U) {KIND_, LIKE_, ktab_stretch_fast_##U, ktab_stretch_##U, ktab_stretch_prior_##U, ktab_dist_##U, ktab_stretch_gibbs_##U, ktab_stretch2_##U, ktab_split1_pt_##U, ktab_iter_##U}
+#define HENS_LIKE_KERNELS(KIND_, LIKE_, U) {KIND_, LIKE_, ktab_stretch_fast_##U, ktab_stretch_##U, ktab_stretch_prior_##U, ktab_dist_##U, ktab_mt_dist_##U, ktab_stretch_gibbs_##U, ktab_stretch2_##U, ktab_split1_pt_##U, ktab_iter_##U}
 const LikeKernels* like_kernels(int likelihood_kind) {
     static const LikeKernels tab[] = {
         HENS_LIKE_KERNELS(HENS_LIKE_GAUSS_DENSE, LIKE_DENSE, dense),
@@ -1751,12 +1760,16 @@ int mh_launch(hens_ctx_impl* c, bool want_keep, LaunchTimer* tm, bool inline_dra
 // DistributionGenerate (hens_dist.h): one full-ensemble proposal from the generator in the MH slot.  forced: the caller's points
 // and log-uniforms are in mh_step / mh_lu (hens_dist_step); else the launch draws both (hens_step).  Always in place, the pool's
 // parity stays; on the HIP stream with its release.  A pending ladder adaptation runs as a kernel of its own in front of it.
-int dist_launch(hens_ctx_impl* c, bool forced, bool want_keep, bool want_factors, LaunchTimer* tm) {
+// MH_MT_DIST: the same launch site for k_mt_dist (hens_mt.h) - the tries and pick uniforms of a forced call are in mt_q / mt_upick,
+// `want_mt`: pick_out and lsw_out are staged as well.
+int dist_launch(hens_ctx_impl* c, bool forced, bool want_keep, bool want_factors, LaunchTimer* tm, bool want_mt = false) {
+    const bool mt = c->mh_kind == MH_MT_DIST;
+    const char* what = mt ? "k_mt_dist" : "k_dist";
     const LikeKernels* lk = like_kernels(c->cfg.likelihood_kind);
-    const void* fn = lk ? lk->dist(c->D) : nullptr;
-    if (!fn) return fail(c, HENS_ERR_UNSUPPORTED, "k_dist: no such instantiation in this build (ndim %d, likelihood kind %d)", c->D, c->cfg.likelihood_kind);
+    const void* fn = lk ? (mt ? lk->mt_dist(c->D) : lk->dist(c->D)) : nullptr;
+    if (!fn) return fail(c, HENS_ERR_UNSUPPORTED, "%s: no such instantiation in this build (ndim %d, likelihood kind %d)", what, c->D, c->cfg.likelihood_kind);
     flush_adapt(c);
-    DistArgs a{};
+    MtArgs a{};
     a.pool = c->pool;
     a.loc = c->loc[c->cur];
     a.L = c->L[c->cur];
@@ -1769,7 +1782,7 @@ int dist_launch(hens_ctx_impl* c, bool forced, bool want_keep, bool want_factors
     a.glo = c->dist_block.lo();
     a.ghi = c->dist_block.hi();
     a.gterms = c->dist_block.terms();
-    a.q = forced ? c->mh_step : nullptr;
+    a.q = forced ? (mt ? c->mt_q : c->mh_step) : nullptr;
     a.lu = forced ? c->mh_lu : nullptr;
     a.accepted = c->accepted_mh;
     a.keep_out = want_keep ? c->mh_keep : nullptr;
@@ -1784,8 +1797,21 @@ int dist_launch(hens_ctx_impl* c, bool forced, bool want_keep, bool want_factors
     const int NW = fast_nw(c->D);
     hipEvent_t e0 = nullptr, e1 = nullptr;
     time_launch(c, tm, 0, e0, e1);
-    const dim3 grid((c->W + TILE - 1) / TILE, c->Tl);      // (never on the AQL queue: aql_able requires mh_kind < 0)
-    if (const int r = on_hip_stream(c, [&] { return launch_by_ptr(c, fn, "k_dist", grid, NW * 64, prior_lds_bytes(c->D, NW, lk->like), false, e0, e1, a); })) return r;
+    int r;
+    if (mt) {                                              // KP tries' rows per walker, 64 / KP walkers per workgroup
+        a.K = c->mt_K;
+        while ((1 << a.kp_shift) < a.K) a.kp_shift += 1;
+        a.u_pick = forced ? c->mt_upick : nullptr;
+        a.pick_out = want_mt ? c->mt_pick : nullptr;
+        a.lsw_out = want_mt ? c->mt_lsw : nullptr;
+        const int G = TILE >> a.kp_shift;
+        const dim3 grid((c->W + G - 1) / G, c->Tl);
+        r = on_hip_stream(c, [&] { return launch_by_ptr(c, fn, what, grid, NW * 64, prior_lds_bytes(c->D, NW, lk->like), false, e0, e1, a); });
+    } else {
+        const dim3 grid((c->W + TILE - 1) / TILE, c->Tl);  // (never on the AQL queue: aql_able requires mh_kind < 0)
+        r = on_hip_stream(c, [&] { return launch_by_ptr(c, fn, what, grid, NW * 64, prior_lds_bytes(c->D, NW, lk->like), false, e0, e1, static_cast<const DistArgs&>(a)); });
+    }
+    if (r) return r;
     c->num_proposals_mh += 1;
     return HENS_OK;
 }
@@ -1794,7 +1820,7 @@ int dist_launch(hens_ctx_impl* c, bool forced, bool want_keep, bool want_factors
 // axis-aligned proposals on the fast row widths are drawn inside the MH launch itself (one Box-Muller pair per
 // lane); a full covariance (Cholesky product) and the generic row widths go through k_mh_draw + the step buffer.
 int mh_iteration(hens_ctx_impl* c, LaunchTimer* tm, bool inplace) {
-    if (c->mh_kind == MH_DIST) return dist_launch(c, false, false, false, tm);      // (in place in either state form)
+    if (c->mh_kind == MH_DIST || c->mh_kind == MH_MT_DIST) return dist_launch(c, false, false, false, tm);      // (in place in either state form)
     const bool inline_draws = c->mh_kind != MH_FULL && fast_path(c);
     if (!inline_draws) {
         MhDrawArgs d{};
@@ -2566,6 +2592,8 @@ int hens_set_gibbs(hens_ctx* ctx, int32_t move, int32_t nblocks, const uint8_t* 
     if (const int r = gibbs_supported(c, move)) return r;
     if (move == HENS_GIBBS_MH && c->mh_kind == MH_DIST)
         return fail(c, HENS_ERR_UNSUPPORTED, "Gibbs blocks are not built for the distribution proposal in the MH slot (hens_set_dist_proposal)");
+    if (move == HENS_GIBBS_MH && c->mh_kind == MH_MT_DIST)
+        return fail(c, HENS_ERR_UNSUPPORTED, "Gibbs blocks are not built for the multiple-try proposal in the MH slot (hens_set_mt_dist_proposal)");
     ParsedGibbs p = parse_gibbs(nblocks, mask, c->D, dim_active(c));
     if (p.why[0]) return fail(c, HENS_ERR_INVALID, "hens_set_gibbs: %s", p.why);
     SETTLE(c, NEED_DEVICE | NEED_FIELDS | NEED_LADDER);      // (the launch path changes)
@@ -3845,6 +3873,47 @@ __global__ void k_dist_draw(double* q, double* u, const double* glo, const doubl
     }
 }
 
+// hens_mt_debug_draws: what k_mt_dist draws in iteration `iter` - q[tl][w][k][d] from dist_draw with the try in the counter word (a
+// pad coordinate reads 0), the pick uniform (mt_pick_uniform) and the accept uniform (mh_uniform) of every walker.  Export only.
+__global__ void k_mt_draw(double* q, double* u_pick, double* u_acc, const double* glo, const double* ghi, const PriorTerm* gterms, uint64_t seed,
+                          uint64_t iter, int Tl, int W, int K, int D, int rung_begin) {
+    const int64_t n = (int64_t)Tl * W * K * D;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const int d = (int)(i % D);
+        const int k = (int)((i / D) % K);
+        const int64_t tw = i / ((int64_t)D * K);
+        const int tl = (int)(tw / W), w = (int)(tw % W);
+        const uint32_t wid = (uint32_t)(rung_begin + tl) * (uint32_t)W + (uint32_t)w;
+        const PriorTerm t = gterms[d];
+        q[i] = t.kind == PRIOR_NONE ? 0.0 : dist_draw(seed, iter, wid, d, t, glo[d], ghi[d], (uint32_t)k);
+        if (d == 0 && k == 0) {
+            u_pick[tw] = mt_pick_uniform(seed, iter, wid);
+            u_acc[tw] = mh_uniform(seed, iter, wid);
+        }
+    }
+}
+
+int hens_mt_debug_draws(hens_ctx* ctx, int64_t iter, double* q, double* u_pick, double* u_acc) {
+    hens_ctx_impl* c = enter(ctx);
+    if (!c || iter < 0) return fail(c, HENS_ERR_INVALID, "null context / negative iteration");
+    if (c->mh_kind != MH_MT_DIST) return fail(c, HENS_ERR_STATE, "no generator set (hens_set_mt_dist_proposal)");
+    SETTLE(c, NEED_DEVICE);
+    const size_t TW = (size_t)c->Tl * c->W, nq = TW * c->mt_K * c->D;
+    DeviceScratch sc;
+    double* dq = sc.grab<double>(nq);
+    double* dp = sc.grab<double>(TW);
+    double* du = sc.grab<double>(TW);
+    if (!dq || !dp || !du) return fail(c, HENS_ERR_HIP, "hens_mt_debug_draws: out of device memory");
+    hipLaunchKernelGGL(k_mt_draw, dim3(grid_for((int64_t)nq)), dim3(256), 0, c->stream, dq, dp, du, c->dist_block.lo(), c->dist_block.hi(),
+                       c->dist_block.terms(), c->cfg.seed, (uint64_t)iter, c->Tl, c->W, c->mt_K, c->D, (int)c->cfg.rung_begin);
+    HIPCHK(c, hipGetLastError());
+    if (q) HIPCHK(c, hipMemcpyAsync(q, dq, nq * 8, hipMemcpyDeviceToHost, c->stream));
+    if (u_pick) HIPCHK(c, hipMemcpyAsync(u_pick, dp, TW * 8, hipMemcpyDeviceToHost, c->stream));
+    if (u_acc) HIPCHK(c, hipMemcpyAsync(u_acc, du, TW * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return HENS_OK;
+}
+
 int hens_debug_draws(hens_ctx* ctx, int64_t iter, int32_t* own, int32_t* cw, double* u_zz, double* u_acc,
                      int32_t* pt_slot, double* u_swap, int32_t* is_mh, double* mh_step, double* mh_u) {
     return hens_debug_draws_block(ctx, iter, 0, own, cw, u_zz, u_acc, pt_slot, u_swap, is_mh, mh_step, mh_u);
@@ -3908,7 +3977,7 @@ int hens_debug_draws_block(hens_ctx* ctx, int64_t iter, int32_t block, int32_t* 
         if (!ds || !du) return fail(c, HENS_ERR_HIP, "hens_debug_draws: out of device memory");
         if (const int r = export_pt_draws(c, ds, du, (uint64_t)iter, pt_slot, u_swap)) return r;
     }
-    if ((mh_step || mh_u) && c->mh_kind == MH_DIST) {      // the drawn points q and the accept uniforms of that iteration
+    if ((mh_step || mh_u) && (c->mh_kind == MH_DIST || c->mh_kind == MH_MT_DIST)) {      // the drawn points q (multiple try: try 0) and the accept uniforms of that iteration
         double* dq = sc.grab<double>(TW * c->D);
         double* du = sc.grab<double>(TW);
         if (!dq || !du) return fail(c, HENS_ERR_HIP, "hens_debug_draws: out of device memory");
@@ -5051,26 +5120,45 @@ int hens_pt_finish_sharded(hens_ctx* ctx, int64_t n_recv) {
 // ---- Metropolis-Hastings proposals ----------------------------------------------------------
 // The teacher-forced MH entry points: the caller's payload ([Tl][W][D]: steps for hens_mh_step, points for hens_dist_step, `dist`) and
 // accept uniforms go to mh_step / mh_u, the move's launch proposes from them, keep_out (and hens_dist_step's factors) are copied out.
-static int forced_mh_step(hens_ctx_impl* c, bool dist, const double* payload, const double* u_acc, uint8_t* keep_out, double* factors_out) {
+// hens_mt_dist_step (`mt`: its pick uniforms and extra outputs; the payload is [Tl][W][K][D] in a buffer of its own) takes the same path.
+struct ForcedMt { const double* u_pick; int32_t* pick_out; double* lsw_out; };
+static int forced_mh_step(hens_ctx_impl* c, bool dist, const double* payload, const double* u_acc, uint8_t* keep_out, double* factors_out,
+                          const ForcedMt* mt = nullptr) {
     int r = ready(c, true);
     if (r) return r;
-    if (!payload || !u_acc) return fail(c, HENS_ERR_INVALID, "null argument");
-    if (dist && c->mh_kind != MH_DIST) return fail(c, HENS_ERR_STATE, "no generator set (hens_set_dist_proposal)");
+    const char* who = mt ? "hens_mt_dist_step" : (dist ? "hens_dist_step" : "hens_mh_step");
+    if (!payload || !u_acc || (mt && !mt->u_pick)) return fail(c, HENS_ERR_INVALID, "null argument");
+    if (mt && c->mh_kind != MH_MT_DIST) return fail(c, HENS_ERR_STATE, "no generator set (hens_set_mt_dist_proposal)");
+    if (dist && !mt && c->mh_kind != MH_DIST) return fail(c, HENS_ERR_STATE, "no generator set (hens_set_dist_proposal)");
     if (!dist && c->cfg.likelihood_kind == HENS_LIKE_HOST) return fail(c, HENS_ERR_UNSUPPORTED, "hens_mh_step needs a device likelihood");
-    if (c->expect_split != 0) return fail(c, HENS_ERR_STATE, "%s between split 0 and split 1", dist ? "hens_dist_step" : "hens_mh_step");
+    if (c->expect_split != 0) return fail(c, HENS_ERR_STATE, "%s between split 0 and split 1", who);
     if (c->pt_pending) return fail(c, HENS_ERR_STATE, "sharded PT exchange in flight");
     if ((r = counter_room(c, 1))) return r;
     SETTLE(c, NEED_DEVICE | NEED_FIELDS);
     if ((r = ensure_mh_buffers(c))) return r;
     SETTLE(c, NEED_LADDER);
     const size_t TW = (size_t)c->Tl * c->W;
-    HIPCHK(c, hipMemcpyAsync(c->mh_step, payload, TW * c->D * 8, hipMemcpyHostToDevice, c->stream));
+    if (mt) {
+        const size_t nq = TW * c->mt_K * c->D;
+        if (c->mt_q_cap < nq) {                  // the tries' staging, on the first teacher-forced call (hens_step draws in the launch); an
+            double* q = nullptr;                 // earlier, smaller buffer stays with the context's allocations
+            if ((r = dalloc(c, &q, nq))) return r;
+            c->mt_q = q;
+            c->mt_q_cap = nq;
+        }
+        HIPCHK(c, hipMemcpyAsync(c->mt_q, payload, nq * 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->mt_upick, mt->u_pick, TW * 8, hipMemcpyHostToDevice, c->stream));
+    } else {
+        HIPCHK(c, hipMemcpyAsync(c->mh_step, payload, TW * c->D * 8, hipMemcpyHostToDevice, c->stream));
+    }
     HIPCHK(c, hipMemcpyAsync(c->mh_u, u_acc, TW * 8, hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(k_mh_prep, dim3(grid_for((int64_t)TW)), dim3(256), 0, c->stream, c->mh_u, c->mh_lu, (int64_t)TW);
     c->win_count = 0;
-    if ((r = dist ? dist_launch(c, true, true, factors_out != nullptr, nullptr) : mh_launch(c, true, nullptr))) return r;
+    if ((r = dist ? dist_launch(c, true, true, factors_out != nullptr, nullptr, mt && (mt->pick_out || mt->lsw_out)) : mh_launch(c, true, nullptr))) return r;
     if (keep_out) HIPCHK(c, hipMemcpyAsync(keep_out, c->mh_keep, TW, hipMemcpyDeviceToHost, c->stream));
     if (factors_out) HIPCHK(c, hipMemcpyAsync(factors_out, c->dist_factors, TW * 8, hipMemcpyDeviceToHost, c->stream));
+    if (mt && mt->pick_out) HIPCHK(c, hipMemcpyAsync(mt->pick_out, c->mt_pick, TW * 4, hipMemcpyDeviceToHost, c->stream));
+    if (mt && mt->lsw_out) HIPCHK(c, hipMemcpyAsync(mt->lsw_out, c->mt_lsw, 2 * TW * 8, hipMemcpyDeviceToHost, c->stream));
     if ((r = check_flags(c, true))) return r;
     if (!has_pt(c)) c->iter += 1;
     return HENS_OK;
@@ -5104,19 +5192,20 @@ int hens_set_mh_proposal(hens_ctx* ctx, int32_t kind, const double* scale, doubl
 }
 
 // ---- DistributionGenerate (distgen.py:10-104): the independence proposal in the context's one MH slot -------------------------------
-int hens_set_dist_proposal(hens_ctx* ctx, const int32_t* kind, const double* lo, const double* hi, const double* c0, const double* c1,
-                           const double* c2, double weight) {
-    hens_ctx_impl* c = enter(ctx);
+// The body of hens_set_dist_proposal and hens_set_mt_dist_proposal (num_try > 0: MH_MT_DIST, `name` = "multiple-try"): one set of
+// refusals, one term validation, one generator block.
+static int set_generator(hens_ctx_impl* c, const char* name, const int32_t* kind, const double* lo, const double* hi, const double* c0,
+                         const double* c1, const double* c2, int num_try, double weight) {
     if (!c) return no_context();
     if (!kind || !lo || !hi || !c0 || !c1 || !c2) return fail(c, HENS_ERR_INVALID, "null argument");
     if (!(weight >= 0.0 && weight <= 1.0)) return fail(c, HENS_ERR_INVALID, "weight must be a probability");
-    if (is_rj(c)) return fail(c, HENS_ERR_UNSUPPORTED, "the distribution proposal is not built for leaf-packing records");
-    if (c->pipe.on) return fail(c, HENS_ERR_STATE, "the distribution proposal is not built for a rank of the ladder pipeline");
-    if (c->cfg.likelihood_kind == HENS_LIKE_HOST) return fail(c, HENS_ERR_UNSUPPORTED, "the distribution proposal needs a device likelihood");
-    if (c->gibbs[1].nblocks > 0) return fail(c, HENS_ERR_UNSUPPORTED, "the distribution proposal is not built under Gibbs blocks on the MH slot (hens_set_gibbs(ctx, HENS_GIBBS_MH, 0, NULL) clears the table)");
+    if (is_rj(c)) return fail(c, HENS_ERR_UNSUPPORTED, "the %s proposal is not built for leaf-packing records", name);
+    if (c->pipe.on) return fail(c, HENS_ERR_STATE, "the %s proposal is not built for a rank of the ladder pipeline", name);
+    if (c->cfg.likelihood_kind == HENS_LIKE_HOST) return fail(c, HENS_ERR_UNSUPPORTED, "the %s proposal needs a device likelihood", name);
+    if (c->gibbs[1].nblocks > 0) return fail(c, HENS_ERR_UNSUPPORTED, "the %s proposal is not built under Gibbs blocks on the MH slot (hens_set_gibbs(ctx, HENS_GIBBS_MH, 0, NULL) clears the table)", name);
     const LikeKernels* lk = like_kernels(c->cfg.likelihood_kind);
-    if (!lk || !lk->dist(c->D))
-        return fail(c, HENS_ERR_UNSUPPORTED, "the distribution proposal is built for row widths 8, 16, 32, 64 and 128 (this context's rows are %d wide)", c->D);
+    if (!lk || !(num_try ? lk->mt_dist(c->D) : lk->dist(c->D)))
+        return fail(c, HENS_ERR_UNSUPPORTED, "the %s proposal is built for row widths 8, 16, 32, 64 and 128 (this context's rows are %d wide)", name, c->D);
     // a distribution one draws from: finite uniform supports, as for the leaves' priors; a padded row's pads have no draw and no term
     const int D = c->D, Da = dim_active(c);
     std::vector<PriorTerm> terms((size_t)D);
@@ -5134,11 +5223,38 @@ int hens_set_dist_proposal(hens_ctx* ctx, const int32_t* kind, const double* lo,
         if ((r = dalloc(c, &f, (size_t)c->Tl * c->W))) return r;
         c->dist_factors = f;
     }
+    const size_t TW = (size_t)c->Tl * c->W;
+    if (num_try && !c->mt_upick) {
+        if ((r = dalloc(c, &c->mt_upick, TW))) return r;
+        if ((r = dalloc(c, &c->mt_pick, TW))) return r;
+        if ((r = dalloc(c, &c->mt_lsw, 2 * TW))) return r;
+    }
     if ((r = c->dist_block.upload(c, lo, hi, terms.data()))) return r;
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->mh_kind = MH_DIST;
+    c->mh_kind = num_try ? MH_MT_DIST : MH_DIST;
+    c->mt_K = num_try;
     c->mh_weight = weight;
     return HENS_OK;
+}
+
+int hens_set_dist_proposal(hens_ctx* ctx, const int32_t* kind, const double* lo, const double* hi, const double* c0, const double* c1,
+                           const double* c2, double weight) {
+    return set_generator(enter(ctx), "distribution", kind, lo, hi, c0, c1, c2, 0, weight);
+}
+
+// ---- MTDistGenMove(independent=True) (mtdistgen.py:7-136, multipletry.py:238-514): num_try tries per walker from the generator ------
+int hens_set_mt_dist_proposal(hens_ctx* ctx, const int32_t* kind, const double* lo, const double* hi, const double* c0, const double* c1,
+                              const double* c2, int32_t num_try, double weight) {
+    hens_ctx_impl* c = enter(ctx);
+    if (c && (num_try < 1 || num_try > TILE)) return fail(c, HENS_ERR_INVALID, "num_try must be in [1, %d] (one tile row per try)", TILE);
+    return set_generator(c, "multiple-try", kind, lo, hi, c0, c1, c2, num_try, weight);
+}
+
+// the teacher-forced twin: the caller's tries, pick uniforms and accept uniforms
+int hens_mt_dist_step(hens_ctx* ctx, const double* q, const double* u_pick, const double* u_acc, uint8_t* keep_out, int32_t* pick_out,
+                      double* lsw_out, double* factors_out) {
+    const ForcedMt mt{u_pick, pick_out, lsw_out};
+    return forced_mh_step(enter(ctx), true, q, u_acc, keep_out, factors_out, &mt);
 }
 
 // the teacher-forced twin of hens_mh_step: the caller's points and accept uniforms
@@ -5165,6 +5281,7 @@ int hens_pipe_init(hens_ctx* ctx, int32_t nranks, int32_t my_rank, void* blob_ou
     if (c->pipe.on) return fail(c, HENS_ERR_STATE, "pipeline already initialised");
     if (c->prior) return fail(c, HENS_ERR_UNSUPPORTED, "prior terms are not built for a rank of the ladder pipeline (hens_set_prior_box returns to the box)");
     if (c->mh_kind == MH_DIST) return fail(c, HENS_ERR_UNSUPPORTED, "the distribution proposal is not built for a rank of the ladder pipeline (hens_set_mh_proposal(-1, ...) returns to the stretch move)");
+    if (c->mh_kind == MH_MT_DIST) return fail(c, HENS_ERR_UNSUPPORTED, "the multiple-try proposal is not built for a rank of the ladder pipeline (hens_set_mh_proposal(-1, ...) returns to the stretch move)");
     if (gibbs_on(c)) return fail(c, HENS_ERR_UNSUPPORTED, "Gibbs blocks are not built for a rank of the ladder pipeline (hens_set_gibbs(ctx, move, 0, NULL) clears a table)");
     if (!c->cfg.tempered || c->T < 2) return fail(c, HENS_ERR_STATE, "the ladder pipeline needs a tempered ladder");
     if (nranks < 1 || nranks > PIPE_MAX_RANKS || my_rank < 0 || my_rank >= nranks)

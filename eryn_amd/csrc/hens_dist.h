@@ -63,9 +63,10 @@ struct DistArgs {
 // (iter lo, iter hi, wid, PURPOSE_DIST | d << 8) keyed by the seed, the words turned into a value by the function that draws births
 // (rj_birth_value).  A uniform or log-uniform draw is clamped into its support: rounding can put exp(log a) one ulp outside [a, b],
 // where logq(new) = -inf and the factor would be +inf.  (Births are not clamped: there the generator is the prior and such a
-// point is rejected.)  k_dist and the export kernel k_dist_draw evaluate this one function.
-__device__ __forceinline__ double dist_draw(uint64_t seed, uint64_t it, uint32_t wid, int d, const PriorTerm& t, double lo, double hi) {
-    const u4 e = philox4x32_10(u4{(uint32_t)it, (uint32_t)(it >> 32), wid, PURPOSE_DIST | ((uint32_t)d << 8)}, (uint32_t)seed, (uint32_t)(seed >> 32));
+// point is rejected.)  k_dist and the export kernel k_dist_draw evaluate this one function.  `k`: the try of a multiple-try move
+// (hens_mt.h: word 3 = PURPOSE_DIST | d << 8 | k << 16); try 0's word is the word of this move.
+__device__ __forceinline__ double dist_draw(uint64_t seed, uint64_t it, uint32_t wid, int d, const PriorTerm& t, double lo, double hi, uint32_t k = 0) {
+    const u4 e = philox4x32_10(u4{(uint32_t)it, (uint32_t)(it >> 32), wid, PURPOSE_DIST | ((uint32_t)d << 8) | (k << 16)}, (uint32_t)seed, (uint32_t)(seed >> 32));
     const double v = rj_birth_value(e, t.kind, lo, hi, t.c0, t.c1);
     return t.kind == PRIOR_NORMAL ? v : fmin(fmax(v, lo), hi);
 }

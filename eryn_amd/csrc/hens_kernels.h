@@ -117,8 +117,9 @@ __device__ __forceinline__ uint32_t prp_inv(uint32_t y, const uint32_t* k, int b
 // (the PT helpers that use these follow the enum)
 enum : uint32_t { PURPOSE_STRETCH = 0, PURPOSE_STRETCH_ACC = 2, PURPOSE_SPLIT = 8, PURPOSE_PTPERM = 9,
                   PURPOSE_PTU = 10, PURPOSE_MH_ACC = 11, PURPOSE_MH_NORMAL = 12, PURPOSE_MOVE = 13,
-                  PURPOSE_DIST = 14 };          // DistributionGenerate's proposal, one call per coordinate: PURPOSE_DIST | d << 8 (hens_dist.h)
-enum { MH_ISO = 0, MH_DIAG = 1, MH_FULL = 2, MH_DIST = 3 };   // (MH_DIST: hens_set_dist_proposal occupies the context's one MH slot)
+                  PURPOSE_DIST = 14,            // DistributionGenerate's proposal, one call per coordinate: PURPOSE_DIST | d << 8 (hens_dist.h)
+                  PURPOSE_MT_PICK = 15 };       // the pick uniform of the multiple-try move (hens_mt.h); its tries: PURPOSE_DIST | d << 8 | k << 16
+enum { MH_ISO = 0, MH_DIAG = 1, MH_FULL = 2, MH_DIST = 3, MH_MT_DIST = 4 };   // (MH_DIST / MH_MT_DIST: hens_set_dist_proposal / hens_set_mt_dist_proposal occupy the context's one MH slot)
 
 // Philox-mode PT draws: column c of the cascade meets slot pt_slot(t, c) of global rung t - every rung its own keyed
 // permutation, i.e. pair (i, i-1) is matched through two permutations like the reference's (tempering.py:526-532) - and

@@ -13,6 +13,7 @@ namespace hens {
     const void* ktab_stretch_##KIND(int mode);                                                                                \
     const void* ktab_stretch_prior_##KIND(int mode, int D);     /* hens_prior.h: the copying half-step under prior terms */      \
     const void* ktab_dist_##KIND(int D);                        /* hens_dist.h: DistributionGenerate's full-ensemble launch */  \
+    const void* ktab_mt_dist_##KIND(int D);                     /* hens_mt.h: the multiple-try independence move */            \
     const void* ktab_stretch_gibbs_##KIND(int mode, int D);     /* hens_prior.h, GIBBS: the half-step of one Gibbs block */      \
     const void* ktab_stretch2_##KIND(int D, bool pipe);                                                                                  \
     const void* ktab_split1_pt_##KIND(int D, bool per, bool shrt, bool pipe, bool col);                                       \

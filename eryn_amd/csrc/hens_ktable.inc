@@ -2,7 +2,8 @@
 // (dense ...) and include.  See hens_ktable.h.  HENS_KT_PART (from the build) halves a unit once more: 0 = the half-step kernels
 // (k_stretch_fast, k_stretch), 1 = the fused ones (k_split1_pt, k_iter), 2 = k_stretch_prior (hens_prior.h: a unit of its own, so that
 // the units of the kernels that were there before compile to the code they compiled to), 3 = k_dist (hens_dist.h: likewise),
-// 4 = k_stretch_prior<GIBBS> (hens_prior.h: the half-step of a Gibbs block, likewise); undefined = all.
+// 4 = k_stretch_prior<GIBBS> (hens_prior.h: the half-step of a Gibbs block, likewise), 5 = k_mt_dist (hens_mt.h: likewise);
+// undefined = all.
 #include "hens_kernels.h"
 #include "hens_iter.h"
 #include "hens_tile2.h"
@@ -116,6 +117,23 @@ const void* KT(ktab_dist_)(int D) {
 #define KT_DIST(DT, NW) if (D == DT) return KPTR(k_dist<DT, L, NW>);
     KT_DIST(32, 8) KT_DIST(64, 8) KT_DIST(16, 4) KT_DIST(8, 4) KT_DIST(128, 8)
 #undef KT_DIST
+    return nullptr;
+#endif
+}
+#endif
+#if !defined(HENS_KT_PART) || HENS_KT_PART == 5
+}  // namespace hens
+#include "hens_mt.h"
+namespace hens {
+const void* KT(ktab_mt_dist_)(int D) {
+    constexpr int L = HENS_KT_LIKE;
+#ifdef HENS_DEV_BUILD
+    (void)D;
+    return nullptr;            // (a dev build carries no multiple-try launch)
+#else
+#define KT_MT(DT, NW) if (D == DT) return KPTR(k_mt_dist<DT, L, NW>);
+    KT_MT(32, 8) KT_MT(64, 8) KT_MT(16, 4) KT_MT(8, 4) KT_MT(128, 8)
+#undef KT_MT
     return nullptr;
 #endif
 }

@@ -88,6 +88,7 @@ class HipEnsemble(ChainStoreCalls):
                          fill_value=float(fill_value), adaptation_lag=float(adaptation_lag),
                          adaptation_time=float(adaptation_time), seed=int(seed) & (2**64 - 1))
         self.tempered = bool(tempered)
+        self.num_try = None          # the tries of the multiple-try generator in the MH slot (set_mt_dist_proposal), None without one
         self.gibbs = dict(stretch=None, mh=None)      # the block tables the context holds (set_gibbs), [nblocks, D] bool or None
         self.state_epoch = 0         # bumped by every call that changes the walkers: a DeviceState (eryn_amd/state.py) is current while it matches
         self.lazy_downloads = 0
@@ -473,6 +474,7 @@ class HipEnsemble(ChainStoreCalls):
         self._move_cfg = None                                  # (DeviceMove._propose_philox's memo of what it asked for last)
         if kind is None:
             check(self.lib.hens_set_mh_proposal(self.ctx, -1, None, 0.0), self.ctx)
+            self.num_try = None
             return
         k = {"iso": 0, "diag": 1, "full": 2}[kind]
         scale = np.ascontiguousarray(np.atleast_1d(scale), dtype=np.float64)
@@ -488,6 +490,7 @@ class HipEnsemble(ChainStoreCalls):
             full[:self.D, :self.D] = scale.reshape(self.D, self.D)
             scale = full
         check(self.lib.hens_set_mh_proposal(self.ctx, k, ptr(scale), float(weight)), self.ctx)
+        self.num_try = None
 
     # -- DistributionGenerate (include/hipensemble.h: hens_set_dist_proposal, hens_dist_step) ------------
     def set_dist_proposal(self, terms, weight):
@@ -498,6 +501,7 @@ class HipEnsemble(ChainStoreCalls):
         self._move_cfg = None
         spec = prior_spec(terms, self.D)
         check(self.lib.hens_set_dist_proposal(self.ctx, *map(ptr, term_arrays(spec.terms, self.RW)), float(weight)), self.ctx)
+        self.num_try = None
 
     def dist_step(self, q, u_acc, want_factors=False):
         """One full-ensemble independence proposal with the caller's points ``q[Tl, W, D]`` and accept uniforms; returns the accept
@@ -509,6 +513,48 @@ class HipEnsemble(ChainStoreCalls):
         fac = np.empty((self.Tl, self.W)) if want_factors else None
         check(self.lib.hens_dist_step(self.ctx, ptr(q), ptr(u_acc), ptr(keep), ptr(fac)), self.ctx)
         return (keep.astype(bool), fac) if want_factors else keep.astype(bool)
+
+    # -- MTDistGenMove (include/hipensemble.h: hens_set_mt_dist_proposal, hens_mt_dist_step, hens_mt_debug_draws) ----
+    def set_mt_dist_proposal(self, terms, num_try, weight):
+        """The generator of the multiple-try independence proposal and its number of tries (1 .. 64) into the context's one MH
+        slot: ``terms`` and ``weight`` as for ``set_dist_proposal``, which it replaces and which replaces it."""
+        self._move_cfg = None
+        spec = prior_spec(terms, self.D)
+        check(self.lib.hens_set_mt_dist_proposal(self.ctx, *map(ptr, term_arrays(spec.terms, self.RW)), int(num_try), float(weight)), self.ctx)
+        self.num_try = int(num_try)
+
+    def mt_dist_step(self, q, u_pick, u_acc, want=()):
+        """One full-ensemble multiple-try proposal with the caller's tries ``q[Tl, W, K, D]``, pick uniforms and accept uniforms;
+        returns the accept mask ``[Tl, W]``, or with ``want`` (names among "pick", "lsw", "aux_lsw", "factors") a dict that holds
+        ``keep`` and those."""
+        self.state_epoch += 1
+        q = np.ascontiguousarray(q, dtype=np.float64)
+        K = q.size // (self.Tl * self.W * self.D)
+        if self.num_try is not None and (K != self.num_try or q.size != self.Tl * self.W * K * self.D):      # (None: no generator set, the call refuses)
+            raise ValueError(f"q must hold {self.num_try} tries per walker: [{self.Tl}, {self.W}, {self.num_try}, {self.D}]")
+        q = self._pad(q.reshape(self.Tl, self.W * K, self.D))
+        u_pick = np.ascontiguousarray(u_pick, dtype=np.float64).reshape(self.Tl, self.W)
+        u_acc = np.ascontiguousarray(u_acc, dtype=np.float64).reshape(self.Tl, self.W)
+        keep = np.empty((self.Tl, self.W), dtype=np.uint8)
+        pick = np.empty((self.Tl, self.W), dtype=np.int32) if "pick" in want else None
+        lsw = np.empty((2, self.Tl, self.W)) if ("lsw" in want or "aux_lsw" in want) else None
+        fac = np.empty((self.Tl, self.W)) if "factors" in want else None
+        check(self.lib.hens_mt_dist_step(self.ctx, ptr(q), ptr(u_pick), ptr(u_acc), ptr(keep), ptr(pick), ptr(lsw), ptr(fac)), self.ctx)
+        if not want:
+            return keep.astype(bool)
+        out = dict(keep=keep.astype(bool), pick=pick, factors=fac)
+        if lsw is not None:
+            out.update(lsw=lsw[0], aux_lsw=lsw[1])
+        return {k: v for k, v in out.items() if k == "keep" or k in want}
+
+    def mt_debug_draws(self, it):
+        """What the multiple-try launch draws in iteration ``it``: tries ``[Tl, W, K, D]``, pick and accept uniforms ``[Tl, W]``."""
+        K = self.num_try or 1
+        q = np.empty((self.Tl, self.W, K, self.RW))
+        u_pick = np.empty((self.Tl, self.W))
+        u_acc = np.empty((self.Tl, self.W))
+        check(self.lib.hens_mt_debug_draws(self.ctx, int(it), ptr(q), ptr(u_pick), ptr(u_acc)), self.ctx)
+        return np.ascontiguousarray(q[..., :self.D]), u_pick, u_acc
 
     # -- Gibbs parameter blocks (include/hipensemble.h: hens_set_gibbs, hens_gibbs_select) ---------------
     GIBBS_MOVES = dict(stretch=0, mh=1)

@@ -14,7 +14,7 @@ import numpy as np
 from .backend import Backend, DeviceBackend
 from .engine import HipEnsemble
 from .model import Model
-from .moves import DeviceMove, DistributionGenerate, GaussianMove, MHMove, StretchMove, TemperatureControl
+from .moves import DeviceMove, DistributionGenerate, GaussianMove, MHMove, MTDistGenMove, StretchMove, TemperatureControl
 from .moves.device import mh_slot_key, push_mh_slot
 from .periodic import PeriodicContainer, period_vector
 from .prior import prior_spec
@@ -111,7 +111,7 @@ class EnsembleSampler:
                       stop_adaptation=tc.stop_adaptation)
         for m in self.moves:
             if not isinstance(m, DeviceMove):
-                raise NotImplementedError("only eryn_amd.moves.StretchMove / GaussianMove / DistributionGenerate run on the device path")
+                raise NotImplementedError("only eryn_amd.moves.StretchMove / GaussianMove / DistributionGenerate / MTDistGenMove run on the device path")
             if m.gibbs_sampling_setup is not None:
                 if hasattr(log_like_fn, "evaluate"):
                     raise NotImplementedError("gibbs_sampling_setup steps on the device: it needs a device likelihood "
@@ -138,13 +138,13 @@ class EnsembleSampler:
             m.attach_engine(self.engine, self._resident)
             m.trust_resident = True
             m.accepted = np.zeros((self.ntemps, self.nwalkers))
-        # device-side draws (rng="philox"): at most one stretch move and one MH move (Gaussian or DistributionGenerate), mixed by weight
+        # device-side draws (rng="philox"): at most one stretch move and one MH move (Gaussian, DistributionGenerate or MTDistGenMove), mixed by weight
         self._philox_moves = None
         if rng == "philox":
             mh = [(m, w) for m, w in zip(self.moves, self.weights) if isinstance(m, MHMove)]
             st = [(m, w) for m, w in zip(self.moves, self.weights) if isinstance(m, StretchMove)]
-            if len(mh) > 1 or len(st) > 1 or any(not isinstance(m, (GaussianMove, DistributionGenerate)) for m, _ in mh):
-                raise NotImplementedError("rng='philox' mixes at most one StretchMove with one GaussianMove or one DistributionGenerate "
+            if len(mh) > 1 or len(st) > 1 or any(not isinstance(m, (GaussianMove, DistributionGenerate, MTDistGenMove)) for m, _ in mh):
+                raise NotImplementedError("rng='philox' mixes at most one StretchMove with one GaussianMove or one DistributionGenerate or one MTDistGenMove "
                                           "(the device context has one MH slot)")
             self._mh_weight = float(mh[0][1]) if mh else 0.0
             self._mh_pushed = None
@@ -286,7 +286,7 @@ class EnsembleSampler:
         return state, thin_by
 
     def _push_mh_proposal(self, mh_move):
-        """Hand the MH move's proposal - a Gaussian move's scale, a DistributionGenerate's terms - to the device if it differs from
+        """Hand the MH move's proposal - a Gaussian move's scale, a DistributionGenerate's or MTDistGenMove's terms - to the device if it differs from
         what the device holds (construction; a ``tune`` hook that rescales the move, ensemble.py:983-984 - the reference's hook
         mutates the move object the next proposal reads)."""
         proposal = mh_move.device_proposal()

@@ -248,11 +248,12 @@ class DeviceMove(Move):
 
 
 # The context's one MH slot as a move describes it (``device_proposal()``): ("iso" | "diag" | "full", scale) of a GaussianMove,
-# ("dist", prior_terms dict) of a DistributionGenerate, None for the stretch move alone.
+# ("dist", prior_terms dict) of a DistributionGenerate, ("mt_dist", prior_terms dict, num_try) of an MTDistGenMove, None for the
+# stretch move alone.
 def mh_slot_key(proposal):
-    kind, what = proposal
-    if kind == "dist":
-        return (kind,) + tuple(np.asarray(what[k]).tobytes() for k in sorted(what))
+    kind, what = proposal[:2]
+    if kind in ("dist", "mt_dist"):
+        return (kind,) + tuple(proposal[2:]) + tuple(np.asarray(what[k]).tobytes() for k in sorted(what))
     return kind, np.asarray(what, dtype=np.float64).tobytes()
 
 
@@ -261,6 +262,8 @@ def push_mh_slot(eng, proposal, weight):
         eng.set_mh_proposal(None, None, 0.0)
     elif proposal[0] == "dist":
         eng.set_dist_proposal(proposal[1], weight)
+    elif proposal[0] == "mt_dist":
+        eng.set_mt_dist_proposal(proposal[1], proposal[2], weight)
     else:
         eng.set_mh_proposal(proposal[0], proposal[1], weight)
 

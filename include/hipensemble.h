@@ -485,6 +485,47 @@ int hens_set_dist_proposal(hens_ctx* ctx, const int32_t* kind, const double* lo,
                            const double* c1, const double* c2, double weight);
 int hens_dist_step(hens_ctx* ctx, const double* q, const double* u_acc, uint8_t* keep_out, double* factors_out);
 
+/* ---- Multiple-try independence proposals: MTDistGenMove(independent=True) (mtdistgen.py:7-136) ----------
+ * Every walker of every resident rung is offered K = num_try fresh points y_k from a generator of one distribution per parameter
+ * (mtdistgen.py:70), with beta the walker's rung (1 in an untempered context):
+ *   w_k     = (beta ll_k + lp_k) - logq(y_k)                                        (multipletry.py:45,221-223)
+ *   lsw     = max w + log(sum exp(w - max w)); NaN if every w is -inf               (multipletry.py:25-33)
+ *   j       = the first k whose running sum of exp(w - lsw) exceeds u_pick, else 0  (multipletry.py:51-57)
+ *   w'_k    = w_k for k != j, w'_j = (beta L_old + P_old) - logq(x_old); aux_lsw from w' as lsw from w  (multipletry.py:381-417,463)
+ *   factors = ((aux_logP_j - aux_lsw) - alq_j + alq_j) - ((logP_j - lsw) - lq_j + lq_j)   (multipletry.py:472-476)
+ * into MHMove.propose's accept test (mh.py:150-171) with logl = ll_j, logp = lp_j, not evaluated again.  An old point outside the
+ * generator has w'_j = +inf and aux_lsw = NaN: it is never moved.  The reference evaluates the likelihood of a try whose prior is
+ * -inf; the launch skips and fills it: such a try has weight -inf either way and can be "picked" only through the j = 0 fallback,
+ * which gives a NaN lnpdiff and a rejection, so the difference cannot be observed.  The sums run in the launch's order, not NumPy's
+ * pairwise one: lsw, aux_lsw and factors agree with the reference to rounding, picks and keeps exactly away from knife edges.
+ * One launch (csrc/hens_mt.h): a workgroup holds 64 / KP walkers, KP = the smallest power of two >= K, one try per tile row; rows
+ * updated in place in either state form.
+ *
+ * hens_set_mt_dist_proposal: the generator as for hens_set_dist_proposal (one validation for both), into the context's ONE MH slot:
+ * it replaces what the slot held and can be replaced by it; hens_set_mh_proposal(-1, ...) stays the one "stretch only" call.  With
+ * probability `weight` an iteration of hens_step is this move, counted as the other MH moves are.  Device draws: coordinate d of
+ * try k of walker wid comes from hens_set_dist_proposal's function with counter word 3 = 14 | d << 8 | k << 16 (try 0 is the point
+ * DistributionGenerate draws); the pick uniform from counter (iter lo, iter hi, wid, 15) by the accept uniform's construction; the
+ * accept uniform is the MH move's.
+ * Refused: num_try outside 1 .. 64 (HENS_ERR_INVALID), and what hens_set_dist_proposal refuses, with its codes: a leaf-packing
+ * context, a host-callable likelihood, an unbuilt row width, a Gibbs table on the MH slot (HENS_ERR_UNSUPPORTED;
+ * hens_set_gibbs(HENS_GIBBS_MH) refuses the other way round), a rank of the ladder pipeline (HENS_ERR_STATE).
+ *
+ * hens_mt_dist_step: the teacher-forced twin - one proposal with the caller's tries.
+ *   q      f64 [Tl][W][K][D]  the tries (mtdistgen.py:70: the container's rvs), taken as they are
+ *   u_pick f64 [Tl][W]        pick uniforms (multipletry.py:57)
+ *   u_acc  f64 [Tl][W]        accept uniforms (mh.py:157)
+ *   keep_out u8 [Tl][W], pick_out i32 [Tl][W], lsw_out f64 [2][Tl][W] (lsw, aux_lsw), factors_out f64 [Tl][W]: each may be NULL
+ * HENS_ERR_STATE if no generator is set.  The PT sweep that ends the reference's propose() is hens_pt_sweep.
+ *
+ * hens_mt_debug_draws: what the launch draws in iteration `iter` - q [Tl][W][K][D] (a pad coordinate reads 0), u_pick and u_acc
+ * [Tl][W]; each may be NULL.  hens_debug_draws keeps its shape: under this move its mh_step is try 0, its mh_u the accept uniform. */
+int hens_set_mt_dist_proposal(hens_ctx* ctx, const int32_t* kind, const double* lo, const double* hi, const double* c0,
+                              const double* c1, const double* c2, int32_t num_try, double weight);
+int hens_mt_dist_step(hens_ctx* ctx, const double* q, const double* u_pick, const double* u_acc, uint8_t* keep_out,
+                      int32_t* pick_out, double* lsw_out, double* factors_out);
+int hens_mt_debug_draws(hens_ctx* ctx, int64_t iter, double* q, double* u_pick, double* u_acc);
+
 /* ---- Gibbs parameter blocks: gibbs_sampling_setup (move.py:113-221) ------------------------------------
  * The reference's moves take a list of parameter blocks and propose block after block: for every block the move's usual draws,
  * the proposal, the old values put back in every coordinate outside the block (move.py:321-324), prior and likelihood of the
