@@ -334,6 +334,7 @@ def free_run(c, seed=SEED):
 
 # ---- the fixtures from the real reference (tests/golden/make_golden_dist.py -> tests/golden/distgen/) ------------------------------------
 FIXTURES = ["dg1_mix", "dg2_prior_draws"]
+PERIODIC_FIXTURES = ["dg3_periodic_mix"]      # both moves of the mix hold a PeriodicContainer (``period`` [D]): tests/test_move_interactions.py
 
 
 def load_fixture(name):

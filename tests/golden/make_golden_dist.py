@@ -11,6 +11,10 @@ and the likelihood of make_golden.py, the global stream's calls wrapped, the mov
                    that mixes the three kinds and is narrower than the start in two coordinates:
                        0 uniform_dist(-1.5, 2.0)   1 log_uniform(0.05, 2.5)   2 scipy.stats.norm(-0.3, 0.6)   3 scipy.stats.norm(2.0, 1.0)
   dg2_prior_draws  untempered, DistributionGenerate alone, generator = the prior, all uniform.
+  dg3_periodic_mix T = 3, W = 16, D = 4, 16 iterations of [(StretchMove(periodic=pc), 0.5), (DistributionGenerate(periodic=pc), 0.5)]
+                   with the same ``PeriodicContainer``: coordinates 0 and 2 periodic (periods 2 and 3), the prior's box and the
+                   generator's uniform terms reach half a period beyond [0, period] on both sides there.  The stretch move wraps
+                   (stretch.py:149-154); the move never does: its accepted points stay outside [0, period).
 
 Every iteration records which move ran (``kind``: 0 stretch, 1 the move), its draws of the sampler's stream R, its proposals ``q``,
 ``factors``, ``logp``, ``logl``, the accept mask, the state after the move and after the sweep, the sweep's draws, swap counts and
@@ -31,10 +35,14 @@ from scipy import stats                     # noqa: E402
 from eryn.ensemble import EnsembleSampler   # noqa: E402
 from eryn.moves import DistributionGenerate, StretchMove  # noqa: E402
 from eryn.prior import ProbDistContainer, log_uniform, uniform_dist  # noqa: E402
+from eryn.utils import PeriodicContainer    # noqa: E402
 
 OUT = os.environ.get("GOLDEN_OUT", os.path.join(HERE, "distgen"))
 GEN1 = (np.array([0, 1, 2, 2]), np.array([-1.5, 0.05, -0.3, 2.0]), np.array([2.0, 2.5, 0.6, 1.0]))
 BOX2 = (np.array([0, 0, 0]), np.array([-3.0, -2.0, -4.0]), np.array([3.0, 4.0, 2.0]))
+PERIOD3 = {0: 2.0, 2: 3.0}                  # [-p / 2, 3 p / 2]: coordinates 0 and 2 of BOX3 and GEN3
+BOX3 = (np.array([0, 0, 0, 0]), np.array([-1.0, -3.0, -1.5, 0.01]), np.array([3.0, 3.0, 4.5, 8.0]))
+GEN3 = (np.array([0, 2, 0, 1]), np.array([-1.0, 0.5, -1.5, 0.05]), np.array([3.0, 0.8, 4.5, 7.5]))
 
 
 def container(kinds, p0, p1):
@@ -42,14 +50,20 @@ def container(kinds, p0, p1):
     return ProbDistContainer({d: make[int(kinds[d])](float(p0[d]), float(p1[d])) for d in range(len(kinds))})
 
 
-def capture(name, T, W, prior, gen, mix, nsteps, mu, x0, seed_construct=123, seed_run=456):
+def periodic_container(periodic):
+    return None if periodic is None else PeriodicContainer({"model_0": dict(periodic)})
+
+
+def capture(name, T, W, prior, gen, mix, nsteps, mu, x0, seed_construct=123, seed_run=456, periodic=None):
     D = len(prior[0])
     rs = np.random.RandomState(0)
     A = rs.randn(D, D)
     invcov = np.linalg.inv(A @ A.T / D + np.eye(D))
     np.random.seed(seed_construct)
-    dist_move = DistributionGenerate({"model_0": container(*gen)})
-    moves = [(StretchMove(), 0.5), (dist_move, 0.5)] if mix else dist_move
+    pc = periodic_container(periodic)            # (handed to both moves; the sampler itself gets none)
+    kw = {} if pc is None else dict(periodic=pc)
+    dist_move = DistributionGenerate({"model_0": container(*gen)}, **kw)
+    moves = [(StretchMove(**kw), 0.5), (dist_move, 0.5)] if mix else dist_move
     s = EnsembleSampler(W, D, mg.log_like_vec, container(*prior), args=[mu, invcov], vectorize=True, moves=moves,
                         **(dict(tempering_kwargs=dict(ntemps=T)) if T > 1 else {}))
     rlog, glog, plog = [], [], []
@@ -121,6 +135,9 @@ def capture(name, T, W, prior, gen, mix, nsteps, mu, x0, seed_construct=123, see
                prior_kind=prior[0], prior_p0=prior[1], prior_p1=prior[2], gen_kind=gen[0], gen_p0=gen[1], gen_p1=gen[2], mix=int(mix))
     if mix:
         out["a"] = float(s.moves[0].a)
+    if periodic is not None:
+        out["period"] = np.array([float(periodic.get(d, 0.0)) for d in range(D)])
+        assert all(m.periodic is pc for m in s.moves)
     if tc is not None:
         out["betas0"] = np.array(tc.betas, copy=True)
         assert bool(tc.adaptive) and bool(tc.permute)
@@ -230,3 +247,6 @@ if __name__ == "__main__":
     mu2 = np.array([0.3, 1.0, -1.2])
     x2 = np.random.RandomState(2).uniform(BOX2[1], BOX2[2], size=(1, 16, 3))
     capture("dg2_prior_draws", 1, 16, BOX2, BOX2, False, 10, mu2, x2)
+    mu3 = np.array([1.0, 0.5, 1.5, 2.0])
+    x3 = np.random.RandomState(3).uniform(BOX3[1] + 0.05 * (BOX3[2] - BOX3[1]), BOX3[2] - 0.05 * (BOX3[2] - BOX3[1]), size=(3, 16, 4))
+    capture("dg3_periodic_mix", 3, 16, BOX3, GEN3, True, 16, mu3, x3, periodic=PERIOD3)

@@ -11,6 +11,8 @@ calls wrapped, the moves' and the sampler's methods hooked):
                    and ladder adaptation; dg1_mix's prior and generator (mixed kinds; old points outside the generator, for which
                    the reference's log-sum-exp is NaN).
   mt2_prior_tries  T = 2, W = 16, D = 3, K = 25, the move alone, generator = the all-uniform prior.
+  mt3_periodic_mix dg3_periodic_mix's problem with [(StretchMove(periodic=pc), 0.5), (MTDistGenMove(num_try=4, periodic=pc), 0.5)]: the
+                   stretch move wraps, the tries and the picked point never are (multipletry.py holds no wrap).
 
 Every iteration records which move ran (``kind``: 0 stretch, 1 the move), its draws of the sampler's stream R, the state after the
 move and after the sweep, the sweep's draws, swap counts and ladder; a move iteration its tries ``q`` [T, W, K, D] (the ONE ``rvs``
@@ -34,14 +36,16 @@ from eryn.moves import MTDistGenMove, StretchMove  # noqa: E402
 OUT = os.environ.get("GOLDEN_OUT", os.path.join(HERE, "mt"))
 
 
-def capture(name, T, W, prior, gen, K, mix, nsteps, mu, x0, seed_construct=123, seed_run=456):
+def capture(name, T, W, prior, gen, K, mix, nsteps, mu, x0, seed_construct=123, seed_run=456, periodic=None):
     D = len(prior[0])
     rs = np.random.RandomState(0)
     A = rs.randn(D, D)
     invcov = np.linalg.inv(A @ A.T / D + np.eye(D))
     np.random.seed(seed_construct)
-    mt_move = MTDistGenMove(mgd.container(*gen), num_try=K, independent=True)
-    moves = [(StretchMove(), 0.5), (mt_move, 0.5)] if mix else mt_move
+    pc = mgd.periodic_container(periodic)
+    kw = {} if pc is None else dict(periodic=pc)
+    mt_move = MTDistGenMove(mgd.container(*gen), num_try=K, independent=True, **kw)
+    moves = [(StretchMove(**kw), 0.5), (mt_move, 0.5)] if mix else mt_move
     s = EnsembleSampler(W, D, mg.log_like_vec, mgd.container(*prior), args=[mu, invcov], vectorize=True, moves=moves,
                         tempering_kwargs=dict(ntemps=T))
     rlog, glog, plog = [], [], []
@@ -142,6 +146,9 @@ def capture(name, T, W, prior, gen, K, mix, nsteps, mu, x0, seed_construct=123, 
                prior_kind=prior[0], prior_p0=prior[1], prior_p1=prior[2], gen_kind=gen[0], gen_p0=gen[1], gen_p1=gen[2], mix=int(mix))
     if mix:
         out["a"] = float(s.moves[0].a)
+    if periodic is not None:
+        out["period"] = np.array([float(periodic.get(d, 0.0)) for d in range(D)])
+        assert all(m.periodic is pc for m in s.moves)
     out["betas0"] = np.array(tc.betas, copy=True)
     assert bool(tc.adaptive) and bool(tc.permute)
     kinds = []
@@ -254,3 +261,6 @@ if __name__ == "__main__":
     mu2 = np.array([0.3, 1.0, -1.2])
     x2 = np.random.RandomState(2).uniform(mgd.BOX2[1], mgd.BOX2[2], size=(2, 16, 3))
     capture("mt2_prior_tries", 2, 16, mgd.BOX2, mgd.BOX2, 25, False, 10, mu2, x2)
+    mu3 = np.array([1.0, 0.5, 1.5, 2.0])                                  # make_golden_dist.py's dg3_periodic_mix
+    x3 = np.random.RandomState(3).uniform(mgd.BOX3[1] + 0.05 * (mgd.BOX3[2] - mgd.BOX3[1]), mgd.BOX3[2] - 0.05 * (mgd.BOX3[2] - mgd.BOX3[1]), size=(3, 16, 4))
+    capture("mt3_periodic_mix", 3, 16, mgd.BOX3, mgd.GEN3, 4, True, 16, mu3, x3, periodic=mgd.PERIOD3)

@@ -380,6 +380,7 @@ def free_run(c, seed=SEED):
 
 # ---- the fixtures from the real reference (tests/golden/make_golden_mt.py -> tests/golden/mt/) ---------------------------------------------
 FIXTURES = ["mt1_mix", "mt2_prior_tries"]
+PERIODIC_FIXTURES = ["mt3_periodic_mix"]      # both moves of the mix hold a PeriodicContainer (``period`` [D]): tests/test_move_interactions.py
 FIXTURE_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "mt")
 
 

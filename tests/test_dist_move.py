@@ -135,7 +135,7 @@ def test_generator_reproduces_the_committed_fixtures(tmp_path):
     r = subprocess.run([sys.executable, str(tmp_path / "make_golden_dist.py")], cwd=str(tmp_path), capture_output=True, text=True, timeout=600,
                        env=dict(os.environ, PYTHONDONTWRITEBYTECODE="1", GOLDEN_OUT=str(out)))
     assert r.returncode == 0, r.stdout + r.stderr
-    for name in dm.FIXTURES:
+    for name in dm.FIXTURES + dm.PERIODIC_FIXTURES:
         new, old = np.load(out / (name + ".npz"), allow_pickle=False), dm.load_fixture(name)
         assert sorted(new.files) == sorted(old) and len(old) > 30
         for k in old:

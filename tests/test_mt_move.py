@@ -122,12 +122,16 @@ def test_generator_reproduces_the_committed_fixtures(tmp_path):
                        env=dict(os.environ, PYTHONDONTWRITEBYTECODE="1", GOLDEN_OUT=str(out)))
     assert r.returncode == 0, r.stdout + r.stderr
     total = 0
-    for name in mt.FIXTURES:
+    for name in mt.FIXTURES + mt.PERIODIC_FIXTURES:
         new, old = np.load(out / (name + ".npz"), allow_pickle=False), mt.load_fixture(name)
         assert sorted(new.files) == sorted(old) and len(old) > 40
         for k in old:
             assert new[k].dtype == old[k].dtype and new[k].shape == old[k].shape and np.array_equal(new[k], old[k], equal_nan=True), k
-        total += os.path.getsize(os.path.join(mt.FIXTURE_DIR, name + ".npz"))
+        size = os.path.getsize(os.path.join(mt.FIXTURE_DIR, name + ".npz"))
+        if name in mt.FIXTURES:
+            total += size
+        else:
+            assert size < 150_000
     assert total < 500_000
 
 
