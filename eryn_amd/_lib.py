@@ -49,6 +49,11 @@ class HensRjDraws(C.Structure):
                [("branch", C.c_int32), ("split", C.c_int32)]
 
 
+class HensRjMtOut(C.Structure):
+    """struct hens_rj_mt_out (include/hipensemble.h)."""
+    _fields_ = [(n, C.c_void_p) for n in ("pick", "lsw", "aux_lsw", "factors", "mt_ll", "mt_lp")]
+
+
 class HensPipeRegions(C.Structure):
     """struct hens_pipe_region_table (include/hipensemble.h)."""
     _fields_ = [(n, C.c_void_p) for n in ("ldn_out", "ldn_rows_out", "ldn_in", "ldn_rows_in", "lup_out", "lup_in",
@@ -162,6 +167,9 @@ SIGNATURES = {
     "hens_rj_set_in_model": (C.c_int, [_P, C.c_int32]),
     "hens_rj_debug_draws_stretch": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P]),
     "hens_rj_bd_all_step": (C.c_int, [_P, _P, _P, _P, _P, _P]),
+    "hens_rj_set_mt_proposal": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, _P]),
+    "hens_rj_mt_bd_step": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, _P, _P]),
+    "hens_rj_mt_debug_draws": (C.c_int, [_P, C.c_int64, _P, _P]),
     "hens_rj_propose": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P]),
     "hens_rj_accept": (C.c_int, [_P, _P, _P]),
     "hens_rj_stretch_split": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P]),

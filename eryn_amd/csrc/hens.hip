@@ -10,6 +10,7 @@
 #include "hens_prior.h"
 #include "hens_dist.h"
 #include "hens_mt.h"
+#include "hens_rj_mt.h"
 #include "hens_gibbs_host.h"
 #include "hens_chain.h"
 #include "hens_chain_stats.h"
@@ -259,6 +260,12 @@ struct hens_ctx_impl {
         bool defer_adapt = false;            // hens_rj_step: the adaptation behind a cascade rides in the next k_rj launch
         uint32_t* acc_bd = nullptr;          // [Tl][W] accept counts of the birth / death move (the in-model move uses `accepted`)
         int64_t num_mh = 0, num_bd = 0;      // moves run
+        // hens_rj_set_mt_proposal: the birth / death move is MTDistGenMoveRJ with mt_K tries (0: the plain move) - k_rj_mt, hens_rj_mt.h
+        int mt_K = 0;
+        double* mt_dens = nullptr;           // [RJ_MAX_BRANCH][2][RJ_MAX_ND][RJ_MT_DENS] per branch the generator's and the prior's terms of one leaf
+        bool mt_gen_box[RJ_MAX_BRANCH] = {}; double mt_gen_logq[RJ_MAX_BRANCH] = {};      // an all-uniform generator and its constant log-density
+        double* mt_tries = nullptr;          // staging of hens_rj_mt_bd_step: the caller's tries [Tl][W][RJ_MT_MAX_TRY x RJ_MAX_ND at most], pick uniforms; the launch's sums
+        double* mt_upick = nullptr; double* mt_out = nullptr;
     } rj;
 
     // debug / timing
@@ -1900,6 +1907,10 @@ struct RjLaunch {
     const int32_t* st_own = nullptr; const int32_t* st_cw = nullptr; const double* st_uzz = nullptr; const double* u_acc = nullptr;
     uint8_t* keep = nullptr;                // RjArgs::keep_out
     bool propose = false;                   // the proposal half of a host-callable move (k_rj<MODE, -2>); k_rj_accept finishes it
+    // the multiple-try birth / death move (k_rj_mt, hens_rj_set_mt_proposal) in place of k_rj<RJ_MODE_BD>: FORCED: the caller's tries and
+    // pick uniforms (birth unused); mt_out: RjMtArgs::out
+    bool mt = false;
+    const double* tries = nullptr; const double* u_pick = nullptr; double* mt_out = nullptr;
 };
 RjLaunch rj_eval() { return RjLaunch{RJ_MODE_EVAL, 0, 0}; }      // every row's templates, log-likelihood and log-prior from its coordinates
 // a Philox move of hens_rj_step: on the resident templates where the model has them, birth / death by difference; `split`: that
@@ -1979,6 +1990,22 @@ int rj_launch(hens_ctx_impl* c, const RjLaunch& l) {
         if (a.tm || l.draws != RjLaunch::FORCED || mode == RJ_MODE_EVAL) return fail(c, HENS_ERR_STATE, "hens_rj_propose: a teacher-forced move with its accept uniforms");
         tmm = -2;
         a.hq = c->rj.hq; a.hlogp = c->rj.hlogp; a.hfac = c->rj.hfac; a.hlu = c->rj.hlu; a.hmoved = c->rj.hmoved;
+    }
+    if (l.mt) {                                       // (one branch, a model with a device likelihood: hens_rj_set_mt_proposal saw to both)
+        const hens_ctx_impl::Rj& s = c->rj;
+        RjMtArgs g{};
+        g.A = a; g.tries = l.tries; g.u_pick = l.u_pick; g.out = l.mt_out;
+        g.gen = s.mt_dens + (size_t)(2 * l.branch) * RJ_MAX_ND * RJ_MT_DENS;
+        g.pri = g.gen + RJ_MAX_ND * RJ_MT_DENS;
+        g.gen_logq = s.mt_gen_logq[l.branch]; g.gen_box = s.mt_gen_box[l.branch] ? 1 : 0;
+        g.pri_logp = s.M.leaf_logp[l.branch]; g.pri_box = s.M.prior_on ? 0 : 1;
+        g.K = s.mt_K;
+        g.per_branch = (s.wide || s.M.prior_on) ? 0 : 1;      // (the order of k_rj's instantiation for this model)
+        if (tmm != -1 && tmm != 1) return fail(c, HENS_ERR_STATE, "k_rj_mt: a birth / death launch, by difference or in full");
+        hipLaunchKernelGGL(a.tm ? k_rj_mt<true> : k_rj_mt<false>, grid, block, 0, c->stream, g);
+        const hipError_t em = hipGetLastError();
+        if (em != hipSuccess) return fail(c, HENS_ERR_HIP, "k_rj_mt launch failed: %s", hipGetErrorString(em));
+        return HENS_OK;
     }
     const bool chol = mode == RJ_MODE_MH && l.draws == RjLaunch::PHILOX && c->rj.have_chol && tmm != -2;
     // (the proposal half of a host-callable move has the widths at run time already; a model under prior terms - pulses and sines
@@ -4079,6 +4106,7 @@ static int rj_set_template_model(hens_ctx_impl* c, int nkinds, int32_t nbranches
     c->rj.M = M;
     c->rj.general = false;
     c->rj.wide = wide;
+    c->rj.mt_K = 0;
     int r;
     if ((r = rj_push_ctab(c))) return r;
     if (!c->rj.t) {
@@ -4152,6 +4180,7 @@ int hens_rj_set_model_general(hens_ctx* ctx, int32_t nbranches, const int32_t* n
     c->rj.M = M;
     c->rj.general = true;
     c->rj.wide = false;
+    c->rj.mt_K = 0;
     int r;
     if ((r = rj_push_ctab(c))) return r;
     if (!c->rj.acc_bd) {
@@ -4254,6 +4283,7 @@ int hens_rj_set_prior_terms(hens_ctx* ctx, const int32_t* kind, const double* lo
     memcpy(c->rj.terms, terms, sizeof(terms));
     if (const int r = rj_push_ctab(c)) { c->rj.M = before; return r; }
     c->rj.tm_valid = false;
+    c->rj.mt_K = 0;                            // (a multiple-try proposal was set against the prior that was: hens_rj_set_mt_proposal anew)
     return HENS_OK;
 }
 
@@ -4387,6 +4417,145 @@ int hens_rj_bd_all_step(hens_ctx* ctx, const int8_t* change, const int32_t* leaf
     return rj_forced_move(enter(ctx), HENS_RJ_MOVE_BD_ALL, d, keep_out, false);
 }
 
+// ---- MTDistGenMoveRJ (mtdistgenrj.py over multipletry.py:238-514, 597-776): the multiple-try birth / death move, k_rj_mt --------
+static int rj_branch_of(const hens_ctx_impl* c, uint64_t it);      // (below, with hens_rj_step)
+// One leaf parameter's density as the kernel reads it (hens_rj_mt.h: RJ_MT_DENS doubles)
+static void rj_mt_row(double* r, double lo, double hi, const PriorTerm& t) {
+    r[0] = lo; r[1] = hi; r[2] = t.c0; r[3] = t.c1; r[4] = t.c2; r[5] = (double)t.kind;
+}
+int hens_rj_set_mt_proposal(hens_ctx* ctx, int32_t num_try, const int32_t* kind, const double* lo, const double* hi, const double* c0,
+                            const double* c1, const double* c2) {
+    hens_ctx_impl* c = enter(ctx);
+    if (!c) return no_context();
+    if (const int rk = need_rj_context(c)) return rk;
+    if (const int rm = need_rj_model(c)) return rm;
+    if (c->rj.accept_pending) return fail(c, HENS_ERR_STATE, "hens_rj_accept must follow hens_rj_propose");
+    if (num_try < 0 || num_try > RJ_MT_MAX_TRY) return fail(c, HENS_ERR_INVALID, "num_try must be in [0, %d] (one lane per try; 0: the plain birth / death move)", RJ_MT_MAX_TRY);
+    if (num_try == 0) { c->rj.mt_K = 0; return HENS_OK; }
+    if (c->rj.general)
+        return fail(c, HENS_ERR_STATE, "this context's model has no device likelihood (hens_rj_set_model_general): the multiple-try move evaluates its tries on the device");
+    if (kind && (!lo || !hi || !c0 || !c1 || !c2)) return fail(c, HENS_ERR_INVALID, "null argument");
+    const RjModel& M = c->rj.M;
+    int slots = 0;
+    for (int b = 0; b < M.nb; ++b) {
+        slots += M.nl[b];
+        if (M.nlmin[b] == M.nl[b])               // multipletry.py:661-664
+            return fail(c, HENS_ERR_INVALID, "MT RJ proposal requires that nleaves_min != nleaves_max. (branch %d)", b);
+    }
+    if (slots > 64) return fail(c, HENS_ERR_UNSUPPORTED, "multiple-try proposal: %d leaf slots, at most 64 over all branches", slots);
+    if (c->D > RJ_MAX_RW) return fail(c, HENS_ERR_UNSUPPORTED, "multiple-try proposal: record width ndim = %d, at most %d doubles", c->D, RJ_MAX_RW);
+    std::vector<double> dens((size_t)RJ_MAX_BRANCH * 2 * RJ_MAX_ND * RJ_MT_DENS, 0.0);
+    bool gbox[RJ_MAX_BRANCH] = {};
+    double glogq[RJ_MAX_BRANCH] = {};
+    int k = 0;
+    for (int b = 0; b < M.nb; ++b) {
+        double* gen = dens.data() + (size_t)(2 * b) * RJ_MAX_ND * RJ_MT_DENS;
+        double* pri = gen + RJ_MAX_ND * RJ_MT_DENS;
+        PriorTerm gt[RJ_MAX_ND] = {};
+        for (int d = 0; d < M.nd[b]; ++d, ++k) {
+            // the prior of the branch's leaf: its terms, or (a box model) the box with the branch's constant, RjModel::leaf_logp
+            PriorTerm pt_{};
+            if (M.prior_on) pt_ = c->rj.terms[b][d];
+            rj_mt_row(pri + d * RJ_MT_DENS, M.lo[b][d], M.hi[b][d], pt_);
+            if (!kind) {                             // the generator is the prior
+                rj_mt_row(gen + d * RJ_MT_DENS, M.lo[b][d], M.hi[b][d], pt_);
+                continue;
+            }
+            const ParsedTerm p = parse_term(kind[k], lo[k], hi[k], c0[k], c1[k], c2[k], /*admit_pad=*/false);
+            if (p.why[0]) return fail(c, HENS_ERR_INVALID, "%s (generator: branch %d, parameter %d)", p.why, b, d);
+            gt[d] = p.term;
+            rj_mt_row(gen + d * RJ_MT_DENS, lo[k], hi[k], p.term);
+        }
+        if (!kind) { gbox[b] = !M.prior_on; glogq[b] = M.leaf_logp[b]; }
+        else { const PriorBox pb = fold_box(gt, M.nd[b]); gbox[b] = pb.box; glogq[b] = pb.logp; }
+    }
+    SETTLE(c, NEED_DEVICE);
+    if (!c->rj.mt_dens)
+        if (const int r = dalloc(c, &c->rj.mt_dens, dens.size())) return r;
+    HIPCHK(c, hipMemcpyAsync(c->rj.mt_dens, dens.data(), dens.size() * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));          // (the vector goes out of scope)
+    memcpy(c->rj.mt_gen_box, gbox, sizeof(gbox));
+    memcpy(c->rj.mt_gen_logq, glogq, sizeof(glogq));
+    c->rj.mt_K = num_try;
+    return HENS_OK;
+}
+
+int hens_rj_mt_bd_step(hens_ctx* ctx, int32_t branch, const int8_t* change, const int32_t* leaf, const double* tries, const double* u_pick,
+                       const double* u_acc, uint8_t* keep_out, const hens_rj_mt_out* out) {
+    hens_ctx_impl* c = enter(ctx);
+    int r = rj_ready(c);
+    if (r) return r;
+    if (!change || !leaf || !tries || !u_pick || !u_acc) return fail(c, HENS_ERR_INVALID, "null argument");
+    if (c->rj.mt_K < 1) return fail(c, HENS_ERR_STATE, "no multiple-try proposal set (hens_rj_set_mt_proposal)");
+    if (branch < 0 || branch >= c->rj.M.nb) return fail(c, HENS_ERR_INVALID, "branch %d out of range", branch);
+    const size_t TW = (size_t)c->Tl * c->W, K = (size_t)c->rj.mt_K, NT = TW * K * (size_t)c->rj.M.ndmax;
+    for (size_t i = 0; i < TW; ++i) {
+        if (change[i] != -1 && change[i] != 1) return fail(c, HENS_ERR_INVALID, "change must be -1 or +1 (MT RJ is only implemented for +1/-1 moves)");
+        if (leaf[i] < 0 || leaf[i] >= c->rj.M.nl[branch]) return fail(c, HENS_ERR_INVALID, "leaf slot out of range");
+    }
+    SETTLE(c, NEED_DEVICE | NEED_FIELDS | NEED_LADDER);
+    if ((r = rj_ensure_staging(c))) return r;
+    // (each once; the tries for the most tries and the widest leaf a proposal can have: a later proposal of more tries finds room)
+    if (!c->rj.mt_tries && (r = dalloc(c, &c->rj.mt_tries, TW * RJ_MT_MAX_TRY * RJ_MAX_ND))) return r;
+    if (!c->rj.mt_upick && (r = dalloc(c, &c->rj.mt_upick, TW))) return r;
+    if (!c->rj.mt_out && (r = dalloc(c, &c->rj.mt_out, (size_t)RJ_MT_NOUT * TW))) return r;
+    HIPCHK(c, hipMemcpyAsync(c->rj.change, change, TW, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->rj.leaf, leaf, TW * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->rj.mt_tries, tries, NT * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->rj.mt_upick, u_pick, TW * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->rj.u, u_acc, TW * 8, hipMemcpyHostToDevice, c->stream));
+    RjLaunch l = rj_forced(c, RJ_MODE_BD, false);
+    l.branch = branch; l.birth = nullptr;
+    l.mt = true; l.tries = c->rj.mt_tries; l.u_pick = c->rj.mt_upick; l.mt_out = c->rj.mt_out;
+    c->rj.tm_valid = false;                   // (teacher-forced move: the reference's full evaluation, no resident templates)
+    if ((r = rj_launch(c, l))) return r;
+    if (keep_out) HIPCHK(c, hipMemcpyAsync(keep_out, c->rj.keep, TW, hipMemcpyDeviceToHost, c->stream));
+    std::vector<double> pk;
+    if (out) {
+        double* const dst[RJ_MT_NOUT] = {nullptr, out->lsw, out->aux_lsw, out->factors, out->mt_ll, out->mt_lp};
+        for (int f = 1; f < RJ_MT_NOUT; ++f)
+            if (dst[f]) HIPCHK(c, hipMemcpyAsync(dst[f], c->rj.mt_out + (size_t)f * TW, TW * 8, hipMemcpyDeviceToHost, c->stream));
+        if (out->pick) {
+            pk.resize(TW);
+            HIPCHK(c, hipMemcpyAsync(pk.data(), c->rj.mt_out, TW * 8, hipMemcpyDeviceToHost, c->stream));
+        }
+    }
+    if ((r = check_flags(c, false))) return r;            // (waits for the stream)
+    for (size_t i = 0; i < pk.size(); ++i) out->pick[i] = (int32_t)pk[i];
+    if (!(c->rj.schedule == 1 && branch != c->rj.M.nb - 1)) c->rj.num_bd += 1;      // ("iterate_branches": one MOVE per walk through the branches)
+    return HENS_OK;
+}
+
+int hens_rj_mt_debug_draws(hens_ctx* ctx, int64_t iter, double* tries, double* u_pick) {
+    hens_ctx_impl* c = enter(ctx);
+    if (!c || iter < 0) return fail(c, HENS_ERR_INVALID, "null context / negative iteration");
+    if (const int rm = need_rj_model(c)) return rm;
+    if (c->rj.mt_K < 1) return fail(c, HENS_ERR_STATE, "no multiple-try proposal set (hens_rj_set_mt_proposal)");
+    if (!tries || !u_pick) return fail(c, HENS_ERR_INVALID, "null output");
+    SETTLE(c, NEED_DEVICE);
+    const size_t TW = (size_t)c->Tl * c->W, per = TW * (size_t)c->rj.mt_K * (size_t)c->rj.M.ndmax;
+    DeviceScratch sc;
+    RjMtDebugArgs a{};
+    a.tries = sc.grab<double>(per); a.u_pick = sc.grab<double>(TW);
+    if (!a.tries || !a.u_pick) return fail(c, HENS_ERR_HIP, "hens_rj_mt_debug_draws: out of device memory");
+    a.iter = (uint64_t)iter; a.seed = c->cfg.seed;
+    a.Tl = c->Tl; a.W = c->W; a.rung_begin = c->cfg.rung_begin; a.K = c->rj.mt_K; a.ndmax = c->rj.M.ndmax;
+    // "separate_branches": the chosen branch's draws in entry 0; "iterate_branches": every branch's, in order (hens_rj_debug_draws)
+    const bool every = c->rj.schedule == 1 || c->rj.schedule == 2;
+    const int nsub = every ? c->rj.M.nb : 1;
+    for (int k = 0; k < nsub; ++k) {
+        a.branch = every ? k : rj_branch_of(c, (uint64_t)iter);
+        a.nd = c->rj.M.nd[a.branch];
+        a.gen = c->rj.mt_dens + (size_t)(2 * a.branch) * RJ_MAX_ND * RJ_MT_DENS;
+        hipLaunchKernelGGL(k_rj_mt_debug_draws, dim3(grid_for((int64_t)TW)), dim3(256), 0, c->stream, a);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(tries + (size_t)k * per, a.tries, per * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(u_pick + (size_t)k * TW, a.u_pick, TW * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    return HENS_OK;
+}
+
 // branch of iteration `it`'s birth / death move (ensemble.py:988-990, "separate_branches"): one counter-based uniform
 static int rj_branch_of(const hens_ctx_impl* c, uint64_t it) {
     return std::min(c->rj.M.nb - 1, (int)(move_uniform(c->cfg.seed ^ 0x9E3779B97F4A7C15ull, it) * c->rj.M.nb));
@@ -4397,9 +4566,11 @@ static int rj_branch_of(const hens_ctx_impl* c, uint64_t it) {
 // death, accept, update per branch -, its accept mask is the last branch's; else one branch's move (ensemble.py:988-990).
 static int rj_step_bd(hens_ctx_impl* c) {
     if (c->rj.schedule == 2) return rj_launch(c, rj_production(c, RJ_MODE_BD, -1));
-    if (c->rj.schedule != 1) return rj_launch(c, rj_production(c, RJ_MODE_BD, rj_branch_of(c, c->iter)));
+    // (under hens_rj_set_mt_proposal the launch is k_rj_mt: same place, same template scheme, same accept counter)
+    auto one = [c](int b) { RjLaunch l = rj_production(c, RJ_MODE_BD, b); l.mt = c->rj.mt_K > 0; return rj_launch(c, l); };
+    if (c->rj.schedule != 1) return one(rj_branch_of(c, c->iter));
     for (int b = 0, r; b < c->rj.M.nb; ++b)
-        if ((r = rj_launch(c, rj_production(c, RJ_MODE_BD, b)))) return r;
+        if ((r = one(b))) return r;
     return HENS_OK;
 }
 
@@ -4419,6 +4590,8 @@ struct RjStepping {
 int RjStepping::begin(int64_t n_iters) {
     int r;
     stretch = c->rj.in_model == HENS_RJ_INMODEL_STRETCH;
+    if (c->rj.mt_K > 0 && c->rj.schedule == 2)        // multipletry.py:635-636
+        return fail(c, HENS_ERR_UNSUPPORTED, "Can only propose change to one model at a time with MT. (rj schedule \"together\" under hens_rj_set_mt_proposal)");
     if (!stretch && !c->rj.have_scale) return fail(c, HENS_ERR_STATE, "in-model step scale not set (hens_rj_set_mh_scale)");
     if (stretch && !c->cfg.live_dangerously && c->W < 2 * c->rj.M.ind_off)           // red_blue.py:103-114 (every slot of every branch counts)
         return fail(c, HENS_ERR_TOO_FEW_WALKERS, "It is unadvisable to use a red-blue move with fewer walkers than twice the number of dimensions. "
@@ -4779,6 +4952,8 @@ int hens_rj_propose(hens_ctx* ctx, int32_t move, const hens_rj_draws* d, double*
     if (!c || !d || !q_out || !logp_out || !moved_out) return fail(c, HENS_ERR_INVALID, "null argument");
     if (const int rk = need_rj_context(c)) return rk;
     if (c->rj.accept_pending) return fail(c, HENS_ERR_STATE, "hens_rj_accept must follow hens_rj_propose");
+    if (c->rj.mt_K > 0)
+        return fail(c, HENS_ERR_UNSUPPORTED, "hens_rj_propose: not under a multiple-try proposal (hens_rj_set_mt_proposal: the tries' likelihoods are the device's)");
     SETTLE(c, NEED_DEVICE);
     const size_t TW = (size_t)c->Tl * c->W, RW = (size_t)c->rj.M.RW;
     int r;

@@ -31,7 +31,8 @@ class MTDistGenMove(MHMove):
 
     Only ``independent=True`` is built.  The reference's default ``independent=False`` raises ``UnboundLocalError`` inside
     ``get_mt_proposal`` (multipletry.py:456 reads a name only the independent branch assigns), so no chain depends on it.
-    ``symmetric=True``, ``rj=True`` (``MTDistGenMoveRJ``) and ``gibbs_sampling_setup`` are not built.
+    ``symmetric=True`` and ``gibbs_sampling_setup`` are not built; ``rj=True`` is ``eryn_amd.rj.MTDistGenMoveRJ``, a move of the
+    leaf-packing sampler.
 
     An untempered sampler steps with beta = 1.  This is beyond the reference, whose move reads ``temperature_control.betas`` and
     raises without one.
@@ -44,7 +45,8 @@ class MTDistGenMove(MHMove):
             raise NotImplementedError("MTDistGenMove(gibbs_sampling_setup=...) is not built: the device draws whole rows from the "
                                       "generator (Gibbs blocks: eryn_amd.moves.StretchMove, GaussianMove)")
         if rj:
-            raise NotImplementedError("MTDistGenMove(rj=True) is the nested reversible-jump form (MTDistGenMoveRJ): not built")
+            raise NotImplementedError("MTDistGenMove(rj=True) is the nested reversible-jump form: eryn_amd.rj.MTDistGenMoveRJ, a move of "
+                                      "RJEnsembleSampler(rj_moves=...) on leaf-packing records")
         if symmetric:
             raise NotImplementedError("MTDistGenMove(symmetric=True) is not built: the device forms the weights of an independence "
                                       "proposal, logP - logq")

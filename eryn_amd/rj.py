@@ -179,6 +179,7 @@ class RJEngine(ChainStoreCalls):
         self.schedule = "separate_branches"
         self.in_model = "gaussian"   # the in-model move of ``step`` (set_in_model)
         self.host_like = None        # a CallableLikelihood: every parity move = propose on the device, evaluate here, accept on the device
+        self.mt_K, self.mt_gen = 0, None     # set_mt_proposal: tries of the multiple-try birth / death move (0: the plain move), its generators
         nb = len(self.branches)
         kinds = np.array([b.kind for b in self.branches], dtype=np.int32)
         nlmax = np.array([b.nleaves_max for b in self.branches], dtype=np.int32)
@@ -327,6 +328,55 @@ class RJEngine(ChainStoreCalls):
         keep = np.empty((self.T, self.W), dtype=np.uint8)
         check(self.lib.hens_rj_bd_all_step(self.ctx, ptr(ch), ptr(lf), ptr(bt), ptr(u), ptr(keep)), self.ctx)
         return keep.astype(bool)
+
+    # -- the multiple-try birth / death move (include/hipensemble.h: hens_rj_set_mt_proposal, hens_rj_mt_bd_step) ------------------
+    def set_mt_proposal(self, num_try, generate_dist=None):
+        """``MTDistGenMoveRJ(generate_dist, num_try=K, rj=True)`` in place of the plain birth / death move: ``num_try`` tries per
+        walker (1 .. 64; 0 returns to the plain move) from ``generate_dist`` - ``{branch name: anything eryn_amd.prior.prior_spec
+        reads}`` (a ProbDistContainer, the dict it is made of, (lo, hi) per leaf parameter) for EVERY branch, or None: the prior."""
+        specs = None          # (mt_K / mt_gen follow the context: a refused call leaves both as they were)
+        if generate_dist is None or int(num_try) == 0:
+            check(self.lib.hens_rj_set_mt_proposal(self.ctx, int(num_try), None, None, None, None, None, None), self.ctx)
+        else:
+            specs = []
+            for b in self.branches:
+                if b.name not in generate_dist:
+                    raise ValueError(f"generate_dist has no entry for branch {b.name}")
+                specs.append(prior_spec(generate_dist[b.name]))
+                if specs[-1].lo.shape != (b.ndim,):
+                    raise ValueError(f"branch {b.name}: a generator of {specs[-1].lo.shape[0]} parameters for leaves of {b.ndim}")
+            check(self.lib.hens_rj_set_mt_proposal(self.ctx, int(num_try), *map(ptr, term_arrays([s.terms for s in specs]))), self.ctx)
+        self.mt_K, self.mt_gen = int(num_try), specs
+
+    def mt_bd_step(self, branch, change, leaf, tries, u_pick, u_acc, out=False):
+        """The move teacher-forced on one branch: change[T, W] in {-1, +1}, leaf[T, W], tries[T, W, K, ndim of the branch] (a death
+        walker's try 0 is ignored: it is the dying leaf), u_pick / u_acc[T, W].  Returns the accept mask, with ``out=True`` also a dict
+        of pick (int32), lsw, aux_lsw, factors, mt_ll, mt_lp, each [T, W]."""
+        if self.host_like is not None:
+            raise NotImplementedError("the multiple-try birth / death move evaluates its tries on the device: a TemplateLikelihood")
+        K, nd = int(getattr(self, "mt_K", 0)), self.branches[int(branch)].ndim
+        ch = np.ascontiguousarray(change, dtype=np.int8)
+        lf = np.ascontiguousarray(leaf, dtype=np.int32)
+        tr = np.zeros((self.T, self.W, max(K, 1), self.ndmax))
+        tr[..., :nd] = f64(tries, (self.T, self.W, max(K, 1), nd))
+        up, ua = f64(u_pick, (self.T, self.W)), f64(u_acc, (self.T, self.W))
+        if ch.shape != (self.T, self.W) or lf.shape != ch.shape:
+            raise ValueError("change / leaf must have shape (ntemps, nwalkers)")
+        keep = np.empty((self.T, self.W), dtype=np.uint8)
+        res = dict(pick=np.empty((self.T, self.W), dtype=np.int32), **{k: np.empty((self.T, self.W)) for k in ("lsw", "aux_lsw", "factors", "mt_ll", "mt_lp")})
+        o = _lib.HensRjMtOut(**{k: v.ctypes.data for k, v in res.items()})
+        self.eng.state_epoch += 1
+        check(self.lib.hens_rj_mt_bd_step(self.ctx, int(branch), ptr(ch), ptr(lf), ptr(tr), ptr(up), ptr(ua), ptr(keep), C.byref(o) if out else None), self.ctx)
+        return (keep.astype(bool), res) if out else keep.astype(bool)
+
+    def mt_debug_draws(self, it):
+        """The tries and pick uniforms ``step`` draws in iteration ``it`` (include/hipensemble.h: hens_rj_mt_debug_draws): tries
+        [ns, T, W, K, ndmax], u_pick [ns, T, W] with the branch axis of ``debug_draws`` (one entry, or one per branch in order)."""
+        nb, K = len(self.branches), int(getattr(self, "mt_K", 0))
+        tries, up = np.zeros((nb, self.T, self.W, max(K, 1), self.ndmax)), np.zeros((nb, self.T, self.W))
+        check(self.lib.hens_rj_mt_debug_draws(self.ctx, int(it), ptr(tries), ptr(up)), self.ctx)
+        ns = nb if self.schedule in ("iterate_branches", "together") else 1
+        return dict(tries=tries[:ns], u_pick=up[:ns])
 
     def _birth_rows(self, birth, nd):
         """[T, W, nd] -> [T, W, ndmax] (the library's stride: the model's widest branch)."""
@@ -607,6 +657,65 @@ class StretchLeafMove:
         self.accepted, self.num_proposals = None, 0
 
 
+class MTDistGenMoveRJ:
+    """``MTDistGenMoveRJ(generate_dist, num_try=25, rj=True)`` of the reference (mtdistgenrj.py over multipletry.py:238-514, 597-776)
+    as the between-model move of ``RJEnsembleSampler(rj_moves=...)``: per walker ``num_try`` (1 .. 64) candidate leaves from
+    ``generate_dist`` - ``{branch name: ProbDistContainer | the dict it is made of | (lo, hi) per leaf parameter}``, uniform,
+    log-uniform and normal entries - one of them picked by importance weight (include/hipensemble.h: hens_rj_set_mt_proposal).  The
+    move acts on one branch (multipletry.py:635-636): one object on a one-branch model, or a list with one object per branch, each
+    with ``gibbs_sampling_setup=<its branch>`` and the same ``num_try``.  ``nleaves_max`` / ``nleaves_min`` are the sampler's: given here
+    (a dict over branches or one number) they must agree with it for the move's branch, else the sampler raises ``ValueError``.
+
+    ``accepted`` / ``num_proposals`` (move.py:404-421) are fed per move under ``rng="numpy"``.  Under ``rng="philox"`` the device counts
+    the birth / death move over all branches together (hens_rj_get_counters): the sampler's ``rj_accepted_all`` /
+    ``rj_num_proposals_all`` carry it and the moves' own counters stay at zero."""
+
+    def __init__(self, generate_dist, nleaves_max=None, nleaves_min=None, num_try=1, rj=True, gibbs_sampling_setup=None):
+        if not rj:
+            raise NotImplementedError("MTDistGenMoveRJ is the nested reversible-jump form of multiple try: rj=True")
+        if isinstance(num_try, bool) or not isinstance(num_try, (int, np.integer)) or not 1 <= int(num_try) <= 64:
+            raise ValueError("num_try must be an integer in [1, 64]")
+        if not isinstance(generate_dist, dict) or not generate_dist:
+            raise ValueError("generate_dist must be a dict {branch name: distribution container}")
+        if gibbs_sampling_setup is not None and gibbs_sampling_setup not in generate_dist:
+            raise ValueError(f"gibbs_sampling_setup must name the branch the move acts on (a key of generate_dist), not {gibbs_sampling_setup!r}")
+        if gibbs_sampling_setup is None and len(generate_dist) != 1:
+            raise ValueError("Can only propose change to one model at a time with MT. (one MTDistGenMoveRJ per branch, each with "
+                             "gibbs_sampling_setup=<its branch>)")
+        self.generate_dist, self.num_try = dict(generate_dist), int(num_try)
+        self.branch = gibbs_sampling_setup if gibbs_sampling_setup is not None else next(iter(generate_dist))
+        self.gibbs_sampling_setup = gibbs_sampling_setup
+        self.nleaves_max, self.nleaves_min = nleaves_max, nleaves_min
+        self.accepted, self.num_proposals = None, 0
+
+
+def _mt_rj_moves(rj_moves, branch_names):
+    """``rj_moves`` made of MTDistGenMoveRJ objects -> {branch name: move}, or None if it holds none.  One object on a one-branch model,
+    or one per branch in a list; anything else is refused with a sentence."""
+    seq = list(rj_moves) if isinstance(rj_moves, (list, tuple)) else [rj_moves]
+    seq = [m[0] if isinstance(m, (list, tuple)) else m for m in seq]          # ((move, weight) pairs: the weights must be uniform)
+    if not any(isinstance(m, MTDistGenMoveRJ) for m in seq):
+        return None
+    if not all(isinstance(m, MTDistGenMoveRJ) for m in seq):
+        raise NotImplementedError("rj_moves: MTDistGenMoveRJ objects cannot be mixed with other moves")
+    if isinstance(rj_moves, (list, tuple)) and any(isinstance(m, (list, tuple)) for m in rj_moves):
+        w = [float(m[1]) for m in rj_moves]
+        if any(x != w[0] for x in w):
+            raise NotImplementedError("rj_moves: the device chooses the branch of a between-model move uniformly (equal weights)")
+    by = {}
+    for m in seq:
+        if m.branch not in branch_names:
+            raise ValueError(f"MTDistGenMoveRJ acts on branch {m.branch!r}, which the sampler does not have")
+        if m.branch in by:
+            raise ValueError(f"two MTDistGenMoveRJ moves act on branch {m.branch!r}")
+        by[m.branch] = m
+    if sorted(by) != sorted(branch_names):
+        raise NotImplementedError("rj_moves: one MTDistGenMoveRJ per branch (every branch takes the multiple-try move, or none does)")
+    if len({m.num_try for m in seq}) != 1:
+        raise NotImplementedError("rj_moves: every MTDistGenMoveRJ must have the same num_try (one launch shape per context)")
+    return by
+
+
 class RJEnsembleSampler:
     """``EnsembleSampler(nwalkers, ndims, log_like_fn, priors, tempering_kwargs=..., branch_names=..., nleaves_max=...,
     nleaves_min=..., moves=GaussianMove(cov), rj_moves="separate_branches")`` (ensemble.py:211-681) for the template model,
@@ -664,6 +773,13 @@ class RJEnsembleSampler:
             log_like_fn = TemplateLikelihood({k: "pulse" for k in names_}, None, None, 1.0)     # (never evaluated: no device likelihood)
         if not isinstance(log_like_fn, TemplateLikelihood):
             raise NotImplementedError("log_like_fn: an eryn_amd.rj.TemplateLikelihood, a CallableLikelihood or a Python function")
+        # rj_moves made of MTDistGenMoveRJ objects: the multiple-try birth / death move on every branch, one of them chosen per
+        # iteration like the plain moves of "separate_branches" (ensemble.py:453-471, 988-990)
+        self.mt_moves = None if isinstance(rj_moves, str) or not rj_moves else _mt_rj_moves(rj_moves, list(branch_names if branch_names is not None else ndims.keys()))
+        if self.mt_moves is not None:
+            if self.host_like is not None:
+                raise NotImplementedError("MTDistGenMoveRJ evaluates its tries on the device: log_like_fn must be a TemplateLikelihood")
+            rj_moves = "separate_branches"
         if rj_moves not in ("separate_branches", "iterate_branches", "together", None, False):
             raise ValueError("When providing a str for rj_moves, must be 'together', 'iterate_branches', or "
                              f"'separate_branches'. Input is {rj_moves}")                # ensemble.py:473-476
@@ -678,6 +794,10 @@ class RJEnsembleSampler:
         nleaves_min = nleaves_min or {k: 0 for k in self.branch_names}            # ensemble.py:388-389
         self.nwalkers, self.ndims = int(nwalkers), dict(ndims)
         self.nleaves_max, self.nleaves_min = dict(nleaves_max), dict(nleaves_min)
+        for k, m in (self.mt_moves or {}).items():          # (a move's own leaf budget, where it was given one, is the sampler's)
+            for what, own, mine in (("nleaves_max", m.nleaves_max, self.nleaves_max), ("nleaves_min", m.nleaves_min, self.nleaves_min)):
+                if own is not None and (dict(own).get(k, mine[k]) if isinstance(own, dict) else own) != mine[k]:
+                    raise ValueError(f"MTDistGenMoveRJ on {k}: {what} differs from the sampler's")
         self.branches = []
         for k in self.branch_names:
             nd = int(self.ndims[k])
@@ -708,6 +828,11 @@ class RJEnsembleSampler:
         self.engine.host_like = self.host_like
         if self.rj_schedule is not None or rng == "philox":
             self.engine.set_schedule(rj_moves or "none")
+        if self.mt_moves is not None:
+            for m in self.mt_moves.values():
+                m.accepted = np.zeros((self.ntemps, self.nwalkers))
+            self.engine.set_mt_proposal(next(iter(self.mt_moves.values())).num_try,
+                                        {k: self.mt_moves[k].generate_dist[k] for k in self.branch_names})
         if rng == "philox" and isinstance(moves, StretchLeafMove):
             self.engine.set_in_model("stretch")
         elif rng == "philox":
@@ -857,12 +982,38 @@ class RJEnsembleSampler:
                 draws[:, d] = np.random.rand(nbirth) * (b.hi[d] - b.lo[d]) + b.lo[d]      # prior.py:60-66, 432-497
         return draws
 
+    @staticmethod
+    def _draw_mt_tries(spec, n, k):
+        """``ProbDistContainer.rvs(size=(n, k))`` of a generator (prior.py:432-497): per parameter, in order, one array of n k values from
+        the GLOBAL stream - the constructions of eryn_amd.prior's distributions."""
+        t = spec.terms
+        out = np.zeros((n, k, t["kind"].shape[0]))
+        for d, kind in enumerate(t["kind"]):
+            if kind == _lib.PRIOR_NORMAL:
+                out[..., d] = np.random.randn(n, k) * t["c1"][d] + t["c0"][d]
+            elif kind == _lib.PRIOR_LOG_UNIFORM:
+                out[..., d] = np.exp(np.random.rand(n, k) * (np.log(t["hi"][d]) - np.log(t["lo"][d])) + np.log(t["lo"][d]))
+            else:
+                out[..., d] = np.random.rand(n, k) * (t["hi"][d] - t["lo"][d]) + t["lo"][d]
+        return out
+
     def _bd_numpy(self, bi):
         """Birth / death on branch ``bi`` with the reference's draws (distgenrj.py:35-222, rj.py:169-352)."""
         eng, tc, R, T, W = self.engine, self.temperature_control, self._random, self.ntemps, self.nwalkers
         _, inds, _, _, betas = eng.download()
         tc.betas = betas
         b = self.branches[bi]
+        if self.mt_moves is not None:
+            # MTDistGenMoveRJ: coins and leaf choices from R; generate_dist.rvs(size=(N, K)) - per parameter, for ALL walkers - and the
+            # one rand(N) of the pick from the global stream (mtdistgenrj.py:68, multipletry.py:57); then R.rand(T, W) (rj.py:332)
+            mv = self.mt_moves[b.name]
+            change, leaf = self._draw_change_leaf(b, inds[b.name])
+            tries = self._draw_mt_tries(eng.mt_gen[bi], T * W, mv.num_try).reshape(T, W, mv.num_try, b.ndim)
+            u_pick = np.random.rand(T * W).reshape(T, W)
+            keep = eng.mt_bd_step(bi, change, leaf, tries, u_pick, R.rand(T, W))
+            mv.accepted += keep
+            mv.num_proposals += 1
+            return keep
         change, leaf, birth = np.zeros((T, W), dtype=np.int64), np.zeros((T, W), dtype=np.int64), np.zeros((T, W, b.ndim))
         if b.nleaves_min != b.nleaves_max:
             change, leaf = self._draw_change_leaf(b, inds[b.name])

@@ -822,6 +822,47 @@ int hens_rj_debug_draws_stretch(hens_ctx* ctx, int64_t iter, uint8_t* labels, in
 int hens_rj_bd_all_step(hens_ctx* ctx, const int8_t* change, const int32_t* leaf, const double* birth, const double* u_acc,
                         uint8_t* keep_out);
 
+/* The multiple-try birth / death move: MTDistGenMoveRJ(generate_dist, num_try = K, rj = True) of the reference (mtdistgenrj.py over
+ * multipletry.py:238-514 - its `elif self.rj` branch - and multipletry.py:597-776) in place of DistributionGenerateRJ.  One branch
+ * per proposal; coin, edge rule and leaf slot are the plain move's.  A birth walker is offered K leaves drawn from the generator
+ * into the free slot, one of them picked by importance weight; a death walker's try 0 IS the dying leaf, tries 1 .. K-1 are fresh
+ * draws into its slot, and the auxiliary side of both is K copies of the walker without the leaf (csrc/hens_rj_mt.h states the
+ * formulas: lsw, pick, aux_lsw, factors).  The multiple-try factors replace the plain move's -+ log q(leaf); edge factors,
+ * fix_logp_gibbs, the accept test and the update are ReversibleJumpMove.propose's (rj.py:236-352).  A try whose walker has a -inf
+ * log-prior is not evaluated (its log-likelihood is the fill value); every weight -inf, or a dying leaf outside the generator's
+ * support, gives NaN sums and a rejection, as in the reference.
+ *
+ * hens_rj_set_mt_proposal: num_try in [1, 64] and the generator's terms per leaf parameter over the branches, in
+ *   hens_rj_set_prior_terms's layout and meaning (kind / lo / hi / c0 / c1 / c2, sum_b ndims[b] entries); kind == NULL: the generator
+ *   is the prior (the other five are not read).  num_try == 0 returns to the plain move.  Refused, the context unchanged:
+ *   num_try outside [0, 64] or an invalid term -> HENS_ERR_INVALID; a branch with nleaves_min == nleaves_max -> HENS_ERR_INVALID
+ *   (multipletry.py:661-664); a model without a device likelihood (hens_rj_set_model_general) -> HENS_ERR_STATE; more than 64 leaf
+ *   slots or 128 record doubles -> HENS_ERR_UNSUPPORTED.  A later hens_rj_set_model* or hens_rj_set_prior_terms call clears it.
+ * hens_rj_mt_bd_step: the move teacher-forced, in the reference's order of operations (every try a full evaluation of the walker's
+ *   active leaves with the try in its slot): change[Tl][W] in {-1, +1}, leaf[Tl][W], tries[Tl][W][K][max(ndims)] (a death walker's
+ *   tries[..][0] is ignored), u_pick, u_acc [Tl][W]; keep_out[Tl][W] or NULL; out NULL, or any of its arrays NULL: pick, lsw,
+ *   aux_lsw, factors (the multiple-try factors, negated on a death, before the edge factors), mt_ll, mt_lp (the proposed state's
+ *   log-likelihood and log-prior before fix_logp_gibbs), each [Tl][W].  Follow it with hens_pt_sweep(adapt = 0), like hens_rj_bd_step.
+ * hens_rj_step / hens_rj_step_chain with a proposal set: the birth / death launch of schedules 0 and 1 is this move (k_rj_mt) on
+ *   the resident templates - try k = base template + leaf k, the base the resident template (birth) or resident - dying leaf
+ *   (death); L after an accepted death is the likelihood of the base.  Schedule 2 ("together") -> HENS_ERR_UNSUPPORTED before
+ *   anything is launched (multipletry.py:635-636); schedule 3 is untouched.  Counters: hens_rj_get_counters.  Draws: coin,
+ *   selector and accept uniform are the plain move's keys; coordinate d of try 0 of a birth is the plain move's birth call, of try
+ *   k >= 1 the call keyed RJ_TRY | d << 8 | k << 10 | branch << 16, turned into a value by hens_rj_set_prior_terms's
+ *   constructions on the generator's terms; the pick uniform: the 53-bit uniform of (x, y) of the call keyed RJ_PICK | branch << 16.
+ * hens_rj_mt_debug_draws: tries [nbranches][Tl][W][K][max(ndims)] (try 0: what a birth walker gets) and u_pick [nbranches][Tl][W]
+ *   of iteration `iter`, entry 0 the chosen branch ("separate_branches") or one entry per branch in order, as hens_rj_debug_draws
+ *   sizes its per-branch outputs - which has the coin, the selector, the accept uniform and the cascades' draws.
+ * hens_rj_propose with a proposal set -> HENS_ERR_UNSUPPORTED. */
+typedef struct hens_rj_mt_out {
+    int32_t* pick; double* lsw; double* aux_lsw; double* factors; double* mt_ll; double* mt_lp;
+} hens_rj_mt_out;
+int hens_rj_set_mt_proposal(hens_ctx* ctx, int32_t num_try, const int32_t* kind, const double* lo, const double* hi, const double* c0,
+                            const double* c1, const double* c2);
+int hens_rj_mt_bd_step(hens_ctx* ctx, int32_t branch, const int8_t* change, const int32_t* leaf, const double* tries,
+                       const double* u_pick, const double* u_acc, uint8_t* keep_out, const hens_rj_mt_out* out);
+int hens_rj_mt_debug_draws(hens_ctx* ctx, int64_t iter, double* tries, double* u_pick);
+
 /* Leaf-packing moves with a HOST-CALLABLE likelihood (round 6).  Replaces, for states of several branches / leaves whose
  * log_like_fn is an arbitrary Python function, the proposal + prior half and the accept + update half of MHMove.propose
  * (mh.py:56-193), ReversibleJumpMove.propose (rj.py:145-388) and RedBlueMove.propose (red_blue.py:103-330); between the two
