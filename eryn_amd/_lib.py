@@ -181,6 +181,9 @@ SIGNATURES = {
     "hens_debug_draws_block": (C.c_int, [_P, C.c_int64, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "hens_set_gibbs": (C.c_int, [_P, C.c_int32, C.c_int32, _P]),
     "hens_gibbs_select": (C.c_int, [_P, C.c_int32, C.c_int32]),
+    "hens_rj_set_gibbs": (C.c_int, [_P, C.c_int32, _P]),
+    "hens_rj_gibbs_select": (C.c_int, [_P, C.c_int32]),
+    "hens_rj_gibbs_debug_draws": (C.c_int, [_P, C.c_int64, C.c_int32, _P, _P]),
     "hens_version": (C.c_char_p, []),
     "hens_device_count": (C.c_int, []),
     "hens_device_pci_bus_id": (C.c_int, [C.c_int32, C.c_char_p, C.c_int32]),

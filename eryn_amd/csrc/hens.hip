@@ -11,7 +11,9 @@
 #include "hens_dist.h"
 #include "hens_mt.h"
 #include "hens_rj_mt.h"
+#include "hens_rj_gibbs.h"
 #include "hens_gibbs_host.h"
+#include "hens_rj_gibbs_host.h"
 #include "hens_chain.h"
 #include "hens_chain_stats.h"
 #include "hens_rj_chain.h"
@@ -266,6 +268,11 @@ struct hens_ctx_impl {
         bool mt_gen_box[RJ_MAX_BRANCH] = {}; double mt_gen_logq[RJ_MAX_BRANCH] = {};      // an all-uniform generator and its constant log-density
         double* mt_tries = nullptr;          // staging of hens_rj_mt_bd_step: the caller's tries [Tl][W][RJ_MT_MAX_TRY x RJ_MAX_ND at most], pick uniforms; the launch's sums
         double* mt_upick = nullptr; double* mt_out = nullptr;
+        // hens_rj_set_gibbs: Gibbs blocks of the in-model Gaussian move over branches and leaf slots - k_rj_gibbs, hens_rj_gibbs.h
+        int gb_n = 0;                        // blocks of the table (0: none)
+        bool gb_whole = false;               // one block, every coordinate true: the move of a context without a table (k_rj's launch)
+        int gb_sel = 0;                      // hens_rj_gibbs_select: the block of the next hens_rj_mh_step
+        uint8_t* gb_tab = nullptr;           // [RJ_GIBBS_MAX_BLOCKS][RJ_MAX_RW at most] the table on the device, rows ind_off apart
     } rj;
 
     // debug / timing
@@ -1911,6 +1918,9 @@ struct RjLaunch {
     // pick uniforms (birth unused); mt_out: RjMtArgs::out
     bool mt = false;
     const double* tries = nullptr; const double* u_pick = nullptr; double* mt_out = nullptr;
+    // the in-model Gaussian move under a Gibbs block table (k_rj_gibbs, hens_rj_set_gibbs) in place of k_rj<RJ_MODE_MH>: blocks [gb0, gb1)
+    bool gibbs = false;
+    int gb0 = 0, gb1 = 0;
 };
 RjLaunch rj_eval() { return RjLaunch{RJ_MODE_EVAL, 0, 0}; }      // every row's templates, log-likelihood and log-prior from its coordinates
 // a Philox move of hens_rj_step: on the resident templates where the model has them, birth / death by difference; `split`: that
@@ -2005,6 +2015,18 @@ int rj_launch(hens_ctx_impl* c, const RjLaunch& l) {
         hipLaunchKernelGGL(a.tm ? k_rj_mt<true> : k_rj_mt<false>, grid, block, 0, c->stream, g);
         const hipError_t em = hipGetLastError();
         if (em != hipSuccess) return fail(c, HENS_ERR_HIP, "k_rj_mt launch failed: %s", hipGetErrorString(em));
+        return HENS_OK;
+    }
+    if (l.gibbs) {                                    // (a model with a device likelihood, the Gaussian move: hens_rj_set_gibbs saw to both)
+        RjGibbsArgs g{};
+        g.A = a; g.btab = c->rj.gb_tab; g.b0 = l.gb0; g.b1 = l.gb1;
+        g.per_branch = (c->rj.wide || c->rj.M.prior_on) ? 0 : 1;      // (the order of k_rj's instantiation for this model)
+        g.chol = (l.draws == RjLaunch::PHILOX && c->rj.have_chol) ? 1 : 0;
+        if (mode != RJ_MODE_MH || (tmm != -1 && tmm != 0) || l.gb0 < 0 || l.gb1 > c->rj.gb_n || l.gb0 >= l.gb1)
+            return fail(c, HENS_ERR_STATE, "k_rj_gibbs: an in-model launch over blocks of the table");
+        hipLaunchKernelGGL(a.tm ? k_rj_gibbs<true> : k_rj_gibbs<false>, grid, block, 0, c->stream, g);
+        const hipError_t eg = hipGetLastError();
+        if (eg != hipSuccess) return fail(c, HENS_ERR_HIP, "k_rj_gibbs launch failed: %s", hipGetErrorString(eg));
         return HENS_OK;
     }
     const bool chol = mode == RJ_MODE_MH && l.draws == RjLaunch::PHILOX && c->rj.have_chol && tmm != -2;
@@ -4107,6 +4129,7 @@ static int rj_set_template_model(hens_ctx_impl* c, int nkinds, int32_t nbranches
     c->rj.general = false;
     c->rj.wide = wide;
     c->rj.mt_K = 0;
+    c->rj.gb_n = 0; c->rj.gb_whole = false; c->rj.gb_sel = 0;      // (a table was laid out on the record that was: hens_rj_set_gibbs anew)
     int r;
     if ((r = rj_push_ctab(c))) return r;
     if (!c->rj.t) {
@@ -4181,6 +4204,7 @@ int hens_rj_set_model_general(hens_ctx* ctx, int32_t nbranches, const int32_t* n
     c->rj.general = true;
     c->rj.wide = false;
     c->rj.mt_K = 0;
+    c->rj.gb_n = 0; c->rj.gb_whole = false; c->rj.gb_sel = 0;
     int r;
     if ((r = rj_push_ctab(c))) return r;
     if (!c->rj.acc_bd) {
@@ -4385,6 +4409,8 @@ static int rj_forced_move(hens_ctx_impl* c, int move, const hens_rj_draws& d, ui
     if ((r = rj_ensure_staging(c))) return r;
     RjLaunch l = rj_forced(c, mode_of[move], propose);
     if ((r = rj_forced_stage(c, move, d, l))) return r;
+    // the move of the selected block (hens_rj_gibbs_select; hens_rj_propose has refused the in-model move under a table)
+    if (move == HENS_RJ_MOVE_MH && c->rj.gb_n > 0 && !c->rj.gb_whole) { l.gibbs = true; l.gb0 = c->rj.gb_sel; l.gb1 = c->rj.gb_sel + 1; }
     c->rj.tm_valid = false;                   // (teacher-forced move: the reference's full evaluation, no resident templates)
     if ((r = rj_launch(c, l))) return r;
     if (propose) c->rj.pending_acc = rj_accept_counter(c, l.mode, l.branch);
@@ -4593,6 +4619,7 @@ int RjStepping::begin(int64_t n_iters) {
     if (c->rj.mt_K > 0 && c->rj.schedule == 2)        // multipletry.py:635-636
         return fail(c, HENS_ERR_UNSUPPORTED, "Can only propose change to one model at a time with MT. (rj schedule \"together\" under hens_rj_set_mt_proposal)");
     if (!stretch && !c->rj.have_scale) return fail(c, HENS_ERR_STATE, "in-model step scale not set (hens_rj_set_mh_scale)");
+    if (stretch && c->rj.gb_n > 0) return fail(c, HENS_ERR_UNSUPPORTED, "Gibbs blocks on leaf-packing records step the Gaussian in-model move");
     if (stretch && !c->cfg.live_dangerously && c->W < 2 * c->rj.M.ind_off)           // red_blue.py:103-114 (every slot of every branch counts)
         return fail(c, HENS_ERR_TOO_FEW_WALKERS, "It is unadvisable to use a red-blue move with fewer walkers than twice the number of dimensions. "
                                                  "If you would like to do this, please set live_dangerously to True.");
@@ -4631,17 +4658,24 @@ int RjStepping::iteration(double* swaps_aside) {
     if (c->rj.tm && c->iter % RJ_REFRESH == RJ_REFRESH - 1 && !fresh && c->rj.tm_drift)
         if ((r = rj_evaluate(c))) return r;
     fresh = false;
-    c->rj.tm_drift = c->rj.tm != nullptr && c->rj.schedule != 3;      // (only birth / death updates a template by +- a leaf)
+    const bool blocks = c->rj.gb_n > 0 && !c->rj.gb_whole;            // (hens_rj_set_gibbs; begin() has refused the stretch move)
+    // (birth / death updates a template by +- a leaf; so does every accepted Gibbs block, on any schedule)
+    c->rj.tm_drift = c->rj.tm != nullptr && (c->rj.schedule != 3 || blocks);
     if (stretch) {
         // red / blue stretch move over every branch and leaf slot: two launches, a half each - the complements of a half
         // belong to the other set, which its launch does not write (red_blue.py:148-323); ONE move (num_mh)
         for (int h = 0; h < 2; ++h)
             if (const RjLaunch half = rj_production(c, RJ_MODE_STRETCH, 0, h); half.ns != 0 && (r = rj_launch(c, half))) return r;
+    } else if (blocks) {
+        // ... block after block of the table (move.py:113-402 under mh.py:79-193): ONE launch walks them all (k_rj_gibbs)
+        RjLaunch l = rj_production(c, RJ_MODE_MH);
+        l.gibbs = true; l.gb0 = 0; l.gb1 = c->rj.gb_n;
+        if ((r = rj_launch(c, l))) return r;
     } else {
         // in-model Gaussian move on the packed leaves (mh.py:56-193)
         if ((r = rj_launch(c, rj_production(c, RJ_MODE_MH)))) return r;
     }
-    c->rj.num_mh += 1;
+    c->rj.num_mh += blocks ? c->rj.gb_n : 1;      // (num_proposals += 1 per block, mh.py:105-193; the device skips no block)
     rj_cascade(c, 2 * c->iter, true);         // swaps + adaptation (mh.py:190-191, red_blue.py:326-328)
     if (c->rj.schedule == 3) {                // no reversible-jump move (EnsembleSampler without rj_moves): counter and keys as ever
         c->iter += 1;
@@ -4954,6 +4988,8 @@ int hens_rj_propose(hens_ctx* ctx, int32_t move, const hens_rj_draws* d, double*
     if (c->rj.accept_pending) return fail(c, HENS_ERR_STATE, "hens_rj_accept must follow hens_rj_propose");
     if (c->rj.mt_K > 0)
         return fail(c, HENS_ERR_UNSUPPORTED, "hens_rj_propose: not under a multiple-try proposal (hens_rj_set_mt_proposal: the tries' likelihoods are the device's)");
+    if (move == HENS_RJ_MOVE_MH && c->rj.gb_n > 0)
+        return fail(c, HENS_ERR_UNSUPPORTED, "Gibbs blocks on leaf-packing records need a device likelihood (hens_rj_set_gibbs(ctx, 0, NULL) clears the table)");
     SETTLE(c, NEED_DEVICE);
     const size_t TW = (size_t)c->Tl * c->W, RW = (size_t)c->rj.M.RW;
     int r;
@@ -5016,6 +5052,8 @@ int hens_rj_set_in_model(hens_ctx* ctx, int32_t kind) {
     if (c->rj.general) return fail(c, HENS_ERR_STATE, "the Philox in-model move belongs to hens_rj_step: template models only");
     if (kind != HENS_RJ_INMODEL_GAUSSIAN && kind != HENS_RJ_INMODEL_STRETCH)
         return fail(c, HENS_ERR_INVALID, "in-model move must be HENS_RJ_INMODEL_GAUSSIAN or HENS_RJ_INMODEL_STRETCH");
+    if (kind == HENS_RJ_INMODEL_STRETCH && c->rj.gb_n > 0)
+        return fail(c, HENS_ERR_UNSUPPORTED, "Gibbs blocks on leaf-packing records step the Gaussian in-model move (hens_rj_set_gibbs(ctx, 0, NULL) clears the table)");
     c->rj.in_model = kind;
     return HENS_OK;
 }
@@ -5118,6 +5156,73 @@ int hens_rj_debug_draws(hens_ctx* ctx, int64_t iter, double* step, double* u_mh,
         for (int k = 0; k < 2; ++k)
             if (const int r = export_pt_draws(c, ds, du, 2 * (uint64_t)iter + (uint64_t)k, k ? slot_bd : slot_mh, k ? uswap_bd : uswap_mh)) return r;
     }
+    return HENS_OK;
+}
+
+// ---- Gibbs blocks over branches and leaf slots for the in-model Gaussian move (include/hipensemble.h; csrc/hens_rj_gibbs.h) --------
+int hens_rj_set_gibbs(hens_ctx* ctx, int32_t nblocks, const uint8_t* mask) {
+    hens_ctx_impl* c = enter(ctx);
+    if (!c) return no_context();
+    if (const int rk = need_rj_context(c)) return rk;
+    if (const int rm = need_rj_model(c)) return rm;
+    if (c->expect_split != 0 || c->propose_pending || c->rj.accept_pending) return fail(c, HENS_ERR_STATE, "a half-step is pending");
+    if (nblocks == 0) { c->rj.gb_n = 0; c->rj.gb_whole = false; c->rj.gb_sel = 0; return HENS_OK; }
+    if (c->rj.general)
+        return fail(c, HENS_ERR_UNSUPPORTED, "Gibbs blocks on leaf-packing records need a device likelihood (this context's model: hens_rj_set_model_general)");
+    if (c->rj.in_model == HENS_RJ_INMODEL_STRETCH)
+        return fail(c, HENS_ERR_UNSUPPORTED, "Gibbs blocks on leaf-packing records step the Gaussian in-model move (hens_rj_set_in_model(HENS_RJ_INMODEL_GAUSSIAN))");
+    const RjModel& M = c->rj.M;
+    int slots = 0;
+    for (int b = 0; b < M.nb; ++b) slots += M.nl[b];
+    if (slots > 64) return fail(c, HENS_ERR_UNSUPPORTED, "Gibbs blocks: %d leaf slots, at most 64 over all branches", slots);
+    if (c->D > RJ_MAX_RW) return fail(c, HENS_ERR_UNSUPPORTED, "Gibbs blocks: record width ndim = %d, at most %d doubles", c->D, RJ_MAX_RW);
+    ParsedRjGibbs p = parse_rj_gibbs(nblocks, mask, M.ind_off);
+    if (p.why[0]) return fail(c, HENS_ERR_INVALID, "hens_rj_set_gibbs: %s", p.why);
+    SETTLE(c, NEED_DEVICE);
+    if (!c->rj.gb_tab)
+        if (const int r = dalloc(c, &c->rj.gb_tab, (size_t)RJ_GIBBS_MAX_BLOCKS * RJ_MAX_RW)) return r;
+    HIPCHK(c, hipMemcpyAsync(c->rj.gb_tab, p.table.data(), p.table.size(), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));          // (the vector goes out of scope; launches in flight have read the old table)
+    c->rj.gb_n = nblocks; c->rj.gb_whole = p.whole; c->rj.gb_sel = 0;
+    return HENS_OK;
+}
+
+// teacher-forced: the block the next hens_rj_mh_step belongs to; between complete moves (hens_gibbs_select's rules)
+int hens_rj_gibbs_select(hens_ctx* ctx, int32_t block) {
+    hens_ctx_impl* c = enter(ctx);
+    if (!c) return no_context();
+    if (const int rk = need_rj_context(c)) return rk;
+    if (c->expect_split != 0 || c->propose_pending || c->rj.accept_pending) return fail(c, HENS_ERR_STATE, "hens_rj_gibbs_select between the half-steps of a move");
+    if (c->rj.gb_n == 0) return fail(c, HENS_ERR_STATE, "no Gibbs table on the in-model move (hens_rj_set_gibbs)");
+    if (block < 0 || block >= c->rj.gb_n) return fail(c, HENS_ERR_INVALID, "block must be in [0, %d)", c->rj.gb_n);
+    c->rj.gb_sel = block;
+    return HENS_OK;
+}
+
+int hens_rj_gibbs_debug_draws(hens_ctx* ctx, int64_t iter, int32_t block, double* step, double* u_mh) {
+    hens_ctx_impl* c = enter(ctx);
+    if (!c || iter < 0) return fail(c, HENS_ERR_INVALID, "null context / negative iteration");
+    if (const int rm = need_rj_model(c)) return rm;
+    if (c->rj.gb_n == 0) return fail(c, HENS_ERR_STATE, "no Gibbs table on the in-model move (hens_rj_set_gibbs)");
+    if (block < 0 || block >= c->rj.gb_n) return fail(c, HENS_ERR_INVALID, "block must be in [0, %d)", c->rj.gb_n);
+    if (!c->rj.have_scale) return fail(c, HENS_ERR_STATE, "in-model step scale not set (hens_rj_set_mh_scale)");
+    if (!step || !u_mh) return fail(c, HENS_ERR_INVALID, "null output");
+    SETTLE(c, NEED_DEVICE);
+    const size_t TW = (size_t)c->Tl * c->W, IO = (size_t)c->rj.M.ind_off;
+    DeviceScratch sc;
+    RjGibbsDebugArgs a{};
+    a.M = c->rj.M;
+    a.step = sc.grab<double>(TW * IO); a.u_mh = sc.grab<double>(TW);
+    if (!a.step || !a.u_mh) return fail(c, HENS_ERR_HIP, "hens_rj_gibbs_debug_draws: out of device memory");
+    a.iter = (uint64_t)iter; a.seed = c->cfg.seed;
+    a.Tl = c->Tl; a.W = c->W; a.rung_begin = c->cfg.rung_begin; a.block = block;
+    a.use_chol = c->rj.have_chol ? 1 : 0;
+    memcpy(a.chol, c->rj.chol, sizeof(a.chol));
+    hipLaunchKernelGGL(k_rj_gibbs_debug_draws, dim3(grid_for((int64_t)TW)), dim3(256), 0, c->stream, a);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(step, a.step, TW * IO * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(u_mh, a.u_mh, TW * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return HENS_OK;
 }
 

@@ -441,6 +441,29 @@ class RJEngine(ChainStoreCalls):
         check(self.lib.hens_rj_set_in_model(self.ctx, code), self.ctx)
         self.in_model = kind
 
+    # -- Gibbs blocks of the in-model Gaussian move (include/hipensemble.h: hens_rj_set_gibbs) -----------------------------------
+    def set_gibbs(self, blocks):
+        """``blocks``: bool / uint8 ``[nblocks, ncoord]`` in record layout (``leaf_gibbs_table``), or None / an empty list: no table."""
+        if blocks is None or len(blocks) == 0:
+            check(self.lib.hens_rj_set_gibbs(self.ctx, 0, None), self.ctx)
+            self.gibbs_nblocks = 0
+            return
+        m = np.ascontiguousarray(np.asarray(blocks) != 0, dtype=np.uint8)
+        if m.ndim != 2 or m.shape[1] != self.ncoord:
+            raise ValueError(f"a Gibbs block table must have shape (nblocks, {self.ncoord})")
+        check(self.lib.hens_rj_set_gibbs(self.ctx, int(m.shape[0]), ptr(m)), self.ctx)
+        self.gibbs_nblocks = int(m.shape[0])
+
+    def gibbs_select(self, block):
+        """The block the next ``mh_step`` belongs to."""
+        check(self.lib.hens_rj_gibbs_select(self.ctx, int(block)), self.ctx)
+
+    def gibbs_debug_draws(self, it, block):
+        """Block ``block``'s in-model draws of iteration ``it`` under ``step``: ``step [T, W, ncoord]`` (record layout) and ``u_mh [T, W]``."""
+        out = dict(step=np.empty((self.T, self.W, self.ncoord)), u_mh=np.empty((self.T, self.W)))
+        check(self.lib.hens_rj_gibbs_debug_draws(self.ctx, int(it), int(block), ptr(out["step"]), ptr(out["u_mh"])), self.ctx)
+        return out
+
     def step(self, n_iters):
         check(self.lib.hens_rj_step(self.ctx, int(n_iters)), self.ctx)
 
@@ -628,8 +651,10 @@ class TemplateLikelihood:
 
 def _no_leaf_gibbs(gibbs_sampling_setup):
     if gibbs_sampling_setup is not None:
-        raise NotImplementedError("gibbs_sampling_setup over leaves and branches is not built: leaf-packing records step every leaf of "
-                                  "every branch in one move (Gibbs blocks: eryn_amd.EnsembleSampler with moves.StretchMove / GaussianMove)")
+        raise NotImplementedError("gibbs_sampling_setup over leaves and branches is not built for this move: it steps every leaf of "
+                                  "every branch of a leaf-packing record in one move (the Gaussian move in blocks over branches and leaf "
+                                  "slots: eryn_amd.rj.GibbsGaussianLeafMove; fixed-dimension Gibbs blocks: eryn_amd.EnsembleSampler with "
+                                  "moves.StretchMove / GaussianMove)")
 
 
 class GaussianLeafMove:
@@ -643,6 +668,100 @@ class GaussianLeafMove:
             if c.ndim != 2 or c.shape[0] != c.shape[1] or not 1 <= c.shape[0] <= 4:
                 raise NotImplementedError("a leaf's proposal covariance must be an ndim x ndim matrix (ndim = 1 .. 4)")
         self.accepted, self.num_proposals = None, 0
+
+
+_GIBBS_TYPES = "gibbs_sampling_setup must be string, dict, tuple, or list."                                 # move.py:125-128
+_GIBBS_ITEM = "If providing a list for gibbs_sampling_setup, each item needs to be a string, tuple, or dict."       # move.py:174-177
+_GIBBS_MASK = ("When inputing gibbs indexing and using a 2-tuple, second item must be None or 2D np.ndarray of shape "
+               "(nleaves_max, ndim).")                                                                                # move.py:120
+
+
+def parse_leaf_gibbs_setup(gibbs_sampling_setup):
+    """``Move._initialize_branch_setup`` (move.py:113-221) for an in-model move: a branch name, ``(name, mask | None)``, ``{name: mask |
+    None, ...}`` (several branches in ONE block), or a list of those -> the blocks in list order, each a list of ``(name, mask |
+    None)`` in the block's own branch order (``branch_names_run_all`` / ``inds_run_all``).  A list inside the list, another type or a
+    mask that is no 2-D array is refused with the reference's ``ValueError``; masks become bool arrays (their shape is the
+    sampler's to check: it knows the branches)."""
+    if type(gibbs_sampling_setup) not in (str, tuple, list, dict):
+        raise ValueError(_GIBBS_TYPES)
+    items = gibbs_sampling_setup if isinstance(gibbs_sampling_setup, list) else [gibbs_sampling_setup]
+
+    def mask_of(v):
+        if v is None:
+            return None
+        if not isinstance(v, np.ndarray) or v.ndim != 2:
+            raise ValueError(_GIBBS_MASK)
+        return v.astype(bool)
+
+    blocks = []
+    for item in items:
+        if isinstance(item, str):
+            blocks.append([(item, None)])
+        elif isinstance(item, tuple):
+            if len(item) != 2 or not isinstance(item[0], str):
+                raise ValueError(_GIBBS_MASK)
+            blocks.append([(item[0], mask_of(item[1]))])
+        elif isinstance(item, dict):
+            if not item or not all(isinstance(k, str) for k in item):
+                raise ValueError(_GIBBS_ITEM)
+            blocks.append([(k, mask_of(v)) for k, v in item.items()])
+        else:
+            raise ValueError(_GIBBS_ITEM)
+    if not blocks:
+        raise ValueError("gibbs_sampling_setup holds no block")
+    return blocks
+
+
+def leaf_gibbs_table(blocks, branches):
+    """The blocks of ``parse_leaf_gibbs_setup`` on the sampler's branches -> ``(table, members)``: ``table`` bool ``[nblocks, ncoord]``
+    in record layout (hens_rj_set_gibbs: branch after branch, slot after slot, the slot's parameters; a branch given by name or with
+    None: every coordinate), ``members`` per block ``{name: bool [nleaves_max]}`` in the block's branch order, the slots with any true
+    coordinate (``ir_keep``, move.py:278).  Refused with a sentence: a branch the sampler has not, a mask of another shape than
+    ``(nleaves_max, ndim)``, a branch whose mask has no true entry (in the reference such a branch takes part in fix_logp_gibbs's count
+    without ever moving; the table has no word for it), more than 128 blocks."""
+    by = {b.name: (bi, b) for bi, b in enumerate(branches)}
+    off = np.cumsum([0] + [b.nleaves_max * b.ndim for b in branches])
+    if len(blocks) > 128:
+        raise ValueError(f"at most 128 Gibbs blocks ({len(blocks)})")
+    table = np.zeros((len(blocks), int(off[-1])), dtype=bool)
+    members = []
+    for k, blk in enumerate(blocks):
+        mem = {}
+        for name, mask in blk:
+            if name not in by:
+                raise ValueError(f"gibbs_sampling_setup names branch {name!r}, which the sampler does not have")
+            if name in mem:
+                raise ValueError(f"gibbs_sampling_setup block {k} names branch {name!r} twice")
+            bi, b = by[name]
+            m = np.ones((b.nleaves_max, b.ndim), dtype=bool) if mask is None else np.asarray(mask, dtype=bool)
+            if m.shape != (b.nleaves_max, b.ndim):
+                raise ValueError(f"gibbs_sampling_setup: the mask of branch {name!r} must have shape {(b.nleaves_max, b.ndim)}, not {m.shape}")
+            if not m.any():
+                raise ValueError(f"gibbs_sampling_setup block {k}: the mask of branch {name!r} has no true entry")
+            table[k, off[bi]:off[bi + 1]] = m.reshape(-1)
+            mem[name] = m.any(axis=-1)
+        members.append(mem)
+    return table, members
+
+
+class GibbsGaussianLeafMove(GaussianLeafMove):
+    """``GaussianMove(cov_all, gibbs_sampling_setup=[...])`` of the reference as the in-model move on leaf-packing records (move.py:
+    113-402 under mh.py:79-193): the Gaussian move block after block over branches and leaf slots.  ``gibbs_sampling_setup``: a
+    branch name, ``(name, mask[nleaves_max, ndim] | None)``, ``{name: mask | None, ...}`` (several branches in one block) or a list
+    of those (``parse_leaf_gibbs_setup``).  Per block the active leaves of its member slots move on their true coordinates; every
+    other coordinate keeps its bits (include/hipensemble.h: hens_rj_set_gibbs).
+
+    ``accepted`` / ``num_proposals`` follow the reference's per-block bookkeeping (mh.py:186-187): + the block's accept mask and + 1
+    per block that ran.  Under ``rng="numpy"`` a block in which no walker of any rung has a leaf to move is skipped before any draw
+    (mh.py:105-107); under ``rng="philox"`` the device walks every block - the walkers of such a block are all rejected - and
+    ``num_proposals`` counts it."""
+
+    def __init__(self, cov_all, gibbs_sampling_setup):
+        if gibbs_sampling_setup is None:
+            raise ValueError("GibbsGaussianLeafMove needs a gibbs_sampling_setup (without blocks the move is GaussianLeafMove)")
+        super().__init__(cov_all)
+        self.gibbs_sampling_setup = gibbs_sampling_setup
+        self.blocks = parse_leaf_gibbs_setup(gibbs_sampling_setup)
 
 
 class StretchLeafMove:
@@ -748,7 +867,9 @@ class RJEnsembleSampler:
         from .backend import RJDeviceBackend
         from .moves.tempering import TemperatureControl
         for m in (moves if isinstance(moves, (list, tuple)) else [moves]):
-            _no_leaf_gibbs(getattr(m[0] if isinstance(m, (list, tuple)) else m, "gibbs_sampling_setup", None))
+            m = m[0] if isinstance(m, (list, tuple)) else m
+            if not isinstance(m, GibbsGaussianLeafMove):
+                _no_leaf_gibbs(getattr(m, "gibbs_sampling_setup", None))
         # backend: None - the stored steps are a list of States (``self.chain``) - or an eryn_amd.backend.RJDeviceBackend: they stay
         # in device memory until somebody reads them (one device call per chain segment, hens_rj_step_chain)
         if backend is not None and not isinstance(backend, RJDeviceBackend):
@@ -768,6 +889,9 @@ class RJEnsembleSampler:
         if isinstance(log_like_fn, CallableLikelihood):
             if rng != "numpy":
                 raise NotImplementedError("a host-callable likelihood steps with rng='numpy' (rng='philox' needs the likelihood on the device)")
+            if isinstance(moves, GibbsGaussianLeafMove):
+                raise NotImplementedError("GibbsGaussianLeafMove updates the walkers' models leaf by leaf on the device: log_like_fn "
+                                          "must be a TemplateLikelihood, not a Python function")
             self.host_like = log_like_fn
             names_ = list(branch_names if branch_names is not None else ndims.keys())
             log_like_fn = TemplateLikelihood({k: "pulse" for k in names_}, None, None, 1.0)     # (never evaluated: no device likelihood)
@@ -780,6 +904,8 @@ class RJEnsembleSampler:
             if self.host_like is not None:
                 raise NotImplementedError("MTDistGenMoveRJ evaluates its tries on the device: log_like_fn must be a TemplateLikelihood")
             rj_moves = "separate_branches"
+        if rj_moves is True:                                 # ensemble.py:413-415: True is "together"
+            rj_moves = "together"
         if rj_moves not in ("separate_branches", "iterate_branches", "together", None, False):
             raise ValueError("When providing a str for rj_moves, must be 'together', 'iterate_branches', or "
                              f"'separate_branches'. Input is {rj_moves}")                # ensemble.py:473-476
@@ -826,6 +952,10 @@ class RJEnsembleSampler:
                                adaptation_time=tc.adaptation_time, stop_adaptation=tc.stop_adaptation,
                                **({"a": moves.a, "live_dangerously": moves.live_dangerously} if isinstance(moves, StretchLeafMove) else {}))
         self.engine.host_like = self.host_like
+        self.gibbs_members = None
+        if isinstance(moves, GibbsGaussianLeafMove):      # the table is pushed once; both rng modes step under it
+            table, self.gibbs_members = leaf_gibbs_table(moves.blocks, self.branches)
+            self.engine.set_gibbs(table)
         if self.rj_schedule is not None or rng == "philox":
             self.engine.set_schedule(rj_moves or "none")
         if self.mt_moves is not None:
@@ -898,6 +1028,25 @@ class RJEnsembleSampler:
                 keep = eng.stretch_split(split, labels, np.stack(rint), u_zz, R.rand(T, Ns))
                 for t in range(T):
                     acc[t, np.flatnonzero(labels[t] == split)] = keep[t]
+        elif self.gibbs_members is not None:
+            # block after block (mh.py:79-187): per branch of the block, in the block's own order, one multivariate_normal over the
+            # active leaves of its member slots in ascending (rung, walker, slot) (gaussian.py:96-108), then the accept uniforms
+            # (mh.py:171); a block without any such leaf is skipped before it draws (mh.py:105-107).  The move's accept mask is
+            # the last block's that ran (zeros if none did, mh.py:77)
+            acc = np.zeros((T, W), dtype=bool)
+            for k, mem in enumerate(self.gibbs_members):
+                x, inds, _, _, _ = eng.download()
+                going = {name: inds[name] & slots[None, None, :] for name, slots in mem.items()}
+                if not any(g.any() for g in going.values()):
+                    continue
+                steps = {b.name: np.zeros(x[b.name].shape) for b in self.branches}
+                for name, g in going.items():
+                    nd = steps[name].shape[-1]
+                    steps[name][g] = 1.0 * R.multivariate_normal(np.zeros(nd), mv.cov[name], size=int(g.sum()))
+                eng.gibbs_select(k)
+                acc = eng.mh_step(steps, R.rand(T, W))
+                mv.accepted += acc
+                mv.num_proposals += 1
         else:
             x, inds, _, _, _ = eng.download()
             # per branch one multivariate_normal over the packed leaves (gaussian.py:96-104, 265-268), the accept uniforms (mh.py:157)
@@ -908,8 +1057,9 @@ class RJEnsembleSampler:
                 s[inds[b.name]] = 1.0 * R.multivariate_normal(np.zeros(b.ndim), mv.cov[b.name], size=n)
                 steps[b.name] = s
             acc = eng.mh_step(steps, R.rand(T, W))
-        mv.accepted += acc
-        mv.num_proposals += 1
+        if self.gibbs_members is None:
+            mv.accepted += acc
+            mv.num_proposals += 1
         iperm, i1perm, u = tc.draw_swap_randoms()                               # mh.py:190-191
         _, swaps = eng.pt_sweep(iperm, i1perm, u, adapt=bool(tc.adaptive))
         tc.swaps_accepted = swaps

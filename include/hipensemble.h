@@ -863,6 +863,41 @@ int hens_rj_mt_bd_step(hens_ctx* ctx, int32_t branch, const int8_t* change, cons
                        const double* u_pick, const double* u_acc, uint8_t* keep_out, const hens_rj_mt_out* out);
 int hens_rj_mt_debug_draws(hens_ctx* ctx, int64_t iter, double* tries, double* u_pick);
 
+/* Gibbs blocks over branches and leaf slots for the in-model Gaussian move of a leaf-packing context: the reference's
+ * GaussianMove(cov, gibbs_sampling_setup=[...]) on a state of several branches and leaves (move.py:113-402 under mh.py:79-193).  A
+ * block is a mask over the record's coordinates; per block, in table order: a leaf slot with any true coordinate is a member
+ * (move.py:278), the ACTIVE leaves of member slots move - q = x + step on their true coordinates, every other coordinate keeps its
+ * bits (move.py:322-324) -, the log-prior is taken over every active leaf, fix_logp_gibbs (move.py:368-402) gives a walker without
+ * a moved leaf -inf (0.0 if it holds no leaf at all), then likelihood, tempered accept test with factors 0 and update; the next
+ * block starts from the state the last one left.  (csrc/hens_rj_gibbs.h states the kernel, k_rj_gibbs.)
+ *
+ * hens_rj_set_gibbs: mask u8 [nblocks][ncoord] in record layout (ncoord = sum_b nleaves_max[b] ndims[b], hens_rj_debug_draws's
+ *   `step` layout), non-zero = the coordinate moves with the block; 1 .. 128 blocks, they may overlap and need not cover every
+ *   coordinate; nblocks == 0 clears the table.  Selects block 0.  Refused, the context unchanged: a block without a true
+ *   coordinate, nblocks outside [0, 128], a null mask (HENS_ERR_INVALID); before a model, or with a half-step pending
+ *   (HENS_ERR_STATE); a model without a device likelihood (hens_rj_set_model_general), the stretch in-model move, more than 64 leaf
+ *   slots (HENS_ERR_UNSUPPORTED) - and, the other way round, hens_rj_set_in_model(HENS_RJ_INMODEL_STRETCH) and hens_rj_propose of
+ *   the in-model move while a table stands (HENS_ERR_UNSUPPORTED).  A later hens_rj_set_model* call clears the table.
+ *   hens_set_gibbs stays closed to leaf-packing contexts.
+ * hens_rj_gibbs_select: the block the next hens_rj_mh_step belongs to - step[Tl][W][ncoord] (read on the moved leaves' true
+ *   coordinates), u_acc, keep_out as ever -, until the next call; HENS_ERR_STATE between the halves of a move or without a table,
+ *   HENS_ERR_INVALID outside [0, nblocks).  The reference skips a block in which no walker of any rung has a moved leaf, before
+ *   any draw (mh.py:105-107): a caller that follows it simply does not call for that block.
+ * hens_rj_step / hens_rj_step_chain with a table: ONE k_rj_gibbs launch walks all blocks of the iteration in place of the k_rj
+ *   in-model launch, on the resident templates: per moved leaf template = (template - leaf_old) + leaf_new per data point, so the
+ *   templates drift by rounding on every schedule (schedule 3 too) and the 64-iteration refresh bounds it as it does for birth /
+ *   death.  DEPARTURE from the reference: the device skips no block - every walker of a block without a moved leaf is rejected by
+ *   fix_logp_gibbs - so num_mh (hens_rj_get_counters) advances by nblocks per iteration, skipped blocks included.  A table of
+ *   exactly one block with every coordinate true is the move of a context without a table: k_rj's launch, the same chain bit for
+ *   bit, num_mh + 1.  Draws: block k's unit normal of record coordinate i is the Philox call keyed RJ_NORMAL(i) | k << 25 (bits
+ *   0 - 24 are the call's of a context without a table), its accept uniform the call keyed RJ_ACC(in-model) | k << 19 (bits 0 - 18
+ *   likewise); block 0's words are those of a context without a table.  Both step setters serve: scale x z, or L z per leaf.
+ * hens_rj_gibbs_debug_draws: block `block`'s step[Tl][W][ncoord] (every coordinate slot's) and u_mh[Tl][W] of iteration `iter`, in
+ *   hens_rj_mh_step's form; birth / death and the cascades: hens_rj_debug_draws. */
+int hens_rj_set_gibbs(hens_ctx* ctx, int32_t nblocks, const uint8_t* mask);
+int hens_rj_gibbs_select(hens_ctx* ctx, int32_t block);
+int hens_rj_gibbs_debug_draws(hens_ctx* ctx, int64_t iter, int32_t block, double* step, double* u_mh);
+
 /* Leaf-packing moves with a HOST-CALLABLE likelihood (round 6).  Replaces, for states of several branches / leaves whose
  * log_like_fn is an arbitrary Python function, the proposal + prior half and the accept + update half of MHMove.propose
  * (mh.py:56-193), ReversibleJumpMove.propose (rj.py:145-388) and RedBlueMove.propose (red_blue.py:103-330); between the two
