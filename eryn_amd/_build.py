@@ -15,7 +15,7 @@ UNITS = [("hens", "hens.hip", [])] + [(f"hens_k_{k}_{part}", f"hens_k_{k}.hip", 
 SOURCES = sorted({os.path.join(SRC_DIR, u[1]) for u in UNITS})
 # what a unit includes, by kind of unit: every unit, hens.hip alone, the kernel units alone (they see neither hens.hip nor the RJ / AQL headers)
 HDRS_ALL = ("hens_kernels.h", "hens_ladder_fold.inc", "hens_iter.h", "hens_tile2.h", "hens_ktable.h", "hens_prior.h", "hens_dist.h", "hens_mt.h", "hens_prior_host.h")
-HDRS_HOST = ("hens_gibbs_host.h", "hens_rj.h", "hens_rj_mt.h", "hens_rj_gibbs.h", "hens_rj_gibbs_host.h", "hens_aql.h", "hens_chain.h", "hens_chain_stats.h", "hens_rj_chain.h", "hens_rj_chain_stats.h", "hens_chain_host.h")
+HDRS_HOST = ("hens_gibbs_host.h", "hens_rj.h", "hens_rj_mt.h", "hens_rj_gibbs.h", "hens_rj_gibbs_host.h", "hens_rj_group.h", "hens_rj_group_host.h", "hens_aql.h", "hens_chain.h", "hens_chain_stats.h", "hens_rj_chain.h", "hens_rj_chain_stats.h", "hens_chain_host.h")
 HDRS_KERNEL = ("hens_ktable.inc",)
 API_HEADER = os.path.join(os.path.dirname(HERE), "include", "hipensemble.h")
 DEPS = SOURCES + [os.path.join(SRC_DIR, h) for h in HDRS_ALL + HDRS_HOST + HDRS_KERNEL] + [API_HEADER]

@@ -40,7 +40,7 @@ class HensTiming(C.Structure):
 
 
 RJ_MOVE_MH, RJ_MOVE_BD, RJ_MOVE_BD_ALL, RJ_MOVE_STRETCH = 0, 1, 2, 3      # include/hipensemble.h: HENS_RJ_MOVE_*
-RJ_INMODEL_GAUSSIAN, RJ_INMODEL_STRETCH = 0, 1                           # include/hipensemble.h: HENS_RJ_INMODEL_*
+RJ_INMODEL_GAUSSIAN, RJ_INMODEL_STRETCH, RJ_INMODEL_GROUP = 0, 1, 2      # include/hipensemble.h: HENS_RJ_INMODEL_*
 
 
 class HensRjDraws(C.Structure):
@@ -184,6 +184,11 @@ SIGNATURES = {
     "hens_rj_set_gibbs": (C.c_int, [_P, C.c_int32, _P]),
     "hens_rj_gibbs_select": (C.c_int, [_P, C.c_int32]),
     "hens_rj_gibbs_debug_draws": (C.c_int, [_P, C.c_int64, C.c_int32, _P, _P]),
+    "hens_rj_set_group": (C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_double]),
+    "hens_rj_group_rebuild": (C.c_int, [_P]),
+    "hens_rj_group_step": (C.c_int, [_P, _P, _P, _P, _P]),
+    "hens_rj_group_debug": (C.c_int, [_P, _P, _P, _P, _P]),
+    "hens_rj_group_debug_draws": (C.c_int, [_P, C.c_int64, _P, _P, _P]),
     "hens_version": (C.c_char_p, []),
     "hens_device_count": (C.c_int, []),
     "hens_device_pci_bus_id": (C.c_int, [C.c_int32, C.c_char_p, C.c_int32]),

@@ -273,6 +273,16 @@ struct hens_ctx_impl {
         bool gb_whole = false;               // one block, every coordinate true: the move of a context without a table (k_rj's launch)
         int gb_sel = 0;                      // hens_rj_gibbs_select: the block of the next hens_rj_mh_step
         uint8_t* gb_tab = nullptr;           // [RJ_GIBBS_MAX_BLOCKS][RJ_MAX_RW at most] the table on the device, rows ind_off apart
+        // hens_rj_set_group: the group stretch move with a stationary friend table - k_rj<RJ_MODE_GROUP>, hens_rj_group.h
+        int gr_nf = 0, gr_update = 0;        // nfriends (0: no group), n_iter_update
+        int64_t gr_m = 0;                    // the move's call number since the last upload / hens_rj_set_group: a rebuild is due at gr_m % gr_update == 0
+        double gr_a = 2.0;                   // its stretch scale
+        int gr_key[RJ_MAX_BRANCH] = {}, gr_koff[RJ_MAX_BRANCH] = {}, gr_nslots = 0;
+        // every buffer of the move, made once by the setter for any model of this context: table and sort scratch [W x 64 entries],
+        // counts, windows and mask snapshots by pool row [2 Tl W], the staging of hens_rj_group_step's picks [Tl W x 64]
+        double *gr_keys = nullptr, *gr_tab = nullptr, *gr_gkey = nullptr;
+        int32_t *gr_cnt = nullptr, *gr_gsrc = nullptr, *gr_start = nullptr, *gr_pick = nullptr;
+        uint32_t* gr_snap = nullptr;
     } rj;
 
     // debug / timing
@@ -1921,6 +1931,7 @@ struct RjLaunch {
     // the in-model Gaussian move under a Gibbs block table (k_rj_gibbs, hens_rj_set_gibbs) in place of k_rj<RJ_MODE_MH>: blocks [gb0, gb1)
     bool gibbs = false;
     int gb0 = 0, gb1 = 0;
+    const int32_t* gr_pick = nullptr;       // RJ_MODE_GROUP, FORCED: the caller's picks (with st_uzz, u_acc)
 };
 RjLaunch rj_eval() { return RjLaunch{RJ_MODE_EVAL, 0, 0}; }      // every row's templates, log-likelihood and log-prior from its coordinates
 // a Philox move of hens_rj_step: on the resident templates where the model has them, birth / death by difference; `split`: that
@@ -1955,6 +1966,7 @@ const RjInst RJ_INSTS[] = {        // (listed in the order the code object has h
     RJ_INST(RJ_MODE_MH, -2, false), RJ_INST(RJ_MODE_BD, -2, false), RJ_INST(RJ_MODE_STRETCH, -2, false), RJ_INST(RJ_MODE_EVAL, -2, false),
     RJ_INST_WIDE(RJ_MODE_EVAL, -1), RJ_INST_WIDE(RJ_MODE_EVAL, 0), RJ_INST_WIDE(RJ_MODE_EVAL, 2), RJ_INST_WIDE(RJ_MODE_MH, -1), RJ_INST_WIDE(RJ_MODE_MH, 0),
     RJ_INST_WIDE(RJ_MODE_BD, -1), RJ_INST_WIDE(RJ_MODE_BD, 1), RJ_INST_WIDE(RJ_MODE_STRETCH, -1), RJ_INST_WIDE(RJ_MODE_STRETCH, 0),
+    RJ_INST(RJ_MODE_GROUP, -1, false), RJ_INST(RJ_MODE_GROUP, 0, false), RJ_INST_WIDE(RJ_MODE_GROUP, -1), RJ_INST_WIDE(RJ_MODE_GROUP, 0),
 };
 #undef RJ_INST
 #undef RJ_INST_WIDE
@@ -1990,6 +2002,15 @@ int rj_launch(hens_ctx_impl* c, const RjLaunch& l) {
         a.st_a = c->cfg.a; a.st_ns = l.ns;
         if (l.draws == RjLaunch::FORCED) { a.st_own = l.st_own; a.st_cw = l.st_cw; a.st_uzz = l.st_uzz; }
         else a.st_hb = l.split | (c->idx_bits << 8);                                              // (Philox, st_own == nullptr)
+    }
+    if (mode == RJ_MODE_GROUP) {                      // (hens_rj_set_group saw to a device likelihood and at most 64 slots)
+        const hens_ctx_impl::Rj& s = c->rj;
+        if (s.gr_nf == 0 || l.propose) return fail(c, HENS_ERR_STATE, "k_rj<RJ_MODE_GROUP>: no group set (hens_rj_set_group)");
+        a.st_a = s.gr_a;
+        a.G.keys = s.gr_keys; a.G.tab = s.gr_tab; a.G.cnt = s.gr_cnt; a.G.start = s.gr_start; a.G.snap = s.gr_snap;
+        a.G.nfriends = s.gr_nf;
+        for (int b = 0; b < RJ_MAX_BRANCH; ++b) { a.G.koff[b] = s.gr_koff[b]; a.G.key[b] = s.gr_key[b]; }
+        if (l.draws == RjLaunch::FORCED) { a.G.pick = l.gr_pick; a.st_uzz = l.st_uzz; }
     }
     const int npr = mode == RJ_MODE_STRETCH ? l.ns : c->W;            // waves per rung
     const dim3 grid((unsigned)((npr + RJ_WAVES - 1) / RJ_WAVES), (unsigned)c->Tl), block(RJ_WAVES * 64);
@@ -2040,6 +2061,41 @@ int rj_launch(hens_ctx_impl* c, const RjLaunch& l) {
     hipLaunchKernelGGL(inst->k, grid, block, 0, c->stream, a);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(c, HENS_ERR_HIP, "k_rj launch failed: %s", hipGetErrorString(e));
+    return HENS_OK;
+}
+
+// ---- the group stretch move's table (hens_rj_set_group; csrc/hens_rj_group.h) ----
+// no group: the in-model move of hens_rj_step falls back to the Gaussian move
+void rj_group_clear(hens_ctx_impl* c) {
+    c->rj.gr_nf = 0; c->rj.gr_m = 0;
+    if (c->rj.in_model == HENS_RJ_INMODEL_GROUP) c->rj.in_model = HENS_RJ_INMODEL_GAUSSIAN;
+}
+// the move's call number restarts, the table is empty and no leaf has a window (all of them are assigned by the rebuild that the
+// first move is due, or - teacher-forced calls without one - as newborn leaves at the head of the next move)
+int rj_group_reset(hens_ctx_impl* c) {
+    const size_t rows = (size_t)2 * c->Tl * c->W;
+    c->rj.gr_m = 0;
+    HIPCHK(c, hipMemsetAsync(c->rj.gr_cnt, 0, RJ_MAX_BRANCH * 4, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->rj.gr_start, 0xff, rows * RJ_GROUP_SLOTS * 4, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->rj.gr_snap, 0, rows * RJ_MAX_BRANCH * 4, c->stream));
+    return HENS_OK;
+}
+// rule 1 and rule 3's "at a rebuild": count / scan / gather, stable sort by rank, every rung's windows - three launches on the
+// context's stream, nothing allocated, nothing read back
+int rj_group_rebuild(hens_ctx_impl* c) {
+    const hens_ctx_impl::Rj& s = c->rj;
+    RjGroupBuildArgs g{};
+    g.pool = c->pool; g.loc = c->loc[c->cur]; g.M = s.M;
+    g.gkey = s.gr_gkey; g.gsrc = s.gr_gsrc; g.keys = s.gr_keys; g.tab = s.gr_tab; g.cnt = s.gr_cnt; g.start = s.gr_start; g.snap = s.gr_snap;
+    int cap = 0;
+    for (int b = 0; b < RJ_MAX_BRANCH; ++b) { g.koff[b] = s.gr_koff[b]; g.key[b] = s.gr_key[b]; }
+    for (int b = 0; b < s.M.nb; ++b) cap = std::max(cap, c->W * s.M.nl[b]);
+    g.Tl = c->Tl; g.W = c->W; g.nfriends = s.gr_nf;
+    hipLaunchKernelGGL(k_rj_group_gather, dim3((unsigned)s.M.nb), dim3(256), 0, c->stream, g);
+    hipLaunchKernelGGL(k_rj_group_rank, dim3((unsigned)((cap + 255) / 256), (unsigned)s.M.nb), dim3(256), 0, c->stream, g);
+    hipLaunchKernelGGL(k_rj_group_windows, dim3(grid_for((int64_t)c->Tl * c->W * RJ_GROUP_SLOTS)), dim3(256), 0, c->stream, g);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(c, HENS_ERR_HIP, "friend table rebuild failed: %s", hipGetErrorString(e));
     return HENS_OK;
 }
 
@@ -2803,6 +2859,8 @@ int hens_upload_state(hens_ctx* ctx, const double* x, const double* logl, const 
     const size_t TW = (size_t)c->Tl * c->W;
     c->cur = 0;
     c->rj.tm_valid = false;
+    if (c->rj.gr_nf > 0)                      // (the group move's call number restarts; no leaf has a window)
+        if (const int rg = rj_group_reset(c)) return rg;
     c->packed = false;
     c->colmode = false;
     c->rows_mixed = false;    // (a failed hens_step call may have left these behind: step_failed)
@@ -4130,6 +4188,7 @@ static int rj_set_template_model(hens_ctx_impl* c, int nkinds, int32_t nbranches
     c->rj.wide = wide;
     c->rj.mt_K = 0;
     c->rj.gb_n = 0; c->rj.gb_whole = false; c->rj.gb_sel = 0;      // (a table was laid out on the record that was: hens_rj_set_gibbs anew)
+    rj_group_clear(c);                                             // (... and so was a friend table: hens_rj_set_group anew)
     int r;
     if ((r = rj_push_ctab(c))) return r;
     if (!c->rj.t) {
@@ -4205,6 +4264,7 @@ int hens_rj_set_model_general(hens_ctx* ctx, int32_t nbranches, const int32_t* n
     c->rj.wide = false;
     c->rj.mt_K = 0;
     c->rj.gb_n = 0; c->rj.gb_whole = false; c->rj.gb_sel = 0;
+    rj_group_clear(c);
     int r;
     if ((r = rj_push_ctab(c))) return r;
     if (!c->rj.acc_bd) {
@@ -4605,7 +4665,7 @@ static int rj_step_bd(hens_ctx_impl* c) {
 namespace {
 struct RjStepping {
     hens_ctx_impl* c;
-    bool stretch = false, fresh = false, armed = false;
+    bool stretch = false, group = false, fresh = false, armed = false;
     explicit RjStepping(hens_ctx_impl* c_) : c(c_) {}
     void finish() { if (armed) { c->rj.defer_adapt = false; flush_adapt(c); armed = false; } }   // the switch off, no adaptation pending ...
     ~RjStepping() { finish(); }                                                                  // ... on every way out
@@ -4616,9 +4676,10 @@ struct RjStepping {
 int RjStepping::begin(int64_t n_iters) {
     int r;
     stretch = c->rj.in_model == HENS_RJ_INMODEL_STRETCH;
+    group = c->rj.in_model == HENS_RJ_INMODEL_GROUP;
     if (c->rj.mt_K > 0 && c->rj.schedule == 2)        // multipletry.py:635-636
         return fail(c, HENS_ERR_UNSUPPORTED, "Can only propose change to one model at a time with MT. (rj schedule \"together\" under hens_rj_set_mt_proposal)");
-    if (!stretch && !c->rj.have_scale) return fail(c, HENS_ERR_STATE, "in-model step scale not set (hens_rj_set_mh_scale)");
+    if (!stretch && !group && !c->rj.have_scale) return fail(c, HENS_ERR_STATE, "in-model step scale not set (hens_rj_set_mh_scale)");
     if (stretch && c->rj.gb_n > 0) return fail(c, HENS_ERR_UNSUPPORTED, "Gibbs blocks on leaf-packing records step the Gaussian in-model move");
     if (stretch && !c->cfg.live_dangerously && c->W < 2 * c->rj.M.ind_off)           // red_blue.py:103-114 (every slot of every branch counts)
         return fail(c, HENS_ERR_TOO_FEW_WALKERS, "It is unadvisable to use a red-blue move with fewer walkers than twice the number of dimensions. "
@@ -4666,6 +4727,12 @@ int RjStepping::iteration(double* swaps_aside) {
         // belong to the other set, which its launch does not write (red_blue.py:148-323); ONE move (num_mh)
         for (int h = 0; h < 2; ++h)
             if (const RjLaunch half = rj_production(c, RJ_MODE_STRETCH, 0, h); half.ns != 0 && (r = rj_launch(c, half))) return r;
+    } else if (group) {
+        // group stretch move toward the stationary friend table (group.py:122-281): the table anew when due, from the state in
+        // front of the move, then ONE launch - a proposal reads no other walker's current state
+        if (c->rj.gr_m % c->rj.gr_update == 0 && (r = rj_group_rebuild(c))) return r;
+        if ((r = rj_launch(c, rj_production(c, RJ_MODE_GROUP)))) return r;
+        c->rj.gr_m += 1;
     } else if (blocks) {
         // ... block after block of the table (move.py:113-402 under mh.py:79-193): ONE launch walks them all (k_rj_gibbs)
         RjLaunch l = rj_production(c, RJ_MODE_MH);
@@ -4990,6 +5057,8 @@ int hens_rj_propose(hens_ctx* ctx, int32_t move, const hens_rj_draws* d, double*
         return fail(c, HENS_ERR_UNSUPPORTED, "hens_rj_propose: not under a multiple-try proposal (hens_rj_set_mt_proposal: the tries' likelihoods are the device's)");
     if (move == HENS_RJ_MOVE_MH && c->rj.gb_n > 0)
         return fail(c, HENS_ERR_UNSUPPORTED, "Gibbs blocks on leaf-packing records need a device likelihood (hens_rj_set_gibbs(ctx, 0, NULL) clears the table)");
+    if ((move == HENS_RJ_MOVE_MH || move == HENS_RJ_MOVE_STRETCH) && c->rj.gr_nf > 0)
+        return fail(c, HENS_ERR_UNSUPPORTED, "hens_rj_propose of the in-model move: not while a group is set (hens_rj_set_group(ctx, 0, ...) clears it)");
     SETTLE(c, NEED_DEVICE);
     const size_t TW = (size_t)c->Tl * c->W, RW = (size_t)c->rj.M.RW;
     int r;
@@ -5050,8 +5119,10 @@ int hens_rj_set_in_model(hens_ctx* ctx, int32_t kind) {
     if (!c) return no_context();
     if (const int rk = need_rj_context(c)) return rk;
     if (c->rj.general) return fail(c, HENS_ERR_STATE, "the Philox in-model move belongs to hens_rj_step: template models only");
-    if (kind != HENS_RJ_INMODEL_GAUSSIAN && kind != HENS_RJ_INMODEL_STRETCH)
-        return fail(c, HENS_ERR_INVALID, "in-model move must be HENS_RJ_INMODEL_GAUSSIAN or HENS_RJ_INMODEL_STRETCH");
+    if (kind != HENS_RJ_INMODEL_GAUSSIAN && kind != HENS_RJ_INMODEL_STRETCH && kind != HENS_RJ_INMODEL_GROUP)
+        return fail(c, HENS_ERR_INVALID, "in-model move must be HENS_RJ_INMODEL_GAUSSIAN, HENS_RJ_INMODEL_STRETCH or HENS_RJ_INMODEL_GROUP");
+    if (kind == HENS_RJ_INMODEL_GROUP && c->rj.gr_nf == 0)
+        return fail(c, HENS_ERR_STATE, "HENS_RJ_INMODEL_GROUP: no group set (hens_rj_set_group first)");
     if (kind == HENS_RJ_INMODEL_STRETCH && c->rj.gb_n > 0)
         return fail(c, HENS_ERR_UNSUPPORTED, "Gibbs blocks on leaf-packing records step the Gaussian in-model move (hens_rj_set_gibbs(ctx, 0, NULL) clears the table)");
     c->rj.in_model = kind;
@@ -5112,7 +5183,7 @@ int hens_rj_debug_draws(hens_ctx* ctx, int64_t iter, double* step, double* u_mh,
     hens_ctx_impl* c = enter(ctx);
     if (!c || iter < 0) return fail(c, HENS_ERR_INVALID, "null context / negative iteration");
     if (const int rm = need_rj_model(c)) return rm;
-    const bool stretch = c->rj.in_model == HENS_RJ_INMODEL_STRETCH;       // (its draws: hens_rj_debug_draws_stretch; step / u_mh are zeros here)
+    const bool stretch = c->rj.in_model != HENS_RJ_INMODEL_GAUSSIAN;      // (its draws: hens_rj_debug_draws_stretch / hens_rj_group_debug_draws; step / u_mh are zeros here)
     if (!stretch && !c->rj.have_scale) return fail(c, HENS_ERR_STATE, "in-model step scale not set (hens_rj_set_mh_scale)");
     if (!step || !u_mh || !branch || !coin || !sel || !birth || !u_bd) return fail(c, HENS_ERR_INVALID, "null output");
     SETTLE(c, NEED_DEVICE);
@@ -5171,6 +5242,8 @@ int hens_rj_set_gibbs(hens_ctx* ctx, int32_t nblocks, const uint8_t* mask) {
         return fail(c, HENS_ERR_UNSUPPORTED, "Gibbs blocks on leaf-packing records need a device likelihood (this context's model: hens_rj_set_model_general)");
     if (c->rj.in_model == HENS_RJ_INMODEL_STRETCH)
         return fail(c, HENS_ERR_UNSUPPORTED, "Gibbs blocks on leaf-packing records step the Gaussian in-model move (hens_rj_set_in_model(HENS_RJ_INMODEL_GAUSSIAN))");
+    if (c->rj.gr_nf > 0)
+        return fail(c, HENS_ERR_UNSUPPORTED, "Gibbs blocks are not built for the group stretch move (hens_rj_set_group(ctx, 0, ...) clears the group)");
     const RjModel& M = c->rj.M;
     int slots = 0;
     for (int b = 0; b < M.nb; ++b) slots += M.nl[b];
@@ -5222,6 +5295,140 @@ int hens_rj_gibbs_debug_draws(hens_ctx* ctx, int64_t iter, int32_t block, double
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(step, a.step, TW * IO * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(u_mh, a.u_mh, TW * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return HENS_OK;
+}
+
+// ---- the group stretch move with a stationary friend table (include/hipensemble.h; csrc/hens_rj_group.h) ---------------------------
+int hens_rj_set_group(hens_ctx* ctx, int32_t nfriends, int32_t n_iter_update, const int32_t* key_dim, double a) {
+    hens_ctx_impl* c = enter(ctx);
+    if (!c) return no_context();
+    if (const int rk = need_rj_context(c)) return rk;
+    if (const int rm = need_rj_model(c)) return rm;
+    if (c->expect_split != 0 || c->propose_pending || c->rj.accept_pending) return fail(c, HENS_ERR_STATE, "a half-step is pending");
+    if (nfriends == 0) { rj_group_clear(c); return HENS_OK; }
+    const RjModel& M = c->rj.M;
+    if (nfriends < 0 || nfriends > RJ_GROUP_MAX_FRIENDS) return fail(c, HENS_ERR_INVALID, "hens_rj_set_group: nfriends must be in [0, %d] (%d)", RJ_GROUP_MAX_FRIENDS, nfriends);
+    if (n_iter_update <= 1 && !(n_iter_update == 1 && c->cfg.live_dangerously))        // group.py:45-46
+        return fail(c, HENS_ERR_INVALID, "n_iter_update must be greather than or equal to 2.");
+    if (!key_dim) return fail(c, HENS_ERR_INVALID, "hens_rj_set_group: null key_dim");
+    if (!(a > 1.0) || !(a < INFINITY)) return fail(c, HENS_ERR_INVALID, "hens_rj_set_group: the stretch scale a must be finite and > 1");
+    if (c->rj.general)
+        return fail(c, HENS_ERR_UNSUPPORTED, "the group stretch move needs a device likelihood (this context's model: hens_rj_set_model_general)");
+    for (int b = 0; b < M.nb; ++b)
+        if (key_dim[b] < 0 || key_dim[b] >= M.nd[b])
+            return fail(c, HENS_ERR_INVALID, "hens_rj_set_group: key_dim[%d] = %d, a leaf of branch %d has parameters 0 .. %d", b, key_dim[b], b, M.nd[b] - 1);
+    int slots = 0;
+    for (int b = 0; b < M.nb; ++b) slots += M.nl[b];
+    if (slots > RJ_GROUP_SLOTS) return fail(c, HENS_ERR_UNSUPPORTED, "group stretch move: %d leaf slots, at most %d over all branches", slots, RJ_GROUP_SLOTS);
+    if (c->D > RJ_MAX_RW) return fail(c, HENS_ERR_UNSUPPORTED, "group stretch move: record width ndim = %d, at most %d doubles", c->D, RJ_MAX_RW);
+    if (c->rj.gb_n > 0)
+        return fail(c, HENS_ERR_UNSUPPORTED, "Gibbs blocks are not built for the group stretch move (hens_rj_set_gibbs(ctx, 0, NULL) clears the table)");
+    const size_t TW = (size_t)c->Tl * c->W, rows = 2 * TW, cap = (size_t)c->W * RJ_GROUP_SLOTS;
+    if (rows >= ((size_t)1 << 25)) return fail(c, HENS_ERR_UNSUPPORTED, "group stretch move: %zu pool rows, fewer than 2^25", rows);
+    SETTLE(c, NEED_DEVICE);
+    hens_ctx_impl::Rj& s = c->rj;
+    if (!s.gr_keys) {
+        int r;
+        if ((r = dalloc(c, &s.gr_keys, cap)) || (r = dalloc(c, &s.gr_tab, cap * RJ_MAX_ND)) || (r = dalloc(c, &s.gr_gkey, cap)) ||
+            (r = dalloc(c, &s.gr_gsrc, cap)) || (r = dalloc(c, &s.gr_cnt, (size_t)RJ_MAX_BRANCH)) ||
+            (r = dalloc(c, &s.gr_start, rows * RJ_GROUP_SLOTS)) || (r = dalloc(c, &s.gr_snap, rows * RJ_MAX_BRANCH)) ||
+            (r = dalloc(c, &s.gr_pick, TW * RJ_GROUP_SLOTS))) {
+            s.gr_keys = nullptr;              // (whatever was made stays with the context until it is destroyed; the next call tries again)
+            return r;
+        }
+    }
+    s.gr_nf = nfriends; s.gr_update = n_iter_update; s.gr_a = a; s.gr_nslots = slots;
+    for (int b = 0, off = 0; b < RJ_MAX_BRANCH; ++b) {
+        s.gr_key[b] = b < M.nb ? key_dim[b] : 0;
+        s.gr_koff[b] = off;
+        if (b < M.nb) off += c->W * M.nl[b];
+    }
+    return rj_group_reset(c);
+}
+
+static int need_rj_group(hens_ctx_impl* c) {
+    return c->rj.gr_nf > 0 ? HENS_OK : fail(c, HENS_ERR_STATE, "no group set (hens_rj_set_group)");
+}
+
+int hens_rj_group_rebuild(hens_ctx* ctx) {
+    hens_ctx_impl* c = enter(ctx);
+    if (const int r = rj_ready(c)) return r;
+    if (const int rg = need_rj_group(c)) return rg;
+    SETTLE(c, NEED_DEVICE | NEED_FIELDS);
+    return rj_group_rebuild(c);
+}
+
+int hens_rj_group_step(hens_ctx* ctx, const int32_t* pick, const double* u_zz, const double* u_acc, uint8_t* keep_out) {
+    hens_ctx_impl* c = enter(ctx);
+    int r = rj_ready(c);
+    if (r) return r;
+    if ((r = need_rj_group(c))) return r;
+    if (!pick || !u_zz || !u_acc) return fail(c, HENS_ERR_INVALID, "hens_rj_group_step: null draws");
+    SETTLE(c, NEED_DEVICE | NEED_FIELDS | NEED_LADDER);
+    if ((r = rj_ensure_staging(c))) return r;
+    const size_t TW = (size_t)c->Tl * c->W;
+    hens_ctx_impl::Rj& s = c->rj;
+    HIPCHK(c, hipMemcpyAsync(s.gr_pick, pick, TW * (size_t)s.gr_nslots * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(s.uzz, u_zz, TW * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(s.u, u_acc, TW * 8, hipMemcpyHostToDevice, c->stream));
+    RjLaunch l{RJ_MODE_GROUP};
+    l.draws = RjLaunch::FORCED; l.u_acc = s.u; l.keep = s.keep; l.st_uzz = s.uzz; l.gr_pick = s.gr_pick;
+    s.tm_valid = false;                       // (teacher-forced move: the reference's full evaluation, no resident templates)
+    if ((r = rj_launch(c, l))) return r;
+    if (keep_out) HIPCHK(c, hipMemcpyAsync(keep_out, s.keep, TW, hipMemcpyDeviceToHost, c->stream));
+    if ((r = check_flags(c, false))) return r;
+    s.num_mh += 1;
+    s.gr_m += 1;
+    if (!has_pt(c)) c->iter += 1;
+    return HENS_OK;
+}
+
+int hens_rj_group_debug(hens_ctx* ctx, int32_t* counts, double* keys, double* tab, int32_t* start) {
+    hens_ctx_impl* c = enter(ctx);
+    if (!c) return no_context();
+    if (const int rm = need_rj_model(c)) return rm;
+    if (const int rg = need_rj_group(c)) return rg;
+    if (!c->have_state) return fail(c, HENS_ERR_STATE, "no state uploaded");
+    SETTLE(c, NEED_DEVICE | NEED_FIELDS);
+    const hens_ctx_impl::Rj& s = c->rj;
+    const size_t TW = (size_t)c->Tl * c->W, cap = (size_t)c->W * s.gr_nslots;
+    if (counts) HIPCHK(c, hipMemcpyAsync(counts, s.gr_cnt, (size_t)s.M.nb * 4, hipMemcpyDeviceToHost, c->stream));
+    if (keys) HIPCHK(c, hipMemcpyAsync(keys, s.gr_keys, cap * 8, hipMemcpyDeviceToHost, c->stream));
+    if (tab) HIPCHK(c, hipMemcpyAsync(tab, s.gr_tab, cap * RJ_MAX_ND * 8, hipMemcpyDeviceToHost, c->stream));
+    DeviceScratch sc;
+    if (start) {
+        int32_t* d = sc.grab<int32_t>(TW * s.gr_nslots);
+        if (!d) return fail(c, HENS_ERR_HIP, "hens_rj_group_debug: out of device memory");
+        hipLaunchKernelGGL(k_rj_group_export, dim3(grid_for((int64_t)TW * s.gr_nslots)), dim3(256), 0, c->stream, s.gr_start, c->loc[c->cur], d, (int64_t)TW, s.gr_nslots);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(start, d, TW * s.gr_nslots * 4, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return HENS_OK;
+}
+
+int hens_rj_group_debug_draws(hens_ctx* ctx, int64_t iter, int32_t* pick, double* u_zz, double* u_acc) {
+    hens_ctx_impl* c = enter(ctx);
+    if (!c || iter < 0) return fail(c, HENS_ERR_INVALID, "null context / negative iteration");
+    if (const int rm = need_rj_model(c)) return rm;
+    if (const int rg = need_rj_group(c)) return rg;
+    if (!pick || !u_zz || !u_acc) return fail(c, HENS_ERR_INVALID, "null output");
+    SETTLE(c, NEED_DEVICE);
+    const hens_ctx_impl::Rj& s = c->rj;
+    const size_t TW = (size_t)c->Tl * c->W;
+    DeviceScratch sc;
+    RjGroupDebugArgs a{};
+    a.M = s.M; a.cnt = s.gr_cnt;
+    a.pick = sc.grab<int32_t>(TW * s.gr_nslots); a.u_zz = sc.grab<double>(TW); a.u_acc = sc.grab<double>(TW);
+    if (!a.pick || !a.u_zz || !a.u_acc) return fail(c, HENS_ERR_HIP, "hens_rj_group_debug_draws: out of device memory");
+    a.iter = (uint64_t)iter; a.seed = c->cfg.seed;
+    a.Tl = c->Tl; a.W = c->W; a.rung_begin = c->cfg.rung_begin; a.nfriends = s.gr_nf;
+    hipLaunchKernelGGL(k_rj_group_debug_draws, dim3(grid_for((int64_t)TW)), dim3(256), 0, c->stream, a);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(pick, a.pick, TW * s.gr_nslots * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(u_zz, a.u_zz, TW * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(u_acc, a.u_acc, TW * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return HENS_OK;
 }

@@ -50,9 +50,10 @@ constexpr int RJ_CTAB_C0 = 7 * RJ_MAX_RW, RJ_CTAB_C1 = 8 * RJ_MAX_RW, RJ_CTAB_C2
 enum { RJ_KIND_PULSE = 0, RJ_KIND_SINE = 1, RJ_KIND_OFFSET = 2, RJ_KIND_RAMP = 3, RJ_KIND_LORENTZ = 4, RJ_KIND_CHIRP = 5, RJ_KIND_BURST = 6,
        RJ_NKINDS = 7 };
 constexpr int RJ_KIND_WIDTH[RJ_NKINDS] = {3, 3, 1, 2, 3, 3, 4};
-enum { RJ_MODE_EVAL = 0, RJ_MODE_MH = 1, RJ_MODE_BD = 2, RJ_MODE_STRETCH = 3 };
+enum { RJ_MODE_EVAL = 0, RJ_MODE_MH = 1, RJ_MODE_BD = 2, RJ_MODE_STRETCH = 3, RJ_MODE_GROUP = 4 };
 enum : uint32_t { PURPOSE_RJ_NORMAL = 20, PURPOSE_RJ_ACC = 21, PURPOSE_RJ_BD = 22, PURPOSE_RJ_BIRTH = 23, PURPOSE_RJ_BRANCH = 24,
-                  PURPOSE_RJ_SPLIT = 25, PURPOSE_RJ_STRETCH = 26 };
+                  PURPOSE_RJ_SPLIT = 25, PURPOSE_RJ_STRETCH = 26,
+                  PURPOSE_RJ_GROUP = 29 };      // (27, 28: hens_rj_mt.h) the group stretch move's picks and zz, hens_rj_group.h
 
 struct RjModel {
     int32_t nb, RW, ndata, ind_off;                 // branches, record width (doubles), data points, offset of the first mask
@@ -66,6 +67,18 @@ struct RjModel {
     // off / 3, 3 for the pulse / sine models; read by the host-likelihood (k_rj<MODE, -2>) and the WIDE instantiations only
     // prior_on: the leaf parameters carry prior terms (hens_rj_set_prior_terms) - the records in RjArgs::ctab rows 7 - 9, leaf_logp unused
     int32_t nd[RJ_MAX_BRANCH], slot0[RJ_MAX_BRANCH], ndmax, prior_on;
+};
+
+// RJ_MODE_GROUP (hens_rj_group.h): the stationary friend table and every leaf's window into it
+struct RjGroup {
+    const double* keys;                 // branch b's sorted keys at [koff[b], koff[b] + cnt[b])
+    const double* tab;                  // the friends' rows, RJ_MAX_ND doubles each, indexed like keys
+    const int32_t* cnt;                 // [RJ_MAX_BRANCH] n_b, on the device: a rebuild crosses no host
+    int32_t* start;                     // [pool rows][64] a leaf slot's window (first table index in its branch), -1: none assigned
+    uint32_t* snap;                     // [pool rows][RJ_MAX_BRANCH] the leaf masks as they stood at the last group move
+    const int32_t* pick;                // teacher-forced: [Tl][W][nslots] friend picks (with RjArgs::st_uzz [Tl][W], u_acc); nullptr: Philox
+    int32_t koff[RJ_MAX_BRANCH], key[RJ_MAX_BRANCH];     // table offset and key parameter of a branch
+    int32_t nfriends;
 };
 
 struct RjArgs {
@@ -124,6 +137,7 @@ struct RjArgs {
     double st_a;                        // stretch scale
     int32_t st_ns;
     int32_t st_hb;                      // production: half that moves | bits of the split permutation << 8
+    RjGroup G;                          // RJ_MODE_GROUP (st_a is its stretch scale too)
 };
 
 // k_adapt's arithmetic (tempering.py:563-596) in one wavefront, T <= 64: lane j owns rung j; same operations in the same order
@@ -324,6 +338,10 @@ __device__ __forceinline__ double rj_leaf_at(const RjLeaf& f, const double t, co
     default: { const double d = t - f.p1, z = d / f.p2; return (f.a * rj_exp_neg(-(z * z), tab)) * cos(f.h * d); }     // burst
     }
 }
+
+}  // namespace hens
+#include "hens_rj_group.h"      // k_rj<RJ_MODE_GROUP>'s proposal phase (needs everything above)
+namespace hens {
 
 #ifndef HENS_RJ_WAVES
 #define HENS_RJ_WAVES 1
@@ -624,6 +642,9 @@ __global__ __launch_bounds__(RJ_WAVES * 64) __attribute__((amdgpu_waves_per_eu(R
         if (lane == 0) q[M.ind_off + B] = (double)mask_of(B);
       }
       factors += edge;
+    } else if constexpr (MODE == RJ_MODE_GROUP) {
+        // every active leaf toward a friend out of the stationary table, one stretch factor for the walker (hens_rj_group.h)
+        factors = rj_group_propose<GEN>(A, lane, gw, wid, cur, q, mk0, mk1, mk2, mk3, u_drawn, u_have);
     }
     RJ_LDS_SYNC();
 

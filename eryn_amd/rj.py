@@ -180,6 +180,8 @@ class RJEngine(ChainStoreCalls):
         self.in_model = "gaussian"   # the in-model move of ``step`` (set_in_model)
         self.host_like = None        # a CallableLikelihood: every parity move = propose on the device, evaluate here, accept on the device
         self.mt_K, self.mt_gen = 0, None     # set_mt_proposal: tries of the multiple-try birth / death move (0: the plain move), its generators
+        self.nslots = sum(b.nleaves_max for b in self.branches)
+        self.group, self.group_m = None, 0   # set_group: (nfriends, n_iter_update, keys, a); the group move's call number since the last upload
         nb = len(self.branches)
         kinds = np.array([b.kind for b in self.branches], dtype=np.int32)
         nlmax = np.array([b.nleaves_max for b in self.branches], dtype=np.int32)
@@ -251,6 +253,7 @@ class RJEngine(ChainStoreCalls):
     # -- state ---------------------------------------------------------------------------------------------------
     def upload(self, x, inds, logl=None, logp=None, betas=None):
         self.eng.upload(self.pack(x, inds), logl, logp, betas)
+        self.group_m = 0                     # (the library restarts the group move's rebuild count at an upload)
 
     def download(self, nan_fill=False):
         rec, L, P, betas = self.eng.download()
@@ -435,9 +438,9 @@ class RJEngine(ChainStoreCalls):
     def set_in_model(self, kind):
         """The in-model move of ``step``: "gaussian" (``set_mh_scale`` / ``set_mh_chol``) or "stretch" (the red / blue stretch move
         with the engine's ``a`` and ``live_dangerously``; include/hipensemble.h: hens_rj_set_in_model)."""
-        code = {"gaussian": _lib.RJ_INMODEL_GAUSSIAN, "stretch": _lib.RJ_INMODEL_STRETCH}.get(kind)
+        code = {"gaussian": _lib.RJ_INMODEL_GAUSSIAN, "stretch": _lib.RJ_INMODEL_STRETCH, "group": _lib.RJ_INMODEL_GROUP}.get(kind)
         if code is None:
-            raise ValueError("in-model move must be 'gaussian' or 'stretch'")
+            raise ValueError("in-model move must be 'gaussian', 'stretch' or 'group' (the last behind set_group)")
         check(self.lib.hens_rj_set_in_model(self.ctx, code), self.ctx)
         self.in_model = kind
 
@@ -463,6 +466,82 @@ class RJEngine(ChainStoreCalls):
         out = dict(step=np.empty((self.T, self.W, self.ncoord)), u_mh=np.empty((self.T, self.W)))
         check(self.lib.hens_rj_gibbs_debug_draws(self.ctx, int(it), int(block), ptr(out["step"]), ptr(out["u_mh"])), self.ctx)
         return out
+
+    # -- the group stretch move with a stationary friend table (include/hipensemble.h: hens_rj_set_group) ----------------------------
+    def set_group(self, nfriends, n_iter_update, key, a=2.0):
+        """``key``: the key parameter of every branch - one int, a list in branch order or ``{branch name: int}``.  ``nfriends == 0``
+        (or None) clears the group.  The rebuild count restarts."""
+        if not nfriends:
+            check(self.lib.hens_rj_set_group(self.ctx, 0, 0, None, 2.0), self.ctx)
+            self.group, self.group_m = None, 0
+            if self.in_model == "group":
+                self.in_model = "gaussian"
+            return
+        if isinstance(key, dict):
+            missing = [b.name for b in self.branches if b.name not in key]
+            if missing:
+                raise ValueError(f"key has no entry for branch {missing[0]}")
+            key = [key[b.name] for b in self.branches]
+        keys = np.ascontiguousarray(np.broadcast_to(np.asarray(key, dtype=np.int32), (len(self.branches),)))
+        check(self.lib.hens_rj_set_group(self.ctx, int(nfriends), int(n_iter_update), ptr(keys), float(a)), self.ctx)
+        self.group, self.group_m = (int(nfriends), int(n_iter_update), keys.copy(), float(a)), 0
+
+    def group_rebuild(self):
+        """The friend table from the cold rung as it stands, and every active leaf's window from its position now."""
+        self.eng.state_epoch += 1
+        check(self.lib.hens_rj_group_rebuild(self.ctx), self.ctx)
+
+    def picks_to_records(self, picks):
+        """{name: pick[T, W, nl]} -> int32 [T, W, nslots], branch after branch."""
+        if not isinstance(picks, dict):
+            p = np.ascontiguousarray(picks, dtype=np.int32)
+        else:
+            p = np.ascontiguousarray(np.concatenate([np.asarray(picks[b.name]).reshape(self.T, self.W, b.nleaves_max) for b in self.branches], axis=-1), dtype=np.int32)
+        if p.shape != (self.T, self.W, self.nslots):
+            raise ValueError(f"picks must have shape {(self.T, self.W, self.nslots)}")
+        return p
+
+    def records_to_slots(self, arr):
+        """[..., nslots] -> {name: [..., nl]}."""
+        out, s0 = {}, 0
+        for b in self.branches:
+            out[b.name] = arr[..., s0:s0 + b.nleaves_max].copy()
+            s0 += b.nleaves_max
+        return out
+
+    def group_step(self, picks, u_zz, u_acc):
+        """The move teacher-forced: picks {name: [T, W, nl]} (read on active leaves: an entry of the leaf's window), u_zz / u_acc
+        [T, W].  Newborn leaves get their windows first; nothing is rebuilt (``group_rebuild``).  Returns the accept mask."""
+        p = self.picks_to_records(picks)
+        uz, ua = f64(u_zz, (self.T, self.W)), f64(u_acc, (self.T, self.W))
+        keep = np.empty((self.T, self.W), dtype=np.uint8)
+        self.eng.state_epoch += 1
+        check(self.lib.hens_rj_group_step(self.ctx, ptr(p), ptr(uz), ptr(ua), ptr(keep)), self.ctx)
+        self.group_m += 1
+        return keep.astype(bool)
+
+    def group_debug(self):
+        """The table and the windows as they stand: ``counts`` int [nbranches]; ``keys`` {name: [n_b]}; ``tab`` {name: [n_b, ndim]};
+        ``start`` {name: int [T, W, nl]} (-1: no window assigned)."""
+        nb = len(self.branches)
+        counts = np.zeros(nb, dtype=np.int32)
+        keys, tab = np.zeros(self.W * self.nslots), np.zeros((self.W * self.nslots, 4))
+        start = np.zeros((self.T, self.W, self.nslots), dtype=np.int32)
+        check(self.lib.hens_rj_group_debug(self.ctx, ptr(counts), ptr(keys), ptr(tab), ptr(start)), self.ctx)
+        out, off = dict(counts=counts, keys={}, tab={}, start=self.records_to_slots(start)), 0
+        for bi, b in enumerate(self.branches):
+            out["keys"][b.name] = keys[off:off + counts[bi]].copy()
+            out["tab"][b.name] = tab[off:off + counts[bi], :b.ndim].copy()
+            off += self.W * b.nleaves_max
+        return out
+
+    def group_debug_draws(self, it):
+        """What ``step`` draws for the group move in iteration ``it``, in ``group_step``'s form: picks {name: [T, W, nl]} (against the
+        table as it stands), u_zz, u_acc [T, W]."""
+        pick = np.zeros((self.T, self.W, self.nslots), dtype=np.int32)
+        u_zz, u_acc = np.empty((self.T, self.W)), np.empty((self.T, self.W))
+        check(self.lib.hens_rj_group_debug_draws(self.ctx, int(it), ptr(pick), ptr(u_zz), ptr(u_acc)), self.ctx)
+        return dict(picks=self.records_to_slots(pick), u_zz=u_zz, u_acc=u_acc)
 
     def step(self, n_iters):
         check(self.lib.hens_rj_step(self.ctx, int(n_iters)), self.ctx)
@@ -776,6 +855,44 @@ class StretchLeafMove:
         self.accepted, self.num_proposals = None, 0
 
 
+class GroupStretchLeafMove:
+    """``GroupStretchMove(nfriends=..., n_iter_update=..., a=...)`` of the reference (moves/group.py:122-281, moves/groupstretch.py:
+    34-120) as the in-model move on leaf-packing records, with ONE friend rule where the reference leaves the rule to a subclass:
+    nearest friends by one key parameter.  Every active leaf is stretched toward a friend, a leaf near it (in ``key``) out of a
+    stationary snapshot of the cold chain that is rebuilt every ``n_iter_update`` moves; one launch per iteration
+    (include/hipensemble.h: hens_rj_set_group; csrc/hens_rj_group.h states the move).
+
+    ``nfriends`` 1 .. 64; ``key`` an int (every branch) or ``{branch: int}``, the leaf parameter that measures nearness;
+    ``n_iter_update`` >= 2, or >= 1 with ``live_dangerously`` (group.py:45-46).
+
+    The friend table is state that a ``State`` does not carry: ``run_mcmc`` restarts the rebuild count, so its first move rebuilds the
+    table from the state it was given, and a chain resumed from a stored ``State`` is the uninterrupted chain only if the resume
+    falls on a rebuild (a multiple of ``n_iter_update`` moves).  Not built: Gibbs blocks for this move, host-callable likelihoods,
+    periodic parameters, more than 64 friends, user-defined friend rules."""
+
+    def __init__(self, nfriends, key, n_iter_update=100, a=2.0, live_dangerously=False, gibbs_sampling_setup=None):
+        if gibbs_sampling_setup is not None:
+            raise NotImplementedError("gibbs_sampling_setup is not built for GroupStretchLeafMove: it stretches every active leaf of every "
+                                      "branch in one move")
+        if isinstance(nfriends, bool) or not isinstance(nfriends, (int, np.integer)) or not 1 <= int(nfriends) <= 64:
+            raise ValueError("nfriends must be an integer in [1, 64]")
+        self.live_dangerously = bool(live_dangerously)
+        if int(n_iter_update) <= 1 and not (self.live_dangerously and int(n_iter_update) == 1):
+            raise ValueError("n_iter_update must be greather than or equal to 2.")             # group.py:45-46
+        if isinstance(key, dict):
+            if not key or not all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) and v >= 0 for v in key.values()):
+                raise ValueError("key must be a non-negative int or {branch name: non-negative int}")
+            self.key = {str(k): int(v) for k, v in key.items()}
+        elif isinstance(key, (int, np.integer)) and not isinstance(key, bool) and key >= 0:
+            self.key = int(key)
+        else:
+            raise ValueError("key must be a non-negative int or {branch name: non-negative int}")
+        if not float(a) > 1.0 or not np.isfinite(a):
+            raise ValueError("the stretch scale a must be finite and > 1")
+        self.nfriends, self.n_iter_update, self.a = int(nfriends), int(n_iter_update), float(a)
+        self.accepted, self.num_proposals = None, 0
+
+
 class MTDistGenMoveRJ:
     """``MTDistGenMoveRJ(generate_dist, num_try=25, rj=True)`` of the reference (mtdistgenrj.py over multipletry.py:238-514, 597-776)
     as the between-model move of ``RJEnsembleSampler(rj_moves=...)``: per walker ``num_try`` (1 .. 64) candidate leaves from
@@ -892,6 +1009,9 @@ class RJEnsembleSampler:
             if isinstance(moves, GibbsGaussianLeafMove):
                 raise NotImplementedError("GibbsGaussianLeafMove updates the walkers' models leaf by leaf on the device: log_like_fn "
                                           "must be a TemplateLikelihood, not a Python function")
+            if isinstance(moves, GroupStretchLeafMove):
+                raise NotImplementedError("GroupStretchLeafMove evaluates its proposals on the device: log_like_fn must be a "
+                                          "TemplateLikelihood, not a Python function")
             self.host_like = log_like_fn
             names_ = list(branch_names if branch_names is not None else ndims.keys())
             log_like_fn = TemplateLikelihood({k: "pulse" for k in names_}, None, None, 1.0)     # (never evaluated: no device likelihood)
@@ -910,8 +1030,8 @@ class RJEnsembleSampler:
             raise ValueError("When providing a str for rj_moves, must be 'together', 'iterate_branches', or "
                              f"'separate_branches'. Input is {rj_moves}")                # ensemble.py:473-476
         self.rj_schedule = rj_moves or None                  # None: no reversible jump - the leaf masks never change
-        if not isinstance(moves, (GaussianLeafMove, StretchLeafMove)):
-            raise NotImplementedError("the in-model move must be an eryn_amd.rj.GaussianLeafMove or StretchLeafMove")
+        if not isinstance(moves, (GaussianLeafMove, StretchLeafMove, GroupStretchLeafMove)):
+            raise NotImplementedError("the in-model move must be an eryn_amd.rj.GaussianLeafMove, StretchLeafMove or GroupStretchLeafMove")
         if rng not in ("numpy", "philox"):
             raise ValueError("rng must be 'numpy' or 'philox'")
         self.branch_names = list(branch_names if branch_names is not None else ndims.keys())
@@ -950,12 +1070,22 @@ class RJEnsembleSampler:
         self.engine = RJEngine(self.ntemps, self.nwalkers, self.branches, log_like_fn.t, log_like_fn.y, log_like_fn.sigma,
                                seed=seed, device_id=device_id, adaptive=tc.adaptive, adaptation_lag=tc.adaptation_lag,
                                adaptation_time=tc.adaptation_time, stop_adaptation=tc.stop_adaptation,
-                               **({"a": moves.a, "live_dangerously": moves.live_dangerously} if isinstance(moves, StretchLeafMove) else {}))
+                               **({"a": moves.a, "live_dangerously": moves.live_dangerously} if isinstance(moves, (StretchLeafMove, GroupStretchLeafMove)) else {}))
         self.engine.host_like = self.host_like
         self.gibbs_members = None
         if isinstance(moves, GibbsGaussianLeafMove):      # the table is pushed once; both rng modes step under it
             table, self.gibbs_members = leaf_gibbs_table(moves.blocks, self.branches)
             self.engine.set_gibbs(table)
+        if isinstance(moves, GroupStretchLeafMove):       # the friend table's buffers are made once; both rng modes step under it
+            if isinstance(moves.key, dict):
+                for k in self.branch_names:
+                    if k not in moves.key:
+                        raise ValueError(f"GroupStretchLeafMove: key has no entry for branch {k}")
+            for b in self.branches:
+                kb = moves.key[b.name] if isinstance(moves.key, dict) else moves.key
+                if kb >= b.ndim:
+                    raise ValueError(f"GroupStretchLeafMove: key {kb} of branch {b.name}, whose leaves have parameters 0 .. {b.ndim - 1}")
+            self.engine.set_group(moves.nfriends, moves.n_iter_update, moves.key, moves.a)
         if self.rj_schedule is not None or rng == "philox":
             self.engine.set_schedule(rj_moves or "none")
         if self.mt_moves is not None:
@@ -965,6 +1095,8 @@ class RJEnsembleSampler:
                                         {k: self.mt_moves[k].generate_dist[k] for k in self.branch_names})
         if rng == "philox" and isinstance(moves, StretchLeafMove):
             self.engine.set_in_model("stretch")
+        elif rng == "philox" and isinstance(moves, GroupStretchLeafMove):
+            self.engine.set_in_model("group")
         elif rng == "philox":
             # axis-aligned steps (hens_rj_set_mh_scale: three standard deviations per branch), or - a covariance with off-diagonal
             # terms - the Cholesky factor of every branch's leaf covariance (hens_rj_set_mh_chol: step = L z)
@@ -1028,6 +1160,24 @@ class RJEnsembleSampler:
                 keep = eng.stretch_split(split, labels, np.stack(rint), u_zz, R.rand(T, Ns))
                 for t in range(T):
                     acc[t, np.flatnonzero(labels[t] == split)] = keep[t]
+        elif isinstance(mv, GroupStretchLeafMove):
+            # the group stretch move (group.py:122-281): the table anew when due, from the state in front of the move; per branch in
+            # order the friends' picks from the GLOBAL stream over the active leaves in ascending (rung, walker, slot) (skipped where
+            # the branch's table is empty), behind branch 0 the walkers' zz uniforms from R (stretch.py:128-132), then the accept
+            # uniforms (group.py:254)
+            if eng.group_m % mv.n_iter_update == 0:
+                eng.group_rebuild()
+            _, inds, _, _, _ = eng.download()
+            counts = eng.group_debug()["counts"]
+            picks, u_zz = {}, None
+            for bi, b in enumerate(self.branches):
+                nf = min(mv.nfriends, int(counts[bi]))
+                picks[b.name] = np.zeros(inds[b.name].shape, dtype=np.int32)
+                if nf > 0:
+                    picks[b.name][inds[b.name]] = np.random.randint(nf, size=int(inds[b.name].sum()))
+                if bi == 0:
+                    u_zz = R.rand(T, W)
+            acc = eng.group_step(picks, u_zz, R.rand(T, W))
         elif self.gibbs_members is not None:
             # block after block (mh.py:79-187): per branch of the block, in the block's own order, one multivariate_normal over the
             # active leaves of its member slots in ascending (rung, walker, slot) (gaussian.py:96-108), then the accept uniforms

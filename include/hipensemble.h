@@ -805,10 +805,12 @@ int hens_rj_set_schedule(hens_ctx* ctx, int32_t schedule);
  *      uniform balanced labelling) -; branch b's complement is a uniform position of the other half (stretch.py:93-100, 205: a
  *      walker per branch), the stretch factor's uniform comes with branch 0's call (stretch.py:128-132), the accept uniform has
  *      the half in its key (red_blue.py:294).  Accept counts: hens_get_counters; hens_rj_get_counters' num_mh counts one per move.
+ *   HENS_RJ_INMODEL_GROUP               the group stretch move toward a stationary friend table (hens_rj_set_group below, which
+ *      must come first: HENS_ERR_STATE otherwise): one launch per iteration, the table rebuilt every n_iter_update moves.
  * Schedule 3 of hens_rj_set_schedule ("none") runs the in-model move and its cascade with adaptation alone - EnsembleSampler
  * without rj_moves: the leaf masks never change, num_bd stays 0; the iteration counter and the cascade's key 2 iter are those of
  * the other schedules, so a chain's in-model draws do not depend on the schedule. */
-enum { HENS_RJ_INMODEL_GAUSSIAN = 0, HENS_RJ_INMODEL_STRETCH = 1 };
+enum { HENS_RJ_INMODEL_GAUSSIAN = 0, HENS_RJ_INMODEL_STRETCH = 1, HENS_RJ_INMODEL_GROUP = 2 };
 int hens_rj_set_in_model(hens_ctx* ctx, int32_t kind);
 
 /* Debug / parity: the stretch move's draws of iteration `iter` IN THE FORM hens_rj_stretch_split TAKES, n0 = ceil(W / 2):
@@ -897,6 +899,41 @@ int hens_rj_mt_debug_draws(hens_ctx* ctx, int64_t iter, double* tries, double* u
 int hens_rj_set_gibbs(hens_ctx* ctx, int32_t nblocks, const uint8_t* mask);
 int hens_rj_gibbs_select(hens_ctx* ctx, int32_t block);
 int hens_rj_gibbs_debug_draws(hens_ctx* ctx, int64_t iter, int32_t block, double* step, double* u_mh);
+
+/* The group stretch move with a stationary friend table on leaf-packing records: the reference's GroupStretchMove (moves/group.py:
+ * 122-281, moves/groupstretch.py:34-120) with ONE friend rule, nearest friends by one key parameter per branch (the reference leaves
+ * the rule to the user; its own test uses this one).  csrc/hens_rj_group.h states the move in full; in short: the friend table holds,
+ * per branch, the active leaves of the cold rung sorted stably by their key parameter; every active leaf of every rung owns a WINDOW
+ * of nf = min(nfriends, table entries) contiguous entries around its key (assigned at a rebuild or, for a leaf born since, at the
+ * head of the next move; it stays with the leaf, travels with the walker through the swaps and is dropped when the leaf dies); the
+ * move stretches every active leaf toward one entry of its window picked uniformly, one stretch factor zz per walker,
+ * q = c - (c - x) zz, factors = (ncoord - 1) log zz, all rungs and walkers in one proposal.
+ *
+ * hens_rj_set_group: nfriends 1 .. 64 (0 clears the group and returns the in-model move of hens_rj_step to the Gaussian one);
+ *   n_iter_update >= 2, or >= 1 on a context with live_dangerously (group.py:45-46); key_dim[nbranches], the key parameter of every
+ *   branch; a, the stretch scale (> 1).  Every buffer of the move is made here, none per rebuild.  The move's call number restarts
+ *   at 0 - so the next hens_rj_step rebuilds the table first - here and at every hens_upload_state; a hens_rj_set_model* call clears
+ *   the group.  Refused, the context unchanged: arguments out of range (HENS_ERR_INVALID); before a model, or with a half-step pending
+ *   (HENS_ERR_STATE); a model without a device likelihood (hens_rj_set_model_general), more than 64 leaf slots, a Gibbs table
+ *   standing (HENS_ERR_UNSUPPORTED) - and, the other way round, hens_rj_set_gibbs and hens_rj_propose of the in-model move while a
+ *   group is set.  The table is state that hens_download_state does not carry: a chain resumed in a new context is the uninterrupted
+ *   chain only if the resume falls on a rebuild.
+ * hens_rj_group_rebuild: the table from the cold rung as it stands, and every active leaf's window from its position now.
+ * hens_rj_group_step: the move teacher-forced, parity order of operations: pick i32 [Tl][W][nslots] (nslots = sum_b nleaves_max[b];
+ *   read on active leaves, an entry of the leaf's window in [0, nf): values outside are clamped), u_zz / u_acc [Tl][W], keep_out
+ *   u8 [Tl][W] or NULL.  It fixes the newborn leaves' windows first and does NOT rebuild: the caller keeps the schedule
+ *   (hens_rj_group_rebuild) and follows it with hens_pt_sweep.
+ * hens_rj_group_debug: the table and the windows as they stand, any of them NULL: counts i32 [nbranches]; keys [W nslots], branch
+ *   b's at offset W sum_{b' < b} nleaves_max[b']; tab [W nslots][4], rows indexed like keys (zeros behind a leaf's width); start i32
+ *   [Tl][W][nslots], the first table entry of a slot's window within its branch, -1 where none is assigned.
+ * hens_rj_group_debug_draws: what hens_rj_step draws for the move in iteration `iter`, in hens_rj_group_step's form; the picks are
+ *   taken against the table as it stands (rj_pick(word, nf); 0 where nf == 0).  Keys: slot s's pick is word x of the Philox call
+ *   keyed RJ_GROUP (29) | s << 8, zz's uniform the call keyed RJ_GROUP | 64 << 8, the accept uniform RJ_ACC | 4 << 8. */
+int hens_rj_set_group(hens_ctx* ctx, int32_t nfriends, int32_t n_iter_update, const int32_t* key_dim, double a);
+int hens_rj_group_rebuild(hens_ctx* ctx);
+int hens_rj_group_step(hens_ctx* ctx, const int32_t* pick, const double* u_zz, const double* u_acc, uint8_t* keep_out);
+int hens_rj_group_debug(hens_ctx* ctx, int32_t* counts, double* keys, double* tab, int32_t* start);
+int hens_rj_group_debug_draws(hens_ctx* ctx, int64_t iter, int32_t* pick, double* u_zz, double* u_acc);
 
 /* Leaf-packing moves with a HOST-CALLABLE likelihood (round 6).  Replaces, for states of several branches / leaves whose
  * log_like_fn is an arbitrary Python function, the proposal + prior half and the accept + update half of MHMove.propose
