@@ -156,6 +156,7 @@ SIGNATURES = {
     "hens_rj_set_model_kinds": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, _P, C.c_int32, _P, _P, C.c_double]),
     "hens_rj_set_mh_scale": (C.c_int, [_P, _P]),
     "hens_rj_set_mh_chol": (C.c_int, [_P, _P]),
+    "hens_rj_set_periodic": (C.c_int, [_P, _P]),
     "hens_rj_set_prior_terms": (C.c_int, [_P, _P, _P, _P, _P, _P, _P]),
     "hens_rj_mh_step": (C.c_int, [_P, _P, _P, _P]),
     "hens_rj_bd_step": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P]),

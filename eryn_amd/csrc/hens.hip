@@ -283,6 +283,9 @@ struct hens_ctx_impl {
         double *gr_keys = nullptr, *gr_tab = nullptr, *gr_gkey = nullptr;
         int32_t *gr_cnt = nullptr, *gr_gsrc = nullptr, *gr_start = nullptr, *gr_pick = nullptr;
         uint32_t* gr_snap = nullptr;
+        // hens_rj_set_periodic: a branch's period per leaf parameter (0: not periodic) - RjArgs::ctab's period row, RjArgs::per_on
+        double period[RJ_MAX_BRANCH][RJ_MAX_ND] = {};
+        bool per_on = false;
     } rj;
 
     // debug / timing
@@ -1894,6 +1897,7 @@ int rj_push_ctab(hens_ctx_impl* c) {
                 const int i = M.off[b] + n * M.nd[b] + d;
                 tab[RJ_CTAB_LO + i] = M.lo[b][d]; tab[RJ_CTAB_HI + i] = M.hi[b][d];
                 tab[RJ_CTAB_SCALE + i] = M.mh_scale[b][d]; tab[RJ_CTAB_LOGP + i] = M.leaf_logp[b];
+                tab[RJ_CTAB_PERIOD + i] = c->rj.per_on ? c->rj.period[b][d] : 0.0;
                 if (c->rj.have_chol && d < RJ_ND)
                     for (int j = 0; j < RJ_ND; ++j) tab[RJ_CTAB_CHOL + j * RJ_MAX_RW + i] = c->rj.chol[b][d][j];
                 bn[i] = b | (n << 4) | (d << 10) | (M.kind[b] << 12) | ((M.slot0[b] + n) << 16);
@@ -1956,9 +1960,11 @@ uint32_t* rj_accept_counter(const hens_ctx_impl* c, int mode, int branch) {
 }
 // k_rj's instantiations: (mode, template scheme or -1 none / -2 proposal half or log-prior alone, Philox in-model move that forms L z,
 // a model with leaf kinds beyond pulse / sine)
-struct RjInst { int mode, tmm; bool chol, wide; void (*k)(const RjArgs); };
-#define RJ_INST(MODE_, TMM_, CHOL_) {MODE_, TMM_, CHOL_, false, k_rj<MODE_, TMM_, CHOL_>}
-#define RJ_INST_WIDE(MODE_, TMM_) {MODE_, TMM_, false, true, k_rj<MODE_, TMM_, false, true>}
+// ... , the stretch half-step under periodic leaf parameters: hens_rj_set_periodic)
+struct RjInst { int mode, tmm; bool chol, wide, per; void (*k)(const RjArgs); };
+#define RJ_INST(MODE_, TMM_, CHOL_) {MODE_, TMM_, CHOL_, false, false, k_rj<MODE_, TMM_, CHOL_>}
+#define RJ_INST_WIDE(MODE_, TMM_) {MODE_, TMM_, false, true, false, k_rj<MODE_, TMM_, false, true>}
+#define RJ_INST_PER(TMM_, WIDE_) {RJ_MODE_STRETCH, TMM_, false, WIDE_, true, k_rj<RJ_MODE_STRETCH, TMM_, false, WIDE_, true>}
 const RjInst RJ_INSTS[] = {        // (listed in the order the code object has had them since they were an if-chain)
     RJ_INST(RJ_MODE_MH, 0, true), RJ_INST(RJ_MODE_MH, -1, true), RJ_INST(RJ_MODE_EVAL, -1, false), RJ_INST(RJ_MODE_EVAL, 0, false), RJ_INST(RJ_MODE_EVAL, 2, false),
     RJ_INST(RJ_MODE_MH, -1, false), RJ_INST(RJ_MODE_MH, 0, false), RJ_INST(RJ_MODE_BD, -1, false), RJ_INST(RJ_MODE_BD, 1, false),
@@ -1967,7 +1973,9 @@ const RjInst RJ_INSTS[] = {        // (listed in the order the code object has h
     RJ_INST_WIDE(RJ_MODE_EVAL, -1), RJ_INST_WIDE(RJ_MODE_EVAL, 0), RJ_INST_WIDE(RJ_MODE_EVAL, 2), RJ_INST_WIDE(RJ_MODE_MH, -1), RJ_INST_WIDE(RJ_MODE_MH, 0),
     RJ_INST_WIDE(RJ_MODE_BD, -1), RJ_INST_WIDE(RJ_MODE_BD, 1), RJ_INST_WIDE(RJ_MODE_STRETCH, -1), RJ_INST_WIDE(RJ_MODE_STRETCH, 0),
     RJ_INST(RJ_MODE_GROUP, -1, false), RJ_INST(RJ_MODE_GROUP, 0, false), RJ_INST_WIDE(RJ_MODE_GROUP, -1), RJ_INST_WIDE(RJ_MODE_GROUP, 0),
+    RJ_INST_PER(-1, false), RJ_INST_PER(0, false), RJ_INST_PER(-2, false), RJ_INST_PER(-1, true), RJ_INST_PER(0, true),
 };
+#undef RJ_INST_PER
 #undef RJ_INST
 #undef RJ_INST_WIDE
 
@@ -1984,6 +1992,7 @@ int rj_launch(hens_ctx_impl* c, const RjLaunch& l) {
     a.step = l.step; a.change = l.change; a.leaf = l.leaf; a.birth = l.birth; a.u_acc = l.u_acc;
     a.flags = c->flags; a.fill = c->cfg.fill_value; a.iter = c->iter; a.seed = c->cfg.seed;
     a.M = c->rj.M;
+    a.per_on = c->rj.per_on ? 1 : 0;
     a.Tl = c->Tl; a.W = c->W; a.rung_begin = c->cfg.rung_begin; a.tempered = c->cfg.tempered; a.mode = mode; a.branch = l.branch;
     if (c->adapt_pending) {
         // the adaptation behind the last cascade: inside this launch (production launches that test against the ladder, up to 64
@@ -2054,9 +2063,10 @@ int rj_launch(hens_ctx_impl* c, const RjLaunch& l) {
     // (the proposal half of a host-callable move has the widths at run time already; a model under prior terms - pulses and sines
     //  too - takes the WIDE instantiations, whose per-point leaf values serve every kind: the box instantiations carry no terms)
     const bool wide = (c->rj.wide || c->rj.M.prior_on) && tmm != -2;
+    const bool per = mode == RJ_MODE_STRETCH && c->rj.per_on;
     const RjInst* inst = nullptr;
     for (const RjInst& i : RJ_INSTS)
-        if (i.mode == mode && i.tmm == tmm && i.chol == chol && i.wide == wide) inst = &i;
+        if (i.mode == mode && i.tmm == tmm && i.chol == chol && i.wide == wide && i.per == per) inst = &i;
     if (!inst) return fail(c, HENS_ERR_INVALID, "k_rj: no instantiation for mode %d with template scheme %d", mode, tmm);
     hipLaunchKernelGGL(inst->k, grid, block, 0, c->stream, a);
     const hipError_t e = hipGetLastError();
@@ -4189,6 +4199,7 @@ static int rj_set_template_model(hens_ctx_impl* c, int nkinds, int32_t nbranches
     c->rj.mt_K = 0;
     c->rj.gb_n = 0; c->rj.gb_whole = false; c->rj.gb_sel = 0;      // (a table was laid out on the record that was: hens_rj_set_gibbs anew)
     rj_group_clear(c);                                             // (... and so was a friend table: hens_rj_set_group anew)
+    c->rj.per_on = false; memset(c->rj.period, 0, sizeof(c->rj.period));        // (... and the periods: hens_rj_set_periodic anew)
     int r;
     if ((r = rj_push_ctab(c))) return r;
     if (!c->rj.t) {
@@ -4265,6 +4276,7 @@ int hens_rj_set_model_general(hens_ctx* ctx, int32_t nbranches, const int32_t* n
     c->rj.mt_K = 0;
     c->rj.gb_n = 0; c->rj.gb_whole = false; c->rj.gb_sel = 0;
     rj_group_clear(c);
+    c->rj.per_on = false; memset(c->rj.period, 0, sizeof(c->rj.period));
     int r;
     if ((r = rj_push_ctab(c))) return r;
     if (!c->rj.acc_bd) {
@@ -4368,6 +4380,40 @@ int hens_rj_set_prior_terms(hens_ctx* ctx, const int32_t* kind, const double* lo
     if (const int r = rj_push_ctab(c)) { c->rj.M = before; return r; }
     c->rj.tm_valid = false;
     c->rj.mt_K = 0;                            // (a multiple-try proposal was set against the prior that was: hens_rj_set_mt_proposal anew)
+    return HENS_OK;
+}
+
+// Periodic leaf parameters (include/hipensemble.h): period[nbranches][ndmax] in the birth arrays' stride, 0 = not periodic; NULL or all
+// zeros clears.  The periods live in the context beside the model and are folded into RjArgs::ctab's period row by rj_push_ctab, which
+// every setter that rebuilds the table goes through - so they survive hens_rj_set_mh_scale / _chol / _prior_terms / _gibbs / _group in
+// any order, and a new model (hens_rj_set_model*) drops them.
+int hens_rj_set_periodic(hens_ctx* ctx, const double* period) {
+    hens_ctx_impl* c = enter(ctx);
+    if (!c) return no_context();
+    if (!is_rj(c)) return fail(c, HENS_ERR_UNSUPPORTED, "hens_rj_set_periodic needs a leaf-packing context (HENS_LIKE_TEMPLATE); hens_set_periodic serves the others");
+    if (const int rm = need_rj_model(c)) return rm;
+    if (c->rj.accept_pending) return fail(c, HENS_ERR_STATE, "hens_rj_accept must follow hens_rj_propose");       // (first: a proposed half-step is both)
+    if (c->expect_split != 0 || c->propose_pending) return fail(c, HENS_ERR_STATE, "hens_rj_set_periodic between the half-steps of a move");
+    const RjModel& M = c->rj.M;
+    double per[RJ_MAX_BRANCH][RJ_MAX_ND] = {};
+    bool any = false;
+    if (period)
+        for (int b = 0; b < M.nb; ++b)
+            for (int d = 0; d < M.ndmax; ++d) {
+                const double v = period[b * M.ndmax + d];
+                if (!(v >= 0.0) || !(v < INFINITY)) return fail(c, HENS_ERR_INVALID, "hens_rj_set_periodic: period of branch %d, parameter %d must be finite and >= 0", b, d);
+                if (v > 0.0 && d >= M.nd[b])
+                    return fail(c, HENS_ERR_INVALID, "hens_rj_set_periodic: branch %d has %d leaf parameters, a period was given for parameter %d", b, M.nd[b], d);
+                per[b][d] = v;
+                any = any || v > 0.0;
+            }
+    SETTLE(c, NEED_DEVICE);
+    double before[RJ_MAX_BRANCH][RJ_MAX_ND];
+    const bool on_before = c->rj.per_on;
+    memcpy(before, c->rj.period, sizeof(before));
+    memcpy(c->rj.period, per, sizeof(per));
+    c->rj.per_on = any;
+    if (const int r = rj_push_ctab(c)) { memcpy(c->rj.period, before, sizeof(before)); c->rj.per_on = on_before; return r; }
     return HENS_OK;
 }
 

@@ -39,7 +39,10 @@ constexpr int RJ_CTAB_LO = 0, RJ_CTAB_HI = RJ_MAX_RW, RJ_CTAB_SCALE = 2 * RJ_MAX
 constexpr int RJ_CTAB_CHOL = 4 * RJ_MAX_RW;                            // rows 4 - 6: L[d][0 .. 2] of the coordinate's dimension d (hens_rj_set_mh_chol)
 // rows 7 - 9: the coordinate's prior term record (hens_rj_set_prior_terms: PriorTerm::c0 / c1 / c2 of hens_prior_host.h; its kind: RJ_CBN_PK,
 // its support: rows lo / hi) - read by the instantiations that serve prior-term models (RjModel::prior_on) only
-constexpr int RJ_CTAB_C0 = 7 * RJ_MAX_RW, RJ_CTAB_C1 = 8 * RJ_MAX_RW, RJ_CTAB_C2 = 9 * RJ_MAX_RW, RJ_CTAB_ROWS = 10;
+constexpr int RJ_CTAB_C0 = 7 * RJ_MAX_RW, RJ_CTAB_C1 = 8 * RJ_MAX_RW, RJ_CTAB_C2 = 9 * RJ_MAX_RW;
+// row 10: the coordinate's period (hens_rj_set_periodic: > 0 on every slot's coordinate of a periodic leaf parameter, 0 elsewhere) - read
+// by the in-model proposals behind the wave-uniform test of RjArgs::per_on only, so a context without periods loads none of it
+constexpr int RJ_CTAB_PERIOD = 10 * RJ_MAX_RW, RJ_CTAB_ROWS = 11;
 // (cbn under prior terms: the term's kind in bits 24 - 25, zero on a box model, so RJ_CBN_SLOT stays a plain shift for the box instantiations)
 #define RJ_CBN_PK(v) (((v) >> 24) & 3)
 #define RJ_CBN_SLOT8(v) (((v) >> 16) & 255)
@@ -138,6 +141,10 @@ struct RjArgs {
     int32_t st_ns;
     int32_t st_hb;                      // production: half that moves | bits of the split permutation << 8
     RjGroup G;                          // RJ_MODE_GROUP (st_a is its stretch scale too)
+    // hens_rj_set_periodic: some leaf parameter is periodic (ctab row RJ_CTAB_PERIOD).  The in-model proposals measure c - s the short
+    // way round and wrap what they propose (periodic_diff / periodic_wrap of hens_kernels.h: stretch.py:136-154, gaussian.py:110-127) -
+    // on EVERY slot's periodic coordinates, active or not, as the reference wraps whole arrays.  Birth / death knows no periods.
+    int32_t per_on;
 };
 
 // k_adapt's arithmetic (tempering.py:563-596) in one wavefront, T <= 64: lane j owns rung j; same operations in the same order
@@ -367,8 +374,12 @@ constexpr int RJ_WPE(int mode, int tmm) { return (mode == RJ_MODE_BD && tmm == 1
 // are the model's run-time values (as in the TMM = -2 code), every per-point site takes the leaf's value from rj_leaf_at, leaves
 // are added to ONE running template (the oracle's order), and there is no uniform-grid form.  Instantiations of their own: the
 // pulse / sine instantiations carry none of it.
-template <int MODE, int TMM, bool CHOL = false, bool WIDE = false>
+// PER: the stretch half-step of a context with periodic leaf parameters (hens_rj_set_periodic) - instantiations of their own, so that
+// the ones a context without periods launches are the parent's code.  The Gaussian move, the group move and k_rj_gibbs test
+// RjArgs::per_on at run time (DESIGN.md 4.15 has the resource counts behind the choice).
+template <int MODE, int TMM, bool CHOL = false, bool WIDE = false, bool PER = false>
 __global__ __launch_bounds__(RJ_WAVES * 64) __attribute__((amdgpu_waves_per_eu(RJ_WPE(MODE, TMM)))) void k_rj(const RjArgs A) {
+    static_assert(!PER || MODE == RJ_MODE_STRETCH, "PER: the stretch half-step (the other moves test RjArgs::per_on)");
     constexpr bool HAVE_TM = TMM >= 0;
     __shared__ double s_cur[RJ_WAVES][RJ_MAX_RW];
     __shared__ double s_q[RJ_WAVES][RJ_MAX_RW];
@@ -518,6 +529,10 @@ __global__ __launch_bounds__(RJ_WAVES * 64) __attribute__((amdgpu_waves_per_eu(R
                 }
                 q[i] = cur[i] + st;
             }
+            if (A.per_on && coord) {                                      // gaussian.py:110-127: the whole copied array is wrapped, dead slots too
+                const double pr = A.ctab[RJ_CTAB_PERIOD + i];
+                if (pr > 0.0) q[i] = periodic_wrap(moves ? q[i] : cur[i], pr);
+            }
         }
         if (draw_u) { u_drawn = __shfl(u_drawn, M.ind_off & 63); u_have = true; }
     } else if (MODE == RJ_MODE_STRETCH) {
@@ -547,6 +562,20 @@ __global__ __launch_bounds__(RJ_WAVES * 64) __attribute__((amdgpu_waves_per_eu(R
                                     : ((cw0 & -(int)(b == 0)) | (cw1 & -(int)(b == 1)) | (cw2 & -(int)(b == 2)) | (cw3 & -(int)(b == 3)));
             const double c = A.pool[(size_t)A.loc[(size_t)tl * A.W + cw] * RW + i];
             q[i] = c - (c - cur[i]) * zz;                                           // stretch.py:141-145
+        }
+        // periodic leaf parameters (hens_rj_set_periodic; stretch.py:136-154): the periodic coordinates once more, c - s the short way
+        // round and the proposal wrapped - in the PER instantiations only (see the template parameters)
+        if constexpr (PER) {
+#pragma unroll 1
+            for (int i = lane; i < M.ind_off; i += 64) {
+                const double pr = A.ctab[RJ_CTAB_PERIOD + i];
+                if (!(pr > 0.0)) continue;
+                const int b = RJ_CBN_B(A.cbn[i]);
+                const int cw = A.st_own ? A.st_cw[(size_t)b * TN + slot]
+                                        : ((cw0 & -(int)(b == 0)) | (cw1 & -(int)(b == 1)) | (cw2 & -(int)(b == 2)) | (cw3 & -(int)(b == 3)));
+                const double c = A.pool[(size_t)A.loc[(size_t)tl * A.W + cw] * RW + i];
+                q[i] = periodic_wrap(c - periodic_diff(cur[i], c, pr) * zz, pr);
+            }
         }
         factors = ((double)M.ind_off - 1.0) * log(zz);                              // stretch.py:223
     } else if (MODE == RJ_MODE_BD) {

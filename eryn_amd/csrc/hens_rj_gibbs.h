@@ -185,6 +185,10 @@ __global__ __launch_bounds__(RJ_WAVES * 64) __attribute__((amdgpu_waves_per_eu(H
                 }
                 v = x + st;                                                  // gaussian.py:96-104
             }
+            // periodic leaf parameters (hens_rj_set_periodic): get_proposal wraps the whole arrays of the block's branches (gaussian.py:
+            // 110-127), cleanup_proposals_gibbs puts back the coordinates outside the block's mask (move.py:322-324) - so every TRUE
+            // coordinate of the mask is wrapped, moved or not, active or not, and every other coordinate keeps its bits
+            if (A.per_on && bm[i] != 0) v = periodic_wrap(v, A.ctab[RJ_CTAB_PERIOD + i]);
             q[i] = v;
         }
         RJ_G_LDS_SYNC();

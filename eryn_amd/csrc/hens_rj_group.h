@@ -34,6 +34,8 @@
 //    if the resume falls on a rebuild.
 //  5 Proposal.  One zz = ((a - 1) u + 1)^2 / a per walker; per active leaf a pick j uniform on [0, nf), c = tab_b[start + j],
 //    q = c - (c - x) zz on all its parameters.  Dead slots, and leaves of a branch with n_b == 0, keep their bits.
+//    Under hens_rj_set_periodic: q = wrap(c - distance(x, c) zz) (stretch.py:136-154), and the slots that keep their bits are wrapped
+//    too (x % period on their periodic coordinates: the reference wraps the whole array).  The friend RULE (2) stays linear in the key.
 //    factors = (sum_b nleaves_max_b ndim_b - 1) log zz: the reference's count (groupstretch.py:112, group.py:195-201: every slot,
 //    active or not), as k_rj<RJ_MODE_STRETCH> has it.
 //  6 Evaluation and acceptance: k_rj's - the log-prior over the active leaves, fix_logp_gibbs with every branch under proposal, the
@@ -120,7 +122,20 @@ __device__ __forceinline__ double rj_group_propose(const RjArgs& A, const int la
         for (int d = 0; d < nd_l; ++d) {
             const int i = off_l + n_of * nd_l + d;
             const double c = c_row[d];
-            q[i] = c - (c - cur[i]) * zz;                                            // stretch.py:141-145
+            if (A.per_on) {                                                          // stretch.py:136-154 (period 0: c - s, no wrap)
+                const double pr = A.ctab[RJ_CTAB_PERIOD + i];
+                q[i] = periodic_wrap(c - periodic_diff(cur[i], c, pr) * zz, pr);
+            } else {
+                q[i] = c - (c - cur[i]) * zz;                                        // stretch.py:141-145
+            }
+        }
+    } else if (A.per_on && is_slot) {
+        // a dead slot, a leaf of a branch without a table: its own friend - c - (c - x) zz = x - 0 zz keeps x's bits, and the reference
+        // wraps the whole array (stretch.py:149-153): x % period on the slot's periodic coordinates
+        for (int d = 0; d < nd_l; ++d) {
+            const int i = off_l + n_of * nd_l + d;
+            const double pr = A.ctab[RJ_CTAB_PERIOD + i];
+            if (pr > 0.0) q[i] = periodic_wrap(cur[i], pr);
         }
     }
     return ((double)M.ind_off - 1.0) * log(zz);                                      // groupstretch.py:112

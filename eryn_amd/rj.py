@@ -178,6 +178,7 @@ class RJEngine(ChainStoreCalls):
         self.lib, self.ctx = self.eng.lib, self.eng.ctx
         self.schedule = "separate_branches"
         self.in_model = "gaussian"   # the in-model move of ``step`` (set_in_model)
+        self.periods = None          # set_periodic: per branch a row of periods, or None
         self.host_like = None        # a CallableLikelihood: every parity move = propose on the device, evaluate here, accept on the device
         self.mt_K, self.mt_gen = 0, None     # set_mt_proposal: tries of the multiple-try birth / death move (0: the plain move), its generators
         self.nslots = sum(b.nleaves_max for b in self.branches)
@@ -434,6 +435,22 @@ class RJEngine(ChainStoreCalls):
             raise NotImplementedError("full leaf covariances: not with log-uniform / normal leaf priors (diagonal steps: set_mh_scale)")
         L = f64(chol, (len(self.branches), 3, 3))
         check(self.lib.hens_rj_set_mh_chol(self.ctx, ptr(L)), self.ctx)
+
+    def set_periodic(self, periods):
+        """Periodic leaf parameters (include/hipensemble.h: hens_rj_set_periodic).  ``periods``: None (clears), a
+        ``{branch: {index: period}}`` dict, a ``PeriodicContainer`` (this package's or the reference's), or per branch in order a row
+        of periods (0 = not periodic).  Every in-model move then measures differences the short way round and wraps what it proposes;
+        a branch that is absent, None or ``{}`` has no periodic parameter."""
+        rows = leaf_periods(periods, self.branches)
+        if rows is None:
+            check(self.lib.hens_rj_set_periodic(self.ctx, None), self.ctx)
+            self.periods = None
+            return
+        p = np.zeros((len(self.branches), self.ndmax))
+        for bi, b in enumerate(self.branches):
+            p[bi, :b.ndim] = rows[bi]
+        check(self.lib.hens_rj_set_periodic(self.ctx, ptr(p)), self.ctx)
+        self.periods = rows
 
     def set_in_model(self, kind):
         """The in-model move of ``step``: "gaussian" (``set_mh_scale`` / ``set_mh_chol``) or "stretch" (the red / blue stretch move
@@ -736,12 +753,49 @@ def _no_leaf_gibbs(gibbs_sampling_setup):
                                   "moves.StretchMove / GaussianMove)")
 
 
+def leaf_periods(periodic, branches):
+    """``periodic`` as ``EnsembleSampler`` takes it (ensemble.py:338-347) - None, ``{branch: {index: period}}``, a container with
+    ``inds_periodic`` / ``periods`` - or a sequence of per-branch rows -> a list of ``[ndim]`` period rows in branch order (0 = not
+    periodic), or None if no parameter is periodic.  Parsed by ``eryn_amd.periodic.period_vector`` per branch."""
+    from .periodic import period_vector
+    if periodic is None:
+        return None
+    if isinstance(periodic, (list, tuple, np.ndarray)):
+        if len(periodic) != len(branches):
+            raise ValueError(f"expected {len(branches)} rows of periods")
+        rows = []
+        for b, r in zip(branches, periodic):
+            r = np.zeros(b.ndim) if r is None else np.asarray(r, dtype=np.float64)
+            if r.shape != (b.ndim,):
+                raise ValueError(f"branch {b.name}: {b.ndim} periods")
+            if not np.all(np.isfinite(r) & (r >= 0.0)):
+                raise ValueError("periods must be finite and >= 0")
+            rows.append(r.copy())
+    else:
+        if isinstance(periodic, dict):
+            unknown = [k for k in periodic if k not in [b.name for b in branches]]
+            if unknown:
+                raise ValueError(f"periodic names branch {unknown[0]!r}, which the sampler does not have")
+        rows = []
+        for b in branches:
+            v = period_vector(periodic, b.name, b.ndim)
+            rows.append(np.zeros(b.ndim) if v is None else v)
+    return rows if any(np.any(r > 0.0) for r in rows) else None
+
+
+def _same_periods(a, b):
+    if a is None or b is None:
+        return a is None and b is None
+    return len(a) == len(b) and all(np.array_equal(x, y) for x, y in zip(a, b))
+
+
 class GaussianLeafMove:
     """``GaussianMove(cov_all)`` of the reference on leaf-packing records (gaussian.py:9-66): ``cov_all[name]`` is the
     3 x 3 proposal covariance of a leaf of that branch (the reference's ``_proposal``: ``multivariate_normal``)."""
 
-    def __init__(self, cov_all, gibbs_sampling_setup=None):
+    def __init__(self, cov_all, gibbs_sampling_setup=None, periodic=None):
         _no_leaf_gibbs(gibbs_sampling_setup)
+        self.periodic = periodic               # (the reference's moves carry one: it must agree with the sampler's, which it gets if None)
         self.cov = {k: np.atleast_2d(np.asarray(v, dtype=np.float64)) for k, v in cov_all.items()}
         for k, c in self.cov.items():
             if c.ndim != 2 or c.shape[0] != c.shape[1] or not 1 <= c.shape[0] <= 4:
@@ -835,10 +889,10 @@ class GibbsGaussianLeafMove(GaussianLeafMove):
     (mh.py:105-107); under ``rng="philox"`` the device walks every block - the walkers of such a block are all rejected - and
     ``num_proposals`` counts it."""
 
-    def __init__(self, cov_all, gibbs_sampling_setup):
+    def __init__(self, cov_all, gibbs_sampling_setup, periodic=None):
         if gibbs_sampling_setup is None:
             raise ValueError("GibbsGaussianLeafMove needs a gibbs_sampling_setup (without blocks the move is GaussianLeafMove)")
-        super().__init__(cov_all)
+        super().__init__(cov_all, periodic=periodic)
         self.gibbs_sampling_setup = gibbs_sampling_setup
         self.blocks = parse_leaf_gibbs_setup(gibbs_sampling_setup)
 
@@ -848,8 +902,9 @@ class StretchLeafMove:
     red_blue.py:103-330): every branch and every leaf slot of a walker moves - one complement walker per branch, one stretch
     factor per walker.  (The reference advises against it beside reversible jump, ensemble.py:509-514, and runs it.)"""
 
-    def __init__(self, a=2.0, live_dangerously=False, gibbs_sampling_setup=None):
+    def __init__(self, a=2.0, live_dangerously=False, gibbs_sampling_setup=None, periodic=None):
         _no_leaf_gibbs(gibbs_sampling_setup)
+        self.periodic = periodic
         self.a = float(a)
         self.live_dangerously = bool(live_dangerously)         # red_blue.py:41-47,108: fewer walkers than 2 x (all leaf slots' coordinates)
         self.accepted, self.num_proposals = None, 0
@@ -867,10 +922,13 @@ class GroupStretchLeafMove:
 
     The friend table is state that a ``State`` does not carry: ``run_mcmc`` restarts the rebuild count, so its first move rebuilds the
     table from the state it was given, and a chain resumed from a stored ``State`` is the uninterrupted chain only if the resume
-    falls on a rebuild (a multiple of ``n_iter_update`` moves).  Not built: Gibbs blocks for this move, host-callable likelihoods,
-    periodic parameters, more than 64 friends, user-defined friend rules."""
+    falls on a rebuild (a multiple of ``n_iter_update`` moves).  Periodic parameters (the sampler's ``periodic=``): the stretch toward
+    the friend goes the short way round and is wrapped; the friend RULE stays nearest by linear distance in ``key``, also where the
+    key parameter is periodic.  Not built: Gibbs blocks for this move, host-callable likelihoods, more than 64 friends, user-defined
+    friend rules."""
 
-    def __init__(self, nfriends, key, n_iter_update=100, a=2.0, live_dangerously=False, gibbs_sampling_setup=None):
+    def __init__(self, nfriends, key, n_iter_update=100, a=2.0, live_dangerously=False, gibbs_sampling_setup=None, periodic=None):
+        self.periodic = periodic
         if gibbs_sampling_setup is not None:
             raise NotImplementedError("gibbs_sampling_setup is not built for GroupStretchLeafMove: it stretches every active leaf of every "
                                       "branch in one move")
@@ -975,12 +1033,17 @@ class RJEnsembleSampler:
     the frozen SciPy ``uniform`` / ``loguniform`` / ``norm`` per leaf parameter (prior.py:219-392).  The prior is also the birth
     proposal (distgenrj.py:188-214): log-prior, the factor -+ log q(leaf) and the born leaf's draw all follow it in both ``rng`` modes
     (include/hipensemble.h: hens_rj_set_prior_terms); with a log-uniform or normal parameter the Philox Gaussian move takes diagonal
-    covariances only."""
+    covariances only.
+
+    periodic: ``{branch: {index: period}}``, this package's ``PeriodicContainer`` or the reference's (``EnsembleSampler(periodic=...)``):
+    every in-model move - Gaussian, Gibbs blocks, stretch, group stretch - measures ``c - s`` the short way round and wraps its proposal
+    with the reference's arithmetic, in both ``rng`` modes; birth / death draws from the prior and knows no periods, as in the
+    reference."""
 
     def __init__(self, nwalkers, ndims, log_like_fn, priors, tempering_kwargs=None, nbranches=None, branch_names=None,
                  nleaves_max=None, nleaves_min=None, moves=None, rj_moves="separate_branches", rng="numpy", seed=None,
                  device_id=0, args=None, kwargs=None, vectorize=False, provide_groups=False, fill_zero_leaves_val=-1e300,
-                 backend=None, **unused):
+                 backend=None, periodic=None, **unused):
         from .backend import RJDeviceBackend
         from .moves.tempering import TemperatureControl
         for m in (moves if isinstance(moves, (list, tuple)) else [moves]):
@@ -1065,6 +1128,14 @@ class RJEnsembleSampler:
         self.temperature_control = tc = TemperatureControl(total_ndim, self.nwalkers, **tk)
         self.ntemps = tc.ntemps
         self.moves, self.rng = [moves], rng
+        # periodic: what EnsembleSampler takes (ensemble.py:338-347) - the in-model moves of both rng modes measure and wrap by it
+        # (hens_rj_set_periodic); a move that carries its own must say the same
+        self.periodic = periodic
+        rows = leaf_periods(periodic, self.branches)
+        if getattr(moves, "periodic", None) is not None and not _same_periods(leaf_periods(moves.periodic, self.branches), rows):
+            raise ValueError("the move's periodic differs from the sampler's (one set of periods per sampler: pass it as "
+                             "RJEnsembleSampler(periodic=...))")
+        moves.periodic = periodic
         if seed is None:
             seed = int(np.random.randint(0, 2**31 - 1)) if rng == "philox" else 0
         self.engine = RJEngine(self.ntemps, self.nwalkers, self.branches, log_like_fn.t, log_like_fn.y, log_like_fn.sigma,
@@ -1072,6 +1143,8 @@ class RJEnsembleSampler:
                                adaptation_time=tc.adaptation_time, stop_adaptation=tc.stop_adaptation,
                                **({"a": moves.a, "live_dangerously": moves.live_dangerously} if isinstance(moves, (StretchLeafMove, GroupStretchLeafMove)) else {}))
         self.engine.host_like = self.host_like
+        if rows is not None:
+            self.engine.set_periodic(rows)
         self.gibbs_members = None
         if isinstance(moves, GibbsGaussianLeafMove):      # the table is pushed once; both rng modes step under it
             table, self.gibbs_members = leaf_gibbs_table(moves.blocks, self.branches)

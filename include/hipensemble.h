@@ -131,7 +131,8 @@ int hens_set_prior_terms(hens_ctx* ctx, const int32_t* kind, const double* lo, c
  *   wrapped into [0, period) with NumPy's remainder (stretch.py:149-154, gaussian.py:110-115 -> periodic.py:118-151);
  *   0 = not periodic; NULL or all zeros = no periodic parameters.  Every entry point honours it (the one- and two-launch
  *   iterations' compile-time-width kernels and the generic-width kernel alike, and the ranks of a ladder pipeline - set it
- *   on every rank BEFORE hens_pipe_init); not available on a leaf-packing context. */
+ *   on every rank BEFORE hens_pipe_init); not available on a leaf-packing context (HENS_ERR_UNSUPPORTED), whose periods go per branch
+ *   and leaf parameter: hens_rj_set_periodic. */
 int hens_set_periodic(hens_ctx* ctx, const double* period);
 int hens_set_gaussian(hens_ctx* ctx, const double* mu, const double* prec);
 int hens_set_rosenbrock(hens_ctx* ctx, double a, double b);
@@ -732,6 +733,28 @@ int hens_rj_set_mh_scale(hens_ctx* ctx, const double* scale);
  * hens_rj_debug_draws exports the correlated step.  Entries above the diagonal must be zero; a non-finite entry or a diagonal
  * entry <= 0 (the covariance was not positive definite) -> HENS_ERR_INVALID.  The last of the two setters called holds. */
 int hens_rj_set_mh_chol(hens_ctx* ctx, const double* chol);
+/* Periodic leaf parameters: the `periodic` argument of EnsembleSampler / Move (a PeriodicContainer, utils/periodic.py:11-151) on a
+ * leaf-packing context, per branch and per leaf parameter.  period[nbranches][widest branch's parameters] in the birth arrays'
+ * stride; period > 0 makes that parameter of every leaf slot of the branch periodic, 0 = not periodic, NULL or all zeros clears.
+ * Every entry point that forms an IN-MODEL proposal honours it, teacher-forced and Philox alike, with hens_set_periodic's arithmetic
+ * (NumPy's remainder; the difference taken again from the moving point shifted by one period):
+ *   Gaussian move (hens_rj_mh_step, hens_rj_step, hens_rj_propose)   q = wrap(x + step) on the active leaves, and wrap(x) on the
+ *       periodic coordinates of every other slot: the reference wraps the whole copied array (gaussian.py:102-127), so an accepted
+ *       walker's record carries x % period in its dead slots
+ *   ... under Gibbs blocks (hens_rj_set_gibbs)   every coordinate that is true in the block's mask is wrapped, moved or not, active or
+ *       not; every other coordinate keeps its bits (move.py:322-324 puts it back)
+ *   stretch move (hens_rj_stretch_split, hens_rj_step, hens_rj_propose)   q = wrap(c - distance(x, c) zz) on every slot
+ *       (stretch.py:136-154), c - x measured the short way round where it exceeds half a period
+ *   group stretch move (hens_rj_group_step, hens_rj_step)   the same with the friend as c; a dead slot and a leaf of a branch with an
+ *       empty table are their own friend: wrap(x).  The friend RULE stays nearest by linear distance in the key parameter, also
+ *       where the key is periodic (a departure that is stated, not refused).
+ * Birth / death, multiple-try birth / death and the cascade know no periods, as in the reference (they draw from the prior).
+ * The periods survive hens_rj_set_mh_scale, hens_rj_set_mh_chol, hens_rj_set_prior_terms, hens_rj_set_gibbs and hens_rj_set_group in
+ * any order; a new model (hens_rj_set_model*) drops them.  A context without periods launches what it launched before and steps the
+ * same chain.  Refused with the context unchanged: a negative, NaN or infinite period, a period on a parameter index >= the branch's
+ * number of leaf parameters (HENS_ERR_INVALID); a context that is not leaf-packing (HENS_ERR_UNSUPPORTED: hens_set_periodic is
+ * its call); between the two stretch half-steps or while hens_rj_accept is pending (HENS_ERR_STATE). */
+int hens_rj_set_periodic(hens_ctx* ctx, const double* period);
 /* Per-parameter prior terms on the leaves: ProbDistContainer({i: dist_i}) per branch with uniform, log-uniform and normal
  * distributions (prior.py:337-392) in place of the box of the hens_rj_set_model* call that came before.  kind / lo / hi / c0 / c1 /
  * c2 run over the branches' leaf parameters one after the other (sum_b ndims[b] entries, as hens_rj_set_model_general takes lo /
