@@ -244,6 +244,7 @@ struct hens_ctx_impl {
         bool wide = false;                   // hens_rj_set_model_kinds with a leaf kind beyond pulse / sine: the WIDE instantiations of k_rj
         PriorTerm terms[RJ_MAX_BRANCH][RJ_MAX_ND] = {};        // hens_rj_set_prior_terms (M.prior_on): a branch's term per leaf parameter, supports in M.lo / hi
         double* t = nullptr; double* y = nullptr;              // [ndata] data of the template likelihood
+        int64_t data_cap = 0;                                  // ... and the data points they have room for
         double* ctab = nullptr; int32_t* cbn = nullptr;        // RjArgs::ctab / cbn: what a lane needs about its record coordinate (rj_push_ctab)
         double* step = nullptr; double* u = nullptr; double* birth = nullptr;         // the caller's draws of a teacher-forced move (rj_ensure_staging)
         int8_t* change = nullptr; int32_t* leaf = nullptr; uint8_t* keep = nullptr;
@@ -251,7 +252,8 @@ struct hens_ctx_impl {
         double *hq = nullptr, *hlogp = nullptr, *hfac = nullptr, *hlu = nullptr, *hlogl = nullptr; uint8_t* hmoved = nullptr;   // host-callable likelihood (hens_rj_propose / hens_rj_accept)
         bool accept_pending = false;         // hens_rj_propose ran: hens_rj_accept is due ...
         uint32_t* pending_acc = nullptr;     // ... and counts the move's accepts here (rj_accept_counter of the proposal)
-        double* tm = nullptr; int64_t tm_ndata = 0;   // [2 Tl W][ndata] every pool row's template, resident (RjArgs::tm), or nullptr (ndata > 512)
+        double* p_aside = nullptr;           // [Tl W] where a refresh's evaluation writes its log-priors (rj_evaluate)
+        double* tm = nullptr; int64_t tm_ndata = 0;  // [2 Tl W][ndata] every pool row's template, resident (RjArgs::tm), or nullptr (ndata > 512)
         bool tm_valid = false;               // ... and they belong to the rows as they are (false after an upload / a teacher-forced move)
         bool tm_drift = false;               // hens_rj_step has updated them by +- a leaf since their last full evaluation
         int schedule = 0;                    // hens_rj_set_schedule: 0 "separate_branches", 1 "iterate_branches", 2 "together" (ensemble.py:414-480), 3 no birth / death move
@@ -1927,7 +1929,8 @@ struct RjLaunch {
     const double* step = nullptr; const int8_t* change = nullptr; const int32_t* leaf = nullptr; const double* birth = nullptr;
     const int32_t* st_own = nullptr; const int32_t* st_cw = nullptr; const double* st_uzz = nullptr; const double* u_acc = nullptr;
     uint8_t* keep = nullptr;                // RjArgs::keep_out
-    bool propose = false;                   // the proposal half of a host-callable move (k_rj<MODE, -2>); k_rj_accept finishes it
+    double* P_out = nullptr;                // RjArgs::P in place of the context's log-priors (rj_evaluate: a refresh leaves them alone)
+    bool propose = false;                  // the proposal half of a host-callable move (k_rj<MODE, -2>); k_rj_accept finishes it
     // the multiple-try birth / death move (k_rj_mt, hens_rj_set_mt_proposal) in place of k_rj<RJ_MODE_BD>: FORCED: the caller's tries and
     // pick uniforms (birth unused); mt_out: RjMtArgs::out
     bool mt = false;
@@ -1985,7 +1988,7 @@ int rj_launch(hens_ctx_impl* c, const RjLaunch& l) {
     if (c->tracing && c->trace_rj == mode) { a.trace = c->d_trace; a.trace_n = (int32_t)(c->trace_words / 8); }
     a.tm = (l.tm_mode >= 0) ? c->rj.tm : nullptr;
     a.tm_mode = l.tm_mode >= 0 ? l.tm_mode : 0;
-    a.pool = c->pool; a.loc = c->loc[c->cur]; a.L = c->L[c->cur]; a.P = c->P[c->cur];
+    a.pool = c->pool; a.loc = c->loc[c->cur]; a.L = c->L[c->cur]; a.P = l.P_out ? l.P_out : c->P[c->cur];
     a.betas = c->cfg.tempered ? c->betas[c->bcur] : nullptr;
     a.accepted = rj_accept_counter(c, mode, l.branch); a.keep_out = l.keep;
     a.tdata = c->rj.t; a.ydata = c->rj.y; a.ctab = c->rj.ctab; a.cbn = c->rj.cbn;
@@ -2110,8 +2113,18 @@ int rj_group_rebuild(hens_ctx_impl* c) {
 }
 
 // full evaluation; behind it the resident templates (where the model keeps them) are exactly those of the rows
-int rj_evaluate(hens_ctx_impl* c) {
-    const int r = rj_launch(c, rj_eval());
+// keep_logp: a REFRESH of a chain's templates and log-likelihoods (every 64 iterations, in front of a download, at the head of a
+// call behind an upload that brought its logs) - the stored log-priors stay what the chain made them.  They are no function of the
+// coordinates: under a Gibbs table fix_logp_gibbs stores 0.0 on a walker whose only leaves sit in non-member slots of the block's
+// branches (hens_rj_gibbs.h, move.py:368-402), and the next accept test reads that 0.0.  The launch writes its log-priors aside.
+int rj_evaluate(hens_ctx_impl* c, bool keep_logp = false) {
+    RjLaunch l = rj_eval();
+    if (keep_logp) {
+        if (!c->rj.p_aside)
+            if (const int ra = dalloc(c, &c->rj.p_aside, (size_t)c->Tl * c->W)) return ra;
+        l.P_out = c->rj.p_aside;
+    }
+    const int r = rj_launch(c, l);
     if (!r) { c->rj.tm_valid = c->rj.tm != nullptr; c->rj.tm_drift = false; }
     return r;
 }
@@ -2905,7 +2918,7 @@ int hens_download_state(hens_ctx* ctx, double* x, double* logl, double* logp, do
     // valid (round 5 invalidated them behind the copy: the stored log_like was the +- value the device then replaced, and every
     // stored step paid the evaluation at the head of the next call instead).
     if (is_rj(c) && (x || logl) && c->rj.tm && c->rj.tm_valid && c->rj.tm_drift) {
-        int r = rj_evaluate(c);
+        int r = rj_evaluate(c, true);
         if (r) return r;
         if ((r = check_flags(c, true))) return r;
     }
@@ -4202,15 +4215,21 @@ static int rj_set_template_model(hens_ctx_impl* c, int nkinds, int32_t nbranches
     c->rj.per_on = false; memset(c->rj.period, 0, sizeof(c->rj.period));        // (... and the periods: hens_rj_set_periodic anew)
     int r;
     if ((r = rj_push_ctab(c))) return r;
-    if (!c->rj.t) {
+    if (!c->rj.t || c->rj.data_cap < ndata) {        // (a second model on the context may bring more data points than the first)
         if ((r = dalloc(c, &c->rj.t, (size_t)ndata))) return r;
         if ((r = dalloc(c, &c->rj.y, (size_t)ndata))) return r;
+        c->rj.data_cap = ndata;
+    }
+    if (!c->rj.acc_bd) {
         if ((r = dalloc(c, &c->rj.acc_bd, (size_t)c->Tl * c->W))) return r;
         HIPCHK(c, hipMemsetAsync(c->rj.acc_bd, 0, (size_t)c->Tl * c->W * 4, c->stream));
     }
     // every pool row's template, resident (birth / death by difference in hens_rj_step): 2 Tl W rows of ndata doubles
-    // (config 4: 131 MB); a lane keeps 8 points, so models of up to 512 data points; HENS_RJ_NO_TEMPLATES=1: A/B knob
-    if (!env().rj_no_templates && ndata <= 512 && (!c->rj.tm || c->rj.tm_ndata != ndata)) {
+    // (config 4: 131 MB); a lane keeps 8 points, so models of up to 512 data points; HENS_RJ_NO_TEMPLATES=1: A/B knob.  A model
+    // past that has none: the buffer of a smaller model before it is let go of (rj_production reads rj.tm), not stepped on
+    if (env().rj_no_templates || ndata > 512) {
+        c->rj.tm = nullptr; c->rj.tm_ndata = 0;
+    } else if (!c->rj.tm || c->rj.tm_ndata != ndata) {
         if ((r = dalloc(c, &c->rj.tm, (size_t)2 * c->Tl * c->W * (size_t)ndata))) return r;
         c->rj.tm_ndata = ndata;
     }
@@ -4743,7 +4762,7 @@ int RjStepping::begin(int64_t n_iters) {
     // download is a function of what the download returned, so a chain is a function of (State, seed, iteration counter,
     // adaptation time): resumed in a new context it is the uninterrupted chain bit for bit (tests/test_hip_rj.py).
     if (c->rj.tm && !c->rj.tm_valid && n_iters > 0) {
-        if ((r = rj_evaluate(c))) return r;
+        if ((r = rj_evaluate(c, c->have_logs))) return r;
         fresh = true;
     }
     const bool fold_off = env().no_fold;          // A/B knob: k_adapt behind every cascade
@@ -4763,7 +4782,7 @@ int RjStepping::iteration(double* swaps_aside) {
     constexpr int64_t RJ_REFRESH = 64;
     int r;
     if (c->rj.tm && c->iter % RJ_REFRESH == RJ_REFRESH - 1 && !fresh && c->rj.tm_drift)
-        if ((r = rj_evaluate(c))) return r;
+        if ((r = rj_evaluate(c, true))) return r;
     fresh = false;
     const bool blocks = c->rj.gb_n > 0 && !c->rj.gb_whole;            // (hens_rj_set_gibbs; begin() has refused the stretch move)
     // (birth / death updates a template by +- a leaf; so does every accepted Gibbs block, on any schedule)
@@ -4949,7 +4968,7 @@ int hens_rj_step_chain(hens_ctx* ctx, int64_t n_store, int64_t iters_per_store) 
         if ((r = st.iteration(ch.swaps_step))) return r;
         SETTLE(c, NEED_LADDER);                   // (the ladder AFTER the step's adaptation - what hens_download_state returns)
         // what hens_download_state runs in front of its copy: the stored log_like is the value the device goes on with
-        if (c->rj.tm && c->rj.tm_valid && c->rj.tm_drift && (r = rj_evaluate(c))) return r;
+        if (c->rj.tm && c->rj.tm_valid && c->rj.tm_drift && (r = rj_evaluate(c, true))) return r;
         if ((r = launch_rj_chain_store(c, tm))) return r;
         ch.mark_valid = true;                     // (k_rj_chain_store moved the mark up to now)
         ch.mark_books = c->rj.num_mh + c->rj.num_bd;

@@ -359,15 +359,16 @@ PRODUCTION_CASES = {
 }
 
 
-def production_problem(name, T=4, W=64, ndata=40, sigma=3.0):
+def production_problem(name, T=4, W=64, ndata=40, sigma=3.0, seed=None):
     """-> dict(branches (tests/leaf_kinds.Branch), obr (the oracle's), periods, t, y, sigma, x, inds, betas, scale, chol, like_fn, key):
     every slot holds a leaf from the box, masks at random; the periodic parameter of the active leaves starts within 0.1 of the seam, on
-    both sides, and that of the dead ones outside [0, 2 pi)."""
+    both sides, and that of the dead ones outside [0, 2 pi).  ``name``: a case of PRODUCTION_CASES, or a row like them with a ``seed``
+    (tests/rj_limit_moves.py)."""
     from tests import leaf_kind_cases as cases
     from tests import leaf_kinds as lk
-    c = PRODUCTION_CASES[name]
+    c = PRODUCTION_CASES[name] if isinstance(name, str) else name
     brs = cases.branches_of(c["kinds"], c["nl"])
-    rs = np.random.RandomState(1000 + sorted(PRODUCTION_CASES).index(name))
+    rs = np.random.RandomState(1000 + sorted(PRODUCTION_CASES).index(name) if seed is None else seed)
     t = np.linspace(-1, 1, ndata)
     y = cases.make_data(brs, t, sigma, rs)
     x, inds = cases.random_state(brs, T, W, rs)

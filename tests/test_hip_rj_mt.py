@@ -52,41 +52,49 @@ def test_teacher_forced_move_matches_the_specification(name):
     eng = _engine(c, p)
     worst = [0.0, 0.0, 0.0]
     try:
-        def on_proposal(o, bi, inputs, info, ex, sweep, pre, mid):
-            what = f"{name}: proposal {len(seen)} on branch {bi}"
-            seen.append(bi)
-            x, inds, L, P = _state(pre, o)
-            eng.upload(x, inds, L, P, betas=o.st.betas)
-            change, leaf, tries, u_pick, u_acc = inputs
-            keep, out = eng.mt_bd_step(bi, change, leaf, tries, u_pick, u_acc, out=True)
-            assert np.array_equal(keep, info["keep"]), f"{what}: accept mask"
-            assert np.array_equal(out["pick"], info["pick"]), f"{what}: picks"
-            assert np.array_equal(out["mt_lp"], info["mt_lp"]), f"{what}: mt_lp"
-            tol.check_logl(out["mt_ll"], info["mt_ll"], RTOL_L, f"{what}: mt_ll")
-            r = rm.mm.assert_sums(out["lsw"], out["aux_lsw"], out["factors"], ex, what)
-            for i in range(3):
-                worst[i] = max(worst[i], r[i])
-            for k in ("lsw", "aux_lsw", "factors"):
-                _same_nonfinite(out[k], info[k], f"{what}: {k}")
-            xm, im, Lm, Pm = _state(mid, o)
-            x1, inds1, L1, P1, _ = eng.download()
-            for b in o.branches:
-                assert np.array_equal(inds1[b.name], im[b.name]) and np.array_equal(x1[b.name], xm[b.name]), f"{what}: records of {b.name}"
-            assert np.array_equal(P1, Pm), f"{what}: log-prior"
-            tol.check_logl(L1, Lm, RTOL_L, f"{what}: log-like after the move")
-            if o.T > 1:
-                eng.upload(xm, im, Lm, Pm, betas=o.st.betas)
-                eng.pt_sweep(sweep["iperm"], sweep["i1perm"], sweep["u_swap"], adapt=False)
-                _assert_records(eng, o, f"{what}: after the sweep")
-
-        seen = []
-        cnt = rm.forced_run(c, on_proposal)
+        cnt = rm.forced_run(c, forced_proposal_hook(eng, name, worst))
         rm.assert_sized(cnt, c, name)
         assert eng.counters()["num_bd"] == c["nprop"]
     finally:
         eng.close()
     # (the ratios go into the tolerance report under this test's name - mt_move.assert_sums; profiles/rj_mt_bound_ratios.txt is made of it)
     print(f"{name}: worst |value - exact| / B: lsw {worst[0]:.3f}, aux_lsw {worst[1]:.3f}, factors {worst[2]:.3f}")
+
+
+def forced_proposal_hook(eng, name, worst):
+    """The ``on_proposal`` of tests/rj_mt_move.forced_run that holds the device to the specification on one proposal (the bars of
+    test_teacher_forced_move_matches_the_specification; tests/test_hip_rj_limit_moves.py runs the limit records through it);
+    ``worst``: the running maxima of |value - exact| / B for lsw, aux_lsw, factors."""
+    seen = []
+
+    def on_proposal(o, bi, inputs, info, ex, sweep, pre, mid):
+        what = f"{name}: proposal {len(seen)} on branch {bi}"
+        seen.append(bi)
+        x, inds, L, P = _state(pre, o)
+        eng.upload(x, inds, L, P, betas=o.st.betas)
+        change, leaf, tries, u_pick, u_acc = inputs
+        keep, out = eng.mt_bd_step(bi, change, leaf, tries, u_pick, u_acc, out=True)
+        assert np.array_equal(keep, info["keep"]), f"{what}: accept mask"
+        assert np.array_equal(out["pick"], info["pick"]), f"{what}: picks"
+        assert np.array_equal(out["mt_lp"], info["mt_lp"]), f"{what}: mt_lp"
+        tol.check_logl(out["mt_ll"], info["mt_ll"], RTOL_L, f"{what}: mt_ll")
+        r = rm.mm.assert_sums(out["lsw"], out["aux_lsw"], out["factors"], ex, what)
+        for i in range(3):
+            worst[i] = max(worst[i], r[i])
+        for k in ("lsw", "aux_lsw", "factors"):
+            _same_nonfinite(out[k], info[k], f"{what}: {k}")
+        xm, im, Lm, Pm = _state(mid, o)
+        x1, inds1, L1, P1, _ = eng.download()
+        for b in o.branches:
+            assert np.array_equal(inds1[b.name], im[b.name]) and np.array_equal(x1[b.name], xm[b.name]), f"{what}: records of {b.name}"
+        assert np.array_equal(P1, Pm), f"{what}: log-prior"
+        tol.check_logl(L1, Lm, RTOL_L, f"{what}: log-like after the move")
+        if o.T > 1:
+            eng.upload(xm, im, Lm, Pm, betas=o.st.betas)
+            eng.pt_sweep(sweep["iperm"], sweep["i1perm"], sweep["u_swap"], adapt=False)
+            _assert_records(eng, o, f"{what}: after the sweep")
+
+    return on_proposal
 
 
 @pytest.mark.parametrize("name", rm.FIXTURES)
@@ -217,7 +225,12 @@ def test_production_step_replayed_through_the_specification(name):
     with an adaptation of a short lag pending into every birth / death launch."""
     cname, schedule, in_model, iters, it0, adapting = rm.REPLAYS[name]
     c = rm.CASES[cname]
-    p = rm.case_problem(c)
+    replay_through_the_specification(name, c, rm.case_problem(c), schedule, in_model, iters, it0, adapting)
+
+
+def replay_through_the_specification(name, c, p, schedule, in_model, iters, it0=0, adapting=False, on_info=None):
+    """The body of test_production_step_replayed_through_the_specification on any case and problem (tests/test_hip_rj_limit_moves.py
+    runs the limit records through it); on_info(o, info): called with every proposal's record of the specification."""
     adapt = dict(adaptation_lag=5, adaptation_time=5) if adapting else {}
     eng = _production_engine(c, p, schedule, in_model, it0, adapt=adapt)
     try:
@@ -252,6 +265,8 @@ def test_production_step_replayed_through_the_specification(name):
         cnt = rm.Counts()
         for info in o.mt_infos:
             cnt.add(o, info, rm.exact_rj_mt(o, info))
+            if on_info is not None:
+                on_info(o, info)
         rm.assert_sized(cnt, dict(c, inf_prior=False, nan_factor=False, edges=False), name)
         assert o.knife_swaps == 0
         if adapting:
